@@ -21,6 +21,19 @@ about step 24 — a compressed column whose divergence solve no longer converges
 the same).  `value` is the whole-run mean the contract asks for and therefore depends on --steps; `regimes` and
 `per_step_ms` / `iters` make that explicit: `first20` = the first 20 timed steps, `settled` = the timed steps whose
 divergence solve hit the cap.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, print the line.  Everything else the bench
+measures runs only with `--full` (and is null in the line without it): `roofline` (the dominant kernels timed on their own with
+HIP events, against the committed PMC profile; `at_8m`, the same kernel at 8 x 10^6 particles), `with_download` (the same steps
+again on a fresh world with a read-back after every step) and `cpu_baseline` (the CPU oracle on the same scene, compiled for the
+host first).  `--no-cpu-baseline`, `--no-download-leg` and `--no-big-leg` leave single legs out of a `--full` run.
+
+`--dump-outputs DIR` writes what the timed steps computed, as a caller of `step` would read it after the last timed step:
+`fluid<i>_positions.npy` and `fluid<i>_velocities.npy` (float32, host order) for every fluid — in a decomposed run, rank 0's
+owned particles as `rank0_gids.npy` (float64), `rank0_positions.npy`, `rank0_velocities.npy`, sorted by gid — and
+`step_stats.npy` (float64: divergence iterations, pressure iterations, divergence error, density error, contacts, particles of
+the last step).  At most 64 MiB in all: beyond that every particle array keeps the same fixed, seeded sample of rows, whose
+indices go to `<prefix>_sample_index.npy` (float64).  The scene is seeded, so equal arguments give equal inputs on every run.
 """
 import argparse
 import json
@@ -235,6 +248,29 @@ def cpu_baseline(config: int, side: int, steps: int, warmup: int, gpu_step_ms, b
                               "sample": f"the {done1} step(s) after those, same build, 1 thread, {dt_one:.1f} s"}}
 
 
+DUMP_BUDGET = 64 << 20  # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(out_dir: str, groups, extra):
+    """Write `groups` = [(prefix, {name: per-particle array})] and `extra` = {name: small array} as out_dir/<name>.npy.  Over
+    DUMP_BUDGET, each group keeps the same fixed, seeded sample of its rows (indices in <prefix>_sample_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = [len(next(iter(arrs.values()))) if arrs else 0 for _, arrs in groups]
+    total = sum(a.nbytes for _, arrs in groups for a in arrs.values()) + sum(np.asarray(a).nbytes for a in extra.values())
+    # sampled, each kept row also costs 8 bytes of index (+ 1 MiB for the .npy headers and the extras)
+    keep = 1.0 if total <= DUMP_BUDGET else (DUMP_BUDGET - (1 << 20)) / (total + 8 * sum(rows))
+    for g, (prefix, arrs) in enumerate(groups):
+        n = rows[g]
+        if keep < 1.0 and n:
+            idx = np.sort(np.random.default_rng(1000 + g).choice(n, max(1, int(n * keep)), replace=False))
+            np.save(os.path.join(out_dir, f"{prefix}_sample_index.npy"), idx.astype(np.float64))
+            arrs = {k: a[idx] for k, a in arrs.items()}
+        for k, a in arrs.items():
+            np.save(os.path.join(out_dir, f"{prefix}_{k}.npy"), np.ascontiguousarray(a))
+    for k, a in extra.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -243,11 +279,15 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS),
                     help="BASELINE configuration (SURVEY.md §8d): 2 DFSPH + XSPH (headline, default), 3 IISPH + Akinci2013, 4 two-phase DFSPH")
     ap.add_argument("--side", type=int, default=100, help="particles per edge of the fluid block (100 -> 1M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: kernel rooflines, the read-back run, the 8 x 10^6 leg, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fluid state after the last timed step (and its step stats) as DIR/<name>.npy, 64 MiB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg (`cpu_baseline`)")
     ap.add_argument("--no-download-leg", action="store_true",
-                    help="skip the second run of the same steps with positions + velocities read back after every step (`with_download`)")
+                    help="with --full: skip the second run of the same steps with positions + velocities read back after every step (`with_download`)")
     ap.add_argument("--no-big-leg", action="store_true",
-                    help="skip the roofline of the dominant kernel at 8 x 10^6 particles (`roofline.at_8m`; default run of config 2 only)")
+                    help="with --full: skip the roofline of the dominant kernel at 8 x 10^6 particles (`roofline.at_8m`; default run of config 2 only)")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of host time for the multi-thread CPU leg")
     ap.add_argument("--transport", choices=("rccl", "peer"), default="rccl",
                     help="slab exchange of a multi-GPU run: RCCL send/recv + all-reduce (default, what BASELINE.json names), or the "
@@ -264,6 +304,8 @@ def main():
     ndev = torch.cuda.device_count()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > ndev and not (args.share_devices and args.transport == "peer"):
         raise SystemExit(f"--gpus {args.gpus} but this node shows {ndev} GPU(s): one rank per GPU over RCCL needs {args.gpus} devices "
                          f"(a functional run with ranks sharing devices: --transport peer --share-devices)")
@@ -375,98 +417,110 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-
-    # ---- roofline of the dominant neighbour-sum kernel, timed live with HIP events on the world's own stream
     it = np.asarray(iters, dtype=np.float64)
-    kid, kname, sbytes = cfg["kernel"]
-    kernel_us = w.time_kernel(kid, 50)
+
+    # ---- what the timed steps computed, read as a caller reads it after the last step (before anything else touches the world)
+    if args.dump_outputs and rank == 0:
+        if not decomposed:
+            groups = [(f"fluid{i}", {"positions": h.positions, "velocities": h.velocities}) for i, h in enumerate(handles)]
+        else:
+            gid, pos, vel, _ = w.owned()
+            groups = [("rank0", {"gids": gid.astype(np.float64), "positions": pos, "velocities": vel})]
+        stats = [st.n_divergence_iters, st.n_pressure_iters, st.divergence_error, st.density_error, st.ncontacts, st.nparticles]
+        dump_outputs(args.dump_outputs, groups, {"step_stats": stats})
+
     if not decomposed:
         kbar = float(sum(w.contact_counts(h).sum() + w.contact_counts(h, True).sum() for h in handles)) / n
     else:  # host-order fields do not exist in a decomposed run: list entries per local particle, from the step report
         kbar = float(st.reserved[3])
-
-    def kernel_roofline(name, us, s_bytes):
-        """One kernel against the HBM roofline, both ways: `frac` / `frac_algorithmic` = SURVEY.md §8d's byte
-        model N (4K + S) over the measured duration; `frac_measured_traffic` = the HBM bytes the kernel really moved (PMC
-        FETCH_SIZE x 2 + WRITE_SIZE of the committed profile of this workload; list entries are 16-bit slots, so this is the
-        smaller figure wherever the lists dominate) over the same duration."""
-        algo = n * (4.0 * kbar + s_bytes)
-        traffic, src = committed_traffic(name, args.config, args.side) if not decomposed else (None, None)
-        ach = algo / (us * 1e-6) / 1e9
-        return {"bound": "hbm", "kernel": name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                "frac_algorithmic": ach / HBM_PEAK_GBS,
-                "frac_measured_traffic": None if traffic is None else traffic / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                "traffic": traffic, "traffic_source": src, "kernel_us": us, "algorithmic_bytes": algo, "mean_contacts": kbar}
-
-    roofline = kernel_roofline(kname, kernel_us, sbytes)
-    # the other kernels a step lives in (DFSPH: the divergence solve's two passes — 86 % of a settled step — and the list build)
-    others = {}
-    if cfg["solver"] == "dfsph":
-        for oid, oname, os_ in ((1, "k_divergence", 48.0), (6, "k_divergence_apply", 44.0), (4, "k_nbr_tile", 12.0)):
-            if oid == 4 and decomposed:
-                continue
-            try:
-                others[oname] = kernel_roofline(oname, w.time_kernel(oid, 30), os_)
-            except Exception as e:  # noqa: BLE001 - a timing aid must not cost the line
-                others[oname] = {"error": str(e)}
-    roofline["other_kernels"] = others
     spec_passes, disc_passes = int(w.counters.speculative_passes), int(w.counters.discarded_passes)
     div_cap = float(getattr(w.solver, "max_divergence_iter", 50))
 
-    # ---- what a user pays who looks at the particles after every step (the reference's API leaves positions / velocities on the
-    # host after `step`; testbed_plugin.rs:361-367 reads them each frame): the SAME warm-up + timed steps on a fresh world, with an
-    # asynchronous read-back of positions and velocities into pinned host arrays after every step, one step late
-    # (salva_hip_get_fluid_async / _wait_download).  Reported beside `value`, never as `value` (state resident: the contract).
-    with_download = None
-    if not decomposed and not args.no_download_leg and rank == 0:
-        try:
-            w = None  # (release the first world's device memory)
-            w2, handles2 = make_config_world(args.config, fluids, shell, local_rank)
-            for _ in range(args.warmup):  # (the warm-up steps read back too: the first read-back allocates the pinned arrays, 6-19 ms once)
-                w2.step(DT, GRAVITY)
-                w2.wait_download()
-                for hd in handles2:
-                    w2.download_async(hd)
-            w2.wait_download()
-            torch.cuda.synchronize()
-            td = time.perf_counter()
-            for _ in range(args.steps):
-                w2.step(DT, GRAVITY)
-                w2.wait_download()
-                for hd in handles2:
-                    w2.download_async(hd)
-            w2.wait_download()
-            torch.cuda.synchronize()
-            el2 = time.perf_counter() - td
-            with_download = {"value": n * args.steps / el2, "unit": "particle-steps/s", "ms_per_step": el2 / args.steps * 1e3,
-                             "what": "the same warm-up and timed steps on a fresh world, positions + velocities of every fluid read back after "
-                                     "every step: asynchronously, into pinned host arrays, overlapping the next step (one step late)",
-                             "bytes_per_step": int(24 * n)}
-            w = w2
-        except Exception as e:  # noqa: BLE001 - a reporting leg must not cost the line
-            with_download = {"error": str(e)}
+    # ---- --full only: the legs beyond the headline (each of them runs the GPU outside the timed steps)
+    roofline = with_download = at_8m = None
+    if args.full:
+        # ---- roofline of the dominant neighbour-sum kernel, timed live with HIP events on the world's own stream
+        kid, kname, sbytes = cfg["kernel"]
+        kernel_us = w.time_kernel(kid, 50)
 
-    # ---- the same kernel where the state does NOT fit the 256 MiB Infinity Cache: 200^3 = 8 x 10^6 particles (config 2 only, a few
-    # steps of free fall; about 5 s with the scene build).  At 10^6 the launch is ~3 rounds of resident tiles deep; at 8 x 10^6, 23.
-    at_8m = None
-    if not decomposed and args.config == 2 and args.side == 100 and not args.no_big_leg and rank == 0:
-        try:
-            w = None
-            fl8, sh8 = build_config(2, 200)
-            w8, h8 = make_config_world(2, fl8, sh8, local_rank)
-            for _ in range(4):
-                w8.step(DT, GRAVITY)
-            n8 = sum(len(p_) for p_, _ in fl8)
-            k8 = float(sum(w8.contact_counts(h).sum() + w8.contact_counts(h, True).sum() for h in h8)) / n8
-            us8 = w8.time_kernel(kid, 30)
-            algo8 = n8 * (4.0 * k8 + sbytes)
-            at_8m = {"kernel": kname, "particles": n8, "kernel_us": us8, "mean_contacts": k8, "algorithmic_bytes": algo8,
-                     "achieved": algo8 / (us8 * 1e-6) / 1e9, "frac": algo8 / (us8 * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                     "what": "the same kernel on a 200^3 block after 4 steps (free fall): state beyond the Infinity Cache"}
-            w8 = None
-        except Exception as e:  # noqa: BLE001
-            at_8m = {"error": str(e)}
-    roofline["at_8m"] = at_8m
+        def kernel_roofline(name, us, s_bytes):
+            """One kernel against the HBM roofline, both ways: `frac` / `frac_algorithmic` = SURVEY.md §8d's byte
+            model N (4K + S) over the measured duration; `frac_measured_traffic` = the HBM bytes the kernel really moved (PMC
+            FETCH_SIZE x 2 + WRITE_SIZE of the committed profile of this workload; list entries are 16-bit slots, so this is the
+            smaller figure wherever the lists dominate) over the same duration."""
+            algo = n * (4.0 * kbar + s_bytes)
+            traffic, src = committed_traffic(name, args.config, args.side) if not decomposed else (None, None)
+            ach = algo / (us * 1e-6) / 1e9
+            return {"bound": "hbm", "kernel": name, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                    "frac_algorithmic": ach / HBM_PEAK_GBS,
+                    "frac_measured_traffic": None if traffic is None else traffic / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                    "traffic": traffic, "traffic_source": src, "kernel_us": us, "algorithmic_bytes": algo, "mean_contacts": kbar}
+
+        roofline = kernel_roofline(kname, kernel_us, sbytes)
+        # the other kernels a step lives in (DFSPH: the divergence solve's two passes — 86 % of a settled step — and the list build)
+        others = {}
+        if cfg["solver"] == "dfsph":
+            for oid, oname, os_ in ((1, "k_divergence", 48.0), (6, "k_divergence_apply", 44.0), (4, "k_nbr_tile", 12.0)):
+                if oid == 4 and decomposed:
+                    continue
+                try:
+                    others[oname] = kernel_roofline(oname, w.time_kernel(oid, 30), os_)
+                except Exception as e:  # noqa: BLE001 - a timing aid must not cost the line
+                    others[oname] = {"error": str(e)}
+        roofline["other_kernels"] = others
+
+        # ---- what a user pays who looks at the particles after every step (the reference's API leaves positions / velocities on the
+        # host after `step`; testbed_plugin.rs:361-367 reads them each frame): the SAME warm-up + timed steps on a fresh world, with an
+        # asynchronous read-back of positions and velocities into pinned host arrays after every step, one step late
+        # (salva_hip_get_fluid_async / _wait_download).  Reported beside `value`, never as `value` (state resident: the contract).
+        if not decomposed and not args.no_download_leg and rank == 0:
+            try:
+                w = None  # (release the first world's device memory)
+                w2, handles2 = make_config_world(args.config, fluids, shell, local_rank)
+                for _ in range(args.warmup):  # (the warm-up steps read back too: the first read-back allocates the pinned arrays, 6-19 ms once)
+                    w2.step(DT, GRAVITY)
+                    w2.wait_download()
+                    for hd in handles2:
+                        w2.download_async(hd)
+                w2.wait_download()
+                torch.cuda.synchronize()
+                td = time.perf_counter()
+                for _ in range(args.steps):
+                    w2.step(DT, GRAVITY)
+                    w2.wait_download()
+                    for hd in handles2:
+                        w2.download_async(hd)
+                w2.wait_download()
+                torch.cuda.synchronize()
+                el2 = time.perf_counter() - td
+                with_download = {"value": n * args.steps / el2, "unit": "particle-steps/s", "ms_per_step": el2 / args.steps * 1e3,
+                                 "what": "the same warm-up and timed steps on a fresh world, positions + velocities of every fluid read back after "
+                                         "every step: asynchronously, into pinned host arrays, overlapping the next step (one step late)",
+                                 "bytes_per_step": int(24 * n)}
+                w = w2
+            except Exception as e:  # noqa: BLE001 - a reporting leg must not cost the line
+                with_download = {"error": str(e)}
+
+        # ---- the same kernel where the state does NOT fit the 256 MiB Infinity Cache: 200^3 = 8 x 10^6 particles (config 2 only, a few
+        # steps of free fall; about 5 s with the scene build).  At 10^6 the launch is ~3 rounds of resident tiles deep; at 8 x 10^6, 23.
+        if not decomposed and args.config == 2 and args.side == 100 and not args.no_big_leg and rank == 0:
+            try:
+                w = None
+                fl8, sh8 = build_config(2, 200)
+                w8, h8 = make_config_world(2, fl8, sh8, local_rank)
+                for _ in range(4):
+                    w8.step(DT, GRAVITY)
+                n8 = sum(len(p_) for p_, _ in fl8)
+                k8 = float(sum(w8.contact_counts(h).sum() + w8.contact_counts(h, True).sum() for h in h8)) / n8
+                us8 = w8.time_kernel(kid, 30)
+                algo8 = n8 * (4.0 * k8 + sbytes)
+                at_8m = {"kernel": kname, "particles": n8, "kernel_us": us8, "mean_contacts": k8, "algorithmic_bytes": algo8,
+                         "achieved": algo8 / (us8 * 1e-6) / 1e9, "frac": algo8 / (us8 * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                         "what": "the same kernel on a 200^3 block after 4 steps (free fall): state beyond the Infinity Cache"}
+                w8 = None
+            except Exception as e:  # noqa: BLE001
+                at_8m = {"error": str(e)}
+        roofline["at_8m"] = at_8m
 
     if rank == 0:
         # ---- the regimes the run went through (see the docstring): rates over the first 20 timed steps and over the timed
@@ -483,7 +537,7 @@ def main():
              "what": f"timed steps whose divergence solve used all {int(cap)} iterations"},
         }
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.config, args.side, args.steps, args.warmup, step_ms, args.cpu_budget)
         value = n * world * args.steps / elapsed
         out = {
@@ -500,6 +554,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": bool(args.full),  # false: roofline, with_download and cpu_baseline were not run (null)
             "config": {
                 "workload": f"BASELINE config {args.config if not decomposed else 5}: 3D {cfg['solver'].upper()} {n * world} fluid particles "
                             f"(+{nshell_total} boundary), {cfg['what']}, r=0.025 h=0.1 dt=1/200",

@@ -1,11 +1,17 @@
 #!/usr/bin/env python
-"""bench/rust_ref/check_against_reference.py [/root/reference] — does src/main.rs still name things salva3d has?
+"""bench/rust_ref/check_against_reference.py [REFERENCE_TREE | --index FILE] — does src/main.rs still name things salva3d has?
 
 The pinning kit has never met cargo (no Rust toolchain where it was written).  This script is the part of `cargo check` that can be
 done with a text search: every `use salva3d::path::{Items}` of main.rs must resolve to a `pub mod` chain under the reference's
 src/ (lib.rs:86-118) ending in a `pub struct / enum / trait / type / fn / use ... Item`, and every `LiquidWorld` / `Fluid` /
-`Boundary` method the runner calls must exist as `pub fn` in the file that defines the type.  Run by tests/test_host_logic.py when
-the reference tree is present (it is not on the GPU boxes)."""
+`Boundary` method the runner calls must exist as `pub fn` in the file that defines the type.
+
+The same resolution, done once over a whole reference tree, is kept as data in tests/golden/salva3d_api.json (every public item
+path the tree resolves, and the `pub fn` names of the three files above):
+  check_against_reference.py REFERENCE_TREE --write-index tests/golden/salva3d_api.json     re-make the index from a tree
+  check_against_reference.py --index tests/golden/salva3d_api.json                          check main.rs against the index
+tests/test_host_logic.py runs the second form, so the check needs nothing outside the repository."""
+import json
 import os
 import re
 import sys
@@ -65,26 +71,66 @@ def defines(file, item, src):
     return False
 
 
-def main():
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
-    src = os.path.join(ref, "src")
-    text = open(os.path.join(HERE, "src", "main.rs")).read()
-    bad = []
-    for path, item in uses(text):
+METHODS = {"liquid_world.rs": ["new", "step", "add_fluid", "add_boundary", "fluids", "boundaries"],
+           "object/fluid.rs": ["new", "num_particles"], "object/boundary.rs": ["new"]}
+
+
+def module_paths(src, path=()):
+    """Every module path reachable from lib.rs through `pub mod name;` declarations, the crate root [] first."""
+    f = module_file(src, list(path)) if path else os.path.join(src, "lib.rs")
+    if f is None:
+        return []
+    out = [list(path)]
+    for name in re.findall(r"^\s*pub\s+mod\s+(\w+)\s*;", open(f).read(), re.M):
+        out.extend(module_paths(src, tuple(path) + (name,)))
+    return out
+
+
+def make_index(src):
+    """The public API of a reference tree as data: every `a::b::Item` that `defines` resolves (candidates: every name declared
+    `pub struct / enum / trait / type / fn / const` anywhere in the tree), and the `pub fn` names of the files in METHODS."""
+    names = set()
+    for d, _, files in os.walk(src):
+        for fn in files:
+            if fn.endswith(".rs"):
+                names.update(re.findall(r"pub\s+(?:struct|enum|trait|type|fn|const)\s+(\w+)", open(os.path.join(d, fn)).read()))
+    items = set()
+    for path in module_paths(src):
         f = module_file(src, path) if path else os.path.join(src, "lib.rs")
-        if f is None or not defines(f, item, src):
-            bad.append("salva3d::" + "::".join(path + [item]))
-    methods = {"liquid_world.rs": ["new", "step", "add_fluid", "add_boundary", "fluids", "boundaries"],
-               "object/fluid.rs": ["new", "num_particles"], "object/boundary.rs": ["new"]}
-    for rel, names in methods.items():
-        t = open(os.path.join(src, rel)).read()
+        items.update("::".join(path + [n]) for n in names if defines(f, n, src))
+    methods = {rel: sorted(set(re.findall(r"pub\s+fn\s+(\w+)", open(os.path.join(src, rel)).read()))) for rel in METHODS}
+    return {"what": "public API of salva3d's src/: item paths and pub fn names (bench/rust_ref/check_against_reference.py --write-index)",
+            "items": sorted(items), "methods": methods}
+
+
+def main():
+    args = sys.argv[1:]
+    text = open(os.path.join(HERE, "src", "main.rs")).read()
+    if "--index" in args:
+        where = args[args.index("--index") + 1]
+        index = json.load(open(where))
+    elif args:
+        where = os.path.join(args[0], "src")
+        index = make_index(where)
+        if "--write-index" in args:
+            out = args[args.index("--write-index") + 1]
+            with open(out, "w") as fh:
+                json.dump(index, fh, indent=1)
+                fh.write("\n")
+            print(f"{out}: {len(index['items'])} item paths")
+    else:
+        print(__doc__)
+        return 2
+    items = set(index["items"])
+    bad = ["salva3d::" + "::".join(path + [item]) for path, item in uses(text) if "::".join(path + [item]) not in items]
+    for rel, names in METHODS.items():
         for n in names:
-            if re.search(r"\.%s\(|::%s\(" % (n, n), text) and not re.search(r"pub\s+fn\s+%s\b" % n, t):
+            if re.search(r"\.%s\(|::%s\(" % (n, n), text) and n not in index["methods"][rel]:
                 bad.append(f"{rel}: pub fn {n}")
     if bad:
         print("bench/rust_ref/src/main.rs names things the reference does not have:\n  " + "\n  ".join(bad))
         return 1
-    print(f"bench/rust_ref/src/main.rs: {len(uses(text))} imported items and the methods it calls exist in {src}")
+    print(f"bench/rust_ref/src/main.rs: {len(uses(text))} imported items and the methods it calls exist in {where}")
     return 0
 
 

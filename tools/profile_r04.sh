@@ -8,14 +8,14 @@ TAG=${1:-r04}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline $@"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline $@"
 cd $R && timeout 900 python bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $R/bench.py $ARGS > $OUT/trace.log 2>&1
 f=$(find $OUT/trace -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/trace_kernel_stats.csv
 find $OUT/trace -name "*kernel_trace.csv" -delete
 KRE='k_pred_density|k_divergence|k_pressure_apply|k_nbr_tile|k_density_alpha|k_xsph|k_iisph|k_akinci|k_tile|k_reorder'
-PARGS="--steps 6 --warmup 3 --no-cpu-baseline $@"
+PARGS="--full --steps 6 --warmup 3 --no-cpu-baseline $@"
 i=0
 for PMC in \
   "SQ_WAVES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" \
