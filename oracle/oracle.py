@@ -75,6 +75,11 @@ def lib(native: bool = False):
         L.so_h.restype = f64
         L.so_h.argtypes = [vp]
         L.so_set_timestep.argtypes = [vp, f32, f32]
+        L.so_get_timestep.argtypes = [vp, dp, dp]
+        L.so_num_fluids.restype = i32
+        L.so_num_fluids.argtypes = [vp]
+        L.so_num_boundaries.restype = i32
+        L.so_num_boundaries.argtypes = [vp]
         L.so_set_cfl.argtypes = [vp, i32, f32, i32, i32]
         L.so_get_substeps.restype = i32
         L.so_get_substeps.argtypes = [vp, C.POINTER(C.c_double), i32]
@@ -83,6 +88,8 @@ def lib(native: bool = False):
         L.so_add_force.argtypes = [vp, i32, i32, fp, i32]
         L.so_set_fluid_velocities.argtypes = [vp, i32, fp]
         L.so_set_fluid_volumes.argtypes = [vp, i32, fp]
+        L.so_set_fluid_vec.argtypes = [vp, i32, i32, fp]
+        L.so_set_fluid_scalar.argtypes = [vp, i32, i32, fp]
         L.so_step.argtypes = [vp, f32, f32, f32, f32, C.POINTER(Stats)]
         L.so_fluid_len.restype = u64
         L.so_fluid_len.argtypes = [vp, i32]
@@ -168,6 +175,18 @@ class OracleWorld:
 
     def set_timestep(self, dt: float, inv_dt: float):
         self._L.so_set_timestep(self._h, dt, inv_dt)
+
+    def timestep(self):
+        """TimestepManager::{dt, inv_dt} as the last step left them."""
+        dt, inv_dt = C.c_double(0), C.c_double(0)
+        self._L.so_get_timestep(self._h, C.byref(dt), C.byref(inv_dt))
+        return dt.value, inv_dt.value
+
+    def num_fluids(self) -> int:
+        return self._L.so_num_fluids(self._h)
+
+    def num_boundaries(self) -> int:
+        return self._L.so_num_boundaries(self._h)
 
     def set_cfl(self, mode: int, cfl_coeff: float = 0.4, min_substeps: int = 1, max_substeps: int = 10):
         """Opt-in CFL sub-stepping: timestep_manager.rs:36-46 (`max_substep`) with the clamp the reference left commented out at
@@ -343,6 +362,55 @@ class OracleWorld:
         v = _f32(volumes)
         assert len(v) == self.fluid_len(fluid)
         self._L.so_set_fluid_volumes(self._h, fluid, _fp(v))
+
+    def set_fluid_vec(self, fluid, field, values):
+        """Write positions / velocities / velocity_changes of `fluid` (rounded to f32 first, like a device checkpoint holds them)."""
+        assert field in ("positions", "velocities", "velocity_changes"), field
+        v = _f32(values, 3)
+        assert len(v) == self.fluid_len(fluid)
+        self._L.so_set_fluid_vec(self._h, fluid, self.VEC_FIELDS[field], _fp(v))
+
+    def set_fluid_scalar(self, fluid, field, values):
+        """Write volumes / IISPH pressures of `fluid`."""
+        assert field in ("volumes", "pressures"), field
+        v = _f32(values).reshape(-1)
+        assert len(v) == self.fluid_len(fluid)
+        self._L.so_set_fluid_scalar(self._h, fluid, self.SCALAR_FIELDS[field], _fp(v))
+
+    def checkpoint(self) -> dict:
+        """The state a step carries over, in the layout of `salva_amd.LiquidWorld.checkpoint()` (f32 arrays; exact for the
+        f32 build)."""
+        nf, nb = self.num_fluids(), self.num_boundaries()
+        st = {"timestep": np.array(self.timestep(), np.float32), "nfluids": np.array(nf), "nboundaries": np.array(nb)}
+        for k in range(nf):
+            for field in ("positions", "velocities", "velocity_changes"):
+                st[f"fluid{k}_{field}"] = self.fluid_vec(k, field).astype(np.float32)
+            for field in ("volumes", "pressures"):
+                st[f"fluid{k}_{field}"] = self.fluid_scalar(k, field).astype(np.float32)
+        for k in range(nb):
+            st[f"boundary{k}_positions"] = self.boundary_vec(k, "positions").astype(np.float32)
+            st[f"boundary{k}_velocities"] = self.boundary_vec(k, "velocities").astype(np.float32)
+        return st
+
+    def restore(self, st: dict):
+        """Load a `checkpoint()` dict (this class's or `LiquidWorld.checkpoint()`'s) into a world built with the same fluids /
+        boundaries: positions, velocities, volumes, velocity_changes and IISPH pressures of every fluid, positions and velocities
+        of every boundary, and the TimestepManager's dt / inv_dt.  Forces, groups and solver parameters stay what they are.
+        Particle counts must match the world's."""
+        nf, nb = self.num_fluids(), self.num_boundaries()
+        if int(st["nfluids"]) != nf or int(st["nboundaries"]) != nb:
+            raise ValueError("the checkpoint was taken from a world with different fluids / boundaries")
+        for k in range(nf):
+            if len(st[f"fluid{k}_positions"]) != self.fluid_len(k):
+                raise ValueError(f"fluid {k}: {len(st[f'fluid{k}_positions'])} particles in the checkpoint, {self.fluid_len(k)} here")
+            for field in ("positions", "velocities", "velocity_changes"):
+                self.set_fluid_vec(k, field, st[f"fluid{k}_{field}"])
+            for field in ("volumes", "pressures"):
+                self.set_fluid_scalar(k, field, st[f"fluid{k}_{field}"])
+        for k in range(nb):
+            self.set_boundary_particles(k, st[f"boundary{k}_positions"], st[f"boundary{k}_velocities"])
+        t = np.asarray(st["timestep"], np.float32)
+        self.set_timestep(float(t[0]), float(t[1]))
 
     def step(self, dt, gravity=(0.0, -9.81, 0.0)) -> Stats:
         self._L.so_step(self._h, dt, gravity[0], gravity[1], gravity[2], C.byref(self.last_stats))

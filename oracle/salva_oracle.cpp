@@ -1902,6 +1902,26 @@ static void copy_v3(const std::vector<V3<R>>& v, double* out) {
 template <typename R>
 static void copy_s(const std::vector<R>& v, double* out) { for (size_t i = 0; i < v.size(); ++i) out[i] = v[i]; }
 
+// Restore of a checkpoint (LiquidWorld::checkpoint): the per-fluid state a step carries over.  The solver's buffers are sized
+// first (init_with_fluids, what the next step would do) so that a world that never stepped can take them.
+// field (as so_get_fluid_vec): 0 positions, 1 velocities, 2 velocity_changes
+template <typename R>
+static void set_fluid_vec_t(World<R>& w, int fluid, int field, const float* v) {
+    w.init_with_fluids();
+    Fluid<R>& f = w.fluids[fluid];
+    std::vector<V3<R>>* dst = field == 0 ? &f.positions : field == 1 ? &f.velocities : field == 2 ? &w.velocity_changes[fluid] : nullptr;
+    if (!dst) return;
+    for (size_t i = 0; i < f.n(); ++i) (*dst)[i] = V3<R>((R)v[3 * i], (R)v[3 * i + 1], (R)v[3 * i + 2]);
+}
+// field (as so_get_fluid_scalar): 4 volumes, 6 IISPH pressures (the Jacobi iteration's starting point)
+template <typename R>
+static void set_fluid_scalar_t(World<R>& w, int fluid, int field, const float* v) {
+    w.init_with_fluids();
+    Fluid<R>& f = w.fluids[fluid];
+    std::vector<R>* dst = field == 4 ? &f.volumes : field == 6 ? &w.pressures[fluid] : nullptr;
+    if (!dst) return;
+    for (size_t i = 0; i < f.n(); ++i) (*dst)[i] = (R)v[i];
+}
 extern "C" {
 
 struct so_stats {
@@ -1951,6 +1971,12 @@ int so_get_substeps(void* p, double* out, int cap) {
     return n;
 }
 double so_h(void* p) { Handle* h = (Handle*)p; double r = 0; DISPATCH(h, r = w.h, r = w.h); return r; }
+void so_get_timestep(void* p, double* dt, double* inv_dt) {
+    Handle* h = (Handle*)p;
+    DISPATCH(h, { *dt = w.dt; *inv_dt = w.inv_dt; }, { *dt = w.dt; *inv_dt = w.inv_dt; });
+}
+int so_num_fluids(void* p) { Handle* h = (Handle*)p; int r = 0; DISPATCH(h, r = (int)w.fluids.size(), r = (int)w.fluids.size()); return r; }
+int so_num_boundaries(void* p) { Handle* h = (Handle*)p; int r = 0; DISPATCH(h, r = (int)w.boundaries.size(), r = (int)w.boundaries.size()); return r; }
 
 int so_add_fluid(void* p, uint64_t n, const float* pos, const float* vel, float density0, uint32_t mem, uint32_t filt) {
     Handle* h = (Handle*)p; int r = -1;
@@ -1983,6 +2009,15 @@ void so_set_fluid_volumes(void* p, int fluid, const float* vol) {
     DISPATCH(h,
         { auto& f = w.fluids[fluid]; for (size_t i = 0; i < f.n(); ++i) f.volumes[i] = vol[i]; },
         { auto& f = w.fluids[fluid]; for (size_t i = 0; i < f.n(); ++i) f.volumes[i] = (double)vol[i]; });
+}
+// Restore of a checkpoint (LiquidWorld::checkpoint): set_fluid_vec_t / set_fluid_scalar_t above.
+void so_set_fluid_vec(void* p, int fluid, int field, const float* v) {
+    Handle* h = (Handle*)p;
+    DISPATCH(h, set_fluid_vec_t(w, fluid, field, v), set_fluid_vec_t(w, fluid, field, v));
+}
+void so_set_fluid_scalar(void* p, int fluid, int field, const float* v) {
+    Handle* h = (Handle*)p;
+    DISPATCH(h, set_fluid_scalar_t(w, fluid, field, v), set_fluid_scalar_t(w, fluid, field, v));
 }
 
 void so_step(void* p, float dt, float gx, float gy, float gz, so_stats* out) {

@@ -1833,9 +1833,10 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
         lds.max_sum = spec ? 0u : tt.max_sum;  // (a speculative pass knows the two maxima only: TileLds::sum_slots falls back to their sum)
         lds.max_raw = spec ? 0u : tt.max_raw;
         if (tile_trace)
-            fprintf(stderr, "salva_hip tiles: nonempty %u max_s %u max_sb %u max_sum %u max_raw %u heavy %u light %u tiny %u split_s %u mass_uniform %g | chained %llu breaks %llu pregrid %llu dropped %llu\n",
+            fprintf(stderr, "salva_hip tiles: nonempty %u max_s %u max_sb %u max_sum %u max_raw %u heavy %u light %u tiny %u split_s %u mass_uniform %g | chained %llu breaks %llu pregrid %llu dropped %llu | fold %u %u %u\n",
                     tt.nonempty, tt.max_s, tt.max_sb, tt.max_sum, tt.max_raw, tt.heavy, tt.nlight, tt.ntiny, split_s_cur, (double)mass_uniform,
-                    (unsigned long long)chain_steps, (unsigned long long)chain_breaks, (unsigned long long)pre_adopted, (unsigned long long)pre_dropped);
+                    (unsigned long long)chain_steps, (unsigned long long)chain_breaks, (unsigned long long)pre_adopted, (unsigned long long)pre_dropped,
+                    gf.mask[0] + 1u, gf.mask[1] + 1u, gf.mask[2] + 1u);  // fold: period of each axis in cells, 0 = not folded
         if (!spec) {
             // next step's splitting: on while the over-full tiles are few (each costs a second workgroup and a third more staging, and
             // buys every other tile of every pass its third resident neighbour); off again when they are the rule — a uniformly

@@ -1,6 +1,8 @@
 """Shared scene construction for the parity tests: the same inputs go to the CPU oracle and to the HIP path."""
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from oracle import oracle as O
@@ -126,3 +128,15 @@ def max_norm_diff(a, b):
     a = np.asarray(a, np.float64).reshape(-1, 3)
     b = np.asarray(b, np.float64).reshape(-1, 3)
     return float(np.max(np.linalg.norm(a - b, axis=1))) if a.size else 0.0
+
+
+def host_threads():
+    """CPUs this process may use: os.cpu_count() capped by the cgroup's CPU quota (the oracle's OpenMP thread count)."""
+    n = os.cpu_count() or 1
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    return n

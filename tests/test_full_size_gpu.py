@@ -4,27 +4,14 @@ At these sizes the oracle still finishes a step in seconds on the box's host cor
 directly (contact counts exact, densities, positions, iteration counts); on top of that the size-independent
 properties: sum of list lengths == reported contacts, run-to-run bitwise determinism, linear momentum of the symmetric
 force passes.  bench.py measures config 2; configs 3 and 4 are parity cases only (their timings are in DESIGN.md)."""
-import os
-
 import numpy as np
 import pytest
 
-from parity import DT, GRAVITY, Scene, max_norm_diff, rel_err
+from parity import DT, GRAVITY, Scene, host_threads, max_norm_diff, rel_err
 from salva_amd import scenes
 
 pytestmark = pytest.mark.gpu
 R = 0.025
-
-
-def host_threads():
-    n = os.cpu_count() or 1
-    try:
-        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()
-        if quota != "max":
-            n = min(n, max(1, int(quota) // int(period)))
-    except (OSError, ValueError):
-        pass
-    return n
 
 
 def check_against_oracle(scene, nsteps, gravity, pos_tol_r, label, noise_floor=False):

@@ -35,8 +35,8 @@ def f32(x):
 TOL_X, TOL_V, TOL_RHO = 5e-6, 2e-5, 8e-6
 
 
-@pytest.mark.parametrize("solver", ["dfsph", "iisph"])
-def test_two_fluid_scene_device_against_the_numpy_reading(hip_lib, solver):
+def two_fluid_worlds(solver):
+    """The scene on the device and in the reading: (device world, lower fluid, upper fluid, DenseWorld)."""
     n = 5
     d = 2 * R
     lower = (scenes.jitter(scenes.cube_fluid_positions(n, n, n, R), 0.12 * R, 21) * 0.9).astype(np.float32)
@@ -78,6 +78,12 @@ def test_two_fluid_scene_device_against_the_numpy_reading(hip_lib, solver):
     dw.add_force("he2014", 0.5, f32(0.3), fluid=1)
     dw.add_boundary(floor, *G_FLOOR)
     dw.add_boundary(wall, *G_WALL)
+    return w, fa, fb, dw
+
+
+@pytest.mark.parametrize("solver", ["dfsph", "iisph"])
+def test_two_fluid_scene_device_against_the_numpy_reading(hip_lib, solver):
+    w, fa, fb, dw = two_fluid_worlds(solver)
     r0, r1 = dw.fluid_rows(0), dw.fluid_rows(1)
     h = dw.h
     worst = {"dx": 0.0, "dv": 0.0, "rho": 0.0}
