@@ -11,4 +11,4 @@ mod liquid_world;
 pub mod coupling;
 
 pub use dist::{Comm, OwnedParticles};
-pub use liquid_world::{Error, GpuPressureSolver, LiquidWorld};
+pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};

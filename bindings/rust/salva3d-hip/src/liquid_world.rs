@@ -62,6 +62,43 @@ impl GpuKernel for salva3d::kernel::ViscosityKernel {
     const KIND: i32 = ffi::SALVA_HIP_KERNEL_VISCOSITY;
 }
 
+/// `Becker2009Elasticity::new(young_modulus, poisson_ratio, nonlinear_strain)` for a device world
+/// (solver/elasticity/becker2009_elasticity.rs:66-82).  salva3d's own struct keeps only the derived coefficients, privately, so
+/// the wrapper carries the constructor's arguments itself; the force runs on the device (`SALVA_HIP_FORCE_BECKER2009`) and its
+/// host `solve` is never called.  `KD` / `KG` are the force's `KernelDensity` / `KernelGradient` type parameters.
+pub struct Becker2009Elasticity<KD: GpuKernel = salva3d::kernel::CubicSplineKernel, KG: GpuKernel = salva3d::kernel::CubicSplineKernel> {
+    pub young_modulus: Real,
+    pub poisson_ratio: Real,
+    pub nonlinear_strain: bool,
+    phantom: std::marker::PhantomData<(KD, KG)>,
+}
+
+impl<KD: GpuKernel, KG: GpuKernel> Becker2009Elasticity<KD, KG> {
+    pub fn new(young_modulus: Real, poisson_ratio: Real, nonlinear_strain: bool) -> Self {
+        Self { young_modulus, poisson_ratio, nonlinear_strain, phantom: std::marker::PhantomData }
+    }
+}
+
+impl<KD: GpuKernel, KG: GpuKernel> salva3d::solver::NonPressureForce for Becker2009Elasticity<KD, KG> {
+    fn solve(
+        &mut self,
+        _timestep: &salva3d::TimestepManager,
+        _kernel_radius: Real,
+        _fluid_fluid_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid_boundaries_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid: &mut Fluid,
+        _boundaries: &[Boundary],
+        _densities: &[Real],
+    ) {
+        unreachable!("Becker2009Elasticity runs on the device (LiquidWorld::step)")
+    }
+
+    fn gpu_desc(&self) -> Option<(i32, [f32; 7])> {
+        let nl = if self.nonlinear_strain { 1.0 } else { 0.0 };
+        Some((ffi::SALVA_HIP_FORCE_BECKER2009, [self.young_modulus, self.poisson_ratio, nl, KD::KIND as f32, KG::KIND as f32, 0.0, 0.0]))
+    }
+}
+
 impl<KD: GpuKernel, KG: GpuKernel> GpuPressureSolver for DFSPHSolver<KD, KG> {
     fn params(&self, particle_radius: Real, smoothing_factor: Real) -> ffi::SalvaHipParams {
         let mut p = default_params();

@@ -79,8 +79,10 @@ enum {
     SALVA_HIP_FORCE_DFSPH_VISCOSITY = 4, /* solver::DFSPHViscosity::new(viscosity_coefficient), dfsph_viscosity.rs:102-118 */
     SALVA_HIP_FORCE_HE2014 = 5,      /* solver::He2014SurfaceTension::new(fluid_tension, boundary_tension), he2014_surface_tension.rs:21-29 */
     SALVA_HIP_FORCE_WCSPH_TENSION = 6, /* solver::WCSPHSurfaceTension::new(fluid_tension, boundary_tension), wcsph_surface_tension.rs:22-28 */
-    SALVA_HIP_FORCE_CUSTOM = 7       /* any other `impl NonPressureForce` (nonpressure_force.rs:10-30): runs on the host through
+    SALVA_HIP_FORCE_CUSTOM = 7,      /* any other `impl NonPressureForce` (nonpressure_force.rs:10-30): runs on the host through
                                         the callback of salva_hip_set_force_callback, at its place in the list */
+    SALVA_HIP_FORCE_BECKER2009 = 8   /* solver::Becker2009Elasticity::new(young_modulus, poisson_ratio, nonlinear_strain),
+                                        becker2009_elasticity.rs:66-82: corotated SPH elasticity with a rest state of its own */
 };
 typedef struct SalvaHipForceDesc {
     int32_t kind;
@@ -91,7 +93,12 @@ typedef struct SalvaHipForceDesc {
      *                  p[3] max_viscosity_error (0.01)          — the pub fields of DFSPHViscosity, dfsph_viscosity.rs:89-99
      * HE2014:     p[0] fluid_tension_coefficient, p[1] boundary_tension_coefficient
      * WCSPH_TENSION: p[0] fluid_tension_coefficient, p[1] boundary_tension_coefficient — must be 0: the reference's boundary
-     *                  loop (wcsph_surface_tension.rs:66-83) indexes the boundaries with fluid-fluid contacts and panics */
+     *                  loop (wcsph_surface_tension.rs:66-83) indexes the boundaries with fluid-fluid contacts and panics
+     * BECKER2009: p[0] young_modulus, p[1] poisson_ratio, p[2] nonlinear_strain (0 / 1), p[3] kernel_density, p[4] kernel_gradient
+     *                  (SALVA_HIP_KERNEL_*, 0 = CubicSplineKernel: the force's own type parameters).  The entry keeps its state
+     *                  (rest positions, rest lists, volumes0, rotations) across salva_hip_set_fluid_forces calls that give entry k the
+     *                  same kind and bit-identical p[]; any other entry k starts empty.  Not available in decomposed worlds
+     *                  (salva_hip_set_domain): the rest lists cross slabs. */
     float p[7];
 } SalvaHipForceDesc;
 
@@ -317,7 +324,10 @@ float salva_hip_time_pred_density(SalvaHipWorld* world, int32_t reps);
 /* The same for the other neighbour-sum kernels bench.py reports a roofline for: `kernel` = 0 k_pred_density (DFSPH, N (4K + 52)
  * algorithmic bytes), 1 k_divergence (N (4K + 48)), 2 k_iisph_next_pressure (IISPH, N (4K + 60)), 3 k_iisph_dij_pj (N (4K + 36))
  * — SURVEY.md §8d; 4 k_nbr_tile (the neighbour-list build, N (12 + 4K)), 6 k_divergence_apply (DFSPH, N (4K + 44); runs on a copy
- * of w).  The IISPH kernels rewrite scratch only (next pressures into the spare buffer). */
+ * of w).  The IISPH kernels rewrite scratch only (next pressures into the spare buffer).  7 and 8: the rotation + stress pass and
+ * the force pass of the first Becker2009Elasticity entry (N_e (4K_e + 164) and N_e (4K_e + 148) + N 28; the
+ * rotation pass writes copies of the stresses and gradients, the force pass adds to a copy of the accelerations: the state keeps what
+ * the step computed). */
 float salva_hip_time_kernel(SalvaHipWorld* world, int32_t kernel, int32_t reps);
 /* `world.counters` after the last step — counters/mod.rs:17-72 */
 int salva_hip_get_counters(const SalvaHipWorld* world, SalvaHipCounters* out);
@@ -567,6 +577,25 @@ int64_t salva_hip_get_fluid_contacts(SalvaHipWorld* world, uint32_t slot, int32_
 /* Iterations and last average error of an iterative NonPressureForce (DFSPHViscosity's solve loop, dfsph_viscosity.rs:307-323)
  * in the last step; 0 / 0 for the other kinds.  `force` indexes the list given to salva_hip_set_fluid_forces. */
 int salva_hip_get_force_stats(SalvaHipWorld* world, uint32_t slot, uint32_t force, int32_t* iters, float* error);
+
+/* The state of the Becker2009Elasticity entry `force` of fluid `slot` (becker2009_elasticity.rs:43-56), in the fluid's host order:
+ * positions0 (3 n), volumes0 (n), rotations (9 n, row-major), stress (6 n: xx, yy, zz, xy, xz, yz) and deformation_gradient_tr
+ * (9 n, row-major) after the last step.  `n` is the state's own particle count (salva_hip_get_elasticity_contacts): the fluid's,
+ * except between a change of that count and the next step, which re-initialises the state from its old length (the reference's
+ * `resize`).  A NULL pointer skips that field; n = 0 only sizes.  Returns the number of rest contacts (self pairs included), 0 when
+ * the entry has no state yet, negative on error.  For parity tests and checkpoints: the reference keeps this state private. */
+int64_t salva_hip_get_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, float* positions0_xyz,
+                                       float* volumes0, float* rotations9, float* stress6, float* grad_tr9);
+/* Replaces that state with one of `n` particles (NULL leaves a field as it is; positions0 is required when the state is new or
+ * changes length, the other fields then start as zero / identity).  The rest lists are rebuilt from positions0 at once; volumes0 is
+ * taken as given.  An `n` other than the fluid's count makes the next step re-initialise from it, as after a count change. */
+int salva_hip_set_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, const float* positions0_xyz,
+                                   const float* volumes0, const float* rotations9);
+/* The rest lists of that entry (contacts0, built by init from positions0) as CSR in host order: offsets (n0 + 1 entries) and the
+ * neighbour index j of each contact, rows ascending in j, self pairs included.  Writes the state's particle count to *n0 (0: no
+ * state yet); returns the number of contacts, writing offsets / j only when `capacity` holds them all (call with 0 to size). */
+int64_t salva_hip_get_elasticity_contacts(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets,
+                                          uint32_t* j, uint64_t capacity);
 
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);

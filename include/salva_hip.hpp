@@ -7,6 +7,7 @@
 //   salva::InteractionGroups        src/object/interaction_groups.rs:6-79
 //   salva::DFSPHSolver/IISPHSolver  src/solver/pressure/dfsph_solver.rs:21-70, iisph_solver.rs:21-64 (pub tuning fields)
 //   salva::XSPHViscosity / ArtificialViscosity / Akinci2013SurfaceTension   src/solver/{viscosity,surface_tension}/*.rs
+//   salva::Becker2009Elasticity     src/solver/elasticity/becker2009_elasticity.rs
 //
 // `Fluid`'s pub fields stay plain std::vector members the caller may edit between steps (faucet3.rs:69-104,
 // heightfield3.rs:40); `LiquidWorld::step` uploads what changed (call `mark_dirty()` after in-place edits of
@@ -121,6 +122,25 @@ struct CubicSplineKernel { static constexpr int kind = SALVA_HIP_KERNEL_CUBIC_SP
 struct Poly6Kernel { static constexpr int kind = SALVA_HIP_KERNEL_POLY6; };
 struct SpikyKernel { static constexpr int kind = SALVA_HIP_KERNEL_SPIKY; };
 struct ViscosityKernel { static constexpr int kind = SALVA_HIP_KERNEL_VISCOSITY; };
+// solver::Becker2009Elasticity (elasticity/becker2009_elasticity.rs:39-82): new(young_modulus, poisson_ratio, nonlinear_strain); the
+// force's own KernelDensity / KernelGradient are the fields below (Becker2009ElasticityT for the type-parameter spelling)
+struct Becker2009Elasticity : NonPressureForce {
+    Real young_modulus, poisson_ratio;
+    bool nonlinear_strain;
+    int kernel_density = SALVA_HIP_KERNEL_CUBIC_SPLINE, kernel_gradient = SALVA_HIP_KERNEL_CUBIC_SPLINE;
+    Becker2009Elasticity(Real e, Real nu, bool nonlinear) : young_modulus(e), poisson_ratio(nu), nonlinear_strain(nonlinear) {}
+    SalvaHipForceDesc desc() const override {
+        SalvaHipForceDesc d{SALVA_HIP_FORCE_BECKER2009, {young_modulus, poisson_ratio, nonlinear_strain ? 1.0f : 0.0f,
+                                                          (Real)kernel_density, (Real)kernel_gradient}};
+        return d;
+    }
+};
+template <class KernelDensity = CubicSplineKernel, class KernelGradient = CubicSplineKernel>
+struct Becker2009ElasticityT : Becker2009Elasticity {
+    Becker2009ElasticityT(Real e, Real nu, bool nonlinear) : Becker2009Elasticity(e, nu, nonlinear) {
+        kernel_density = KernelDensity::kind; kernel_gradient = KernelGradient::kind;
+    }
+};
 template <class KernelDensity = CubicSplineKernel, class KernelGradient = CubicSplineKernel>
 struct DFSPHSolverT : PressureSolver {
     DFSPHSolverT() { kind = SALVA_HIP_SOLVER_DFSPH; kernel_density = KernelDensity::kind; kernel_gradient = KernelGradient::kind; }

@@ -8,6 +8,7 @@ from . import coupling, dist, scenes  # noqa: F401
 from .world import (  # noqa: F401
     Akinci2013SurfaceTension,
     ArtificialViscosity,
+    Becker2009Elasticity,
     Boundary,
     Counters,
     CubicSplineKernel,
@@ -27,7 +28,7 @@ from .world import (  # noqa: F401
 )
 
 __all__ = [
-    "Akinci2013SurfaceTension", "ArtificialViscosity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "Fluid", "He2014SurfaceTension", "IISPHSolver",
+    "Akinci2013SurfaceTension", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "Fluid", "He2014SurfaceTension", "IISPHSolver",
     "InteractionGroups", "LiquidWorld", "NonPressureForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "dist", "scenes",
 ]
 

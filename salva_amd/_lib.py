@@ -17,7 +17,8 @@ if os.environ.get("SALVA_HIP_LIB_VARIANT"):  # kernel experiments only (tools/va
 
 OK, E_HIP, E_INVALID, E_NUMERIC, E_CAPACITY = 0, -1, -2, -3, -4
 SOLVER_DFSPH, SOLVER_IISPH = 0, 1
-FORCE_XSPH, FORCE_ARTIFICIAL, FORCE_AKINCI2013, FORCE_DFSPH_VISCOSITY, FORCE_HE2014, FORCE_WCSPH_TENSION, FORCE_CUSTOM = 1, 2, 3, 4, 5, 6, 7
+(FORCE_XSPH, FORCE_ARTIFICIAL, FORCE_AKINCI2013, FORCE_DFSPH_VISCOSITY, FORCE_HE2014, FORCE_WCSPH_TENSION, FORCE_CUSTOM,
+ FORCE_BECKER2009) = 1, 2, 3, 4, 5, 6, 7, 8
 DIRTY_POSITIONS, DIRTY_VELOCITIES, DIRTY_VOLUMES, DIRTY_ACCELERATIONS, DIRTY_ALL = 1, 2, 4, 8, 15
 (FIELD_DENSITY, FIELD_ALPHA, FIELD_NUM_FLUID_CONTACTS, FIELD_NUM_BOUNDARY_CONTACTS, FIELD_VELOCITY_CHANGE,
  FIELD_PRESSURE, FIELD_VOLUME, FIELD_ACCELERATION) = range(8)
@@ -43,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_set_cfl", "salva_hip_get_substeps", "salva_hip_particles_intersecting_host_shape",
     "salva_hip_set_coupling_callback",
     "salva_hip_get_dist_timing", "salva_hip_local_len", "salva_hip_get_local", "salva_hip_get_local_contacts", "salva_hip_force_add_local_accelerations",
+    "salva_hip_get_elasticity_state", "salva_hip_set_elasticity_state", "salva_hip_get_elasticity_contacts",
 ]
 
 
@@ -270,6 +272,11 @@ def lib():
     L.salva_hip_get_fluid_contacts.argtypes = [vp, u32, i32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), u64]
     L.salva_hip_get_fluid_contacts.restype = C.c_int64
     L.salva_hip_get_force_stats.argtypes = [vp, u32, u32, C.POINTER(i32), fp]
+    L.salva_hip_get_elasticity_state.argtypes = [vp, u32, u32, u64, fp, fp, fp, fp, fp]
+    L.salva_hip_get_elasticity_state.restype = C.c_int64
+    L.salva_hip_set_elasticity_state.argtypes = [vp, u32, u32, u64, fp, fp, fp]
+    L.salva_hip_get_elasticity_contacts.argtypes = [vp, u32, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), u64]
+    L.salva_hip_get_elasticity_contacts.restype = C.c_int64
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

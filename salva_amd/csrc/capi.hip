@@ -687,6 +687,37 @@ int salva_hip_get_force_stats(SalvaHipWorld* world, uint32_t slot, uint32_t forc
     });
 }
 
+int64_t salva_hip_get_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, float* positions0_xyz,
+                                       float* volumes0, float* rotations9, float* stress6, float* grad_tr9) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        r = (int64_t)world->w->get_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9, stress6, grad_tr9);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int salva_hip_set_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, const float* positions0_xyz,
+                                   const float* volumes0, const float* rotations9) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        world->w->set_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9);
+        return SALVA_HIP_OK;
+    });
+}
+
+int64_t salva_hip_get_elasticity_contacts(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets,
+                                          uint32_t* j, uint64_t capacity) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        r = (int64_t)world->w->get_elasticity_contacts(slot, force, n0, offsets, j, capacity);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -12,6 +12,7 @@
 #include "comm.h"
 #include "dist.h"
 #include "kernels.h"
+#include "elastic.h"
 
 namespace salva {
 
@@ -25,6 +26,9 @@ struct FluidSlot {
     std::vector<SalvaHipForceDesc> forces;
     std::vector<uint32_t> force_iters;  // iterative forces (DFSPHViscosity): iterations / last error of the last step
     std::vector<float> force_errs;
+    // SALVA_HIP_FORCE_BECKER2009 entries: their state, by force index (nullptr for the other kinds).  Shared pointers, so that the
+    // state moves with the fluid in remove_fluid's swap-remove.
+    std::vector<std::shared_ptr<ElasticState>> elastic;
 };
 struct BoundarySlot {
     uint64_t n = 0;
@@ -76,6 +80,12 @@ class World {
     void map_query_hits(std::vector<uint64_t>& keys, uint32_t* kinds, uint32_t* slots, uint32_t* indices);
     void get_fluid(uint32_t slot, float* pos, float* vel);
     void get_force_stats(uint32_t slot, uint32_t force, int32_t* iters, float* err);
+    // Becker2009Elasticity's state in host order (elastic.h); the getter returns the rest contact count (0: no state yet)
+    uint64_t get_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, float* positions0, float* volumes0, float* rotations,
+                                  float* stress, float* grad_tr);
+    void set_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, const float* positions0, const float* volumes0,
+                              const float* rotations);
+    uint64_t get_elasticity_contacts(uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets, uint32_t* j, uint64_t capacity);
     uint64_t get_fluid_contacts(uint32_t slot, int boundary, uint64_t* offsets, uint32_t* j_model, uint32_t* j, uint64_t capacity);
     void get_fluid_field(uint32_t slot, int field, float* out);
     void get_boundary(uint32_t slot, float* volumes, float* forces);
@@ -177,6 +187,11 @@ class World {
     bool spec_apply_off = false;  // SALVA_HIP_NO_SPEC_APPLY (A/B, tests)
     void wait_stream();  // low-latency wait for the world's stream (spins on an event)
     void run_forces(const StepCtx& c);
+    void run_elasticity(const StepCtx& c, uint32_t slot, uint32_t force);
+    ElasticState& elastic_state(uint32_t slot, uint32_t force);
+    bool elastic_stale() const;  // some Becker2009Elasticity entry (re)builds its rest state in the next step
+    bool has_elastic() const;
+    void commit_elastic();
     void dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, int resume = 0);  // dt: in = the step, out = the substep advanced by
     void iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st);
     int substep(float& dt, const float g[3], SalvaHipStepStats& st);  // one pass of the reference's substep loop (liquid_world.rs:85-147)

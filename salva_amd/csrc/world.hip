@@ -460,8 +460,16 @@ uint64_t World::delete_particles(uint32_t slot, const uint8_t* mask) {
 void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
     if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
     for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_CUSTOM)
+        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_BECKER2009)
             throw HipError(SALVA_HIP_E_INVALID, "unknown non-pressure force kind (only built-ins run on the device)");
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009) {
+            if (comm)  // the rest lists cross slabs and have no ghost protocol
+                throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity is not available in a decomposed world (salva_hip_set_domain)");
+            for (int q = 3; q < 5; ++q)
+                if (!(f[k].p[q] == 0.0f || f[k].p[q] == 1.0f || f[k].p[q] == 2.0f || f[k].p[q] == 3.0f))
+                    throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity: p[3] / p[4] must be a SALVA_HIP_KERNEL_* kind");
+        }
     for (uint32_t k = 0; k < nf; ++k)
         if (f[k].kind == SALVA_HIP_FORCE_DFSPH_VISCOSITY && !(f[k].p[0] >= 0.0f && f[k].p[0] <= 1.0f))
             throw HipError(SALVA_HIP_E_INVALID, "The viscosity coefficient must be between 0.0 and 1.0.");  // dfsph_viscosity.rs:104-108
@@ -469,7 +477,16 @@ void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t
         if (f[k].kind == SALVA_HIP_FORCE_WCSPH_TENSION && f[k].p[1] != 0.0f)
             // wcsph_surface_tension.rs:66-83 walks the fluid-fluid contacts while indexing the boundaries: it panics
             throw HipError(SALVA_HIP_E_INVALID, "WCSPHSurfaceTension: a non-zero boundary coefficient panics in the reference (index out of bounds)");
-    fluids[slot].forces.assign(f, f + nf);
+    // an elastic entry keeps its state when entry k is what it was (same kind, bit-identical p[]): the Python mirror re-uploads the
+    // whole list when any coefficient changes, and a block must not lose its rest shape because another force was appended
+    FluidSlot& fs = fluids[slot];
+    std::vector<std::shared_ptr<ElasticState>> el(nf);
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009 && k < fs.forces.size() && k < fs.elastic.size() && fs.elastic[k] &&
+            fs.forces[k].kind == f[k].kind && memcmp(fs.forces[k].p, f[k].p, sizeof(f[k].p)) == 0)
+            el[k] = fs.elastic[k];
+    fs.forces.assign(f, f + nf);
+    fs.elastic = std::move(el);
 }
 
 void World::remove_fluid(uint32_t slot) {
@@ -1179,6 +1196,7 @@ void World::run_forces(const StepCtx& c) {
                     if (rc != 0) throw HipError(SALVA_HIP_E_INVALID, "the force callback reported an error");
                     break;
                 }
+                case SALVA_HIP_FORCE_BECKER2009: run_elasticity(c, f, (uint32_t)(&d - fluids[f].forces.data())); break;
                 case SALVA_HIP_FORCE_AKINCI2013:
                     launch_akinci_normals(c, lds, f, stream);
                     // (normals of the inner ghost plane are complete: rho was refreshed on both planes)
@@ -1308,7 +1326,148 @@ bool World::chain_allowed() const {
     for (const FluidSlot& f : fluids)
         for (const SalvaHipForceDesc& d : f.forces)
             if (d.kind == SALVA_HIP_FORCE_CUSTOM || d.kind == SALVA_HIP_FORCE_DFSPH_VISCOSITY) return false;
+    if (elastic_stale()) return false;  // (the rest build reads its contact total back)
     return true;
+}
+
+// ------------------------------------------------------------------------------------------------ Becker2009Elasticity (elastic.hip)
+ElasticState& World::elastic_state(uint32_t slot, uint32_t force) {
+    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
+    FluidSlot& fs = fluids[slot];
+    if (force >= fs.forces.size() || fs.forces[force].kind != SALVA_HIP_FORCE_BECKER2009)
+        throw HipError(SALVA_HIP_E_INVALID, "that force entry is not a Becker2009Elasticity");
+    if (fs.elastic.size() < fs.forces.size()) fs.elastic.resize(fs.forces.size());
+    if (!fs.elastic[force]) fs.elastic[force] = std::make_shared<ElasticState>();
+    return *fs.elastic[force];
+}
+
+bool World::has_elastic() const {
+    for (const FluidSlot& f : fluids)
+        for (const SalvaHipForceDesc& d : f.forces)
+            if (d.kind == SALVA_HIP_FORCE_BECKER2009) return true;
+    return false;
+}
+
+bool World::elastic_stale() const {
+    for (const FluidSlot& f : fluids)
+        for (size_t k = 0; k < f.forces.size(); ++k)
+            if (f.forces[k].kind == SALVA_HIP_FORCE_BECKER2009 && f.n) {
+                const ElasticState* e = k < f.elastic.size() ? f.elastic[k].get() : nullptr;
+                if (!e || e->n0 != f.n || !e->list_valid) return true;
+            }
+    return false;
+}
+
+// Becker2009Elasticity::solve (becker2009_elasticity.rs:268-334) at its place in the force list
+void World::run_elasticity(const StepCtx& c, uint32_t slot, uint32_t force) {
+    ElasticState& e = elastic_state(slot, force);
+    const ElasticParams ep = elastic_params(fluids[slot].forces[force].p);
+    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
+    // init (:84-112) runs when positions0.len() != the particle count: volumes0 and rotations are `resize`d — the first
+    // min(old, new) entries keep their values (quirk 1), new volumes0 are 0 and new rotations the identity
+    const bool init = e.n0 != nn;
+    if (init) {
+        const uint64_t keep = std::min<uint64_t>(e.n0, nn);
+        e.vol0.ensure(nn, stream, true, 1.1f);
+        e.rot.ensure(9 * nn, stream, true, 1.1f);
+        if (nn > keep) SALVA_HIP_CHECK(hipMemsetAsync(e.vol0.p + keep, 0, (nn - keep) * sizeof(float), stream));
+        launch_elastic_identity(e, keep, nn, stream);
+        e.p0.ensure(nn, stream, false, 1.1f); e.hp.ensure(nn, stream, false, 1.1f);
+        e.rot_new.ensure(9 * nn, stream, false, 1.1f); e.sig.ensure(6 * nn, stream, false, 1.1f); e.F.ensure(9 * nn, stream, false, 1.1f);
+        e.n0 = nn;
+        e.list_valid = false;
+    }
+    if (nn == 0) return;
+    launch_elastic_gather(c, (uint32_t)off, e, stream);
+    if (init) {
+        launch_elastic_take_rest(e, stream);  // positions0 = fluid.positions
+        elastic_build_rest(e, c.sc, ep, false, stream);
+    } else if (!e.list_valid) {
+        elastic_build_rest(e, c.sc, ep, true, stream);  // a restored state: the lists from its positions0, its volumes0 as given
+    }
+    launch_elastic_rot_stress(c, e, ep, stream);
+    launch_elastic_forces(c, (uint32_t)off, e, ep, c.acc, stream);
+    e.ran = true;
+}
+
+// the step completed: its rotations become the warm start of the next one
+void World::commit_elastic() {
+    for (FluidSlot& f : fluids)
+        for (auto& p : f.elastic)
+            if (p && p->ran) {
+                std::swap(p->rot.p, p->rot_new.p);
+                std::swap(p->rot.cap, p->rot_new.cap);
+                p->ran = false;
+            }
+}
+
+// The state is read and written at its own particle count n0: the fluid's count, except between a change of that count and the
+// next step, when the state still has the old length (the next step re-initialises it from there: quirk 1 needs the old volumes0).
+uint64_t World::get_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, float* positions0, float* volumes0, float* rotations,
+                                     float* stress, float* grad_tr) {
+    use_device();
+    ElasticState& e = elastic_state(slot, force);
+    if (e.n0 == 0) return 0;
+    if (nn == 0) return e.nnz;  // (sizing call)
+    if (nn != e.n0) throw HipError(SALVA_HIP_E_INVALID, "n is not the elastic state's particle count (salva_hip_get_elasticity_contacts)");
+    if (positions0) {
+        std::vector<float4> t(nn);
+        SALVA_HIP_CHECK(hipMemcpyAsync(t.data(), e.p0.p, nn * sizeof(float4), hipMemcpyDeviceToHost, stream));
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        for (uint64_t i = 0; i < nn; ++i) { positions0[3 * i] = t[i].x; positions0[3 * i + 1] = t[i].y; positions0[3 * i + 2] = t[i].z; }
+    }
+    auto down = [&](float* dst, const float* src, size_t cnt) {
+        if (dst) SALVA_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * sizeof(float), hipMemcpyDeviceToHost, stream));
+    };
+    down(volumes0, e.vol0.p, nn);
+    down(rotations, e.rot.p, 9 * nn);
+    down(stress, e.sig.p, 6 * nn);
+    down(grad_tr, e.F.p, 9 * nn);
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    return e.nnz;
+}
+
+uint64_t World::get_elasticity_contacts(uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets, uint32_t* j, uint64_t capacity) {
+    use_device();
+    ElasticState& e = elastic_state(slot, force);
+    if (n0) *n0 = e.n0;
+    if (e.n0 == 0 || capacity < e.nnz) return e.n0 ? e.nnz : 0;
+    if (offsets) SALVA_HIP_CHECK(hipMemcpyAsync(offsets, e.off.p, (e.n0 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (j) SALVA_HIP_CHECK(hipMemcpyAsync(j, e.nbr.p, e.nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    return e.nnz;
+}
+
+void World::set_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, const float* positions0, const float* volumes0,
+                                 const float* rotations) {
+    use_device();
+    ElasticState& e = elastic_state(slot, force);
+    if (nn == 0) throw HipError(SALVA_HIP_E_INVALID, "an elastic state needs at least one particle");
+    const bool fresh = e.n0 != nn;
+    if (fresh && !positions0) throw HipError(SALVA_HIP_E_INVALID, "positions0 is required when the state is new or changes length");
+    e.p0.ensure(nn, stream, !fresh, 1.1f); e.hp.ensure(nn, stream, false, 1.1f);
+    e.vol0.ensure(nn, stream, !fresh, 1.1f); e.rot.ensure(9 * nn, stream, !fresh, 1.1f);
+    e.rot_new.ensure(9 * nn, stream, false, 1.1f); e.sig.ensure(6 * nn, stream, false, 1.1f); e.F.ensure(9 * nn, stream, false, 1.1f);
+    if (fresh) {
+        SALVA_HIP_CHECK(hipMemsetAsync(e.vol0.p, 0, nn * sizeof(float), stream));
+        SALVA_HIP_CHECK(hipMemsetAsync(e.sig.p, 0, 6 * nn * sizeof(float), stream));
+        SALVA_HIP_CHECK(hipMemsetAsync(e.F.p, 0, 9 * nn * sizeof(float), stream));
+        launch_elastic_identity(e, 0, nn, stream);
+    }
+    if (positions0) {
+        std::vector<float4> t(nn);
+        for (uint64_t i = 0; i < nn; ++i) t[i] = make_float4(positions0[3 * i], positions0[3 * i + 1], positions0[3 * i + 2], 0.0f);
+        SALVA_HIP_CHECK(hipMemcpyAsync(e.p0.p, t.data(), nn * sizeof(float4), hipMemcpyHostToDevice, stream));
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    if (volumes0) SALVA_HIP_CHECK(hipMemcpyAsync(e.vol0.p, volumes0, nn * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (rotations) SALVA_HIP_CHECK(hipMemcpyAsync(e.rot.p, rotations, 9 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    e.n0 = nn;
+    e.ran = false;
+    // the rest lists from positions0 now (the same lists the state had: rows are sorted); volumes0 stays as given
+    elastic_build_rest(e, make_sph_consts(prm.particle_radius * prm.smoothing_factor * 2.0f), elastic_params(fluids[slot].forces[force].p),
+                       true, stream);
 }
 
 // DFSPHSolver::step (dfsph_solver.rs:667-708)
@@ -2081,6 +2240,7 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     lists_checked = true;  // (every path to here has compared the longest lists with the capacity)
     break;
     }  // attempts
+    commit_elastic();
     acc_user = false;
     // decomposed runs: the contacts whose first particle this rank owns (fluid) / whose first particle lies in its slab
     // (boundary-boundary, k_boundary_volumes) — the ranks' counts add up to the undivided domain's counters.cd.ncontacts
@@ -3176,8 +3336,42 @@ float World::time_kernel(int kernel, int reps) {
         SALVA_HIP_CHECK(hipMemcpyAsync(w2.p, w.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         cd.w = w2.p; cd.w2 = w2.p; cd.spec_k = -1; cd.bforce = nullptr;
     }
+    ElasticState* el = nullptr;
+    uint32_t el_slot = 0, el_force = 0;
+    DevBuf<float4> acc_copy;
+    DevBuf<float> el_sig, el_F;
+    bool el_swapped = false;
+    struct Unswap {  // (also when a launch throws)
+        ElasticState*& e; DevBuf<float>& s; DevBuf<float>& f; bool& on;
+        ~Unswap() { if (on) { std::swap(e->sig.p, s.p); std::swap(e->sig.cap, s.cap); std::swap(e->F.p, f.p); std::swap(e->F.cap, f.cap); } }
+    } unswap{el, el_sig, el_F, el_swapped};
+    if (kernel == 7 || kernel == 8) {  // the first Becker2009Elasticity entry, on the last step's state
+        for (uint32_t f = 0; f < fluids.size() && !el; ++f)
+            for (uint32_t k = 0; k < fluids[f].forces.size() && !el; ++k)
+                if (fluids[f].forces[k].kind == SALVA_HIP_FORCE_BECKER2009 && k < fluids[f].elastic.size() && fluids[f].elastic[k] &&
+                    fluids[f].elastic[k]->list_valid && fluids[f].elastic[k]->n0 == fluids[f].n) {
+                    el = fluids[f].elastic[k].get(); el_slot = f; el_force = k;
+                }
+        if (!el) throw HipError(SALVA_HIP_E_INVALID, "no Becker2009Elasticity entry has run");
+        if (comm) throw HipError(SALVA_HIP_E_INVALID, "not available in a multi-GPU run");
+        cd.gate = nullptr;
+        acc_copy.ensure(n);
+        SALVA_HIP_CHECK(hipMemcpyAsync(acc_copy.p, cd.acc, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        // the force pass reads the rotations of the step, which its completion moved into `rot`
+        SALVA_HIP_CHECK(hipMemcpyAsync(el->rot_new.p, el->rot.p, 9 * el->n0 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        if (kernel == 7) {  // the pass rewrites sigma and F: it runs on copies, and the state keeps what the step computed
+            el_sig.ensure(6 * el->n0); el_F.ensure(9 * el->n0);
+            std::swap(el->sig.p, el_sig.p); std::swap(el->sig.cap, el_sig.cap);
+            std::swap(el->F.p, el_F.p); std::swap(el->F.cap, el_F.cap);
+            el_swapped = true;
+        }
+    }
+    const ElasticParams el_p = el ? elastic_params(fluids[el_slot].forces[el_force].p) : ElasticParams{};
+    const uint32_t el_off = el ? (uint32_t)fluid_offset(el_slot) : 0u;
     auto launch = [&]() {
         switch (kernel) {
+            case 7: launch_elastic_rot_stress(cd, *el, el_p, stream); break;  // (reads rot; writes rot_new and the copies of sigma, F)
+            case 8: launch_elastic_forces(cd, el_off, *el, el_p, acc_copy.p, stream); break;
             case 1: launch_divergence(cd, lds, stream); break;
             case 6: launch_divergence_apply(cd, lds, inv_dt_prev, stream); break;
             case 2: launch_iisph_next_pressure(cd, lds, last_dt, 0.5f, kappa.p, kappa2.p, stream); break;

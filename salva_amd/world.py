@@ -263,6 +263,28 @@ class ViscosityKernel:
     kind = L.KERNEL_VISCOSITY
 
 
+class Becker2009Elasticity(NonPressureForce):
+    """solver::Becker2009Elasticity (becker2009_elasticity.rs): corotated SPH elasticity after Becker et al. 2009.
+    `Becker2009Elasticity(young_modulus, poisson_ratio, nonlinear_strain)`; `kernel_density` / `kernel_gradient` mirror the force's
+    own type parameters `Becker2009Elasticity<KernelDensity, KernelGradient>` (:39-42), both CubicSplineKernel by default.  The
+    rest state (positions0, rest contacts, volumes0, rotations) is taken at the first step and again after any change in the
+    fluid's particle count; `LiquidWorld.elasticity_state` reads it.  Not available in decomposed worlds."""
+
+    def __init__(self, young_modulus: float, poisson_ratio: float, nonlinear_strain: bool,
+                 kernel_density=CubicSplineKernel, kernel_gradient=CubicSplineKernel):
+        self.young_modulus = young_modulus
+        self.poisson_ratio = poisson_ratio
+        self.nonlinear_strain = bool(nonlinear_strain)
+        self.kernel_density, self.kernel_gradient = kernel_density, kernel_gradient
+
+    def _desc(self):
+        d = L.ForceDesc()
+        d.kind = L.FORCE_BECKER2009
+        d.p[0], d.p[1], d.p[2] = self.young_modulus, self.poisson_ratio, 1.0 if self.nonlinear_strain else 0.0
+        d.p[3], d.p[4] = self.kernel_density.kind, self.kernel_gradient.kind
+        return d
+
+
 class DFSPHSolver:
     """dfsph_solver.rs:54-70 defaults.  `DFSPHSolver(KernelDensity, KernelGradient)` mirrors the type parameters of
     `DFSPHSolver<KernelDensity, KernelGradient>` (:17-20); both default to CubicSplineKernel."""
@@ -1080,6 +1102,64 @@ class LiquidWorld:
         acc[sel] = np.asarray(view.accelerations, F32)
         L.check(self._L.salva_hip_force_add_local_accelerations(self._h, _fp(acc)))
 
+    # ---- Becker2009Elasticity state (include/salva_hip.h salva_hip_get_elasticity_state)
+    def elasticity_contacts(self, fluid: Fluid, force_index: int = 0):
+        """The rest lists of that force (contacts0) as CSR in host order: (offsets, j), rows ascending in j, self pairs included;
+        None while the force has no state."""
+        self.sync_to_device()
+        n0 = C.c_uint64(0)
+        nnz = self._L.salva_hip_get_elasticity_contacts(self._h, fluid._slot, force_index, C.byref(n0), None, None, 0)
+        if nnz < 0:
+            L.check(int(nnz))
+        if n0.value == 0:
+            return None
+        off = np.zeros(n0.value + 1, np.uint32)
+        j = np.zeros(max(nnz, 1), np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        r = self._L.salva_hip_get_elasticity_contacts(self._h, fluid._slot, force_index, C.byref(n0), off.ctypes.data_as(u32p),
+                                                      j.ctypes.data_as(u32p), nnz)
+        if r < 0:
+            L.check(int(r))
+        return off, j[:nnz]
+
+    def elasticity_state(self, fluid: Fluid, force_index: int = 0) -> Optional[dict]:
+        """The state of the `force_index`-th force of `fluid` (a Becker2009Elasticity) after the last step, in the fluid's host
+        order: positions0 (n, 3), volumes0 (n,), rotations (n, 3, 3), stress (n, 6: xx, yy, zz, xy, xz, yz), grad_tr (n, 3, 3)
+        and the rest contact count `ncontacts0`.  n is the state's own count: the fluid's, except between a change of that count
+        and the next step (the old length, which the next step re-initialises from).  None while the force has no state."""
+        self.sync_to_device()
+        n0 = C.c_uint64(0)
+        r = self._L.salva_hip_get_elasticity_contacts(self._h, fluid._slot, force_index, C.byref(n0), None, None, 0)
+        if r < 0:
+            L.check(int(r))
+        n = n0.value
+        if n == 0:
+            return None
+        st = {"positions0": np.zeros((n, 3), F32), "volumes0": np.zeros(n, F32), "rotations": np.zeros((n, 3, 3), F32),
+              "stress": np.zeros((n, 6), F32), "grad_tr": np.zeros((n, 3, 3), F32)}
+        r = self._L.salva_hip_get_elasticity_state(self._h, fluid._slot, force_index, n, *(_fp(st[k]) for k in
+                                                   ("positions0", "volumes0", "rotations", "stress", "grad_tr")))
+        if r < 0:
+            L.check(int(r))
+        st["ncontacts0"] = int(r)
+        return st
+
+    def set_elasticity_state(self, fluid: Fluid, force_index: int, positions0, volumes0=None, rotations=None):
+        """Replace that state (host order, any length: a length other than the fluid's count re-initialises at the next step, as
+        after a count change); the rest contacts are rebuilt from `positions0`."""
+        self.sync_to_device()
+        p0 = np.ascontiguousarray(positions0, F32).reshape(-1, 3)
+        n = len(p0)
+        v0 = None if volumes0 is None else np.ascontiguousarray(volumes0, F32).reshape(n)
+        r = None if rotations is None else np.ascontiguousarray(rotations, F32).reshape(n, 3, 3)
+        L.check(self._L.salva_hip_set_elasticity_state(self._h, fluid._slot, force_index, n, _fp(p0), _fp(v0), _fp(r)))
+
+    def _elastic_entries(self):
+        for k, f in enumerate(self._fluids):
+            for q, force in enumerate(f.nonpressure_forces):
+                if isinstance(force, Becker2009Elasticity):
+                    yield k, f, q
+
     # ---- checkpoint / restart (SURVEY.md §8 row f4; include/salva_hip.h "Checkpoint / restart")
     def checkpoint(self) -> dict:
         """Everything `step` carries over to the next call, as numpy arrays (np.savez-able): fluid positions / velocities /
@@ -1098,6 +1178,11 @@ class LiquidWorld:
         for k, b in enumerate(self._boundaries):
             st[f"boundary{k}_positions"] = np.asarray(b.positions, F32).copy()
             st[f"boundary{k}_velocities"] = np.asarray(b.velocities, F32).copy()
+        for k, f, q in self._elastic_entries():  # Becker2009Elasticity: its rest state and the rotations' warm start
+            es = self.elasticity_state(f, q)
+            if es is not None:
+                for name in ("positions0", "volumes0", "rotations"):
+                    st[f"fluid{k}_force{q}_{name}"] = es[name]
         return st
 
     def restore(self, st: dict):
@@ -1122,6 +1207,9 @@ class LiquidWorld:
                 b.positions = st[f"boundary{k}_positions"]
                 b.velocities = st[f"boundary{k}_velocities"]
         self.sync_to_device()
+        for k, f, q in self._elastic_entries():
+            if f"fluid{k}_force{q}_positions0" in st:
+                self.set_elasticity_state(f, q, *(st[f"fluid{k}_force{q}_{name}"] for name in ("positions0", "volumes0", "rotations")))
         t = np.asarray(st["timestep"], F32)
         L.check(self._L.salva_hip_set_timestep(self._h, float(t[0]), float(t[1])))
 
