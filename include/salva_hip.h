@@ -329,6 +329,16 @@ float salva_hip_time_pred_density(SalvaHipWorld* world, int32_t reps);
  * rotation pass writes copies of the stresses and gradients, the force pass adds to a copy of the accelerations: the state keeps what
  * the step computed). */
 float salva_hip_time_kernel(SalvaHipWorld* world, int32_t kernel, int32_t reps);
+/* The tile tables of the last step as the tile kernels behind the list builder read them (tests of the referenced-only halo; not a
+ * hot path).  `slot` = index among the step's non-empty tiles.  info[16]: 0 number of slots, 1 / 2 the slot's own particles
+ * [first, one past the last) in the sorted order, 3 fluid halo slots it stages, 4 boundary halo slots, 5 / 6 / 7 the fluid | fluid +
+ * boundary | padded fluid + boundary halo the solver launches of the step were cut for (what picks their layouts), 8 the fullest
+ * fluid halo box of the step, 9 = 1 when the step kept the referenced halo slots only, 10 / 11 such passes so far and those repeated
+ * because a kept halo outgrew its bound, 12 the list entries written to `entries`.  halo_row[s] = sorted index of the particle
+ * staged in slot s; counts[k] = fluid-fluid list length of the slot's k-th own particle; entries = those lists one after the other,
+ * as halo slots.  Each output is cut at its capacity (in elements); returns SALVA_HIP_OK or an error code. */
+int salva_hip_get_tile_tables(SalvaHipWorld* world, uint32_t slot, uint32_t* info16, uint32_t* halo_row, uint32_t cap_row,
+                              uint32_t* counts, uint32_t cap_counts, uint32_t* entries, uint32_t cap_entries);
 /* `world.counters` after the last step — counters/mod.rs:17-72 */
 int salva_hip_get_counters(const SalvaHipWorld* world, SalvaHipCounters* out);
 /* `Counters::enable()` / `disable()` (counters/mod.rs:56-72): switches the timers (SalvaHipParams::enable_timers) from the next step

@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_comm_peer_abort", "salva_hip_comm_selftest", "salva_hip_comm_time", "salva_hip_clear_boundary_sampling", "salva_hip_get_fluid_async", "salva_hip_wait_download",
     "salva_hip_host_alloc", "salva_hip_host_free", "salva_hip_host_register", "salva_hip_host_unregister",
     "salva_hip_set_cfl", "salva_hip_get_substeps", "salva_hip_particles_intersecting_host_shape",
-    "salva_hip_set_coupling_callback",
+    "salva_hip_set_coupling_callback", "salva_hip_get_tile_tables",
     "salva_hip_get_dist_timing", "salva_hip_local_len", "salva_hip_get_local", "salva_hip_get_local_contacts", "salva_hip_force_add_local_accelerations",
     "salva_hip_get_elasticity_state", "salva_hip_set_elasticity_state", "salva_hip_get_elasticity_contacts",
 ]
@@ -240,6 +240,10 @@ def lib():
     L.salva_hip_delete_owned.restype = C.c_int64
     L.salva_hip_rebalance.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.salva_hip_time_kernel.argtypes = [vp, i32, i32]
+    # (a variant library of kernel experiments may be built from an older tree that lacks the newest entry points)
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_get_tile_tables"):
+        L.salva_hip_get_tile_tables.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32]
+        L.salva_hip_get_tile_tables.restype = C.c_int
     L.salva_hip_time_kernel.restype = f32
     L.salva_hip_get_counters.argtypes = [vp, C.POINTER(CountersStruct)]
     L.salva_hip_set_cfl.argtypes = [vp, i32, C.c_float, i32, i32]

@@ -412,6 +412,15 @@ float salva_hip_time_pred_density(SalvaHipWorld* world, int32_t reps) { WorldLoc
     return rc == SALVA_HIP_OK ? us : (float)rc;
 }
 
+int salva_hip_get_tile_tables(SalvaHipWorld* world, uint32_t slot, uint32_t* info16, uint32_t* halo_row, uint32_t cap_row,
+                              uint32_t* counts, uint32_t cap_counts, uint32_t* entries, uint32_t cap_entries) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !info16) throw salva::HipError(SALVA_HIP_E_INVALID, "null world or info");
+        world->w->tile_tables(slot, info16, halo_row, cap_row, counts, cap_counts, entries, cap_entries);
+        return SALVA_HIP_OK;
+    });
+}
+
 float salva_hip_time_kernel(SalvaHipWorld* world, int32_t kernel, int32_t reps) { WorldLock _lk(world);
     float us = -1.0f;
     int rc = guarded([&]() -> int {

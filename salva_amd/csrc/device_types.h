@@ -89,7 +89,7 @@ struct alignas(16) SolveCtl {
 static_assert(sizeof(SolveCtl) == 32, "SolveCtl: two 16-byte halves");
 
 // per-tile list statistics of k_nbr_tile (grid.hip), folded by k_list_stats or by the end-of-step publication
-struct TileListStats { uint32_t sum_ff, sum_fb, max_ff, max_fb, own_ff, own_fb; };  // own_*: lists of particles this rank OWNS (no ghosts)
+struct TileListStats { uint32_t sum_ff, sum_fb, max_ff, max_fb, own_ff, own_fb, ref_s, ref_sb; };  // own_*: lists of particles this rank OWNS (no ghosts); ref_s / ref_sb: fluid halo slots some list of the tile names and its boundary halo slots (0, 0: not counted)
 
 // what the end-of-step publication needs to decide Readback::pre_ok
 struct PrePub { int32_t on, chained; int32_t bbox[6]; };
@@ -127,6 +127,12 @@ struct StepCtx {
     uint32_t* slice_near;       // per slice: some particle has a neighbour closer than 1e-5 h (k_density_alpha; dfsph.hip)
     uint32_t cap_ff, cap_fb;    // dwords (= pairs of contacts) reserved per particle
     const TileAcc* tile_off;    // [nslots+1] exclusive prefix of per-tile {halo slots, boundary halo slots, slices}, by SLOT
+                                // Referenced-only halo (grid.hip k_nbr_tile_ref, k_ref_offsets): in a step that builds it, the list
+                                // builder drops the fluid halo slots no list of the tile names — the tile's row of halo_src is
+                                // compacted in place (same relative order), the list entries are rewritten through the rank — and
+                                // `.s` is then replaced by the prefix of the KEPT counts: every tile kernel behind the builder
+                                // stages the kept slots and none of them knows.  Fixed-stride rows only (halo_stride > 0: a row's
+                                // address does not depend on `.s`).
     const uint32_t* halo_src;   // sorted fluid index of every halo slot of every tile (tile-major)
     const uint32_t* bhalo_src;  // sorted boundary index of every boundary halo slot
     uint32_t halo_stride;       // > 0: tile t's slot table starts at t * halo_stride (address known before any load
@@ -269,7 +275,9 @@ struct Readback {
     // the grid part of the NEXT step enqueued at the end of this one (World::pre_enqueue_grid): 1 when the box the position update
     // found is the box that part was enqueued for (and the chain held) — the gate of those launches
     uint32_t pre_ok;
-    uint32_t pad3_;
+    // referenced-only halos of the step (StepCtx::tile_off; 0: not built): the fullest fluid | fluid + boundary | fluid padded to 64 +
+    // boundary halo of one tile; they travel with the list statistics
+    uint32_t max_ref[3];
 };
 #ifdef __HIPCC__
 // gate[0] = Readback::chain_ok (or pre_ok), gate[1] = the word behind it (chain_stage)

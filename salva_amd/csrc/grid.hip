@@ -656,14 +656,24 @@ void scan_tiles(void* temp, size_t temp_bytes, const TileAcc* in, TileAcc* out, 
 #define SALVA_NBR_MIN_WAVES 8
 #endif
 // MM: 0 = one mass or the general kernels (no mass code at all), 1 = two masses, 2 = three or four (StepCtx::two_mass / nmass)
-template <int V, int MM>
-__global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4) void k_nbr_tile(StepCtx c, TileListStats* __restrict__ tile_stats) {
+// REF (V = 1 only): the referenced-only halo (device_types.h StepCtx::tile_off).  While the lists are written every accepted candidate
+// and every own particle sets its bit in an LDS bitmap over the halo slots; afterwards the marked slots are ranked (a prefix sum in
+// the halo's own order, so the map is monotone: every list keeps its order and every sum its bits), the tile's row of halo_src is
+// compacted in place, every list dword of the tile is rewritten through the rank table, and slot_info[slot].w takes the
+// compacted count (k_ref_offsets below turns those into the offsets every later tile kernel takes its halo size from).  The rank table and the copy of the source row reuse the staged planes, whose tests are done by then.  `cap`: the most
+// slots a tile may keep (fluid | fluid + boundary | fluid padded to 64 + boundary) — what the host sized the LDS of this step's
+// solver kernels for from the PREVIOUS step's maxima; a tile beyond it raises flag 16 and publishes a count within the caps and
+// in-bounds (wrong) entries, and the host repeats the pass.
+template <int V, int MM, bool REF>
+__device__ __forceinline__ void nbr_tile_body(const StepCtx& c, TileListStats* __restrict__ tile_stats, uint32_t* __restrict__ halo_src_w,
+                                              uint4* __restrict__ slot_info_w, const RefCaps cap) {
+    static_assert(!REF || V == 1, "the referenced-only halo is built by the V = 1 kernel");
     __shared__ uint32_t red[8][TILE_MAX_WAVES];
     Tile t;
     t.setup(c, false);
     if (t.empty()) {
         if (threadIdx.x == 0) {
-            tile_stats[t.slot] = TileListStats{0, 0, 0, 0, 0, 0};
+            tile_stats[t.slot] = TileListStats{0, 0, 0, 0, 0, 0, 0, 0};
             if (MM != 0) { c.tile_mass_bits[t.slot] = 0u; c.tile_massb_bits[t.slot] = 0u; if (MM == 2) c.tile_masscd_bits[t.slot] = make_uint2(0u, 0u); }
         }
         return;
@@ -685,6 +695,10 @@ __global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4)
     uint32_t* Lm = multi ? t.carve<uint32_t>(t.S) : nullptr;
     float4* Bp = t.carve<float4>(t.SB);
     float4* Bv = t.carve<float4>(t.SB);
+    // (REF: one bit per halo slot, + one word for the chunk masks that straddle a word; cleared before the staging barrier)
+    const uint32_t nwords = (t.S + 31u) >> 5;
+    uint32_t* bm = REF ? t.carve<uint32_t>(nwords + 1u) : nullptr;
+    if (REF) for (uint32_t k = threadIdx.x; k <= nwords; k += blockDim.x) bm[k] = 0u;
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     // (worlds with a few masses, StepCtx::two_mass: which of the host's mass classes does this halo hold?  One bit per class)
     uint32_t pm = 0u;
@@ -846,6 +860,11 @@ __global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4)
                         uint32_t mask = __builtin_bitreverse32(rev) >> (32u - 4u * nq);
                         if (base < b) mask &= ~((1u << (b - base)) - 1u);
                         mask &= nc >= 32u ? 0xffffffffu : ((1u << nc) - 1u);
+                        if (REF && paired && mask) {  // (the chunk starts at a multiple of 4, not of 32: its bits may reach into the next word)
+                            const uint32_t sh = base & 31u;
+                            atomicOr(&bm[base >> 5], mask << sh);
+                            if (sh && (mask >> (32u - sh))) atomicOr(&bm[(base >> 5) + 1u], mask >> (32u - sh));
+                        }
                         if (paired) {
                             // two accepted candidates per trip = one finished list dword per trip: the lanes of a wave leave this
                             // loop after max(ceil(bits / 2)) trips instead of max(bits), and no trip branches on the parity of cnt
@@ -868,7 +887,10 @@ __global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4)
                             while (mask) {
                                 const uint32_t s = base + (uint32_t)__builtin_ctz(mask);
                                 mask &= mask - 1u;
-                                if (ff_allowed(s)) append(s);
+                                if (ff_allowed(s)) {
+                                    append(s);
+                                    if (REF) atomicOr(&bm[s >> 5], 1u << (s & 31u));
+                                }
                             }
                         }
                     }
@@ -897,6 +919,7 @@ __global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4)
         // an odd list is padded with the particle's own slot (for_each_ff2: the self contact adds nothing to gradient sums)
         const int hself = (lx * HY + ly) * HZ + lz;
         self_slot = tc.lstart[hself] + (i - tc.gstart[hself]);
+        if (REF) atomicOr(&bm[self_slot >> 5], 1u << (self_slot & 31u));  // (own particles stay: self contacts and padding name them)
         if ((cnt & 1u) && (cnt >> 1) < c.cap_ff) out[ellq(cnt >> 1)] = pend | (self_slot << 16);
         if ((cntb & 1u) && (cntb >> 1) < c.cap_fb) outb[ellq(cntb >> 1)] = pendb;
         // (a list longer than the capacity was cut: the consumers must not walk past the rows that exist; the statistics below
@@ -936,67 +959,174 @@ __global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4)
     const uint32_t wv = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
     if (lane == 0) { red[0][wv] = sum_ff; red[1][wv] = sum_fb; red[2][wv] = max_ff; red[3][wv] = max_fb; red[4][wv] = own_ff; red[5][wv] = own_fb; }
     __syncthreads();
+    uint32_t nref = 0u;
+    if (REF) {
+        // (the barrier above has completed the bitmap.)  Ranks: wave 0 scans the words' population counts, 64 at a time; the
+        // exclusive prefixes go where the x plane was.
+        uint32_t* pref = reinterpret_cast<uint32_t*>(Lx);
+        uint32_t* srcv = reinterpret_cast<uint32_t*>(Ly);
+        unsigned short* rk = reinterpret_cast<unsigned short*>(Lz);
+        if (wv == 0) {
+            uint32_t carry = 0u;
+            for (uint32_t w0 = 0; w0 < nwords; w0 += WAVE) {
+                const uint32_t k = w0 + lane;
+                uint32_t word = k < nwords ? bm[k] : 0u;
+                if (k == nwords - 1u && (t.S & 31u)) word &= (1u << (t.S & 31u)) - 1u;  // (bits past the halo: padding of the planes)
+                const uint32_t v = (uint32_t)__builtin_popcount(word);
+                uint32_t inc = v;
+#pragma unroll
+                for (int o = 1; o < WAVE; o <<= 1) {
+                    const uint32_t up = (uint32_t)__shfl_up((int)inc, o, WAVE);
+                    if (lane >= (uint32_t)o) inc += up;
+                }
+                if (k < nwords) pref[k] = carry + inc - v;
+                carry += (uint32_t)__shfl((int)inc, WAVE - 1, WAVE);
+            }
+            if (lane == 0) pref[nwords] = carry;
+        }
+        __syncthreads();
+        nref = pref[nwords];
+        // (the host keeps cap.raw and cap.sum at or above the fullest boundary halo: the subtractions cannot wrap)
+        const bool over = nref > cap.s || nref + t.SB > cap.raw || ((nref + 63u) & ~63u) + t.SB > cap.sum;
+        const uint32_t keep = over ? min(min(nref, cap.s), min(cap.raw - t.SB, (cap.sum - t.SB) & ~63u)) : nref;
+        // rank of every slot (a dropped slot gets the rank of the next kept one: nobody names it), and the source row aside
+        for (uint32_t s = threadIdx.x; s < t.S; s += blockDim.x) {
+            const uint32_t word = bm[s >> 5];
+            const uint32_t r = pref[s >> 5] + (uint32_t)__builtin_popcount(word & ((1u << (s & 31u)) - 1u));
+            rk[s] = (unsigned short)(keep ? min(r, keep - 1u) : 0u);
+            srcv[s] = halo_src_w[t.hoff + s];
+        }
+        __syncthreads();
+        for (uint32_t s = threadIdx.x; s < t.S; s += blockDim.x) {
+            const uint32_t word = bm[s >> 5];
+            const uint32_t r = pref[s >> 5] + (uint32_t)__builtin_popcount(word & ((1u << (s & 31u)) - 1u));
+            if (((word >> (s & 31u)) & 1u) && r < keep) halo_src_w[t.hoff + r] = srcv[s];
+        }
+        // every list dword of the tile (pads included) through the rank table; each lane re-reads what it wrote itself
+        t.for_own([&](uint32_t i, uint32_t gs, bool active) {
+            const uint32_t cnt = active ? c.nff[i] : 0u;
+            const uint32_t nq_max = min(wave_max_u32((cnt + 1u) >> 1), c.cap_ff);
+            if (!active) return;
+            uint32_t* out = c.nbr_ff + (size_t)gs * c.cap_ff * WAVE + 4u * lane;
+            for (uint32_t q = 0; q < nq_max; ++q) {
+                const uint32_t d = out[ellq(q)];
+                out[ellq(q)] = (uint32_t)rk[d & 0xffffu] | ((uint32_t)rk[d >> 16] << 16);
+            }
+        });
+        if (threadIdx.x == 0) {
+            if (over) atomicOr(c.flags, 16u);
+            slot_info_w[t.slot].w = keep | (t.SB << 16);
+        }
+    }
     if (threadIdx.x == 0) {
-        TileListStats st{0, 0, 0, 0, 0, 0};
+        TileListStats st{0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t k = 0; k < nw; ++k) {
             st.sum_ff += red[0][k]; st.sum_fb += red[1][k]; st.own_ff += red[4][k]; st.own_fb += red[5][k];
             st.max_ff = max(st.max_ff, red[2][k]); st.max_fb = max(st.max_fb, red[3][k]);
         }
+        if (REF) { st.ref_s = nref; st.ref_sb = t.SB; }
         tile_stats[t.slot] = st;
     }
 }
+template <int V, int MM>
+__global__ __launch_bounds__(TILE_MAX_THREADS, V == 1 ? SALVA_NBR_MIN_WAVES : 4) void k_nbr_tile(StepCtx c, TileListStats* __restrict__ tile_stats) {
+    nbr_tile_body<V, MM, false>(c, tile_stats, nullptr, nullptr, RefCaps{0xffffffffu, 0xffffffffu, 0xffffffffu});
+}
+template <int MM>
+__global__ __launch_bounds__(TILE_MAX_THREADS, SALVA_NBR_MIN_WAVES) void k_nbr_tile_ref(StepCtx c, TileListStats* __restrict__ tile_stats,
+                                                                                       uint32_t* __restrict__ halo_src_w, uint4* __restrict__ slot_info_w, RefCaps cap) {
+    nbr_tile_body<1, MM, true>(c, tile_stats, halo_src_w, slot_info_w, cap);
+}
+// tile_off[k].s = the number of kept fluid halo slots of the slots before k (slot_info[k].w, low half), k in [0, nslots]: one block,
+// a contiguous run of slots per thread.  Once per step that keeps the referenced slots only.
+constexpr int REF_SCAN_THREADS = 1024;
+__global__ __launch_bounds__(REF_SCAN_THREADS) void k_ref_offsets(const uint4* __restrict__ slot_info, uint32_t nslots, TileAcc* __restrict__ tile_off) {
+    __shared__ unsigned long long part[REF_SCAN_THREADS];
+    const uint32_t per = (nslots + REF_SCAN_THREADS - 1u) / REF_SCAN_THREADS;
+    const uint32_t b = min(threadIdx.x * per, nslots), e = min(b + per, nslots);
+    unsigned long long sum = 0;
+    for (uint32_t k = b; k < e; ++k) sum += slot_info[k].w & 0xffffu;
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < REF_SCAN_THREADS; o <<= 1) {  // inclusive scan of the threads' sums
+        const unsigned long long up = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0ull;
+        __syncthreads();
+        part[threadIdx.x] += up;
+        __syncthreads();
+    }
+    unsigned long long run = part[threadIdx.x] - sum;
+    for (uint32_t k = b; k < e; ++k) { tile_off[k].s = run; run += slot_info[k].w & 0xffffu; }
+    if (threadIdx.x == REF_SCAN_THREADS - 1) tile_off[nslots].s = part[threadIdx.x];
+}
 // fold the per-tile list statistics: out = {ncontacts_ff, ncontacts_fb} (u64) and {max_ff, max_fb} (u32)
 __global__ __launch_bounds__(BLOCK) void k_list_stats(const TileListStats* __restrict__ ts, uint32_t ntiles,
-                                                      unsigned long long* totals2, uint32_t* maxima2, unsigned long long* own2) {
+                                                      unsigned long long* totals2, uint32_t* maxima2, unsigned long long* own2, uint32_t* ref3) {
     __shared__ unsigned long long sred[4][BLOCK / WAVE];
-    __shared__ uint32_t mred[2][BLOCK / WAVE];
+    __shared__ uint32_t mred[5][BLOCK / WAVE];
     unsigned long long a = 0, b = 0, oa = 0, ob = 0;
-    uint32_t ma = 0, mb = 0;
+    uint32_t ma = 0, mb = 0, rs = 0, rr = 0, rm = 0;  // (referenced halos: fullest fluid | fluid + boundary | padded fluid + boundary)
     for (uint32_t k = threadIdx.x; k < ntiles; k += BLOCK) {
         const TileListStats s = ts[k];
         a += s.sum_ff; b += s.sum_fb; oa += s.own_ff; ob += s.own_fb; ma = max(ma, s.max_ff); mb = max(mb, s.max_fb);
+        if (s.ref_s) { rs = max(rs, s.ref_s); rr = max(rr, s.ref_s + s.ref_sb); rm = max(rm, ((s.ref_s + 63u) & ~63u) + s.ref_sb); }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         a += __shfl_xor(a, o, WAVE); b += __shfl_xor(b, o, WAVE);
         oa += __shfl_xor(oa, o, WAVE); ob += __shfl_xor(ob, o, WAVE);
     }
-    ma = wave_max_u32(ma); mb = wave_max_u32(mb);
+    ma = wave_max_u32(ma); mb = wave_max_u32(mb); rs = wave_max_u32(rs); rr = wave_max_u32(rr); rm = wave_max_u32(rm);
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    if (lane == 0) { sred[0][wv] = a; sred[1][wv] = b; sred[2][wv] = oa; sred[3][wv] = ob; mred[0][wv] = ma; mred[1][wv] = mb; }
+    if (lane == 0) {
+        sred[0][wv] = a; sred[1][wv] = b; sred[2][wv] = oa; sred[3][wv] = ob; mred[0][wv] = ma; mred[1][wv] = mb;
+        mred[2][wv] = rs; mred[3][wv] = rr; mred[4][wv] = rm;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long ta = 0, tb = 0, toa = 0, tob = 0; uint32_t xa = 0, xb = 0;
+        unsigned long long ta = 0, tb = 0, toa = 0, tob = 0; uint32_t xa = 0, xb = 0, xs = 0, xr = 0, xm = 0;
         for (int k = 0; k < BLOCK / WAVE; ++k) {
             ta += sred[0][k]; tb += sred[1][k]; toa += sred[2][k]; tob += sred[3][k]; xa = max(xa, mred[0][k]); xb = max(xb, mred[1][k]);
+            xs = max(xs, mred[2][k]); xr = max(xr, mred[3][k]); xm = max(xm, mred[4][k]);
         }
         totals2[0] = ta; totals2[1] = tb; maxima2[0] = xa; maxima2[1] = xb;
         if (own2) { own2[0] = toa; own2[1] = tob; }
+        if (ref3) { ref3[0] = xs; ref3[1] = xr; ref3[2] = xm; }
     }
 }
 
 size_t tile_list_stats_bytes(uint32_t ntiles) { return (size_t)ntiles * sizeof(TileListStats); }
 void launch_nbr_build(const StepCtx& c, const TileLds& L, void* tile_stats, unsigned long long* totals2, uint32_t* maxima2,
-                      unsigned long long* own2, hipStream_t s) {
+                      unsigned long long* own2, hipStream_t s, const RefBuild* ref) {
     if (c.n == 0) return;
     TileListStats* ts = static_cast<TileListStats*>(tile_stats);
     if (c.nmodels > 32u || c.nbmodels > 32u) {  // (the bit-mask group tests of V = 1 hold 32 models)
+        // (the host never asks this builder for the referenced-only halo: slot_info keeps the full counts, which stay consistent)
         SALVA_LAUNCH_TILE((k_nbr_tile<0, 0>), c, L, L.bytes(20, 32, 4, true) + 64u, s, c, ts);  // (worlds with a few masses have at most 32 fluids)
     } else {
         // what V = 1 carves: the cell tables, three 4-byte planes of (S + 8 rounded to 4) slots, the model ids when there is more
-        // than one fluid, two 16-byte boundary arrays
+        // than one fluid, two 16-byte boundary arrays (REF: and one bit per fluid slot)
         // (a function of the TileLds it is handed: the launch macro evaluates it once per launch class)
-        auto nbr_lds = [](const TileLds& T, uint32_t nmodels) {
+        auto nbr_lds = [](const TileLds& T, uint32_t nmodels, bool with_bitmap) {
             auto r16 = [](uint32_t b) { return (b + 15u) & ~15u; };
             const uint32_t plane = ((T.max_halo_fluid + 8u + 63u) & ~63u) + 64u;
-            return r16(TILE_TABLE_BYTES) + 3u * r16(plane * 4u) + (nmodels > 1 ? r16(T.max_halo_fluid * 4u) : 0u) + 2u * T.max_halo_boundary * 16u + 64u;
+            return r16(TILE_TABLE_BYTES) + 3u * r16(plane * 4u) + (nmodels > 1 ? r16(T.max_halo_fluid * 4u) : 0u) + 2u * T.max_halo_boundary * 16u + 64u +
+                   (with_bitmap ? r16((((T.max_halo_fluid + 31u) >> 5) + 1u) * 4u) : 0u);
         };
-        if (!c.two_mass) SALVA_LAUNCH_TILE((k_nbr_tile<1, 0>), c, L, nbr_lds(L, c.nmodels), s, c, ts);
-        else if (c.nmass <= 2u) SALVA_LAUNCH_TILE((k_nbr_tile<1, 1>), c, L, nbr_lds(L, c.nmodels), s, c, ts);
-        else SALVA_LAUNCH_TILE((k_nbr_tile<1, 2>), c, L, nbr_lds(L, c.nmodels), s, c, ts);
+        if (ref) {
+            // (the builder itself stages the full box — it needs every candidate: the descriptors it meets carry no kept count yet)
+            uint32_t* hs = ref->halo_src; uint4* si = ref->slot_info; const RefCaps cap = ref->cap;
+            if (!c.two_mass) SALVA_LAUNCH_TILE((k_nbr_tile_ref<0>), c, L, nbr_lds(L, c.nmodels, true), s, c, ts, hs, si, cap);
+            else if (c.nmass <= 2u) SALVA_LAUNCH_TILE((k_nbr_tile_ref<1>), c, L, nbr_lds(L, c.nmodels, true), s, c, ts, hs, si, cap);
+            else SALVA_LAUNCH_TILE((k_nbr_tile_ref<2>), c, L, nbr_lds(L, c.nmodels, true), s, c, ts, hs, si, cap);
+        } else {
+            if (!c.two_mass) SALVA_LAUNCH_TILE((k_nbr_tile<1, 0>), c, L, nbr_lds(L, c.nmodels, false), s, c, ts);
+            else if (c.nmass <= 2u) SALVA_LAUNCH_TILE((k_nbr_tile<1, 1>), c, L, nbr_lds(L, c.nmodels, false), s, c, ts);
+            else SALVA_LAUNCH_TILE((k_nbr_tile<1, 2>), c, L, nbr_lds(L, c.nmodels, false), s, c, ts);
+        }
     }
+    if (ref) k_ref_offsets<<<1, REF_SCAN_THREADS, 0, s>>>(ref->slot_info, c.nlaunch, ref->tile_off);
     // (totals2 == nullptr: the statistics are folded by the end-of-step publication, World::publish_enqueue — one launch less per step)
-    if (totals2) k_list_stats<<<1, BLOCK, 0, s>>>(static_cast<const TileListStats*>(tile_stats), c.nlaunch, totals2, maxima2, own2);
+    if (totals2) k_list_stats<<<1, BLOCK, 0, s>>>(static_cast<const TileListStats*>(tile_stats), c.nlaunch, totals2, maxima2, own2, ref ? ref->maxima3 : nullptr);
 }
 
 }  // namespace salva

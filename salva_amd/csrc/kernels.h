@@ -63,8 +63,13 @@ void scan_tiles(void* temp, size_t temp_bytes, const TileAcc* in, TileAcc* out, 
 // in one pass; totals2 = {ff, fb} contact counts, maxima2 = longest {ff, fb} list (> 2*cap means overflow: rebuild)
 size_t tile_list_stats_bytes(uint32_t ntiles);
 // own2 (may be null) = the same totals over the particles this rank owns (no ghosts)
+// ref (may be null) = build the referenced-only halo as well (device_types.h StepCtx::tile_off): the slot table and the per-slot sizes
+// it rewrites, the most slots a tile may keep, and where k_list_stats leaves the three maxima {fluid, fluid + boundary, padded
+// fluid + boundary} of the kept halos (with totals2 == nullptr the end-of-step publication folds them)
+struct RefCaps { uint32_t s, raw, sum; };
+struct RefBuild { uint32_t* halo_src; uint4* slot_info; TileAcc* tile_off; RefCaps cap; uint32_t* maxima3; };
 void launch_nbr_build(const StepCtx& c, const TileLds& L, void* tile_stats, unsigned long long* totals2, uint32_t* maxima2,
-                      unsigned long long* own2, hipStream_t s);
+                      unsigned long long* own2, hipStream_t s, const RefBuild* ref = nullptr);
 size_t select_flagged_temp_bytes(uint32_t n);
 void select_flagged_f4(void* temp, size_t temp_bytes, const float4* in, const uint8_t* flags, float4* out, uint32_t* num_selected,
                        uint32_t n, hipStream_t s);

@@ -129,6 +129,8 @@ class World {
     uint32_t owned_count() const { return comm ? n_owned : n; }
     float time_pred_density(int reps);
     float time_kernel(int kernel, int reps);
+    void tile_tables(uint32_t slot, uint32_t* info16, uint32_t* halo_row, uint32_t cap_row, uint32_t* counts, uint32_t cap_counts, uint32_t* entries,
+                     uint32_t cap_entries);  // salva_hip_get_tile_tables
 #ifdef SALVA_HIP_DIAG
     // kernel experiments (diag/world_diag.hip, salva_hip_time_variant): time variant `variant` of k_pred_density; *checksum =
     // FNV-1a of the kappa it wrote
@@ -391,6 +393,18 @@ class World {
     bool classes_off = false, classes_forced = false, light_on = false;  // SALVA_HIP_NO_CLASSES=1 / SALVA_HIP_CLASSES=1 / SALVA_HIP_LIGHT=1 (the light class: opt-in, it lost)
     // splitting of over-full tiles (device_types.h StepCtx::split_s)
     bool split_off = false;        // SALVA_HIP_NO_SPLIT=1
+    // Referenced-only halo (device_types.h StepCtx::tile_off; World::substep)
+    bool ref_off = false, ref_forced = false;  // SALVA_HIP_FULL_HALO=1 (A/B: stage the full box) / SALVA_HIP_REF_HALO=1 (in every step: tests)
+    bool ref_tight = false;        // SALVA_HIP_REF_TIGHT=1 (tests): cut the launches for LESS than the previous step's kept maxima — every such pass misses
+    bool ref_on_cur = false;       // this pass's list build kept the referenced slots only
+    bool ref_bounded = false;      // ... and were cut for the previous step's kept maxima plus a margin (flag 16 = the pass is repeated)
+    bool ref_pred_valid = false;   // ref_pred = {fluid, fluid + boundary, padded fluid + boundary} maxima of the last step's kept halos
+    uint32_t ref_pred[3] = {0, 0, 0}, ref_pred_n = 0;
+    bool ref_last = false;         // the last step built it, with these caps, on launches cut for lds_full (salva_hip_time_kernel 4)
+    RefCaps ref_last_caps{0xffffffffu, 0xffffffffu, 0xffffffffu};
+    TileLds lds_full;
+    uint32_t ref_last_nslots_bound = 0;
+    uint64_t ref_passes = 0, ref_misses = 0;  // (salva_hip_get_tile_tables)
     uint32_t split_forced = 0;     // SALVA_HIP_SPLIT_S=k: split at k halo particles whatever the statistics say (tests)
     bool split_on = false;         // the previous step's totals say: a few tiles are over-full
     uint32_t split_s_cur = 0;      // what this step's tables are built with

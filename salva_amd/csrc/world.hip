@@ -143,6 +143,9 @@ World::World(const SalvaHipParams& p) : prm(p) {
     classes_off = getenv("SALVA_HIP_NO_CLASSES") != nullptr;
     classes_forced = getenv("SALVA_HIP_CLASSES") != nullptr;
     light_on = getenv("SALVA_HIP_LIGHT") != nullptr;
+    ref_off = getenv("SALVA_HIP_FULL_HALO") != nullptr;
+    ref_forced = getenv("SALVA_HIP_REF_HALO") != nullptr;
+    ref_tight = getenv("SALVA_HIP_REF_TIGHT") != nullptr;
     if (const char* e = getenv("SALVA_HIP_SPLIT_S")) split_forced = (uint32_t)std::max(atoi(e), 1);
     no_planes = getenv("SALVA_HIP_NO_PLANES") != nullptr;
     two_mass_off = getenv("SALVA_HIP_NO_TWO_MASS") != nullptr;
@@ -854,26 +857,32 @@ __global__ __launch_bounds__(BLOCK) void k_publish_readback(Readback* __restrict
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
     if (ep.ts) {  // (block-uniform) the fold of k_list_stats, grid.hip
         unsigned long long a = 0, b = 0, oa = 0, ob = 0;
-        uint32_t ma = 0, mb = 0;
+        uint32_t ma = 0, mb = 0, rs = 0, rr = 0, rm = 0;
         for (uint32_t k = threadIdx.x; k < ep.nts; k += blockDim.x) {
             const TileListStats t = ep.ts[k];
             a += t.sum_ff; b += t.sum_fb; oa += t.own_ff; ob += t.own_fb; ma = max(ma, t.max_ff); mb = max(mb, t.max_fb);
+            if (t.ref_s) { rs = max(rs, t.ref_s); rr = max(rr, t.ref_s + t.ref_sb); rm = max(rm, ((t.ref_s + 63u) & ~63u) + t.ref_sb); }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             a += __shfl_xor(a, o, WAVE); b += __shfl_xor(b, o, WAVE);
             oa += __shfl_xor(oa, o, WAVE); ob += __shfl_xor(ob, o, WAVE);
         }
-        ma = wave_max_u32(ma); mb = wave_max_u32(mb);
-        if (lane == 0) { sred[0][wv] = a; sred[1][wv] = b; sred[2][wv] = oa; sred[3][wv] = ob; ired[wv] = (int)ma; ired[nw + wv] = (int)mb; }
+        ma = wave_max_u32(ma); mb = wave_max_u32(mb); rs = wave_max_u32(rs); rr = wave_max_u32(rr); rm = wave_max_u32(rm);
+        if (lane == 0) {
+            sred[0][wv] = a; sred[1][wv] = b; sred[2][wv] = oa; sred[3][wv] = ob; ired[wv] = (int)ma; ired[nw + wv] = (int)mb;
+            ired[2 * nw + wv] = (int)rs; ired[3 * nw + wv] = (int)rr; ired[4 * nw + wv] = (int)rm;
+        }
         __syncthreads();
         if (threadIdx.x == 0) {
-            unsigned long long ta = 0, tb = 0, toa = 0, tob = 0; uint32_t xa = 0, xb = 0;
+            unsigned long long ta = 0, tb = 0, toa = 0, tob = 0; uint32_t xa = 0, xb = 0, xs = 0, xr = 0, xm = 0;
             for (int k = 0; k < nw; ++k) {
                 ta += sred[0][k]; tb += sred[1][k]; toa += sred[2][k]; tob += sred[3][k];
                 xa = max(xa, (uint32_t)ired[k]); xb = max(xb, (uint32_t)ired[nw + k]);
+                xs = max(xs, (uint32_t)ired[2 * nw + k]); xr = max(xr, (uint32_t)ired[3 * nw + k]); xm = max(xm, (uint32_t)ired[4 * nw + k]);
             }
             src->ncontacts_ff = ta; src->ncontacts_fb = tb; src->max_cnt_ff = xa; src->max_cnt_fb = xb;
+            src->max_ref[0] = xs; src->max_ref[1] = xr; src->max_ref[2] = xm;
             if (ep.own) { src->ncontacts_own_ff = toa; src->ncontacts_own_fb = tob; }
         }
         __syncthreads();
@@ -904,6 +913,7 @@ __global__ __launch_bounds__(BLOCK) void k_publish_readback(Readback* __restrict
             pub_rb->ncontacts_ff = src->ncontacts_ff; pub_rb->ncontacts_fb = src->ncontacts_fb;
             pub_rb->max_cnt_ff = src->max_cnt_ff; pub_rb->max_cnt_fb = src->max_cnt_fb;
             pub_rb->ncontacts_own_ff = src->ncontacts_own_ff; pub_rb->ncontacts_own_fb = src->ncontacts_own_fb;
+            for (int k = 0; k < 3; ++k) pub_rb->max_ref[k] = src->max_ref[k];
         }
         if (end_of_step) {
             pub_rb->flags = src->flags;
@@ -962,6 +972,7 @@ void World::publish_wait(uint32_t seq, bool totals, bool lists, bool end_of_step
     if (lists) {
         h_rb->ncontacts_ff = p.ncontacts_ff; h_rb->ncontacts_fb = p.ncontacts_fb; h_rb->max_cnt_ff = p.max_cnt_ff; h_rb->max_cnt_fb = p.max_cnt_fb;
         h_rb->ncontacts_own_ff = p.ncontacts_own_ff; h_rb->ncontacts_own_fb = p.ncontacts_own_fb;
+        memcpy(h_rb->max_ref, p.max_ref, sizeof(p.max_ref));
     }
     if (end_of_step) {
         h_rb->flags = p.flags; memcpy(h_rb->bbox, p.bbox, sizeof(p.bbox));
@@ -1891,6 +1902,7 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     for (int attempt = 0;; ++attempt) {
     bool spec = can_speculate && attempt == 0;
     chain_pending = false;
+    ref_on_cur = false;
     const bool defer_lists = can_redo && !defer_off && attempt == 0 && lists_checked;
     if (attempt > 0) SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));  // (whatever the discarded pass flagged)
     const bool have_grid = adopted && attempt == 0;  // keys, sort, tile tables and the totals publication are enqueued already
@@ -2099,19 +2111,53 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
         if (class_ntiny || class_nlight) slot_order.ensure(nlaunch, stream, false, 1.5f);
         if (class_nlight) ++counters.light_class_passes;
         if (class_ntiny) ++counters.sparse_class_passes;
-        {
+        auto fill_tables = [&](bool again) {
             const uint32_t keep_t = class_ntiny, keep_l = class_nlight;
             class_ntiny = class_nlight = 0u;  // (the table builder itself runs over every slot in one launch)
             c = make_ctx();
+            // (again: behind a list build that kept the referenced slots only — tile_off back to the full box's counts first)
+            if (again) scan_tiles(cub_temp.p, tb, G().tile_cnt.p, G().tile_off.p, nslots_bound + 1, stream);
             launch_tile_halo_fill(c, halo_src.p, bhalo_src.p, slot_info.p, stream, (keep_t || keep_l) ? slot_order.p : nullptr, keep_l, keep_t);
             class_ntiny = keep_t; class_nlight = keep_l;
-        }
+        };
+        fill_tables(false);
         c = make_ctx();
+
+        // Referenced-only halo (device_types.h StepCtx::tile_off): the list builder drops the halo slots no list names — a seventh of
+        // the 6x6x6 box lies further than h from the own cube — and the solver kernels stage what is left.  It runs where that can
+        // XX
+        // the steps before the impact gain nothing), never in a speculative pass (whose tables are clamped), and with the V = 1
+        // builder only.  SALVA_HIP_FULL_HALO=1: never (the A/B); SALVA_HIP_REF_HALO=1: in every step (tests).
+        // The kept maxima are results of the builder.  Where the list statistics are waited for in the middle of the step the
+        // solver kernels are sized by them exactly; where they travel with the end-of-step publication (defer_lists) the kernels
+        // are sized by the PREVIOUS step's kept maxima plus a margin, never beyond the full box's: the builder holds every tile to
+        // those caps, raises flag 16 where one does not fit, and the pass is repeated with the full box's bounds — the way a list
+        // longer than the capacity is handled.
+        const bool beyond3 = tt.max_s > P3_DS_THREE || tt.max_raw > P2_DS_THREE || tt.max_sum > FIXED_DS_SMALL;
+        const bool ref_step = !ref_off && !spec && n > 0 && halo_stride > 0u && c.nmodels <= 32u && c.nbmodels <= 32u && (ref_forced || beyond3);
+        RefBuild refb{halo_src.p, slot_info.p, G().tile_off.p, RefCaps{0xffffffffu, 0xffffffffu, 0xffffffffu}, d_rb.p->max_ref};
+        ref_bounded = false;
+        if (ref_step && defer_lists && ref_pred_valid && ref_pred_n == n) {
+            // (the fullest kept halo moves by a few slots per step in a settled fluid and by a layer of particles — a hundred — when one
+            // crosses a tile face: an eighth of room, which costs LDS bytes only where no layout is at stake; a bound just above a
+            // three-per-CU layout is held to that layout while the prediction leaves it eight slots)
+            auto bound = [&](uint32_t pred, uint32_t full, uint32_t layout) {
+                if (ref_tight) return std::min(pred - pred / 8u, full);  // (tests: a bound every fullest tile outgrows)
+                uint32_t b = pred + std::max<uint32_t>(96u, pred / 8u);
+                if (b > layout && pred + 8u <= layout) b = layout;
+                return std::min(b, full);
+            };
+            refb.cap.s = bound(ref_pred[0], tt.max_s, P3_DS_THREE);
+            refb.cap.raw = std::max(bound(ref_pred[1], tt.max_raw, P2_DS_THREE), tt.max_sb);
+            refb.cap.sum = std::max(bound(ref_pred[2], tt.max_sum, FIXED_DS_SMALL), tt.max_sb);
+            ref_bounded = true;
+        }
 
         // ---- neighbour lists   (compute_contacts, contacts.rs:154-252): one pass into fixed-capacity ELL rows; if a list
         // turns out longer than the capacity the pass is repeated with room to spare (rare: the capacity follows the
         // longest list seen so far).  Speculative passes check at the end of the step instead.
         for (int nattempt = 0;; ++nattempt) {
+            if (nattempt > 0 && ref_step) { fill_tables(true); }  // (the first build compacted the slot tables in place)
             const bool r1 = nbr_ff.ensure((size_t)nslices * cap_ff * WAVE + 1, stream, false, 1.1f);
             const bool r2 = nbr_fb.ensure(nb ? (size_t)nslices * cap_fb * WAVE + 1 : 1, stream, false, 1.1f);
             slice_near.ensure((size_t)nslices + 1, stream, false, 1.1f);
@@ -2120,7 +2166,8 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
             // (a pass whose list statistics are only looked at with the end-of-step publication lets that publication fold them)
             fold_stats = (spec || defer_lists) && n > 0;
             launch_nbr_build(c, lds, tile_list_stats.p, fold_stats ? nullptr : reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff),
-                             &d_rb.p->max_cnt_ff, comm ? reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_own_ff) : nullptr, stream);
+                             &d_rb.p->max_cnt_ff, comm ? reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_own_ff) : nullptr, stream,
+                             ref_step ? &refb : nullptr);
             if (spec || defer_lists) break;
             static_assert(offsetof(Readback, max_cnt_ff) == offsetof(Readback, ncontacts_ff) + 2 * sizeof(uint64_t), "list statistics travel in one copy");
             publish_and_wait(nullptr, true, false);
@@ -2129,6 +2176,17 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
             if (nattempt >= 2) throw HipError(SALVA_HIP_E_HIP, "internal error: neighbour list capacity did not converge");
             if (need_ff > cap_ff) cap_ff = (need_ff + need_ff / 4 + 4u) & ~3u;
             if (need_fb > cap_fb) cap_fb = (need_fb + need_fb / 4 + 4u) & ~3u;
+        }
+        lds_full = lds; ref_last = ref_step; ref_last_caps = refb.cap; ref_last_nslots_bound = nslots_bound;
+        if (ref_step) {
+            // from here on the tiles hold their kept slots only, and the launches are cut for them
+            if (!defer_lists) { lds.max_halo_fluid = std::max<uint32_t>(h_rb->max_ref[0], 1u); lds.max_raw = h_rb->max_ref[1]; lds.max_sum = h_rb->max_ref[2]; }
+            else if (ref_bounded) { lds.max_halo_fluid = refb.cap.s; lds.max_raw = refb.cap.raw; lds.max_sum = refb.cap.sum; }
+            ref_on_cur = true;
+            ++ref_passes;
+            if (tile_trace && !defer_lists)
+                fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (exact)\n",
+                        tt.max_s, tt.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid);
         }
 #ifdef SALVA_HIP_DIAG
         // kernel-development builds: bank-conflict-aware list order (diag/sched.hip), SALVA_HIP_SCHED=1
@@ -2176,7 +2234,14 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     if (comm && prm.enable_timers) dist_time_fold();  // (the stream has drained up to the publication: every pair has completed)
     if (defer_lists && !spec) {
         const uint32_t need_ff = (h_rb->max_cnt_ff + 1) / 2, need_fb = (h_rb->max_cnt_fb + 1) / 2;
-        if (need_ff > cap_ff || need_fb > cap_fb) {
+        // (flag 16: a tile kept more halo slots than the launches of this pass were cut for — k_nbr_tile's REF part)
+        const bool ref_miss = ref_bounded && (h_rb->flags & 16u) != 0u;
+        if (ref_miss) { ref_pred_valid = false; ++ref_misses; }
+        if (ref_on_cur && tile_trace)
+            fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (%s)%s\n",
+                    lds_full.max_halo_fluid, lds_full.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid,
+                    ref_bounded ? "previous step + margin" : "full box", ref_miss ? " MISS: pass repeated" : "");
+        if (need_ff > cap_ff || need_fb > cap_fb || ref_miss) {
             // a list was cut at the capacity: everything this pass computed is discarded; the pre-sort buffers are intact
             ++counters.discarded_passes;
             cur = cur0; dt_prev = dt_prev0; inv_dt_prev = inv_dt_prev0;
@@ -2237,6 +2302,8 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
         if (stage == 0u) { st.n_pressure_iters = (int32_t)h_ctl[1].iters; st.density_error = h_ctl[1].err; }
     }
     pred_tt = h_rb->tile_total; pred_n = n; pred_valid = true;
+    if (ref_on_cur) { memcpy(ref_pred, h_rb->max_ref, sizeof(ref_pred)); ref_pred_n = n; ref_pred_valid = true; }
+    else ref_pred_valid = false;
     lists_checked = true;  // (every path to here has compared the longest lists with the capacity)
     break;
     }  // attempts
@@ -2278,7 +2345,7 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     }
     counters.cd.ncontacts = st.ncontacts;
     counters.n_divergence_iters = st.n_divergence_iters; counters.n_pressure_iters = st.n_pressure_iters;
-    st.reserved[0] = (float)lds.max_halo_fluid; st.reserved[1] = (float)lds.max_halo_boundary; st.reserved[2] = (float)lds.threads;
+    st.reserved[0] = (float)lds_full.max_halo_fluid;  /* (the full box's count, whatever the solver kernels staged: SALVA_HIP_TILE_TRACE prints both) */ st.reserved[1] = (float)lds.max_halo_boundary; st.reserved[2] = (float)lds.threads;
     st.reserved[3] = (float)((double)(h_rb->ncontacts_ff + (nb ? h_rb->ncontacts_fb : 0)) / (double)std::max<uint32_t>(n, 1u));  // list entries per local particle
     st.reserved[4] = (float)(n - owned_count());  // ghosts
     if (h_rb->flags & 1u) {
@@ -2292,6 +2359,10 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     if (h_rb->flags & 8u) {
         bbox_known = false;
         throw HipError(SALVA_HIP_E_HIP, "internal error: a third particle mass in a world the host took for a two-mass world");
+    }
+    if (h_rb->flags & 16u) {
+        bbox_known = false;
+        throw HipError(SALVA_HIP_E_HIP, "internal error: a referenced halo beyond its bound in a pass that had none");
     }
     if (h_rb->flags & 4u)
         // k_dist_flags: such a particle was handed to the adjacent rank, which does not own its cells either — it would
@@ -3318,6 +3389,44 @@ float World::time_pred_density(int reps) {
 
 // Average duration (microseconds) of one launch of a neighbour-sum kernel on the last step's lists (HIP events on the world's
 // stream): 0 k_pred_density, 1 k_divergence, 2 k_iisph_next_pressure, 3 k_iisph_dij_pj.  Scratch outputs only.
+void World::tile_tables(uint32_t slot, uint32_t* info, uint32_t* halo_row, uint32_t cap_row, uint32_t* counts, uint32_t cap_counts, uint32_t* entries,
+                        uint32_t cap_entries) {
+    use_device();
+    if (!have_last_ctx || !sorted_valid || n == 0) throw HipError(SALVA_HIP_E_INVALID, "no completed step to look at");
+    const StepCtx& c = last_ctx;
+    if (slot >= c.nlaunch) throw HipError(SALVA_HIP_E_INVALID, "no such tile slot");
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    TileAcc a[2];
+    uint4 desc;
+    SALVA_HIP_CHECK(hipMemcpy(a, c.tile_off + slot, sizeof(a), hipMemcpyDeviceToHost));
+    SALVA_HIP_CHECK(hipMemcpy(&desc, c.slot_desc + slot, sizeof(desc), hipMemcpyDeviceToHost));
+    const uint32_t S = (uint32_t)(a[1].s - a[0].s), SB = (uint32_t)(a[1].sb - a[0].sb), own_n = desc.z - desc.y;
+    const uint64_t hoff = c.halo_stride ? (uint64_t)slot * c.halo_stride : a[0].s;
+    memset(info, 0, 16 * sizeof(uint32_t));
+    info[0] = c.nlaunch; info[1] = desc.y; info[2] = desc.z; info[3] = S; info[4] = SB;
+    info[5] = lds.max_halo_fluid; info[6] = lds.raw_slots(); info[7] = lds.sum_slots(); info[8] = lds_full.max_halo_fluid;
+    info[9] = ref_last ? 1u : 0u; info[10] = (uint32_t)ref_passes; info[11] = (uint32_t)ref_misses;
+    if (halo_row && cap_row && S)
+        SALVA_HIP_CHECK(hipMemcpy(halo_row, c.halo_src + hoff, (size_t)std::min(S, cap_row) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!own_n) return;
+    std::vector<uint32_t> cnt(own_n);
+    SALVA_HIP_CHECK(hipMemcpy(cnt.data(), c.nff + desc.y, (size_t)own_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (counts) memcpy(counts, cnt.data(), (size_t)std::min(own_n, cap_counts) * sizeof(uint32_t));
+    if (!entries || !cap_entries) return;
+    const uint32_t nsl = (own_n + WAVE - 1) / WAVE;
+    std::vector<uint32_t> blk((size_t)nsl * c.cap_ff * WAVE);
+    SALVA_HIP_CHECK(hipMemcpy(blk.data(), c.nbr_ff + (size_t)a[0].nsl * c.cap_ff * WAVE, blk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    uint32_t o = 0;
+    for (uint32_t k = 0; k < own_n; ++k) {
+        const uint32_t* p = blk.data() + (size_t)(k / WAVE) * c.cap_ff * WAVE + 4u * (k % WAVE);
+        for (uint32_t e = 0; e < cnt[k] && o < cap_entries; ++e) {
+            const uint32_t d = p[ellq(e >> 1)];
+            entries[o++] = (e & 1u) ? (d >> 16) : (d & 0xffffu);
+        }
+    }
+    info[12] = o;
+}
+
 float World::time_kernel(int kernel, int reps) {
     use_device();
     if (!have_last_ctx || !sorted_valid || n == 0) throw HipError(SALVA_HIP_E_INVALID, "no completed step to time");
@@ -3380,6 +3489,19 @@ float World::time_kernel(int kernel, int reps) {
                      // particle's cell is taken from its sorted key (as after a DynamicContactSampling push-out): without that a
                      // particle that left its cell indexes the tile's cell table out of range and the kernel never returns.
                 cd.stale_keys = G().keys[1].p;
+                if (ref_last) {
+                    // (the step compacted its slot tables in place: every build starts from the full box's tables again, so the
+                    // figure holds the tile scan and k_tile_halo_fill as well)
+                    StepCtx cf = cd;
+                    cf.slot_order = nullptr; cf.ntiny = cf.nlight = 0u; cf.slot_base = 0u;
+                    const size_t tb = scan_tiles_temp_bytes(ref_last_nslots_bound + 1);
+                    ensure_cub_temp(tb);
+                    scan_tiles(cub_temp.p, tb, G().tile_cnt.p, G().tile_off.p, ref_last_nslots_bound + 1, stream);
+                    launch_tile_halo_fill(cf, halo_src.p, bhalo_src.p, slot_info.p, stream);
+                    const RefBuild rb{halo_src.p, slot_info.p, G().tile_off.p, ref_last_caps, d_rb.p->max_ref};
+                    launch_nbr_build(cd, lds_full, tile_list_stats.p, reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff), &d_rb.p->max_cnt_ff, nullptr, stream, &rb);
+                    break;
+                }
                 launch_nbr_build(cd, lds, tile_list_stats.p, reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff), &d_rb.p->max_cnt_ff, nullptr, stream);
                 break;
 #ifdef SALVA_HIP_DIAG

@@ -1486,6 +1486,19 @@ class LiquidWorld:
             L.check(int(us))
         return us, int(cs.value)
 
+    def tile_tables(self, slot: int):
+        """The tile tables of the last step for one non-empty tile (salva_hip_get_tile_tables): (info[16], halo_row, counts, entries)."""
+        info = np.zeros(16, np.uint32)
+        L.check(self._L.salva_hip_get_tile_tables(self._h, slot, info.ctypes.data, None, 0, None, 0, None, 0))
+        row = np.zeros(max(int(info[3]), 1), np.uint32)
+        counts = np.zeros(max(int(info[2] - info[1]), 1), np.uint32)
+        L.check(self._L.salva_hip_get_tile_tables(self._h, slot, info.ctypes.data, row.ctypes.data, len(row), counts.ctypes.data, len(counts), None, 0))
+        counts = counts[:int(info[2] - info[1])]
+        entries = np.zeros(max(int(counts.sum()), 1), np.uint32)
+        L.check(self._L.salva_hip_get_tile_tables(self._h, slot, info.ctypes.data, row.ctypes.data, len(row), counts.ctypes.data, max(len(counts), 1),
+                                                  entries.ctypes.data, len(entries)))
+        return info, row[:int(info[3])], counts, entries[:int(info[12])]
+
     def time_kernel(self, kernel: int, reps: int = 20) -> float:
         """Average launch duration (us) of 0 k_pred_density, 1 k_divergence, 2 k_iisph_next_pressure, 3 k_iisph_dij_pj."""
         us = float(self._L.salva_hip_time_kernel(self._h, kernel, reps))
