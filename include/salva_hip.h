@@ -327,7 +327,12 @@ float salva_hip_time_pred_density(SalvaHipWorld* world, int32_t reps);
  * of w).  The IISPH kernels rewrite scratch only (next pressures into the spare buffer).  7 and 8: the rotation + stress pass and
  * the force pass of the first Becker2009Elasticity entry (N_e (4K_e + 164) and N_e (4K_e + 148) + N 28; the
  * rotation pass writes copies of the stresses and gradients, the force pass adds to a copy of the accelerations: the state keeps what
- * the step computed). */
+ * the step computed).
+ * Every id leaves the particle state and the run that follows untouched (tests/test_time_kernel_gpu.py).  Kernel 4 is the one id
+ * that rewrites something a reader can see: it builds the lists again from the positions as they are AFTER the step (behind a step
+ * that kept the referenced halo: the tile scan, the slot tables and their compaction as well), so until the next step the contact
+ * counts, salva_hip_get_fluid_contacts / _get_local_contacts and salva_hip_get_tile_tables describe THOSE lists, not the step's:
+ * read the step's contacts before timing kernel 4.  The next step rebuilds all of it. */
 float salva_hip_time_kernel(SalvaHipWorld* world, int32_t kernel, int32_t reps);
 /* The tile tables of the last step as the tile kernels behind the list builder read them (tests of the referenced-only halo; not a
  * hot path).  `slot` = index among the step's non-empty tiles.  info[16]: 0 number of slots, 1 / 2 the slot's own particles

@@ -183,6 +183,11 @@ struct StepCtx {
     float4* bvel;        // (vx, vy, vz, boundary model id)
     uint32_t* bperm;     // sorted -> canonical boundary index
     float4* bforce;      // canonical order accumulators (nullptr if no boundary wants forces)
+    // what a step's kernels add to: three 64-bit fixed-point sums per boundary particle (canonical order), in units of
+    // 1 / bforce_scale.  Integer addition is associative, so the sum does not depend on the order the atomics land in — float
+    // atomics made boundary.forces differ in the last bits from run to run.  World::substep folds them into bforce at its end.
+    unsigned long long* bforce_fx;
+    float bforce_scale;
     const uint8_t* bwants;  // per boundary model: forces requested?
     TileGrid gb;
 

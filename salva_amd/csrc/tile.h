@@ -1144,10 +1144,11 @@ struct TileErrC {
 __device__ __forceinline__ void apply_boundary_force(const StepCtx& c, uint32_t jb_sorted, uint32_t bmodel, float fx,
                                                      float fy, float fz) {
     if (c.bforce == nullptr || !c.bwants[bmodel]) return;
-    float* f = reinterpret_cast<float*>(&c.bforce[c.bperm[jb_sorted]]);
-    atomicAdd(f + 0, fx);
-    atomicAdd(f + 1, fy);
-    atomicAdd(f + 2, fz);
+    // (fixed point: the same sum whatever the order of arrival, device_types.h StepCtx::bforce_fx)
+    unsigned long long* f = c.bforce_fx + 3ull * c.bperm[jb_sorted];
+    atomicAdd(f + 0, (unsigned long long)__float2ll_rn(fx * c.bforce_scale));
+    atomicAdd(f + 1, (unsigned long long)__float2ll_rn(fy * c.bforce_scale));
+    atomicAdd(f + 2, (unsigned long long)__float2ll_rn(fz * c.bforce_scale));
 }
 __device__ __forceinline__ uint32_t boundary_sorted_of_slot(const StepCtx& c, const Tile& t, uint32_t slot) {
     return c.bhalo_src[t.hboff + slot];

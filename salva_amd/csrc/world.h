@@ -339,6 +339,9 @@ class World {
     // boundaries: canonical + sorted
     DevBuf<float4> bst_pos, bst_vel;
     DevBuf<float4> bposv, bvel, bforce;
+    DevBuf<unsigned long long> bforce_fx;  // this step's reaction forces in fixed point (StepCtx::bforce_fx); all zero between steps
+    uint32_t bforce_fx_n = 0;              // boundary particles it is zeroed for
+    float bforce_scale() const;            // a power of two: 2^-36 of the force that accelerates a particle's mass by 1 m/s^2
     DevBuf<uint32_t> bperm, cell_start_b, bkeys[2], bidx[2];
     bool b_dirty = true;
     uint64_t ncontacts_bb = 0;

@@ -48,6 +48,19 @@ __global__ void k_pack_w(uint32_t n, const float* __restrict__ src, float4* __re
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < n) reinterpret_cast<float*>(&dst[i])[3] = src[i];
 }
+// StepCtx::bforce_fx -> boundary.forces: the substep's fixed-point sums are added to the float accumulators and cleared
+__global__ void k_bforce_fold(uint32_t nb, unsigned long long* __restrict__ fx, float4* __restrict__ bforce, float inv_scale) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb) return;
+    unsigned long long* f = fx + 3ull * i;
+    float4 b = bforce[i];
+    b.x += (float)((double)(long long)f[0] * (double)inv_scale);
+    b.y += (float)((double)(long long)f[1] * (double)inv_scale);
+    b.z += (float)((double)(long long)f[2] * (double)inv_scale);
+    bforce[i] = b;
+    f[0] = f[1] = f[2] = 0ull;
+}
+
 __global__ void k_fill_f4(uint32_t n, float4* __restrict__ dst, float4 v, int keep_w) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -689,8 +702,18 @@ void World::upload_tables() {
     b_dirty = true;  // group changes alter the boundary-boundary sums
 }
 
+float World::bforce_scale() const {
+    const float r = prm.particle_radius;
+    return std::exp2f(36.0f - std::ceil(std::log2(1000.0f * r * r * r)));
+}
+
 StepCtx World::make_ctx() {
     StepCtx c{};
+    if (any_wants_forces && bforce_fx_n != nb) {  // (all zero between steps: a change of the boundary set starts from zeros again)
+        bforce_fx.ensure(3 * (size_t)std::max<uint32_t>(nb, 1u), stream, false, 1.2f);
+        SALVA_HIP_CHECK(hipMemsetAsync(bforce_fx.p, 0, 3 * (size_t)std::max<uint32_t>(nb, 1u) * sizeof(unsigned long long), stream));
+        bforce_fx_n = nb;
+    }
     c.sc = sc;
     {   // groups of 64 slots (what one XCD's 32 CUs hold at a time), fewer for launches of less than 1024 tiles
         uint32_t lg = 1u;
@@ -718,6 +741,8 @@ StepCtx World::make_ctx() {
     c.nb = nb;
     c.bposv = bposv.p; c.bvel = bvel.p; c.bperm = bperm.p;
     c.bforce = any_wants_forces ? bforce.p : nullptr;
+    c.bforce_fx = any_wants_forces ? bforce_fx.p : nullptr;
+    c.bforce_scale = bforce_scale();
     c.bwants = bwants.p;
     c.gb = gb.device(cell_start_b.p);
     c.nmodels = (uint32_t)std::max<size_t>(fluids.size(), 1);
@@ -2308,6 +2333,8 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     break;
     }  // attempts
     commit_elastic();
+    // the reaction forces of this substep, summed in fixed point: into boundary.forces, and back to zero
+    if (any_wants_forces && nb) k_bforce_fold<<<nblk(nb), BLOCK, 0, stream>>>(nb, bforce_fx.p, bforce.p, 1.0f / bforce_scale());
     acc_user = false;
     // decomposed runs: the contacts whose first particle this rank owns (fluid) / whose first particle lies in its slab
     // (boundary-boundary, k_boundary_volumes) — the ranks' counts add up to the undivided domain's counters.cd.ncontacts

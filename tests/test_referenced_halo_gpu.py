@@ -8,77 +8,15 @@ through the compacted table: the same source particle, in the same place, as wit
 
 SALVA_HIP_REF_HALO=1 builds it in every step (by default only where some halo is beyond a three-per-CU layout), SALVA_HIP_FULL_HALO=1
 never."""
-import os
-
 import numpy as np
 import pytest
 
-from parity import DT, GRAVITY, Scene
+from parity import Scene
+from ref_halo_ab import (FIXED_DS_SMALL, OFF, ON, P2_DS_THREE, P3_DS_THREE, R, _bench_block, _make, _run, _same,  # noqa: F401 - the shared A/B harness
+                         _same_exports)
 from salva_amd import scenes
 
 pytestmark = pytest.mark.gpu
-R = 0.025
-SWITCHES = ("SALVA_HIP_FULL_HALO", "SALVA_HIP_REF_HALO", "SALVA_HIP_NO_SPLIT", "SALVA_HIP_FOLD_CELLS", "SALVA_HIP_CLASSES", "SALVA_HIP_NO_PLANES",
-            "SALVA_HIP_REF_TIGHT")
-ON, OFF = {"SALVA_HIP_REF_HALO": "1"}, {"SALVA_HIP_FULL_HALO": "1"}
-# what a step's launches were cut for and what was built, from LiquidWorld.tile_tables (salva_hip_get_tile_tables): info[5] / [6] / [7] =
-# the fluid | fluid + boundary | padded fluid + boundary halo that picks the layouts (pairs.h pick_ds_p3 / pick_ds_p2 / pick_ds),
-# [8] the fullest box, [9] = 1 when the step kept the referenced slots only, [10] / [11] such passes so far / those repeated
-P3_DS_THREE, P2_DS_THREE, FIXED_DS_SMALL = 2080, 2464, 2448  # tile.h
-
-
-def _make(env, scene):
-    old = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update(env)
-    try:
-        return scene.make_hip()
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
-def _run(env, scene, nsteps, look=(0, 1, -1)):
-    w, fls, _ = _make(env, scene)
-    look = {k % nsteps for k in look}
-    trace, halos, seen, infos = [], [], [], []
-    for k in range(nsteps):
-        st = w.step(DT, GRAVITY)
-        trace.append((st.n_divergence_iters, st.n_pressure_iters, int(st.ncontacts)))
-        halos.append(int(st.reserved[0]))
-        infos.append(w.tile_tables(0)[0])
-        if k in look:
-            seen.append([w.fluid_contacts(f) for f in fls] + [w.fluid_contacts(f, True) for f in fls])
-    return w, fls, trace, halos, seen, infos
-
-
-def _same(wa, fa, wb, fb):
-    for x, y in zip(fa, fb):
-        assert np.array_equal(x.positions, y.positions) and np.array_equal(x.velocities, y.velocities)
-        assert np.array_equal(wa.densities(x), wb.densities(y))
-        assert np.array_equal(wa.contact_counts(x), wb.contact_counts(y)) and np.array_equal(wa.contact_counts(x, True), wb.contact_counts(y, True))
-
-
-def _same_exports(sa, sb):
-    assert len(sa) == len(sb) > 0
-    for a, b in zip(sa, sb):
-        for (o1, m1, j1), (o2, m2, j2) in zip(a, b):
-            assert np.array_equal(o1, o2) and np.array_equal(m1, m2) and np.array_equal(j1, j2)  # the same neighbours, in the same ORDER
-
-
-def _bench_block(side, solver="dfsph", forces=(("xsph", 0.5, 0.0),), strays=0):
-    """The bench scene at a reduced side: a jittered block in a tank, falling."""
-    s = Scene(R, 2.0, solver)
-    fluid, shell = scenes.tank(side, side, side, R)
-    fluid = scenes.jitter(fluid, 0.1 * R, seed=11)
-    if strays:  # single particles far from the block and from each other: one tile each (the sparse class)
-        rng = np.random.default_rng(5)
-        far = (fluid.max(axis=0) + np.float32(40 * R) + rng.uniform(0.0, 400 * R, size=(strays, 3))).astype(np.float32)
-        fluid = np.ascontiguousarray(np.concatenate([fluid, far]))
-    s.add_fluid(fluid, scenes.random_velocities(len(fluid), 0.2, seed=4), 1000.0, forces=list(forces))
-    s.add_boundary(shell)
-    return s
 
 
 def _two_fluids():
