@@ -1,4 +1,4 @@
-// device_types.h — kernel argument bundles and the launcher interface between world.hip (host
+// device_types.h — kernel argument bundles and the launcher interface between world.hip / world_step.hip (host
 // orchestration) and the kernel translation units (grid.hip, dfsph.hip, iisph.hip, forces.hip).
 //
 // Data layout in HBM: every per-particle array is SoA over the *cell-sorted* particle
@@ -55,12 +55,12 @@ struct TileAcc {
     uint32_t max_sum;  // running maximum of (fluid halo slots padded to 64) + (boundary halo slots) of one tile (TileLds::max_sum)
     uint32_t max_raw;  // running maximum of (fluid halo slots) + (boundary halo slots) of one tile, no padding: the plane layouts
                        // (tile.h stage_p3), which are filled through registers, slot by slot
-    uint32_t wsl;      // sum of (slices of the tile)^2: wsl / nsl = the slice count of the tile the average PARTICLE lives in (world.hip:
+    uint32_t wsl;      // sum of (slices of the tile)^2: wsl / nsl = the slice count of the tile the average PARTICLE lives in (World::size_pass:
                        // the workgroup size)
     uint32_t ntiny;    // slots of the SPARSE class (tile.h TILE_TINY_*: one slice of own particles, a halo of a few cells' worth): a
                        // prefix gives a sparse slot its rank among its kind, the total decides whether they get a launch of their own
     uint32_t heavy;    // slots that are PARTS of a split tile + whole tiles whose fluid halo is beyond the three-tiles-per-CU layouts
-                       // (tile.h TILE_SPLIT_S): what World::substep decides the next step's splitting by
+                       // (tile.h TILE_SPLIT_S): what World::size_pass decides the next step's splitting by
     uint32_t nlight;   // slots of the LIGHT class (tile.h tile_is_light: not sparse, and the halo fits the smallest compile-time layout
                        // of every kernel family): when other slots of the step do not, these get a launch of their own on that layout
     __host__ __device__ TileAcc operator+(const TileAcc& o) const {
@@ -185,7 +185,7 @@ struct StepCtx {
     float4* bforce;      // canonical order accumulators (nullptr if no boundary wants forces)
     // what a step's kernels add to: three 64-bit fixed-point sums per boundary particle (canonical order), in units of
     // 1 / bforce_scale.  Integer addition is associative, so the sum does not depend on the order the atomics land in — float
-    // atomics made boundary.forces differ in the last bits from run to run.  World::substep folds them into bforce at its end.
+    // atomics made boundary.forces differ in the last bits from run to run.  World::finish_substep folds them into bforce.
     unsigned long long* bforce_fx;
     float bforce_scale;
     const uint8_t* bwants;  // per boundary model: forces requested?

@@ -57,6 +57,12 @@ struct GridDims {          // tile-aligned dense grid (tile.h)
     size_t ncells() const { return ntiles() * TCELLS; }
 };
 
+// helpers world.hip and world_step.hip share (bits_for and dims_from_bbox are defined in world.hip)
+inline unsigned nblk(uint64_t n) { return div_up(n ? n : 1, BLOCK); }
+int bits_for(uint64_t ncells);  // key bits of a radix sort over `ncells` cells
+struct FoldRule { double budget, target; uint32_t min_period[3]; bool axis[3]; };  // fold when the box exceeds `budget` cells, then down to `target`; axis[a]: may fold
+void dims_from_bbox(const int32_t* bb, GridDims& g, const FoldRule* fold = nullptr);
+
 class World {
   public:
     explicit World(const SalvaHipParams& p);
@@ -155,6 +161,8 @@ class World {
     void upload_tables();
     void build_boundary_grid();
     void resize_boundary_slot(uint32_t slot, uint64_t nn);
+    void stamp_fluid_models();
+    void stamp_boundary_models();
     bool has_dynamic_sampling() const;
     void run_dynamic_sampling();   // between the cell keys and the sort (fluids_pipeline.rs:193-259 inside liquid_world.rs:94-103)
     DevBuf<float4> dcs_cand, dcs_out, dcs_proj, dcs_cand2;  // (_proj, _cand2: the host-shape arm)
@@ -188,6 +196,7 @@ class World {
     DevBuf<SolveCtl> spec_ring;   // their two alternating control records
     bool spec_apply_off = false;  // SALVA_HIP_NO_SPEC_APPLY (A/B, tests)
     void wait_stream();  // low-latency wait for the world's stream (spins on an event)
+    template <typename Arrived> void spin_until(Arrived&& arrived, const char* drained);  // ... for a host-mapped word (world_step.hip)
     void run_forces(const StepCtx& c);
     void run_elasticity(const StepCtx& c, uint32_t slot, uint32_t force);
     ElasticState& elastic_state(uint32_t slot, uint32_t force);
@@ -197,6 +206,35 @@ class World {
     void dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, int resume = 0);  // dt: in = the step, out = the substep advanced by
     void iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st);
     int substep(float& dt, const float g[3], SalvaHipStepStats& st);  // one pass of the reference's substep loop (liquid_world.rs:85-147)
+    // ---- the phases of a substep, in the order it runs them (world_step.hip).  What they share travels in a Pass; PassSnapshot is
+    // the one place that knows what a discarded pass has to put back.
+    struct GridTabs;
+    struct GridShape;
+    struct Attempt;
+    struct Pass;
+    struct PassSnapshot;
+    void prepare_working_set(SalvaHipStepStats& st);
+    GridShape choose_grid();
+    void ensure_slot_tables(uint32_t nslots_bound);
+    bool run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st);
+    void enqueue_grid_keys(GridTabs& T, const GridShape& gs, bool counting, bool mass, const uint32_t* gate);
+    void enqueue_grid_sort(GridTabs& T, const GridShape& gs, bool counting, const uint32_t* gate);
+    size_t tile_scan_temp(const GridShape& gs);
+    uint32_t enqueue_grid_tiles(GridTabs& T, const GridShape& gs, StepCtx c, size_t tb, const uint32_t* gate, bool publish);
+    bool predict_totals(const GridShape& gs, TileAcc& tt) const;
+    void reorder_working_set(bool timers);
+    void size_pass(Pass& p, uint32_t seq_totals);
+    void fill_tile_tables(Pass& p, bool again);
+    void build_lists(Pass& p);
+    void density_and_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers);
+    void publish_end_of_step(const Pass& p, const PassSnapshot& snap);
+    void adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers);
+    int finish_substep(const Pass& p, float dt, SalvaHipStepStats& st);
+    void record_timers(const Pass& p, SalvaHipStepStats& st);
+    void raise_step_flags();
+    bool has_force(int kind) const;                        // some fluid carries a force of this kind
+    bool counting_sort_for(size_t ncf, uint32_t np) const;  // the counting sort by cell serves a table of ncf cells over np particles
+    void grow_list_caps(uint32_t need_ff, uint32_t need_fb);
     // Opt-in CFL sub-stepping (salva_hip_set_cfl): TimestepManager's cfl_coeff / min / max_num_substeps (timestep_manager.rs:23-34)
     // and the clamp its compute_substep left commented out (:90-93).  0 = off: one substep per step, as the reference runs.
     int cfl_mode = 0;
@@ -289,7 +327,7 @@ class World {
                                   // tools/r06/multi_mass_probe.py) the general kernels are 8-10 % faster than the segments of three and four masses
     bool two_mass_off = false;    // SALVA_HIP_NO_TWO_MASS=1 (A/B, tests): such a world keeps the general kernels
     bool fold_off = false;        // SALVA_HIP_NO_FOLD=1: the fluid grid is never folded (device_types.h TileGrid)
-    struct FoldRetry {};          // thrown by substep when the tile totals show a fold that piled the bulk onto itself (World::step retries)
+    struct FoldRetry {};          // thrown by World::choose_grid / size_pass when the tile totals show a fold that piled the bulk onto itself (World::step retries)
     uint32_t fold_relax = 0;      // how often that happened: the fold rule is loosened eightfold per level, given up at 3
     bool fold_locked = false;     // the looser fold did not fit the cell-table budget: keep the tighter one
     uint32_t fold_forced = 0;     // SALVA_HIP_FOLD_CELLS=P: every axis longer than P cells is folded to exactly P (tests)
@@ -396,7 +434,7 @@ class World {
     bool classes_off = false, classes_forced = false, light_on = false;  // SALVA_HIP_NO_CLASSES=1 / SALVA_HIP_CLASSES=1 / SALVA_HIP_LIGHT=1 (the light class: opt-in, it lost)
     // splitting of over-full tiles (device_types.h StepCtx::split_s)
     bool split_off = false;        // SALVA_HIP_NO_SPLIT=1
-    // Referenced-only halo (device_types.h StepCtx::tile_off; World::substep)
+    // Referenced-only halo (device_types.h StepCtx::tile_off; World::size_pass / build_lists, world_step.hip)
     bool ref_off = false, ref_forced = false;  // SALVA_HIP_FULL_HALO=1 (A/B: stage the full box) / SALVA_HIP_REF_HALO=1 (in every step: tests)
     bool ref_tight = false;        // SALVA_HIP_REF_TIGHT=1 (tests): cut the launches for LESS than the previous step's kept maxima — every such pass misses
     bool ref_on_cur = false;       // this pass's list build kept the referenced slots only
@@ -414,10 +452,10 @@ class World {
     int32_t bbox_used_last[6] = {0, 0, 0, 0, 0, 0};  // the cell box the previous step ran on
     bool bbox_used_valid = false;
     uint64_t pre_adopted = 0, pre_dropped = 0;
-    void pre_enqueue_grid(uint32_t nslots_bound);
+    void pre_enqueue_grid(const GridShape& gs);
     void pre_drop();
     void publish_wait(uint32_t seq, bool totals, bool lists, bool end_of_step);
-    // what the next end-of-step publication folds (world.hip Epilogue): the list statistics of this pass, the position update's boxes
+    // what the next end-of-step publication folds (world_step.hip Epilogue): the list statistics of this pass, the position update's boxes
     bool fold_stats = false;
     uint32_t fold_bbox_blocks = 0;
     const uint32_t* fold_bbox_gate = nullptr;

@@ -1,0 +1,1531 @@
+// world_step.hip — the step path of libsalva_hip's host side: World::step and the phases of World::substep, the solves they run and the
+// host <-> device publications they wait for.  (world.hip: construction, object edits, tables, queries, downloads.)
+//
+// Restates the control flow of /root/reference/src/liquid_world.rs:67-158 (step_with_coupling with the no-op
+// `()` coupling manager), src/solver/pressure/dfsph_solver.rs:667-708 (DFSPH step, iteration protocol :432-503)
+// and src/solver/pressure/iisph_solver.rs:643-711 on top of the kernels in grid/dfsph/iisph/forces.hip.
+// `step` works on HBM-resident state and reads back a few scalars (convergence errors, list sizes, the next cell bounding box).
+#include "world.h"
+#include "bbox.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cstddef>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <limits>
+
+namespace salva {
+
+// StepCtx::bforce_fx -> boundary.forces: the substep's fixed-point sums are added to the float accumulators and cleared
+__global__ void k_bforce_fold(uint32_t nb, unsigned long long* __restrict__ fx, float4* __restrict__ bforce, float inv_scale) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb) return;
+    unsigned long long* f = fx + 3ull * i;
+    float4 b = bforce[i];
+    b.x += (float)((double)(long long)f[0] * (double)inv_scale);
+    b.y += (float)((double)(long long)f[1] * (double)inv_scale);
+    b.z += (float)((double)(long long)f[2] * (double)inv_scale);
+    bforce[i] = b;
+    f[0] = f[1] = f[2] = 0ull;
+}
+
+// The convergence loops read one float back per iteration; an interrupt-driven hipStreamSynchronize costs tens of
+// microseconds per wake-up, polling an event a few.
+// The per-step read-backs without a copy engine: one wave copies the few words the host is waiting for into host-mapped memory,
+// fences to system scope, then bumps the sequence word the host polls.  (A hipMemcpyAsync + event costs ~20 us of idle GPU each
+// time the host has to wait for it: tools/gap_tsv_report.py.)
+// What an end-of-step publication folds before it publishes (round 6: one launch where k_list_stats, k_bbox_final and the publication
+// were three, each a few microseconds long with a launch gap on either side).
+struct Epilogue {
+    const TileListStats* ts; uint32_t nts; int own;   // k_nbr_tile's per-tile list statistics -> ncontacts_*, max_cnt_* (nullptr: k_list_stats ran)
+    const int32_t* bbox_partials; uint32_t nbb;        // the position update's per-block cell boxes -> bbox (nullptr: nothing to fold)
+    const uint32_t* chain_gate;                        // ... which was gated by this word (a chained step; nullptr: it ran)
+};
+__global__ __launch_bounds__(BLOCK) void k_publish_readback(Readback* __restrict__ src, const TileAcc* __restrict__ totals, int lists, int end_of_step,
+                                                            uint32_t* mass_slots, Readback* pub_rb, volatile uint32_t* pub_seq, uint32_t seq,
+                                                            const SolveCtl* __restrict__ ctl, PrePub pre, const uint32_t* gate, Epilogue ep) {
+    if (gate && *gate == 0u) return;  // (the totals of a pre-enqueued grid that did not come true: nobody waits for them)
+    __shared__ unsigned long long sred[4][BLOCK / WAVE];
+    __shared__ int ired[6 * (BLOCK / WAVE)];
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
+    if (ep.ts) {  // (block-uniform) the fold of k_list_stats, grid.hip
+        unsigned long long a = 0, b = 0, oa = 0, ob = 0;
+        uint32_t ma = 0, mb = 0, rs = 0, rr = 0, rm = 0;
+        for (uint32_t k = threadIdx.x; k < ep.nts; k += blockDim.x) {
+            const TileListStats t = ep.ts[k];
+            a += t.sum_ff; b += t.sum_fb; oa += t.own_ff; ob += t.own_fb; ma = max(ma, t.max_ff); mb = max(mb, t.max_fb);
+            if (t.ref_s) { rs = max(rs, t.ref_s); rr = max(rr, t.ref_s + t.ref_sb); rm = max(rm, ((t.ref_s + 63u) & ~63u) + t.ref_sb); }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a += __shfl_xor(a, o, WAVE); b += __shfl_xor(b, o, WAVE);
+            oa += __shfl_xor(oa, o, WAVE); ob += __shfl_xor(ob, o, WAVE);
+        }
+        ma = wave_max_u32(ma); mb = wave_max_u32(mb); rs = wave_max_u32(rs); rr = wave_max_u32(rr); rm = wave_max_u32(rm);
+        if (lane == 0) {
+            sred[0][wv] = a; sred[1][wv] = b; sred[2][wv] = oa; sred[3][wv] = ob; ired[wv] = (int)ma; ired[nw + wv] = (int)mb;
+            ired[2 * nw + wv] = (int)rs; ired[3 * nw + wv] = (int)rr; ired[4 * nw + wv] = (int)rm;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long ta = 0, tb = 0, toa = 0, tob = 0; uint32_t xa = 0, xb = 0, xs = 0, xr = 0, xm = 0;
+            for (int k = 0; k < nw; ++k) {
+                ta += sred[0][k]; tb += sred[1][k]; toa += sred[2][k]; tob += sred[3][k];
+                xa = max(xa, (uint32_t)ired[k]); xb = max(xb, (uint32_t)ired[nw + k]);
+                xs = max(xs, (uint32_t)ired[2 * nw + k]); xr = max(xr, (uint32_t)ired[3 * nw + k]); xm = max(xm, (uint32_t)ired[4 * nw + k]);
+            }
+            src->ncontacts_ff = ta; src->ncontacts_fb = tb; src->max_cnt_ff = xa; src->max_cnt_fb = xb;
+            src->max_ref[0] = xs; src->max_ref[1] = xr; src->max_ref[2] = xm;
+            if (ep.own) { src->ncontacts_own_ff = toa; src->ncontacts_own_fb = tob; }
+        }
+        __syncthreads();
+    }
+    if (ep.bbox_partials && !(ep.chain_gate && gate_words_closed(ep.chain_gate[0], ep.chain_gate[1], 0u))) {  // the fold of k_bbox_final
+        int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+        for (uint32_t k = threadIdx.x; k < ep.nbb; k += blockDim.x) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], ep.bbox_partials[6 * k + a]); mx[a] = max(mx[a], ep.bbox_partials[6 * k + 3 + a]); }
+        }
+        block_bbox_store(mn, mx, ired, src->bbox);  // (ends with a barrier: thread 0 below reads what threads 0..5 stored)
+        __threadfence_block();
+    }
+    uint32_t mlo = 0u, mhi = 0u;
+    if (totals && wv == 0) {  // did k_cell_keys see a mass other than particle 0's since the last such publication?  start the next one
+        static_assert(MASS_SLOTS == WAVE, "one flag per lane of the publishing wave");
+        const uint32_t differs = wave_max_u32(mass_slots[lane]);
+        mass_slots[lane] = 0u;
+        mlo = mass_slots[MASS_SLOTS];
+        mhi = differs ? ~mlo : mlo;
+    }
+    if (threadIdx.x == 0) {
+        if (totals) {
+            pub_rb->tile_total = *totals;
+            pub_rb->mass_mm[0] = mlo; pub_rb->mass_mm[1] = mhi;
+        }
+        if (lists) {
+            pub_rb->ncontacts_ff = src->ncontacts_ff; pub_rb->ncontacts_fb = src->ncontacts_fb;
+            pub_rb->max_cnt_ff = src->max_cnt_ff; pub_rb->max_cnt_fb = src->max_cnt_fb;
+            pub_rb->ncontacts_own_ff = src->ncontacts_own_ff; pub_rb->ncontacts_own_fb = src->ncontacts_own_fb;
+            for (int k = 0; k < 3; ++k) pub_rb->max_ref[k] = src->max_ref[k];
+        }
+        if (end_of_step) {
+            pub_rb->flags = src->flags;
+            src->flags = 0u;  // (the next step starts from clear flags without a memset of its own: World::flags_clean)
+            const volatile int32_t* bb = src->bbox;  // (stored by threads 0..5 of this block a moment ago: not through a stale register)
+            int32_t box[6];
+            for (int a = 0; a < 6; ++a) { box[a] = bb[a]; pub_rb->bbox[a] = box[a]; }
+            // chained steps (device_types.h StepCtx::gate): did every solve converge within its batch, and what they found
+            pub_rb->chain_ok = src->chain_ok; pub_rb->chain_stage = src->chain_stage;
+            uint32_t pok = (pre.on && (!pre.chained || src->chain_ok)) ? 1u : 0u;
+            for (int a = 0; a < 6; ++a) pok &= (box[a] == pre.bbox[a]) ? 1u : 0u;
+            src->pre_ok = pok; pub_rb->pre_ok = pok;
+            for (int k = 0; k < 2; ++k) {
+                pub_rb->solve[k][0] = ctl[k].done; pub_rb->solve[k][1] = ctl[k].iters;
+                pub_rb->solve[k][2] = __float_as_uint(ctl[k].err); pub_rb->solve[k][3] = ctl[k].seq;
+            }
+        }
+        __threadfence_system();
+        *pub_seq = seq;
+    }
+}
+// Spin on a host-mapped word until `arrived`; `pause` keeps the sibling hyper-thread usable (loopback tests run one host thread
+// per rank), and every ~100 us the stream is queried so that a fault on it surfaces instead of spinning forever.
+template <typename Arrived>
+void World::spin_until(Arrived&& arrived, const char* drained) {
+    auto last_query = std::chrono::steady_clock::now();
+    for (uint32_t spins = 0; !arrived(); ++spins) {
+        __builtin_ia32_pause();
+        if ((spins & 0xffu) != 0xffu) continue;
+        const auto now = std::chrono::steady_clock::now();
+        if (now - last_query < std::chrono::microseconds(100)) continue;
+        last_query = now;
+        const hipError_t e = hipStreamQuery(stream);
+        if (e != hipSuccess && e != hipErrorNotReady) SALVA_HIP_CHECK(e);
+        if (e == hipSuccess && !arrived()) throw HipError(SALVA_HIP_E_HIP, drained);
+    }
+}
+// enqueue the publication on the world's stream ...
+uint32_t World::publish_enqueue(const TileAcc* totals, bool lists, bool end_of_step, const PrePub* pre, const uint32_t* gate) {
+    const uint32_t seq = ++hostpub_seq;
+    Epilogue ep{nullptr, 0u, 0, nullptr, 0u, nullptr};
+    if (end_of_step) {  // what this step left for the publication to fold (World::build_lists and the solvers set them, one publication consumes them)
+        if (fold_stats) { ep.ts = reinterpret_cast<const TileListStats*>(tile_list_stats.p); ep.nts = nlaunch; ep.own = comm ? 1 : 0; }
+        if (fold_bbox_blocks) { ep.bbox_partials = bbox_partials.p; ep.nbb = fold_bbox_blocks; ep.chain_gate = fold_bbox_gate; }
+        fold_stats = false; fold_bbox_blocks = 0u; fold_bbox_gate = nullptr;
+    }
+    const unsigned threads = (ep.ts || ep.bbox_partials) ? BLOCK : WAVE;
+    k_publish_readback<<<1, threads, 0, stream>>>(d_rb.p, totals, lists ? 1 : 0, end_of_step ? 1 : 0, mass_slots.p, &h_hostpub->rb, &h_hostpub->seq, seq,
+                                                  d_ctl.p, pre ? *pre : PrePub{0, 0, {0, 0, 0, 0, 0, 0}}, gate, ep);
+    SALVA_HIP_CHECK(hipGetLastError());
+    return seq;
+}
+// ... and wait for it (kernels enqueued in between keep the GPU busy meanwhile); the published words are folded into h_rb
+void World::publish_wait(uint32_t seq, bool totals, bool lists, bool end_of_step) {
+    // (sequence numbers only grow; the totals of a pre-enqueued grid may follow the end-of-step publication before the host has
+    // looked — the two write different fields)
+    spin_until([&] { return (int32_t)(__atomic_load_n(&h_hostpub->seq, __ATOMIC_ACQUIRE) - seq) >= 0; },
+               "internal error: the stream drained without publishing its read-back");
+    const Readback& p = h_hostpub->rb;
+    if (totals) { h_rb->tile_total = p.tile_total; h_rb->mass_mm[0] = p.mass_mm[0]; h_rb->mass_mm[1] = p.mass_mm[1]; }
+    if (lists) {
+        h_rb->ncontacts_ff = p.ncontacts_ff; h_rb->ncontacts_fb = p.ncontacts_fb; h_rb->max_cnt_ff = p.max_cnt_ff; h_rb->max_cnt_fb = p.max_cnt_fb;
+        h_rb->ncontacts_own_ff = p.ncontacts_own_ff; h_rb->ncontacts_own_fb = p.ncontacts_own_fb;
+        memcpy(h_rb->max_ref, p.max_ref, sizeof(p.max_ref));
+    }
+    if (end_of_step) {
+        h_rb->flags = p.flags; memcpy(h_rb->bbox, p.bbox, sizeof(p.bbox));
+        h_rb->chain_ok = p.chain_ok; h_rb->chain_stage = p.chain_stage; memcpy(h_rb->solve, p.solve, sizeof(p.solve));
+        h_rb->pre_ok = p.pre_ok;
+    }
+}
+void World::publish_and_wait(const TileAcc* totals, bool lists, bool end_of_step) {
+    publish_wait(publish_enqueue(totals, lists, end_of_step), totals != nullptr, lists, end_of_step);
+}
+
+void World::wait_stream() {
+    SALVA_HIP_CHECK(hipEventRecord(ev_sync, stream));
+    for (;;) {
+        const hipError_t e = hipEventQuery(ev_sync);
+        if (e == hipSuccess) return;
+        if (e != hipErrorNotReady) SALVA_HIP_CHECK(e);
+    }
+}
+
+// One iterative solve with the reference's protocol (dfsph_solver.rs:439-463 / :474-502 / iisph_solver.rs:422-456):
+//   for i in 0..max { err = evaluate(); if err <= tol && i >= min { break }; apply(); }
+// The break decision is taken on the device (k_finalize_error -> SolveCtl); iterations are enqueued in growing batches
+// and the control block is read back once per batch.  Kernels enqueued after convergence return immediately.
+__global__ void k_ghost_posmr(uint32_t n, const uint32_t* __restrict__ gtag, const float4* __restrict__ posm, const float* __restrict__ rho,
+                              float4* __restrict__ posmr) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !(gtag[i] & 0x80000000u)) return;
+    reinterpret_cast<float*>(&posmr[i])[3] = posm[i].w / rho[i];
+}
+__global__ void k_init_ctl(SolveCtl* ctl, SolveCtl* ring, SolveCtl init, uint32_t* chain_open, SolveCtl* ctl_b, SolveCtl init_b) {
+    *ctl = init;
+    if (ctl_b) *ctl_b = init_b;  // (the step's second solve, whose parameters are known as well: one launch for both)
+    if (chain_open) { chain_open[0] = 1u; chain_open[1] = 0u; }  // (Readback::chain_ok / chain_stage: the first solve of a chained step)
+    if (ring) { ring[0] = init; ring[1] = init; }  // (dfsph.hip spec_decide: the test rides in the apply pass; iteration k reads spec_ring[k & 1])
+}
+template <typename Eval, typename Apply>
+World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_iter, int max_iter, uint32_t mode, Eval&& eval,
+                                    Apply&& apply, bool spec_apply, int chain_stage, int from, bool chain_open) {
+    // Every convergence test publishes its outcome to host-mapped memory (k_finalize_error; in a decomposed run k_decide,
+    // behind the all-reduce), and the host waits for the test count it enqueued — it then decides (and enqueues what
+    // follows) while the batch's last apply pass is still running.
+    static const bool no_publish = getenv("SALVA_HIP_NO_PUBLISH") != nullptr;  // (diagnostics: A/B against the copy + wait)
+    SolveCtl* const pub = no_publish ? nullptr : h_pub + which;
+    c.ctl = d_ctl.p + which;
+    if (from == 0) {
+        SolveCtl& init = h_ctl[NUM_SOLVES + which];
+        init = SolveCtl{0u, 0u, 0.0f, 0u, tol, (uint32_t)std::max(min_iter, 0), mode, 0u};
+        h_ctl[which] = init;
+        // (one tiny kernel with the record as its argument instead of up to three copies from pageable host memory, each of which
+        // stalls the host until its staging copy is done; the first solve of a chained step also opens the chain)
+        const bool have = which == 1 && pre_init1_valid && memcmp(&pre_init1, &init, sizeof(SolveCtl)) == 0 && !chain_open;
+        if (!have) {
+            const bool both = which == 0 && pre_init1_valid;  // (World::dfsph_solve has said what the pressure solve will start from)
+            k_init_ctl<<<1, 1, 0, stream>>>(d_ctl.p + which, spec_apply ? spec_ring.p : nullptr, init, chain_open ? &d_rb.p->chain_ok : nullptr,
+                                            both ? d_ctl.p + 1 : nullptr, both ? pre_init1 : init);
+            SALVA_HIP_CHECK(hipGetLastError());
+        }
+        if (which == 1) pre_init1_valid = false;
+        if (pub) { pub->done = 0u; pub->iters = 0u; pub->err = 0.0f; __atomic_store_n(&pub->seq, 0u, __ATOMIC_RELEASE); }
+    }
+    // First batch: what the previous step's solve needed (iters applies + the converged evaluate) — consecutive steps
+    // need about the same, so the usual cost is one read-back per solve; a batch that overshoots only enqueues kernels
+    // that return at once, one that falls short continues in doubling batches.
+    int i = from, batch = std::max(2, std::min<int>((int)last_iters[which] + 1, max_iter));
+    const bool multi = comm && comm->size() > 1;
+    // Two launches a solve does not need (round 6; a kernel that returns at once still costs a launch of 2 200 workgroups, ~5 us, and
+    // a one-block test ~4.6 us plus its gaps — 23 us of a 0.61 ms free-fall step):
+    //  * the tests of iterations i < min_iter cannot end the solve (`err <= tol && i >= min`): they are not launched — the next test
+    //    that is counts them (`skipped`: iters and seq advance as if they had failed).  In a decomposed run that is an all-reduce less.
+    //  * the apply behind the LAST test of a batch runs only if that test fails, which the batch is sized not to expect: it is
+    //    enqueued by whoever continues the solve (`owed`), and never when the solve has converged.  Not in decomposed runs (a ghost
+    //    refresh rides behind every apply) and not where the test rides in the apply pass itself (spec_apply).
+    const bool lazy_apply = !multi && !spec_apply;
+    uint32_t skipped = 0u;
+    auto test = [&](int it, bool last_of_batch, const uint32_t* gate, uint32_t* close, uint32_t stage) {
+        if (it < min_iter && it + 1 < max_iter && !last_of_batch) { ++skipped; return; }
+        if (!multi) launch_finalize_error(partials.p, nlaunch, (uint32_t)std::max<size_t>(fluids.size(), 1), model_counts.p, d_ctl.p + which, pub, stream, gate, close, stage, skipped);
+        else finalize_solve(d_ctl.p + which, pub, skipped);
+        skipped = 0u;
+    };
+    if (from > 0 && solve_owes_apply[which]) apply(c, from - 1);  // (the apply the batch before left to its successor)
+    solve_owes_apply[which] = false;
+    if (chain_stage) {
+        // Chained (device_types.h StepCtx::gate): ONE batch and no wait.  The batch is what the previous step needed plus, while the
+        // count is rising (the impact: 2, 4, 14, 18, 30 ... iterations in consecutive steps), what it rose by last time — a surplus
+        // iteration costs three kernels that return at once, a batch that falls short costs the chain (every kernel behind this
+        // solve returns at once and the host comes back here with `from` = this batch).  Its LAST test closes the chain when it
+        // fails, unless the batch runs to max_iter: then the solve is over whatever that test says.
+        const int rise = (int)last_iters[which] > (int)prev_iters[which] ? std::min((int)last_iters[which] - (int)prev_iters[which], 8) : 0;
+        const int nbatch = std::min(batch + rise, max_iter);
+        c.gate_stage = (uint32_t)chain_stage;  // (its own last test may shut the gate: the apply behind that test still runs)
+        for (int k = 0; k < nbatch; ++k) {
+            eval(c, k);
+            const bool closes = k == nbatch - 1 && nbatch < max_iter;
+            test(k, k == nbatch - 1, c.gate, closes ? &d_rb.p->chain_ok : nullptr, (uint32_t)chain_stage);
+            if (closes && lazy_apply) solve_owes_apply[which] = true;  // (only a continuation needs it)
+            else apply(c, k);
+        }
+        chain_batch[which] = nbatch;
+        return SolveResult{0u, 0.0f};  // (pending: World::adopt_chain_outcome reads it from the end-of-step publication)
+    }
+    if (from > 0) batch = (from <= 2) ? 4 : 8;
+    while (i < max_iter) {
+        const int nbatch = std::min(batch, max_iter - i);
+        bool owes = false;
+        for (int k = 0; k < nbatch; ++k) {
+            if (spec_apply && multi) {
+                // A decomposed solve with speculative applies (round 6): the all-reduced test and the apply pass do not wait for
+                // each other.  Main stream: error sums -> all-reduce -> k_decide_ring (the record of iteration it + 1).  Second
+                // stream: the apply pass, into the other w buffer, reading the record of iteration `it` only.  Then the ghost
+                // refresh of what the apply wrote, behind both — one communicator, one operation at a time.  A converged test leaves
+                // the apply and its refresh unused (w stays where it was), exactly as in the single domain (dfsph.hip spec_decide).
+                const int it = i + k;
+                c.spec_k = it; c.spec_external = 1u; c.spec_pub = nullptr;
+                eval(c, it);
+                SALVA_HIP_CHECK(hipEventRecord(ev_spec_eval, stream));
+                SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_spec_eval, 0));
+                spec_dist_stream = stream2;
+                apply(c, it);  // (the kernel only: World::dfsph_solve's lambda leaves the refresh to the lines below)
+                spec_dist_stream = nullptr;
+                SALVA_HIP_CHECK(hipEventRecord(ev_spec_apply, stream2));
+                const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
+                const size_t tm = dist_time_begin(1);
+                launch_sum_partials(partials.p, nlaunch, nm, spec_ring.p + (it & 1), d_sums.p, stream);
+                comm->allreduce_sum_f32(d_sums.p, (int)nm, stream);
+                launch_decide_ring(d_sums.p, nm, model_counts.p, spec_ring.p, it, pub, stream);
+                dist_time_end(tm);
+                SALVA_HIP_CHECK(hipStreamWaitEvent(stream, ev_spec_apply, 0));
+                refresh_f4((it & 1) ? w.p : w2.p);  // what the apply of iteration `it` wrote: the buffer of parity it + 1
+                continue;
+            }
+            if (spec_apply) { c.spec_k = i + k; c.spec_pub = pub; }
+            eval(c, i + k);
+            if (!spec_apply) test(i + k, k == nbatch - 1, nullptr, nullptr, 0u);
+            if (lazy_apply && k == nbatch - 1 && i + nbatch < max_iter) owes = true;
+            else apply(c, i + k);
+        }
+        if (pub) {
+            const uint32_t expect = (uint32_t)(i + nbatch);
+            spin_until([&] { return __atomic_load_n(&pub->seq, __ATOMIC_ACQUIRE) >= expect; },
+                       "internal error: a solver batch finished without publishing its control block");
+            h_ctl[which].done = pub->done; h_ctl[which].iters = pub->iters; h_ctl[which].err = pub->err;
+        } else {
+            // (no publication: read the newest record back — after i + nbatch iterations that is spec_ring[(i + nbatch) & 1])
+            const SolveCtl* src = spec_apply ? spec_ring.p + ((i + nbatch) & 1) : d_ctl.p + which;
+            SALVA_HIP_CHECK(hipMemcpyAsync(&h_ctl[which], src, sizeof(SolveCtl), hipMemcpyDeviceToHost, stream));
+            wait_stream();
+        }
+        i += nbatch;
+        if (h_ctl[which].done) break;
+        if (owes) apply(c, i - 1);  // the batch's last test failed: the apply it counted
+        batch = (i <= 2) ? 4 : 8;
+    }
+    prev_iters[which] = last_iters[which];
+    last_iters[which] = h_ctl[which].iters;
+    return SolveResult{h_ctl[which].iters, h_ctl[which].err};
+}
+
+// predict_advection's loop over `fluid.nonpressure_forces` (dfsph_solver.rs:580-603): fluids in slot order, forces in list order.
+void World::run_forces(const StepCtx& c) {
+    for (uint32_t f = 0; f < fluids.size(); ++f) {
+        if (fluids[f].n == 0) continue;
+        for (const SalvaHipForceDesc& d : fluids[f].forces) {
+            switch (d.kind) {
+                case SALVA_HIP_FORCE_XSPH: launch_xsph(c, lds, f, d.p[0], d.p[1], inv_dt_prev, stream); break;
+                case SALVA_HIP_FORCE_ARTIFICIAL: launch_artificial_viscosity(c, lds, f, d.p[0], d.p[1], d.p[2], d.p[3], d.p[4], stream); break;
+                case SALVA_HIP_FORCE_DFSPH_VISCOSITY: {
+                    // DFSPHViscosity::solve (dfsph_viscosity.rs:290-327); timestep.dt() / inv_dt() are the previous step's here
+                    const float coef = d.p[0], max_err = d.p[3];
+                    const int min_it = (int)d.p[1], max_it = (int)d.p[2];
+                    visc_beta.ensure((size_t)36 * n, stream, false, 1.1f); visc_target.ensure((size_t)6 * n, stream, false, 1.1f);
+                    visc_u0.ensure(n, stream, false, 1.1f); visc_u1.ensure(n, stream, false, 1.1f); visc_va.ensure(n, stream, false, 1.1f);
+                    launch_visc_betas(c, lds, f, visc_beta.p, stream);
+                    launch_visc_va(c, dt_prev, visc_va.p, stream);
+                    if (comm) refresh_f4(visc_va.p);
+                    launch_visc_strain(c, lds, f, 0, coef, visc_va.p, visc_beta.p, visc_target.p, visc_u0.p, visc_u1.p, stream);
+                    const SolveResult rv = run_solve(
+                        c, 2, max_err, min_it, max_it, 0u,
+                        [&](const StepCtx& cc, int) {
+                            launch_visc_strain(cc, lds, f, 1, coef, visc_va.p, visc_beta.p, visc_target.p, visc_u0.p, visc_u1.p, stream);
+                        },
+                        [&](const StepCtx& cc, int) {
+                            // (u of the inner ghost plane was computed here from refreshed v + a dt: no exchange needed)
+                            launch_visc_accel(cc, lds, f, inv_dt_prev, dt_prev, visc_u0.p, visc_u1.p, visc_va.p, stream);
+                            if (comm) refresh_f4(visc_va.p);
+                        });
+                    fluids[f].force_iters.resize(fluids[f].forces.size(), 0u);
+                    fluids[f].force_errs.resize(fluids[f].forces.size(), 0.0f);
+                    fluids[f].force_iters[&d - fluids[f].forces.data()] = rv.iters;
+                    fluids[f].force_errs[&d - fluids[f].forces.data()] = rv.err;
+                    break;
+                }
+                case SALVA_HIP_FORCE_HE2014:
+                    // He2014SurfaceTension::solve (he2014_surface_tension.rs:109-181): colors -> gradcs -> forces
+                    he_colors.ensure(n, stream, false, 1.1f); he_gradcs.ensure(n, stream, false, 1.1f);
+                    launch_he2014_colors(c, lds, f, he_colors.p, stream);
+                    // the outer ghost plane's colors are sums over an incomplete neighbourhood, and the inner plane's gradcs read them
+                    if (comm) refresh_f32(he_colors.p);
+                    launch_he2014_gradc(c, lds, f, he_colors.p, he_gradcs.p, stream);
+                    launch_he2014_forces(c, lds, f, d.p[0], d.p[1], he_gradcs.p, stream);
+                    break;
+                case SALVA_HIP_FORCE_WCSPH_TENSION: launch_wcsph_tension(c, lds, f, d.p[0], stream); break;
+                case SALVA_HIP_FORCE_CUSTOM: {
+                    // a host `NonPressureForce::solve` at its place in the list (nonpressure_force.rs:10-30)
+                    if (!force_cb) throw HipError(SALVA_HIP_E_INVALID, "a SALVA_HIP_FORCE_CUSTOM entry needs salva_hip_set_force_callback");
+                    // (in a decomposed run the callback runs on every rank and works on the rank's local view:
+                    // salva_hip_get_local / _get_local_contacts / _force_add_local_accelerations)
+                    last_ctx = c; last_ctx.ctl = nullptr; have_last_ctx = true;  // what the contact export reads
+                    wait_stream();
+                    in_force_cb = true;
+                    int rc = 0;
+                    try {
+                        rc = force_cb(force_user, force_owner, f, (uint32_t)(&d - fluids[f].forces.data()), dt_prev, inv_dt_prev);
+                    } catch (...) {
+                        in_force_cb = false; have_last_ctx = false;
+                        throw;
+                    }
+                    in_force_cb = false; have_last_ctx = false;
+                    if (rc != 0) throw HipError(SALVA_HIP_E_INVALID, "the force callback reported an error");
+                    break;
+                }
+                case SALVA_HIP_FORCE_BECKER2009: run_elasticity(c, f, (uint32_t)(&d - fluids[f].forces.data())); break;
+                case SALVA_HIP_FORCE_AKINCI2013:
+                    launch_akinci_normals(c, lds, f, stream);
+                    // (normals of the inner ghost plane are complete: rho was refreshed on both planes)
+                    launch_akinci_forces(c, lds, f, d.p[0], d.p[1], stream);
+                    break;
+                default: break;
+            }
+        }
+    }
+}
+
+// An evaluate pass of a decomposed run, overlapped with the ghost exchange that precedes it: the tiles whose halo box
+// touches no ghost plane (all but the two tile layers at the faces) start on the second stream as soon as everything before
+// the exchange is done; the exchange itself (gather, grouped send / recv with the neighbours, scatter: latency-bound, tens
+// of microseconds) proceeds on the main stream, followed by the border tiles; the main stream then waits for the interior.
+// (Not for the first evaluate of a solve: its control block is initialised on the main stream after the exchange was
+// enqueued, and the interior launch would read the previous solve's `done`.)
+template <typename Launch>
+void World::evaluate_split(const StepCtx& c, int iteration, Launch&& launch) {
+    // (nothing to overlap with when no ghost is refreshed: a one-rank communicator, or a rank whose faces hold no particle)
+    if (!comm || !overlap_exchange || iteration == 0 || nghost_lo + nghost_hi + nborder_lo + nborder_hi == 0) { launch(c, stream); return; }
+    StepCtx ci = c, cb = c;
+    ci.phase = 1; cb.phase = 2;
+    SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_pre_refresh, 0));
+    launch(ci, stream2);
+    SALVA_HIP_CHECK(hipEventRecord(ev_interior, stream2));
+    launch(cb, stream);
+    SALVA_HIP_CHECK(hipStreamWaitEvent(stream, ev_interior, 0));
+}
+
+// Worlds with a few masses (device_types.h StepCtx::two_mass): a single-domain DFSPH world with the default kernels in which every
+// non-empty fluid has one particle mass (FluidSlot::vol_uniform x density0, the product launch_stage_to_sorted forms) and two, three
+// or four different masses occur — BASELINE config 4 has two.  Sets mass_classes / mass_cmask / nmass.
+bool World::decide_two_mass() {
+    mass_cmask = 0ull; nmass = 0u;
+    for (float& m : mass_classes) m = 0.0f;
+    if (two_mass_off || no_planes || comm || prm.solver != SALVA_HIP_SOLVER_DFSPH || prm.kernel_density != 0 || prm.kernel_gradient != 0) return false;
+    if (fluids.size() < 2 || fluids.size() > 32 || bounds.size() > 32) return false;
+    float ms[4];
+    uint32_t distinct = 0;
+    for (const FluidSlot& f : fluids) {
+        if (f.n == 0) continue;
+        const float m = f.vol_uniform * f.density0;
+        if (!(m > 0.0f) || !std::isfinite(m)) return false;  // (NaN: the fluid's volumes differ)
+        bool seen = false;
+        for (uint32_t k = 0; k < distinct; ++k) seen |= ms[k] == m;
+        if (seen) continue;
+        if (distinct == max_masses) return false;  // one mass too many: the general kernels
+        ms[distinct++] = m;
+    }
+    if (distinct < 2) return false;
+    std::sort(ms, ms + distinct);
+    for (uint32_t k = 0; k < distinct; ++k) mass_classes[k] = ms[k];
+    for (uint32_t f = 0; f < fluids.size(); ++f) {
+        if (!fluids[f].n) continue;  // (an empty fluid has no particle whose class could be asked for)
+        const float m = fluids[f].vol_uniform * fluids[f].density0;
+        for (uint32_t k = 0; k < distinct; ++k)
+            if (ms[k] == m) mass_cmask |= (uint64_t)k << (2u * f);
+    }
+    nmass = distinct;
+    return true;
+}
+
+void World::set_cfl(int mode, float coeff, int min_sub, int max_sub) {
+    if (mode < 0 || mode > 2) throw HipError(SALVA_HIP_E_INVALID, "cfl mode must be 0 (off), 1 (the reference's commented clamp) or 2 (the same, cut at the end of the step)");
+    if (mode && (!(coeff > 0.0f) || !std::isfinite(coeff))) throw HipError(SALVA_HIP_E_INVALID, "cfl_coeff must be positive");
+    if (mode && (min_sub < 1 || max_sub < min_sub)) throw HipError(SALVA_HIP_E_INVALID, "need 1 <= min_num_substeps <= max_num_substeps");
+    cfl_mode = mode; cfl_coeff = coeff; cfl_min_sub = min_sub; cfl_max_sub = max_sub;
+}
+// TimestepManager::max_substep (timestep_manager.rs:36-46) + the body of compute_substep the reference left commented out (:90-93):
+//   max_sq_vel = max over all fluid particles of |v + a * remaining_time|^2        (f32::max ignores a NaN operand)
+//   computed   = particle_radius * 2 / sqrt(max_sq_vel) * cfl_coeff
+//   substep    = clamp(computed, total / max_num_substeps, total / min_num_substeps)
+// The maximum is order-independent and |.|^2 is evaluated as the reference does ((x x + y y) + z z, no contraction: the library is
+// compiled -ffp-contract=off), so the substep is bit for bit the CPU's for the same v and a.  Non-negative floats order like
+// their bit patterns: one atomicMax per wave.
+__global__ __launch_bounds__(BLOCK) void k_cfl_max(uint32_t n, const float4* __restrict__ vel, const float4* __restrict__ acc,
+                                                   const uint32_t* __restrict__ gtag, float remaining, uint32_t* __restrict__ out_bits) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t bits = 0u;
+    if (i < n && !(gtag && (gtag[i] & 0x80000000u))) {  // (a ghost is its owner's to report)
+        const float4 v = vel[i], a = acc[i];
+        const float ux = v.x + a.x * remaining, uy = v.y + a.y * remaining, uz = v.z + a.z * remaining;
+        const float sq = (ux * ux + uy * uy) + uz * uz;
+        if (sq == sq) bits = __float_as_uint(sq);
+    }
+    bits = wave_max_u32(bits);
+    if ((threadIdx.x & (WAVE - 1)) == 0 && bits) atomicMax(out_bits, bits);
+}
+float World::choose_substep(const StepCtx& c) {
+    uint32_t* const d_bits = &d_rb.p->cfl_max_bits;
+    SALVA_HIP_CHECK(hipMemsetAsync(d_bits, 0, sizeof(uint32_t), stream));
+    if (n) k_cfl_max<<<nblk(n), BLOCK, 0, stream>>>(n, c.vel, c.acc, comm ? gtag[cur].p : nullptr, step_remaining, d_bits);
+    SALVA_HIP_CHECK(hipGetLastError());
+    float max_sq = 0.0f;
+    if (comm && comm->size() > 1) {
+        // max over the ranks through the sum all-reduce: every rank writes its value into its own slot of a zeroed row (x + 0 = x)
+        const int size = comm->size();
+        d_sums.ensure((size_t)std::max(size, 8));
+        SALVA_HIP_CHECK(hipMemsetAsync(d_sums.p, 0, (size_t)size * sizeof(float), stream));
+        SALVA_HIP_CHECK(hipMemcpyAsync(d_sums.p + comm->rank(), d_bits, sizeof(float), hipMemcpyDeviceToDevice, stream));
+        comm->allreduce_sum_f32(d_sums.p, size, stream);
+        std::vector<float> all((size_t)size, 0.0f);
+        SALVA_HIP_CHECK(hipMemcpyAsync(all.data(), d_sums.p, (size_t)size * sizeof(float), hipMemcpyDeviceToHost, stream));
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        for (float v : all) max_sq = std::max(max_sq, v);
+    } else {
+        SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->cfl_max_bits, d_bits, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        wait_stream();
+        memcpy(&max_sq, &h_rb->cfl_max_bits, sizeof(float));
+    }
+    const float total = step_total;
+    const float min_substep = total / (float)cfl_max_sub, max_substep = total / (float)cfl_min_sub;
+    const float computed = prm.particle_radius * 2.0f / std::sqrt(max_sq) * cfl_coeff;
+    float sub = computed > max_substep ? max_substep : (computed < min_substep ? min_substep : computed);  // na::clamp
+    // (mode 2: cut at the remaining time; a remainder of float residue — below 1e-4 of the step — goes along with this substep instead
+    // of becoming a last one of a few ulps with inv_dt ~ 1e6; the CPU restatement the tests hold this against does the same)
+    if (cfl_mode == 2 && (sub > step_remaining || step_remaining - sub < total * 1e-4f)) sub = step_remaining;
+    return sub;
+}
+
+// Can this step's solves be chained (device_types.h StepCtx::gate)?  Everything between the first solve and the end of the step has
+// to be a kernel that honours the gate and needs no host decision: a single domain, no CFL choice (a read-back inside the solver), no
+// host force callback, no force with a solve of its own (DFSPHViscosity).  SALVA_HIP_NO_CHAIN=1 switches it off (A/B, tests).
+bool World::chain_allowed() const {
+    if (chain_off || comm || cfl_mode || spec_mode || prm.solver != SALVA_HIP_SOLVER_DFSPH) return false;
+    if (has_force(SALVA_HIP_FORCE_CUSTOM) || has_force(SALVA_HIP_FORCE_DFSPH_VISCOSITY)) return false;
+    if (elastic_stale()) return false;  // (the rest build reads its contact total back)
+    return true;
+}
+
+// Becker2009Elasticity::solve (becker2009_elasticity.rs:268-334) at its place in the force list
+void World::run_elasticity(const StepCtx& c, uint32_t slot, uint32_t force) {
+    ElasticState& e = elastic_state(slot, force);
+    const ElasticParams ep = elastic_params(fluids[slot].forces[force].p);
+    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
+    // init (:84-112) runs when positions0.len() != the particle count: volumes0 and rotations are `resize`d — the first
+    // min(old, new) entries keep their values (quirk 1), new volumes0 are 0 and new rotations the identity
+    const bool init = e.n0 != nn;
+    if (init) {
+        const uint64_t keep = std::min<uint64_t>(e.n0, nn);
+        e.vol0.ensure(nn, stream, true, 1.1f);
+        e.rot.ensure(9 * nn, stream, true, 1.1f);
+        if (nn > keep) SALVA_HIP_CHECK(hipMemsetAsync(e.vol0.p + keep, 0, (nn - keep) * sizeof(float), stream));
+        launch_elastic_identity(e, keep, nn, stream);
+        e.p0.ensure(nn, stream, false, 1.1f); e.hp.ensure(nn, stream, false, 1.1f);
+        e.rot_new.ensure(9 * nn, stream, false, 1.1f); e.sig.ensure(6 * nn, stream, false, 1.1f); e.F.ensure(9 * nn, stream, false, 1.1f);
+        e.n0 = nn;
+        e.list_valid = false;
+    }
+    if (nn == 0) return;
+    launch_elastic_gather(c, (uint32_t)off, e, stream);
+    if (init) {
+        launch_elastic_take_rest(e, stream);  // positions0 = fluid.positions
+        elastic_build_rest(e, c.sc, ep, false, stream);
+    } else if (!e.list_valid) {
+        elastic_build_rest(e, c.sc, ep, true, stream);  // a restored state: the lists from its positions0, its volumes0 as given
+    }
+    launch_elastic_rot_stress(c, e, ep, stream);
+    launch_elastic_forces(c, (uint32_t)off, e, ep, c.acc, stream);
+    e.ran = true;
+}
+
+// the step completed: its rotations become the warm start of the next one
+void World::commit_elastic() {
+    for (FluidSlot& f : fluids)
+        for (auto& p : f.elastic)
+            if (p && p->ran) {
+                std::swap(p->rot.p, p->rot_new.p);
+                std::swap(p->rot.cap, p->rot_new.cap);
+                p->ran = false;
+            }
+}
+
+// DFSPHSolver::step (dfsph_solver.rs:667-708)
+// `resume`: 0 = the step's solver part from its start.  Chained, it returns with everything enqueued and nothing waited for
+// (chain_pending); World::adopt_chain_outcome learns from the end-of-step publication whether both solves converged within their batches and,
+// if one did not, calls again with resume = 1 (continue the divergence solve, then everything behind it) or 2 (continue the pressure
+// solve, then the position update) — the classic way, one wait per batch.
+void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, int resume) {
+    if (resume) { dt_prev = chain_dt_prev; inv_dt_prev = chain_inv_dt_prev; }  // (TimestepManager's state as the chained attempt found it)
+    chain_dt_prev = dt_prev; chain_inv_dt_prev = inv_dt_prev;
+    // divergence_solve (:466-503).  NOTE the dt lag: inv_dt is still the previous step's here (0 on the first step).
+    const float inv_dt_lag = inv_dt_prev;
+    const bool timers = prm.enable_timers != 0;
+    if (timers && !resume) SALVA_HIP_CHECK(hipEventRecord(evc[3], stream));  // counters.custom (:492)
+    // Speculative applies (dfsph.hip, spec_decide): the convergence test rides in the apply pass instead of a launch of its own.
+    // Worth ~3 us per iteration (measured: a 50-iteration step 5.13 -> 4.99 ms); the apply that follows the converging evaluate is
+    // then computed in vain (~30 us once per solve), so: only when the previous step's solve ran 16 iterations or more; not with boundary reaction forces (an
+    // apply that is thrown away must not have added to them) and not in decomposed runs (the test sits behind an all-reduce).
+    // Decomposed runs (round 6): the same double buffer lets the apply run BESIDE the all-reduced test instead of behind it
+    // (World::run_solve); there the wasted apply is cheaper than the all-reduces it hides from four iterations on.
+    const bool multi_rank = comm && comm->size() > 1;
+    const bool spec_apply = !resume && !spec_apply_off && !any_wants_forces &&
+                            (multi_rank ? (!spec_dist_off && last_iters[0] >= 4u) : (!comm && last_iters[0] >= 16u));
+    if (spec_apply) { w2.ensure(n, stream, false, 1.1f); spec_ring.ensure(2); c.w2 = w2.p; c.spec_ring = spec_ring.p; }
+    // Chained: neither solve is waited for (the w / w2 swap below is a host decision on the iteration count: not with speculative applies)
+    const bool chain = !resume && !spec_apply && chain_allowed();
+    // ... except that the divergence solve keeps its waits while its iteration count is RISING (the impact: 2, 4, 14, 18, 30, 44
+    // iterations in consecutive steps): every such step's batch would fall short, and a broken chain costs more than the wait it was
+    // meant to save (the gated kernels behind it, a publication, the continuation).  The chain then starts behind it.
+    const bool chain_div = chain && !(last_iters[0] > prev_iters[0]);
+    StepCtx cg = c;   // the context of everything BEHIND the first chained solve: gated
+    if (chain) cg.gate = &d_rb.p->chain_ok;
+    const StepCtx& ca = chain_div ? cg : c;  // ... which the kernels between the two solves are only when the first one is chained
+    auto div_eval = [&](const StepCtx& cc, int it) {
+        if (it == 0 && fused_first_divergence) return;  // (k_density_alpha_div_p3 wrote kappa and the error partials already)
+        evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_divergence(cs, lds, s); });
+    };
+    auto div_apply = [&](const StepCtx& cc, int) {
+        // decomposed runs: kappa of the inner ghost plane was computed here from refreshed w — the applies of the
+        // owned particles read nothing else, so only w travels, once per iteration
+        launch_divergence_apply(cc, lds, inv_dt_lag, spec_dist_stream ? spec_dist_stream : stream);
+        if (comm && !spec_dist_stream) refresh_f4(w.p);  // (a speculative decomposed apply: run_solve refreshes the buffer it wrote)
+    };
+    const float div_tol = prm.max_divergence_error * inv_dt_prev * 0.01f;
+    SolveResult rd{0u, 0.0f};
+    // (the pressure solve's control block is initialised by the divergence solve's launch — unless that solve has to open the chain)
+    pre_init1_valid = false;
+    if (resume == 0 && (!chain || chain_div)) {
+        pre_init1 = SolveCtl{0u, 0u, 0.0f, 0u, prm.max_density_error, (uint32_t)std::max(prm.min_pressure_iter, 0), 0u, 0u};
+        pre_init1_valid = true;
+    }
+    if (resume <= 1) {
+        rd = run_solve(c, 0, div_tol, prm.min_divergence_iter, prm.max_divergence_iter, 0u, div_eval, div_apply, spec_apply, chain_div ? 1 : 0,
+                       resume == 1 ? chain_batch[0] : 0, chain_div);
+        if (spec_apply && multi_rank) {
+            static const bool trace = getenv("SALVA_HIP_DIST_TRACE") != nullptr;
+            if (trace) fprintf(stderr, "salva_hip dist[%d]: divergence solve with applies beside the all-reduce, %u iterations\n", comm->rank(), rd.iters);
+        }
+        if (spec_apply && (rd.iters & 1u)) {  // an odd number of committed applies: w lives in the second buffer
+            std::swap(w.p, w2.p); std::swap(w.cap, w2.cap);
+            c.w = w.p; c.w2 = w2.p; cg.w = w.p; cg.w2 = w2.p;
+        }
+        if (timers) SALVA_HIP_CHECK(hipEventRecord(evc[4], stream));  // :501
+        st.n_divergence_iters = (int32_t)rd.iters;
+        st.divergence_error = rd.err;
+        launch_finish_divergence(ca, g[0], g[1], g[2], acc_user, stream);  // update_velocities + dv = 0 + gravity
+        run_forces(ca);
+    }
+    // timestep.advance (:702): dt := total step (or, opted in, the CFL substep), inv_dt := 1/dt
+    if (cfl_mode) dt = choose_substep(c);
+    const float inv_dt = (dt == 0.0f) ? 0.0f : 1.0f / dt;
+    if (resume <= 1) {
+        launch_integrate(ca, dt, stream);
+        if (comm) refresh_f4(w.p);
+    }
+    // pressure_solve (:432-464)
+    const SolveResult rp = run_solve(
+        cg, 1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 0u,
+        [&](const StepCtx& cc, int it) { evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_pred_density(cs, lds, dt, s); }); },
+        [&](const StepCtx& cc, int) {
+            launch_pressure_apply(cc, lds, inv_dt, stream);
+            if (comm) refresh_f4(w.p);
+        }, false, chain ? 2 : 0, resume == 2 ? chain_batch[1] : 0, chain && !chain_div);
+    st.n_pressure_iters = (int32_t)rp.iters;
+    st.density_error = rp.err;
+    launch_update_positions(cg, dt, bbox_partials.p, nullptr, stream);  // (the per-block boxes are folded by the end-of-step publication)
+    fold_bbox_blocks = n ? num_blocks(n) : 0u; fold_bbox_gate = cg.gate;
+    dt_prev = dt;
+    inv_dt_prev = inv_dt;
+    chain_pending = chain;
+    chain_div_pending = chain_div;
+}
+
+// IISPHSolver::step (iisph_solver.rs:643-711)
+void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st) {
+    st.n_divergence_iters = 0;
+    st.divergence_error = 0.0f;
+    launch_iisph_begin(c, g[0], g[1], g[2], acc_user, stream);
+    run_forces(c);  // forces still see the previous inv_dt (:654-662)
+    if (cfl_mode) dt = choose_substep(c);  // timestep.advance (:662)
+    const float inv_dt = (dt == 0.0f) ? 0.0f : 1.0f / dt;
+    launch_integrate(c, dt, stream);
+    if (comm) refresh_f4(w.p);             // a ghost's own forces were summed over an incomplete neighbourhood
+    if (!iisph_dii_fused) launch_iisph_dii(c, lds, dt, stream);  // also p = 0.5 * p_prev (a per-particle operation: right for ghosts too)
+    // (d_ii depends on positions only: right on the inner ghost plane without an exchange)
+    launch_iisph_pred_density(c, lds, dt, stream);
+    if (!iisph_dii_fused) launch_iisph_aii(c, lds, dt, stream);  // (fused: a_ii came out of the density pass with d_ii)
+    float* const pa = kappa.p;
+    float* const pb = kappa2.p;
+    const float omega = 0.5f;  // :53
+    // pressure_solve (:422-456): iteration j reads p_j and writes p_{j+1}; the two buffers alternate (the reference swaps)
+    const SolveResult rp = run_solve(
+        c, 1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 1u,
+        [&](const StepCtx& cc, int j) {
+            const float* pr = (j & 1) ? pb : pa;
+            float* pw = (j & 1) ? pa : pb;
+            launch_iisph_dij_pj(cc, lds, dt, pr, stream);
+            launch_iisph_next_pressure(cc, lds, dt, omega, pr, pw, stream);
+            if (comm) refresh_f32(pw);
+        },
+        [&](const StepCtx&, int) {});
+    st.n_pressure_iters = (int32_t)rp.iters;
+    st.density_error = rp.err;
+    const float* p = (rp.iters & 1u) ? pb : pa;
+    launch_iisph_velocity_changes(c, lds, dt, p, stream);
+    launch_iisph_finish(c, dt, p, bbox_partials.p, nullptr, stream);  // (the per-block boxes are folded by the end-of-step publication)
+    fold_bbox_blocks = n ? num_blocks(n) : 0u; fold_bbox_gate = nullptr;
+    dt_prev = dt;
+    inv_dt_prev = inv_dt;
+}
+
+// ------------------------------------------------------------------------------------------------ step
+int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
+    use_device();
+    SalvaHipStepStats st{};
+    st.nparticles = n;
+    {   // self.counters.reset() (liquid_world.rs:73); the pass counters of this implementation are cumulative
+        const SalvaHipCounters last = counters;
+        counters = SalvaHipCounters{};
+        counters.speculative_passes = last.speculative_passes; counters.discarded_passes = last.discarded_passes;
+        counters.chained_passes = last.chained_passes; counters.chain_breaks = last.chain_breaks;
+        counters.pregrid_adopted = last.pregrid_adopted; counters.pregrid_dropped = last.pregrid_dropped;
+        counters.light_class_passes = last.light_class_passes; counters.sparse_class_passes = last.sparse_class_passes;
+    }
+    sticky.clear();  // init_with_fluids runs at the top of every step, substeps or not (liquid_world.rs:76)
+    substeps.clear();  // (also for a step that runs no substep at all: salva_hip_get_substeps then agrees with counters.nsubsteps = 0)
+    // TimestepManager::is_done (timestep_manager.rs:56-58): no substep at all for dt <= eps
+    if ((n == 0 && !comm) || !(dt > FLT_EPSILON)) {
+        if (stats) *stats = st;
+        return SALVA_HIP_OK;
+    }
+    if (comm && acc_user)
+        throw HipError(SALVA_HIP_E_INVALID, "host-set accelerations (SALVA_HIP_DIRTY_ACCELERATIONS) are not carried through the slab decomposition: "
+                                            "apply them as velocity changes, or use a single domain");
+    // `while !self.timestep_manager.is_done()` (liquid_world.rs:85): one substep of the whole step as the reference runs today
+    // (compute_substep returns total_step_size, timestep_manager.rs:88); with salva_hip_set_cfl the clamp the reference left
+    // commented out (:90-93) decides each substep's length inside the solver (`timestep.advance`, dfsph_solver.rs:702).
+    step_total = dt;
+    step_remaining = dt;
+    if (cfl_mode) {
+        upload_tables();  // (any_wants_forces)
+        if (any_wants_forces && !coupling_cb)
+            for (const BoundarySlot& b : bounds)
+                if (b.wants_forces && (b.sampling || b.dyn_kind))
+                    // the reference clears a coupled boundary's forces and transmits their impulse in EVERY substep with that substep's
+                    // dt (fluids_pipeline.rs:262, :266-287): one wrench per step() cannot carry that.  The caller's own loop can.
+                    throw HipError(SALVA_HIP_E_INVALID, "CFL sub-stepping with a coupled boundary that wants forces needs salva_hip_set_coupling_callback "
+                                                        "(update_boundaries / transmit_forces per substep, as the reference's manager does), or salva_hip_set_cfl off");
+    }
+    while (!(step_remaining <= FLT_EPSILON)) {  // is_done, timestep_manager.rs:56-58
+        float used = dt;
+        int rc;
+        try {
+            call_coupling(0, dt_prev);  // coupling.update_boundaries(&timestep, ...) (liquid_world.rs:94-103): dt() is the last substep's
+            for (;;) {
+                try { rc = substep(used, g, st); break; }
+                catch (const FoldRetry&) { used = dt; pre.valid = false; flags_clean = false; }  // (the grid changes: again from the top)
+            }
+            if (rc == SALVA_HIP_OK) call_coupling(1, used);  // coupling.transmit_forces(&timestep, boundaries) (:146): this substep's dt
+        } catch (...) {
+            if (stats) *stats = st;  // (what the failed substep got to: the caller's report is filled either way)
+            throw;
+        }
+        substeps.push_back(used);
+        step_remaining -= used;  // advance, :84
+        ++counters.nsubsteps;
+        if (rc != SALVA_HIP_OK) { if (stats) *stats = st; return rc; }
+        if (substeps.size() > 4096) throw HipError(SALVA_HIP_E_INVALID, "internal error: the substep loop does not terminate");
+    }
+    if (stats) *stats = st;
+    return SALVA_HIP_OK;
+}
+
+
+void World::call_coupling(int phase, float dt) {
+    if (!coupling_cb) return;
+    if (coupling_cb(coupling_user, coupling_owner, phase, dt) != 0)
+        throw HipError(SALVA_HIP_E_INVALID, "the coupling callback reported an error");
+}
+
+// ------------------------------------------------------------------------------------------------ substep: what its phases share
+// What World::choose_grid settles for a substep: the size of the (folded) cell table, of the dense tile table, and the bound of the
+// compact per-slot tables.
+struct World::GridShape { size_t ncf = 0; uint32_t ntiles = 0, nslots_bound = 0; };
+
+// What each pass (World::run_pass) decides for the phases behind it: reset at the top of every attempt.
+struct World::Attempt {
+    bool spec = false;          // launch shapes from the previous step's totals (World::substep: "One pass over the step")
+    bool defer_lists = false;   // the list capacity is checked with the end-of-step publication
+    bool have_grid = false;     // keys, sort, tile tables and the totals publication are enqueued already (world.h PreGrid)
+    TileAcc tt{};               // the totals the launch shapes and buffers of this pass are cut for
+    uint32_t nslices = 0;
+    size_t scan_tb = 0;         // temporary bytes of the tile-table scans
+    size_t need_f = 0, need_b = 0;  // entries of the two halo slot tables
+    bool ref_step = false;      // the list build keeps the referenced halo slots only (World::size_pass)
+    RefBuild refb{};
+    StepCtx c{};                // (the committed pass's becomes World::last_ctx)
+};
+// ... on top of what the substep decides before its first pass, the same for every attempt
+struct World::Pass : World::Attempt {
+    bool timers = false, has_dyn = false, adopted = false, can_redo = false, can_speculate = false;
+    GridShape gs;
+    double dcs_ms = 0.0;        // host milliseconds of DynamicContactSampling (counters.cd.boundary_update_time)
+    int attempt = 0;            // the pass that runs: 0, or the repeat of a discarded one
+};
+
+// State a pass touches, and where a discarded pass leaves it (extend this list — and restore() — with every new side effect, or
+// exclude the feature in can_redo):
+//   particle arrays of buffer cur^1 (the sort's output: positions, velocities, dv / pressures, models, permutation) ....
+//       recomputed by the repeated pass; buffer `cur` (the pre-sort state) is read-only until the pass commits
+//   cur, dt_prev / inv_dt_prev, h_rb->bbox, last_iters / prev_iters ........ snapshot here, restored on discard
+//   the next step's pre-enqueued grid (world.h PreGrid) ........ dropped on discard: it was built from the discarded positions
+//   per-step scratch (acc, w, rho, alpha, kappa, lists, tables, partials, control blocks) ........ rewritten from the start
+//   d_flags ........ cleared at the top of every attempt
+//   counters / stats ........ filled after the loop; discarded_passes counts the discards
+//   boundary force accumulators, host force callbacks, DynamicContactSampling push-outs, ghost exchanges ........ not
+//       repeatable: can_redo is false for worlds that have them
+struct World::PassSnapshot {
+    int32_t bbox[6];  // the cell box the substep runs on
+    float dt_prev, inv_dt_prev;  // TimestepManager's state
+    int cur;
+    uint32_t last_iters[NUM_SOLVES], prev_iters[NUM_SOLVES];
+    explicit PassSnapshot(const World& w) : dt_prev(w.dt_prev), inv_dt_prev(w.inv_dt_prev), cur(w.cur) {
+        memcpy(bbox, w.h_rb->bbox, sizeof(bbox));
+        memcpy(last_iters, w.last_iters, sizeof(last_iters));
+        memcpy(prev_iters, w.prev_iters, sizeof(prev_iters));
+    }
+    // everything a pass computed is discarded; the pre-sort buffers are intact
+    void restore(World& w) const {
+        w.cur = cur; w.dt_prev = dt_prev; w.inv_dt_prev = inv_dt_prev;
+        memcpy(w.h_rb->bbox, bbox, sizeof(bbox));
+        memcpy(w.last_iters, last_iters, sizeof(last_iters)); memcpy(w.prev_iters, prev_iters, sizeof(prev_iters));
+        if (w.pre.valid) { w.pre.valid = false; w.pre_drop(); }
+    }
+};
+
+bool World::has_force(int kind) const {
+    for (const FluidSlot& f : fluids)
+        for (const SalvaHipForceDesc& d : f.forces)
+            if (d.kind == kind) return true;
+    return false;
+}
+
+// The sort is a counting sort by cell (grid.hip cell_sort: same result as the radix sort it replaced, bit for bit) while the
+// cell table is not much larger than the particle set — it costs a memset and a scan of that table, where the radix sort
+// with k_cell_start writes it once: a bounding box blown up by a few strays (4 x 10^8 cells around 25 k particles) keeps
+// the radix sort.  SALVA_HIP_RADIX_SORT=1 / 0 forces one or the other.
+bool World::counting_sort_for(size_t ncf, uint32_t n) const {
+    return ncf + 1 < 0x7fffffffull && (sort_mode == 0 || (sort_mode < 0 && ncf <= 16ull * n + (1ull << 20)));
+}
+
+// a list was cut at the ELL capacity: room for the longest list seen, and a quarter to spare
+void World::grow_list_caps(uint32_t need_ff, uint32_t need_fb) {
+    if (need_ff > cap_ff) cap_ff = (need_ff + need_ff / 4 + 4u) & ~3u;
+    if (need_fb > cap_fb) cap_fb = (need_fb + need_fb / 4 + 4u) & ~3u;
+}
+
+// Does the fullest halo of these totals fit any LDS layout of the tile kernels?  max_sum: TileAcc::max_sum where the totals are
+// exact, 0 where only the two maxima are known (a prediction).
+static bool halo_fits(const TileAcc& tt, uint32_t max_sum) {
+    TileLds probe; probe.max_halo_fluid = tt.max_s; probe.max_halo_boundary = tt.max_sb; probe.max_sum = max_sum;
+    return tt.max_s < 65536u && tt.max_sb < 65536u && probe.bytes(52, 32, 6) <= 160u * 1024u;
+}
+
+// ------------------------------------------------------------------------------------------------ the grid part of a step
+// Cell keys (+ counts) -> sort by cell -> non-empty tiles -> per-tile counts -> their scan (-> publication of the totals), in three
+// parts: a step runs DynamicContactSampling between the first two and builds the boundary grid between the last two.  World::run_pass
+// enqueues them for the current step into G(); World::pre_enqueue_grid for the NEXT step into the other set of tables, every kernel
+// gated.  `counting`: counting_sort_for — the radix sort knows no gate.
+void World::enqueue_grid_keys(GridTabs& T, const GridShape& gs, bool counting, bool mass, const uint32_t* gate) {
+    const uint32_t nslots = std::max<uint32_t>(gs.nslots_bound, 1u);
+    T.cell_start_f.ensure(gs.ncf + 1, stream, false, 1.5f);
+    T.tile_flags.ensure((size_t)gs.ntiles + 1, stream, false, 1.5f);
+    T.tile_rank.ensure((size_t)gs.ntiles + 1, stream, false, 1.5f);
+    T.tile_ids.ensure(nslots, stream, false, 1.5f);
+    T.slot_desc.ensure(nslots, stream, false, 1.5f);
+    T.tile_cnt.ensure((size_t)gs.nslots_bound + 1, stream, false, 1.5f);
+    T.tile_off.ensure((size_t)gs.nslots_bound + 1, stream, false, 1.5f);
+    if (counting) {
+        T.cell_rank.ensure(n, stream, false, 1.1f);
+        SALVA_HIP_CHECK(hipMemsetAsync(T.cell_start_f.p, 0, (gs.ncf + 1) * sizeof(uint32_t), stream));
+    }
+    launch_cell_keys(posm[cur].p, n, sc.h, gf.device(nullptr), T.keys[0].p, T.idx[0].p, d_flags.p, mass ? mass_slots.p : nullptr,
+                     counting ? T.cell_start_f.p : nullptr, counting ? T.cell_rank.p : nullptr, stream, gate);
+}
+// keys -> radix sort -> reorder -> cell table   (hgrid.clear + insert_fluids_to_grid, liquid_world.rs:90-91)
+void World::enqueue_grid_sort(GridTabs& T, const GridShape& gs, bool counting, const uint32_t* gate) {
+    if (counting) {
+        const size_t tb = cell_sort_temp_bytes((uint32_t)gs.ncf);
+        ensure_cub_temp(tb);
+        cell_sort(cub_temp.p, tb, n, (uint32_t)gs.ncf, T.keys[0].p, T.cell_rank.p, T.cell_start_f.p, T.keys[1].p, T.idx[0].p, T.idx[1].p, stream, gate);
+    } else {
+        const int end_bit = bits_for(gs.ncf);
+        const size_t tb = sort_pairs_temp_bytes(n, end_bit);
+        ensure_cub_temp(tb);
+        sort_pairs(cub_temp.p, tb, T.keys[0].p, T.keys[1].p, T.idx[0].p, T.idx[1].p, n, end_bit, stream);
+        launch_cell_start(T.keys[1].p, n, (uint32_t)gs.ncf, T.cell_start_f.p, stream);
+    }
+}
+size_t World::tile_scan_temp(const GridShape& gs) {
+    const size_t tb = std::max(scan_tiles_temp_bytes(gs.nslots_bound + 1), scan_temp_bytes(gs.ntiles + 1));
+    ensure_cub_temp(tb);
+    return tb;
+}
+// tile tables: per-tile halo sizes / slice counts -> prefix.  `c`: the step's context, pointed at the tables of T here.  Returns the
+// sequence number of the totals' publication (publish: somebody will wait for it).
+uint32_t World::enqueue_grid_tiles(GridTabs& T, const GridShape& gs, StepCtx c, size_t tb, const uint32_t* gate, bool publish) {
+    launch_tile_slots(gf.device(T.cell_start_f.p), gs.ntiles, T.tile_flags.p, T.tile_rank.p, T.tile_ids.p, cub_temp.p, tb, stream, gate, split_s_cur);
+    // (k_tile_count zeroes the entries of its surplus workgroups and the scan's extra element itself: no memset —
+    // unless there is no workgroup at all, a rank that holds no particle)
+    if (gs.nslots_bound == 0) SALVA_HIP_CHECK(hipMemsetAsync(T.tile_cnt.p, 0, sizeof(TileAcc), stream));
+    c.gf = gf.device(T.cell_start_f.p);
+    c.tile_off = T.tile_off.p; c.tile_ids = T.tile_ids.p; c.tile_rank = T.tile_rank.p; c.slot_desc = T.slot_desc.p;
+    c.gate = gate;
+    launch_tile_count(c, gs.nslots_bound, T.tile_cnt.p, T.slot_desc.p, stream);
+    scan_tiles(cub_temp.p, tb, T.tile_cnt.p, T.tile_off.p, gs.nslots_bound + 1, stream);
+    return publish ? publish_enqueue(T.tile_off.p + gs.nslots_bound, false, false, nullptr, gate) : 0u;
+}
+
+// The grid part of the NEXT step, behind this step's end-of-step publication (world.h PreGrid): the launches World::run_pass makes
+// at its start (enqueue_grid_*, always with the counting sort: World::publish_end_of_step asks for it only then) on the positions
+// this step leaves behind, for the grid this step ran on, into the OTHER set of tables, every kernel gated by Readback::pre_ok.
+void World::pre_enqueue_grid(const GridShape& gs) {
+    GridTabs& T = gtab[gsel ^ 1];
+    const uint32_t* gate = &d_rb.p->pre_ok;
+    pre.check_mass = !(mass_known && mass_uniform == 0.0f);
+    enqueue_grid_keys(T, gs, true, pre.check_mass, gate);
+    enqueue_grid_sort(T, gs, true, gate);
+    pre.seq = enqueue_grid_tiles(T, gs, make_ctx(), tile_scan_temp(gs), gate, true);
+    pre.n = n; pre.ncf = gs.ncf; pre.ntiles = gs.ntiles; pre.nslots_bound = gs.nslots_bound; pre.gf = gf; pre.split_s = split_s_cur;
+    pre.valid = true;
+}
+// The next step could not use it.  If its launches ran (the gate was open) they have raised flags and mass marks that belong to no step.
+void World::pre_drop() {
+    ++pre_dropped; ++counters.pregrid_dropped;
+    if (!h_rb->pre_ok) return;
+    SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));
+    SALVA_HIP_CHECK(hipMemsetAsync(mass_slots.p, 0, MASS_SLOTS * sizeof(uint32_t), stream));
+}
+
+// ------------------------------------------------------------------------------------------------ substep: prologue
+// The working set of a substep: the sorted particle arrays (rebuilt from the canonical ones after host edits; a decomposed run
+// migrates and mirrors its ghosts here, which changes n) and the per-particle scratch of the step.
+void World::prepare_working_set(SalvaHipStepStats& st) {
+    // ---- persistent particle arrays (double buffered for the sort)
+    ensure_particle_capacity(n);
+
+    // ---- (re)build the sorted working set from the canonical arrays after host edits
+    if (!sorted_valid) {
+        mass_known = false;  // (the host edited the particles: their masses are read again by this step's k_cell_keys)
+        launch_stage_to_sorted(n, st_pos.p, st_vel.p, st_dv.p, st_model.p, rho0_tab.p, arrays(cur), stream);
+        sorted_valid = true;
+        if (comm) {  // global particle ids replace the host-order permutation; nothing is a ghost yet
+            launch_iota_u32(n, gid_offset, perm[cur].p, stream);
+            SALVA_HIP_CHECK(hipMemsetAsync(gtag[cur].p, 0, (size_t)n * sizeof(uint32_t), stream));
+        }
+    }
+    staging_current = false;
+    if (comm) { dist_prepare(); st.nparticles = n_owned; }  // migration + ghost planes: changes n
+
+    // ---- per-step scratch
+    acc.ensure(n, stream, false, 1.1f); w.ensure(n, stream, false, 1.1f); rho.ensure(n, stream, false, 1.1f);
+    posmr.ensure(n, stream, false, 1.1f);
+    alpha.ensure(n, stream, false, 1.1f); kappa.ensure(n, stream, false, 1.1f); nff.ensure(n, stream, false, 1.1f);
+    nfb.ensure(n, stream, false, 1.1f);
+    if (has_force(SALVA_HIP_FORCE_AKINCI2013)) normal.ensure(n, stream, false, 1.1f);
+    if (prm.solver == SALVA_HIP_SOLVER_IISPH) { kappa2.ensure(n); rho_star.ensure(n); aii.ensure(n); dii.ensure(n); dijpj.ensure(n); iisph_q.ensure(n); iisph_pr.ensure(n); }
+    bbox_partials.ensure(6 * std::max<size_t>(std::max<size_t>(num_blocks(n), bbox_blocks(n)), 1024));
+    two_mass = decide_two_mass();
+    if (two_mass) nffb.ensure(n, stream, false, 1.1f);
+    if (two_mass && nmass > 2u) nffc.ensure(n, stream, false, 1.1f);
+}
+
+// The fluid grid of this substep: gf from the cell bounding box (known from the previous step's position update unless the host
+// moved particles) and the fold rule, split_s_cur, and the sizes that follow from them.  Throws FoldRetry (World::step runs the
+// substep again) when a looser fold does not fit the cell-table budget.
+World::GridShape World::choose_grid() {
+    if (!bbox_known) {
+        launch_bbox(posm[cur].p, n, sc.h, bbox_partials.p, d_rb.p->bbox, d_flags.p, stream);
+        SALVA_HIP_CHECK(hipMemcpyAsync(h_rb->bbox, d_rb.p->bbox, sizeof(int32_t) * 6, hipMemcpyDeviceToHost, stream));
+        wait_stream();
+        bbox_known = true;
+    }
+    // Fold the fluid grid when its box is mostly empty (device_types.h TileGrid): more than 4 cells per particle + 2^20 — a block at
+    // rest fills a cell with eight particles, the box of an L-shaped or splashing scene a few times the cells it occupies; leaked or
+    // sprayed particles falling away from the scene are what this is for (tools/r05/soak.sh: the bench scene's box grows from 1.2 x 10^5
+    // to 2.3 x 10^8 cells in a thousand steps).  The periods stay at least 64 cells and at least as long as the boundary grid is wide
+    // (a folded fluid tile addresses the boundary cells modulo its own periods: tile.h TileCells::build), so the boundary grid has
+    // to exist first.  Not in decomposed runs (ghost planes are found by absolute cell coordinate) and not with dynamic contact
+    // sampling (dcs.hip decodes cell coordinates from the keys).  SALVA_HIP_NO_FOLD=1: never; SALVA_HIP_FOLD_CELLS=P: every axis
+    // longer than P cells to exactly P (a power of two >= 8; the tests' way to fold small scenes).
+    // (fold_relax: a fold that piled the bulk of the fluid onto itself — the rule below looks at the box, not at where the particles
+    // sit — was found out by the tile totals of an earlier attempt, which then threw FoldRetry: every level loosens the fold
+    // eightfold, the third gives it up.  Sticky for the world.)
+    const uint32_t forced = fold_forced ? fold_forced << (2u * std::min(fold_relax, 3u)) : 0u;
+    constexpr bool tiles_pow2 = (TX & (TX - 1)) == 0 && (TY & (TY - 1)) == 0 && (TZ & (TZ - 1)) == 0;  // (a period is a whole number of tiles)
+    // (a decomposed run finds its ghost planes by absolute x-cell: it folds y and z only.  Dynamically sampled colliders read cells
+    // back from the keys: dcs.hip picks the image by the particle's position.)
+    const bool can_fold = tiles_pow2 && !fold_off && fold_relax < 3u;
+    if (can_fold && nb && b_dirty) build_boundary_grid();
+    // (once it folds, it folds tight — to half a cell per particle if the periods allow: the particles that have left the scene
+    // then land on the tiles of the bulk instead of owning a tile each; a tile with one particle costs a quarter of a full one)
+    const double loosen = (double)(1u << (3u * std::min(fold_relax, 3u)));
+    FoldRule rule{forced ? 0.0 : 4.0 * (double)n + 1048576.0, forced ? 0.0 : std::max(0.5 * (double)n, 262144.0) * loosen,
+                  {forced ? forced : 64u, forced ? forced : 64u, forced ? forced : 64u}, {!comm, true, true}};
+    if (nb)
+        for (int a = 0; a < 3; ++a) {
+            static const int T[3] = {TX, TY, TZ};
+            const uint64_t bcells = (uint64_t)gb.nt[a] * T[a];
+            while (rule.min_period[a] < bcells) rule.min_period[a] *= 2u;
+        }
+    try {
+        dims_from_bbox(h_rb->bbox, gf, can_fold ? &rule : nullptr);
+    } catch (const HipError& e) {
+        // the looser fold does not fit the cell-table budget: back to the tighter one, and live with what its tiles hold
+        if (e.code != SALVA_HIP_E_CAPACITY || fold_relax == 0u || fold_locked) throw;
+        --fold_relax; fold_locked = true;
+        throw FoldRetry{};
+    }
+    GridShape gs;
+    gs.ncf = gf.ncells();
+    gs.ntiles = (uint32_t)gf.ntiles();
+    // only the cell table and one flag per tile are dense over the bounding box; every other per-tile table is compact
+    // over the non-empty tiles ("slots"), of which there are at most min(ntiles, n)
+    // Splitting of over-full tiles (device_types.h StepCtx::split_s): where the plane layouts run (one or two particle masses, single
+    // domain), and while the tiles beyond the three-per-CU layouts are a minority — decided from the totals of the step before
+    // (split_on, World::size_pass).  SALVA_HIP_NO_SPLIT=1: never; SALVA_HIP_SPLIT_S=k: always, at k halo particles (tests).
+    split_s_cur = 0u;
+    if (split_forced) split_s_cur = split_forced;
+    else if (!split_off && split_on && !comm && spec_off && mass_known && (mass_uniform != 0.0f || two_mass)) split_s_cur = TILE_SPLIT_S;
+    gs.nslots_bound = (uint32_t)std::min<uint64_t>((uint64_t)gs.ntiles * (split_s_cur ? (uint64_t)TX : 1ull), n);
+    return gs;
+}
+
+// the per-slot tables of a pass that are not part of a GridTabs (those: enqueue_grid_keys)
+void World::ensure_slot_tables(uint32_t nslots_bound) {
+    const uint32_t nslots = std::max<uint32_t>(nslots_bound, 1u);
+    slot_info.ensure(nslots, stream, false, 1.5f);
+    d_maxhalo.ensure(4);
+    partials.ensure((size_t)nslots * std::max<size_t>(fluids.size(), 1), stream, false, 1.5f);
+    tile_list_stats.ensure(tile_list_stats_bytes(nslots), stream, false, 1.5f);
+    if (two_mass) {  // (per slot; Tile::setup reads them in every tile kernel, k_nbr_tile writes them)
+        tile_mass_bits.ensure(nslots, stream, false, 1.5f);
+        tile_massb_bits.ensure(nslots, stream, false, 1.5f);
+        if (nmass > 2u) tile_masscd_bits.ensure(nslots, stream, false, 1.5f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ substep: the phases of a pass
+// The particle arrays are permuted into the sorted order AFTER the tile tables have been counted: those need the cell table
+// only, and the host then waits for their totals while the GPU moves the 136 bytes per particle of the reorder.
+void World::reorder_working_set(bool timers) {
+    launch_reorder_fluid(n, G().idx[1].p, arrays(cur), arrays(cur ^ 1), w.p, stream);
+    cur ^= 1;
+    if (timers) SALVA_HIP_CHECK(hipEventRecord(evc[0], stream));
+    if (acc_user && !comm) launch_gather_f4(n, perm[cur].p, st_acc.p, acc.p, stream);
+    if (comm) dist_build_lists();
+}
+
+// A speculative pass's totals: the previous step's + a margin; false = the LDS would not hold the padded halo (no speculation this step)
+bool World::predict_totals(const GridShape& gs, TileAcc& tt) const {
+    const TileAcc& l = pred_tt;
+    tt = l;
+    const uint32_t m = spec_tight ? 0u : 1u;  // (SALVA_HIP_SPEC_TIGHT: no margin at all — the tests' way to force misses)
+    tt.nonempty = std::min<uint32_t>(gs.nslots_bound, l.nonempty + m * std::max<uint32_t>(16u, l.nonempty / 16u));
+    tt.max_s = (l.max_s + m * std::max<uint32_t>(32u, l.max_s / 16u) + m * 63u) & ~(m * 63u);
+    tt.max_sb = nb ? ((l.max_sb + m * std::max<uint32_t>(32u, l.max_sb / 8u) + m * 63u) & ~(m * 63u)) : 0u;
+    tt.nsl = std::min<uint32_t>(n / WAVE + gs.nslots_bound + 1, l.nsl + m * std::max<uint32_t>(64u, l.nsl / 32u));
+    tt.s = l.s + m * (l.s / 8 + 4096); tt.sb = l.sb + m * (l.sb / 4 + 4096);
+    return halo_fits(tt, 0u);
+}
+
+// Everything that turns a TileAcc into launch shapes: the totals themselves (waited for — `seq_totals` is their publication — or
+// predicted: p.tt holds the prediction), the lds fields, the workgroup size, the halo tables' stride and size, the launch classes,
+// the referenced halo's caps.  Enqueues the reorder.  Throws FoldRetry when the exact totals show a fold that piled the fluid up.
+void World::size_pass(Pass& p, uint32_t seq_totals) {
+    TileAcc& tt = p.tt;
+    const bool spec = p.spec;
+    reorder_working_set(p.timers);  // (the host waits for the totals while the GPU moves the particles)
+    if (!spec) {  // (else mass_uniform: what the last exact pass found — nothing has touched the particles since, see can_speculate)
+        publish_wait(seq_totals, true, false, false);
+        tt = h_rb->tile_total;
+        if (check_mass) {  // every particle of the working set has the same mass: the evaluate kernels stage 24 bytes per halo slot
+            float m;
+            memcpy(&m, &h_rb->mass_mm[0], sizeof(m));
+            mass_uniform = (h_rb->mass_mm[0] == h_rb->mass_mm[1] && m > 0.0f && std::isfinite(m) && !no_planes) ? m : 0.0f;
+            mass_known = true;
+        }
+    }
+    nlaunch = tt.nonempty;
+    lds.max_halo_fluid = tt.max_s; lds.max_halo_boundary = tt.max_sb;
+    lds.max_sum = spec ? 0u : tt.max_sum;  // (a speculative pass knows the two maxima only: TileLds::sum_slots falls back to their sum)
+    lds.max_raw = spec ? 0u : tt.max_raw;
+    if (tile_trace)
+        fprintf(stderr, "salva_hip tiles: nonempty %u max_s %u max_sb %u max_sum %u max_raw %u heavy %u light %u tiny %u split_s %u mass_uniform %g | chained %llu breaks %llu pregrid %llu dropped %llu | fold %u %u %u\n",
+                tt.nonempty, tt.max_s, tt.max_sb, tt.max_sum, tt.max_raw, tt.heavy, tt.nlight, tt.ntiny, split_s_cur, (double)mass_uniform,
+                (unsigned long long)chain_steps, (unsigned long long)chain_breaks, (unsigned long long)pre_adopted, (unsigned long long)pre_dropped,
+                gf.mask[0] + 1u, gf.mask[1] + 1u, gf.mask[2] + 1u);  // fold: period of each axis in cells, 0 = not folded
+    if (!spec) {
+        // next step's splitting: on while the over-full tiles are few (each costs a second workgroup and a third more staging, and
+        // buys every other tile of every pass its third resident neighbour); off again when they are the rule — a uniformly
+        // compressed fluid is better served by the two-tiles-per-CU layouts than by twice the tiles (smaller
+        // tiles lose).  `heavy` counts whole over-full tiles, or — while splitting — the parts they were cut into.
+        if (!split_on) split_on = tt.heavy > 0u && (uint64_t)tt.heavy * 5u <= tt.nonempty;
+        else if ((uint64_t)tt.heavy * 2u > tt.nonempty) split_on = false;
+    }
+    // Workgroup size: one wave per 64-particle slice of the tile the average PARTICLE lives in (TileAcc::wsl / nsl; fuller tiles
+    // loop over their extra slices) — the plain average over the tiles drops to four waves as soon as a few thousand stray
+    // particles own a tile each, and the full tiles, where nearly all the work is, then run on half the waves.  Never fewer waves
+    // than the halo-table build needs threads, and never more than EIGHT: the neighbour-sum kernels hold 80 VGPRs so that three
+    // tiles of eight waves share a CU (24 of its waves), k_nbr_tile 64 for four; a ninth wave per tile costs each of them a
+    // whole resident tile.  Where the fluid is compressed past 512 particles per tile — every bench scene, from the impact on —
+    // round 4's limit of twelve waves did exactly that: 6.2 against 4.9 ms per step in steps 100..150 of config 2, 3.2 against
+    // 2.5 in steps 150..200 (profiles/r05_experiments/r05l_waves_ab.log; seven waves lose to eight there, and six / seven to
+    // eight on the block at rest: 1.31 / 1.32 against 1.20 ms).  The particle-weighted size lost while the limit was twelve
+    // (r05k_fold_ab.log, session 1: it asked for nine and ten waves) and wins under the limit of eight (r05m_weighted_ab.log:
+    // 1000 steps of config 2 2.73 -> 2.58 ms per step, 500 of config 3 2.84 -> 2.41, 300 of config 4 9.98 -> 9.57).
+#ifndef SALVA_TILE_WAVES_CAP
+#define SALVA_TILE_WAVES_CAP 8
+#endif
+    static_assert(SALVA_TILE_WAVES_CAP <= TILE_MAX_WAVES, "the launch bounds are written for TILE_MAX_WAVES");
+    const uint32_t avg = (n + tt.nonempty - 1) / std::max<uint32_t>(tt.nonempty, 1u);
+    const uint32_t lo = (HCELLS + WAVE - 1) / WAVE, hi = std::min<uint32_t>(std::max<uint32_t>(tt.max_nsl, lo), (uint32_t)(SALVA_TILE_WAVES_CAP));
+#ifdef SALVA_TILE_WAVES_PLAIN_AVERAGE  // (A/B: round 4's rule)
+    const uint32_t weighted = 0u;
+#else
+    const uint32_t weighted = tt.nsl ? (uint32_t)((double)tt.wsl / (double)tt.nsl + 0.5) : 0u;
+#endif
+    lds.threads = WAVE * std::min<uint32_t>(std::max<uint32_t>(std::max<uint32_t>((avg + WAVE - 1) / WAVE, weighted), lo), hi);
+#ifdef SALVA_HIP_DIAG
+    if (const char* e = getenv("SALVA_HIP_TILE_THREADS")) lds.threads = (uint32_t)atoi(e);
+#endif
+    if (gf.folded() && !fold_locked && !spec && !halo_fits(tt, tt.max_sum)) {
+        // Did the fold pile the fluid onto itself?  (a long sheet of fluid without an enclosing boundary folds onto its
+        // own bulk, cells hold several times the particles, and a scene that ran fine on the unfolded table dies of "halo does
+        // not fit".)  The totals say so before any solver kernel has run: loosen the fold and run the pass again — the
+        // particle arrays are merely permuted so far.
+        ++fold_relax;
+        throw FoldRetry{};
+    }
+    if (lds.max_halo_fluid >= 65536u || lds.max_halo_boundary >= 65536u)
+        throw HipError(SALVA_HIP_E_CAPACITY, "more than 65535 particles in one tile halo");
+    // every tile wastes less than one 64-particle slice
+    if (tt.nsl > n / WAVE + p.gs.nslots_bound + 1) throw HipError(SALVA_HIP_E_HIP, "internal error: slice count exceeds its bound");
+    // slot tables: one fixed-stride row per tile when that costs at most ~3x the compact size (dense scenes), so
+    // that a tile kernel can fetch its rows before it knows its sizes; compact rows otherwise (sparse scenes)
+    const uint64_t st_f = (lds.max_halo_fluid + 63u) & ~63u, st_b = nb ? ((lds.max_halo_boundary + 63u) & ~63u) : 0u;
+    const uint64_t strided = (uint64_t)nlaunch * (st_f + st_b), compact = tt.s + tt.sb;
+    const bool use = strided <= 3 * compact + (1u << 20) && !getenv("SALVA_HIP_COMPACT_HALO");
+    halo_stride = use ? (uint32_t)st_f : 0u; bhalo_stride = use ? (uint32_t)st_b : 0u;
+#ifdef SALVA_HIP_DIAG
+    // persistent pipeline kernels (pipe.h): one wave per slice of the fullest tile, at most PIPE_MAX_WAVES
+    pipe.enabled = halo_stride > 0 && !getenv("SALVA_HIP_NO_PIPELINE");
+    pipe.scap = halo_stride; pipe.sbcap = bhalo_stride;
+    pipe.num_cus = (uint32_t)num_cus; pipe.nlaunch = nlaunch;
+    uint32_t waves = std::min<uint32_t>(std::max<uint32_t>(tt.max_nsl, 4u), (uint32_t)PIPE_MAX_WAVES);
+    if (const char* e = getenv("SALVA_HIP_PIPE_WAVES")) waves = std::min<uint32_t>(std::max(atoi(e), 1), PIPE_MAX_WAVES);
+    pipe.threads = waves * WAVE;
+#endif
+    p.need_f = halo_stride ? (size_t)nlaunch * halo_stride : (size_t)tt.s;
+    p.need_b = halo_stride ? (size_t)nlaunch * bhalo_stride : (size_t)tt.sb;
+    halo_src.ensure(p.need_f ? p.need_f : 1, stream, false, 1.2f);
+    bhalo_src.ensure(p.need_b ? p.need_b : 1, stream, false, 1.2f);
+    p.nslices = tt.nsl;
+    if (spec) {  // what the kernels clamp themselves to (StepCtx::spec)
+        spec_mode = true;
+        halo_cap = lds.max_halo_fluid; bhalo_cap = lds.max_halo_boundary; nslices_cap = p.nslices;
+        halo_len = p.need_f; bhalo_len = p.need_b;
+    }
+    // Launch classes (device_types.h StepCtx::slot_order).  Sparse slots: worth a launch of their own per pass once they are many —
+    // a thousand of them hold a CU's LDS for a round and a third of the chip each pass.  Light slots: the class the round-5 review
+    // asked for (tiles under the three-per-CU limit in one launch, those above it in another) — built, bit-identical, and a
+    // LOSS on the scene it was meant for: in steps 300-399 of config 2 (1015 full tiles, 860 light ones) 2.35 against 2.00 ms per
+    // step, 2.71 against 2.36 in steps 900-999 (profiles/r06_experiments/r06j_light_class_lost.log) — a second launch per pass
+    // ends in a second tail of straggling tiles (~13 us per pass here), which is more than the third resident tile gives back
+    // to the light half.  Opt-in: SALVA_HIP_LIGHT=1 (when the fullest halo is beyond a three-per-CU layout and the light slots
+    // are >= 256).  SALVA_HIP_NO_CLASSES=1: no class ever; SALVA_HIP_CLASSES=1: both, whenever there is a slot of the kind and
+    // one outside it (tests).
+    const bool beyond3 = tt.max_s > P3_DS_THREE || tt.max_raw > P2_DS_THREE || tt.max_sum > FIXED_DS_SMALL;
+    class_ntiny = class_nlight = 0u;
+    if (!spec && !classes_off) {
+        if (tt.ntiny > 0u && tt.ntiny < tt.nonempty && (classes_forced || tt.ntiny >= 512u)) class_ntiny = tt.ntiny;
+        const uint32_t nfull = tt.nonempty - tt.nlight - tt.ntiny;
+        if (tt.nlight > 0u && nfull > 0u && (classes_forced || (light_on && beyond3 && tt.nlight >= 256u))) class_nlight = tt.nlight;
+        // (sparse slots without a launch of their own are light ones — tile_is_light holds for them — when the light class runs)
+        if (class_nlight && !class_ntiny) class_nlight += tt.ntiny;
+    }
+    if (class_ntiny || class_nlight) slot_order.ensure(nlaunch, stream, false, 1.5f);
+    if (class_nlight) ++counters.light_class_passes;
+    if (class_ntiny) ++counters.sparse_class_passes;
+
+    // Referenced-only halo (device_types.h StepCtx::tile_off): the list builder drops the halo slots no list names — a seventh of
+    // the 6x6x6 box lies further than h from the own cube — and the solver kernels stage what is left.  It runs where that can
+    // buy a launch shape: in a step where some halo of the full box is beyond a three-per-CU layout (`ref_forced || beyond3` below:
+    // the steps before the impact gain nothing), never in a speculative pass (whose tables are clamped), and with the V = 1
+    // builder only.  SALVA_HIP_FULL_HALO=1: never (the A/B); SALVA_HIP_REF_HALO=1: in every step (tests).
+    // The kept maxima are results of the builder.  Where the list statistics are waited for in the middle of the step the
+    // solver kernels are sized by them exactly; where they travel with the end-of-step publication (defer_lists) the kernels
+    // are sized by the PREVIOUS step's kept maxima plus a margin, never beyond the full box's: the builder holds every tile to
+    // those caps, raises flag 16 where one does not fit, and the pass is repeated with the full box's bounds — the way a list
+    // longer than the capacity is handled.
+    p.ref_step = !ref_off && !spec && n > 0 && halo_stride > 0u && p.c.nmodels <= 32u && p.c.nbmodels <= 32u && (ref_forced || beyond3);
+    p.refb = RefBuild{halo_src.p, slot_info.p, G().tile_off.p, RefCaps{0xffffffffu, 0xffffffffu, 0xffffffffu}, d_rb.p->max_ref};
+    ref_bounded = false;
+    if (p.ref_step && p.defer_lists && ref_pred_valid && ref_pred_n == n) {
+        // (the fullest kept halo moves by a few slots per step in a settled fluid and by a layer of particles — a hundred — when one
+        // crosses a tile face: an eighth of room, which costs LDS bytes only where no layout is at stake; a bound just above a
+        // three-per-CU layout is held to that layout while the prediction leaves it eight slots)
+        auto bound = [&](uint32_t pred, uint32_t full, uint32_t layout) {
+            if (ref_tight) return std::min(pred - pred / 8u, full);  // (tests: a bound every fullest tile outgrows)
+            uint32_t b = pred + std::max<uint32_t>(96u, pred / 8u);
+            if (b > layout && pred + 8u <= layout) b = layout;
+            return std::min(b, full);
+        };
+        p.refb.cap.s = bound(ref_pred[0], tt.max_s, P3_DS_THREE);
+        p.refb.cap.raw = std::max(bound(ref_pred[1], tt.max_raw, P2_DS_THREE), tt.max_sb);
+        p.refb.cap.sum = std::max(bound(ref_pred[2], tt.max_sum, FIXED_DS_SMALL), tt.max_sb);
+        ref_bounded = true;
+    }
+}
+
+// flat halo slot tables (again: behind a list build that kept the referenced slots only — tile_off back to the full box's counts first)
+void World::fill_tile_tables(Pass& p, bool again) {
+    const uint32_t keep_t = class_ntiny, keep_l = class_nlight;
+    class_ntiny = class_nlight = 0u;  // (the table builder itself runs over every slot in one launch)
+    p.c = make_ctx();
+    if (again) scan_tiles(cub_temp.p, p.scan_tb, G().tile_cnt.p, G().tile_off.p, p.gs.nslots_bound + 1, stream);
+    launch_tile_halo_fill(p.c, halo_src.p, bhalo_src.p, slot_info.p, stream, (keep_t || keep_l) ? slot_order.p : nullptr, keep_l, keep_t);
+    class_ntiny = keep_t; class_nlight = keep_l;
+}
+
+// The halo slot tables and the neighbour lists   (compute_contacts, contacts.rs:154-252): one pass into fixed-capacity ELL rows; if a
+// list turns out longer than the capacity the pass is repeated with room to spare (rare: the capacity follows the
+// longest list seen so far).  Speculative passes and those that defer the check look at the end of the step instead.
+void World::build_lists(Pass& p) {
+    fill_tile_tables(p, false);
+    for (int nattempt = 0;; ++nattempt) {
+        if (nattempt > 0 && p.ref_step) fill_tile_tables(p, true);  // (the first build compacted the slot tables in place)
+        nbr_ff.ensure((size_t)p.nslices * cap_ff * WAVE + 1, stream, false, 1.1f);
+        nbr_fb.ensure(nb ? (size_t)p.nslices * cap_fb * WAVE + 1 : 1, stream, false, 1.1f);
+        slice_near.ensure((size_t)p.nslices + 1, stream, false, 1.1f);
+        p.c = make_ctx();
+        // (a pass whose list statistics are only looked at with the end-of-step publication lets that publication fold them)
+        fold_stats = (p.spec || p.defer_lists) && n > 0;
+        launch_nbr_build(p.c, lds, tile_list_stats.p, fold_stats ? nullptr : reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff),
+                         &d_rb.p->max_cnt_ff, comm ? reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_own_ff) : nullptr, stream,
+                         p.ref_step ? &p.refb : nullptr);
+        if (p.spec || p.defer_lists) break;
+        static_assert(offsetof(Readback, max_cnt_ff) == offsetof(Readback, ncontacts_ff) + 2 * sizeof(uint64_t), "list statistics travel in one copy");
+        publish_and_wait(nullptr, true, false);
+        const uint32_t need_ff = (h_rb->max_cnt_ff + 1) / 2, need_fb = (h_rb->max_cnt_fb + 1) / 2;
+        if (need_ff <= cap_ff && need_fb <= cap_fb) break;
+        if (nattempt >= 2) throw HipError(SALVA_HIP_E_HIP, "internal error: neighbour list capacity did not converge");
+        grow_list_caps(need_ff, need_fb);
+    }
+    lds_full = lds; ref_last = p.ref_step; ref_last_caps = p.refb.cap; ref_last_nslots_bound = p.gs.nslots_bound;
+    if (p.ref_step) {
+        // from here on the tiles hold their kept slots only, and the launches are cut for them
+        if (!p.defer_lists) { lds.max_halo_fluid = std::max<uint32_t>(h_rb->max_ref[0], 1u); lds.max_raw = h_rb->max_ref[1]; lds.max_sum = h_rb->max_ref[2]; }
+        else if (ref_bounded) { lds.max_halo_fluid = p.refb.cap.s; lds.max_raw = p.refb.cap.raw; lds.max_sum = p.refb.cap.sum; }
+        ref_on_cur = true;
+        ++ref_passes;
+        if (tile_trace && !p.defer_lists)
+            fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (exact)\n",
+                    p.tt.max_s, p.tt.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid);
+    }
+#ifdef SALVA_HIP_DIAG
+    // kernel-development builds: bank-conflict-aware list order (diag/sched.hip), SALVA_HIP_SCHED=1
+    if (sched_mode > 0) launch_list_schedule(p.c, lds, stream);
+#endif
+}
+
+// solver   (evaluate_kernels + compute_densities + solver.step, liquid_world.rs:123-144)
+void World::density_and_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers) {
+    // (DFSPH: the first evaluate of the divergence solve rides in the density pass when the plane layout applies, dfsph.hip)
+    fused_first_divergence = prm.solver == SALVA_HIP_SOLVER_DFSPH && !no_fused_div && launch_density_alpha_div(c, lds, stream);
+    // (single-domain IISPH: d_ii rides in the density pass, dfsph.hip k_density_alpha<true>)
+    // (not with CFL sub-stepping: d_ii carries dt^2, and the substep is only chosen inside the solver)
+    iisph_dii_fused = prm.solver == SALVA_HIP_SOLVER_IISPH && !comm && !no_fused_div && !cfl_mode;
+    if (!fused_first_divergence) launch_density_alpha(c, lds, iisph_dii_fused ? dt : 0.0f, stream);
+    if (comm) {
+        refresh_f32(rho.p);
+        // (the density pass wrote posmr.w = m / rho from each rank's OWN sum; a ghost's rho has just been replaced by its owner's,
+        // so its volume follows — XSPH takes the neighbour's volume from there.  ADVICE r03)
+        if (nghost_lo + nghost_hi) k_ghost_posmr<<<nblk(n), BLOCK, 0, stream>>>(n, gtag[cur].p, posm[cur].p, rho.p, posmr.p);
+    }
+    if (timers) SALVA_HIP_CHECK(hipEventRecord(evc[2], stream));
+    if (prm.solver == SALVA_HIP_SOLVER_DFSPH) dfsph_solve(c, dt, g, st);
+    else iisph_solve(c, dt, g, st);
+}
+
+// end of step: next bbox + flags (+ in a speculative pass: the true table totals and list statistics), published and waited for.
+// The next step's grid part rides behind this step's publication when the cell box has been standing still (world.h PreGrid):
+// the device compares the box this step's position update found with the one this step ran on, and opens the gate if equal.
+void World::publish_end_of_step(const Pass& p, const PassSnapshot& snap) {
+    static_assert(offsetof(Readback, bbox) == offsetof(Readback, flags) + sizeof(uint32_t), "flags and bbox travel in one copy");
+    const bool stable = bbox_used_valid && memcmp(bbox_used_last, snap.bbox, sizeof(snap.bbox)) == 0;
+    const bool want_pre = !pre_off && p.attempt == 0 && !p.spec && !comm && !p.timers && !p.has_dyn && !has_force(SALVA_HIP_FORCE_CUSTOM) && !cfl_mode &&
+                          counting_sort_for(p.gs.ncf, n) && stable && n > 0 && p.gs.nslots_bound > 0;
+    memcpy(bbox_used_last, snap.bbox, sizeof(snap.bbox)); bbox_used_valid = true;
+    PrePub pp{want_pre ? 1 : 0, chain_pending ? 1 : 0, {snap.bbox[0], snap.bbox[1], snap.bbox[2], snap.bbox[3], snap.bbox[4], snap.bbox[5]}};
+    const uint32_t seq_end = publish_enqueue(p.spec ? G().tile_off.p + p.gs.nslots_bound : nullptr, p.spec || p.defer_lists, true, &pp);
+    if (want_pre) pre_enqueue_grid(p.gs);
+    publish_wait(seq_end, p.spec, p.spec || p.defer_lists, true);
+    flags_clean = true;  // (k_publish_readback cleared them behind the copy)
+}
+
+// A chained step (World::dfsph_solve): the publication says whether both solves converged within the batches they were given.
+void World::adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers) {
+    chain_pending = false;
+    auto adopt = [&](int which) {  // the outcome of a solve nobody waited for
+        prev_iters[which] = last_iters[which];
+        last_iters[which] = h_rb->solve[which][1];
+        h_ctl[which].done = h_rb->solve[which][0]; h_ctl[which].iters = h_rb->solve[which][1];
+        memcpy(&h_ctl[which].err, &h_rb->solve[which][2], sizeof(float));
+    };
+    uint32_t stage = h_rb->chain_ok ? 0u : h_rb->chain_stage;
+    if (stage == 0u) {
+        if (chain_div_pending) adopt(0);
+        adopt(1);
+        ++chain_steps; ++counters.chained_passes;
+    } else {
+        // one of them fell short: every kernel behind it returned at once.  Continue that solve the classic way (batches with a
+        // wait each) and run what follows it; the flags raised so far were published (and cleared) by the first publication.
+        if (stage != 1u && stage != 2u) throw HipError(SALVA_HIP_E_HIP, "internal error: a chained step broke at an unknown stage");
+        ++chain_breaks; ++counters.chain_breaks;
+        pre.valid = false;  // (its gate stayed shut: Readback::pre_ok needs the chain)
+        const uint32_t flags0 = h_rb->flags;
+        if (stage == 2u && chain_div_pending) adopt(0);
+        dfsph_solve(c, dt, g, st, (int)stage);
+        if (timers) SALVA_HIP_CHECK(hipEventRecord(ev[2], stream));  // (the solver's part of the step ends here, not at the first publication)
+        publish_and_wait(nullptr, false, true);
+        h_rb->flags |= flags0;
+    }
+    if (stage != 1u) { st.n_divergence_iters = (int32_t)h_ctl[0].iters; st.divergence_error = h_ctl[0].err; }
+    if (stage == 0u) { st.n_pressure_iters = (int32_t)h_ctl[1].iters; st.density_error = h_ctl[1].err; }
+}
+
+// One attempt at the substep: grid -> launch shapes -> lists -> solver -> end-of-step publication.  True: the pass committed.
+// False: the publication showed that it ran on too little room (a list cut at the capacity, a kept halo or a predicted total
+// outgrown); `snap` has put the world back and the pass is to be repeated, with p.attempt + 1.
+bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st) {
+    const GridShape& gs = p.gs;
+    static_cast<Attempt&>(p) = Attempt{};
+    p.spec = p.can_speculate && p.attempt == 0;
+    chain_pending = false;
+    ref_on_cur = false;
+    p.defer_lists = p.can_redo && !defer_off && p.attempt == 0 && lists_checked;
+    if (p.attempt > 0) SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));  // (whatever the discarded pass flagged)
+    p.have_grid = p.adopted && p.attempt == 0;
+    // (a scene known to hold different masses — two fluids of different density0 — is not asked again until the host edits the
+    // particles: every wave of the lighter fluid would raise a flag, 71 us per launch at 2 x 10^6 particles)
+    check_mass = p.have_grid ? pre.check_mass : !(mass_known && mass_uniform == 0.0f);
+    const bool counting = counting_sort_for(gs.ncf, n);
+    if (!p.have_grid) {
+        enqueue_grid_keys(G(), gs, counting, check_mass, nullptr);
+        if (p.has_dyn) {  // coupling.update_boundaries (liquid_world.rs:94-103): may push particles, cells stay
+            // (host clock: the pass ends with a read-back of the emitted count, so the stream is drained when it returns)
+            if (p.timers) wait_stream();
+            const auto t1 = std::chrono::steady_clock::now();
+            run_dynamic_sampling();
+            p.dcs_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+        }
+        enqueue_grid_sort(G(), gs, counting, nullptr);
+    }
+    build_boundary_grid();  // insert_boundaries_to_grid (liquid_world.rs:106) + boundary volumes, only when dirty
+    if (p.timers) SALVA_HIP_CHECK(hipEventRecord(evc[1], stream));
+
+    nlaunch = 0;  // not known yet
+    spec_mode = false; halo_cap = bhalo_cap = 0xffffffffu; nslices_cap = 0xffffffffu; halo_len = bhalo_len = ~0ull;
+    p.c = make_ctx();
+    p.scan_tb = tile_scan_temp(gs);
+    if (p.spec) p.spec = predict_totals(gs, p.tt);
+    uint32_t seq_totals = pre.seq;  // (an adopted grid published its totals already)
+    if (!p.have_grid) seq_totals = enqueue_grid_tiles(G(), gs, p.c, p.scan_tb, nullptr, !p.spec);
+    size_pass(p, seq_totals);
+    build_lists(p);
+    if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[1], stream));
+
+    density_and_solve(p.c, dt, g, st, p.timers);
+    if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[2], stream));
+    publish_end_of_step(p, snap);
+    if (comm && prm.enable_timers) dist_time_fold();  // (the stream has drained up to the publication: every pair has completed)
+
+    const uint32_t need_ff = (h_rb->max_cnt_ff + 1) / 2, need_fb = (h_rb->max_cnt_fb + 1) / 2;  // (where the publication carried them)
+    bool miss = false;
+    if (p.defer_lists && !p.spec) {
+        // (flag 16: a tile kept more halo slots than the launches of this pass were cut for — k_nbr_tile's REF part)
+        const bool ref_miss = ref_bounded && (h_rb->flags & 16u) != 0u;
+        if (ref_miss) { ref_pred_valid = false; ++ref_misses; }
+        if (ref_on_cur && tile_trace)
+            fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (%s)%s\n",
+                    lds_full.max_halo_fluid, lds_full.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid,
+                    ref_bounded ? "previous step + margin" : "full box", ref_miss ? " MISS: pass repeated" : "");
+        miss = need_ff > cap_ff || need_fb > cap_fb || ref_miss;  // a list was cut at the capacity, or a kept halo at its bound
+    }
+    if (p.spec) {
+        const TileAcc& a = h_rb->tile_total;
+        miss = !(a.nonempty <= p.tt.nonempty && a.max_s <= p.tt.max_s && a.max_sb <= p.tt.max_sb && a.nsl <= p.tt.nsl &&
+                 (halo_stride || (a.s <= p.tt.s && a.sb <= p.tt.sb)) && need_ff <= cap_ff && need_fb <= cap_fb);
+        if (miss) ++spec_misses;  // the prediction did not hold
+        ++counters.speculative_passes;
+    }
+    if (miss) {
+        ++counters.discarded_passes;
+        snap.restore(*this);
+        grow_list_caps(need_ff, need_fb);
+        return false;
+    }
+    if (chain_pending) adopt_chain_outcome(p.c, dt, g, st, p.timers);
+    pred_tt = h_rb->tile_total; pred_n = n; pred_valid = true;
+    if (ref_on_cur) { memcpy(ref_pred, h_rb->max_ref, sizeof(ref_pred)); ref_pred_n = n; ref_pred_valid = true; }
+    else ref_pred_valid = false;
+    lists_checked = true;  // (every path to here has compared the longest lists with the capacity)
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ substep: its tails
+void World::record_timers(const Pass& p, SalvaHipStepStats& st) {
+    // ev[2] was recorded before the end-of-step publication, whose arrival the host has seen through host-mapped memory — which
+    // says nothing about the EVENT's completion signal: without the synchronisation hipEventElapsedTime can still answer
+    // hipErrorNotReady (it did, on a fresh box: VERDICT r04).  Every other event of the step precedes ev[2] on the stream.
+    // An interval that cannot be read is reported as NaN ("untimed"), never as 0.
+    const double untimed = std::numeric_limits<double>::quiet_NaN();
+    bool ok = hipEventSynchronize(ev[2]) == hipSuccess;
+    if (!ok) (void)hipGetLastError();
+    auto ms = [&](hipEvent_t from, hipEvent_t to) -> double {
+        float t = 0.0f;
+        if (!ok) return untimed;
+        if (hipEventElapsedTime(&t, from, to) != hipSuccess) { (void)hipGetLastError(); return untimed; }
+        return (double)t;
+    };
+    const double a = ms(ev[0], ev[1]), b = ms(ev[1], ev[2]);
+    // the reference's tree (liquid_world.rs:73-156); every interval is taken on the world's stream.  The timers are resumed and
+    // paused in every substep (:88-147): they add up over the substeps of a step.
+    st.grid_ms += (float)a; st.solver_ms += (float)b; st.step_ms += (float)(a + b);
+    counters.step_time += a + b;
+    counters.stages.collision_detection_time += a;
+    counters.stages.solver_time += b;
+    counters.cd.boundary_update_time += p.dcs_ms;  // DynamicContactSampling runs inside the step (liquid_world.rs:94-103)
+    const double gi = ms(ev[0], evc[1]);
+    counters.cd.grid_insertion_time += std::isnan(gi) ? gi : std::max(0.0, gi - p.dcs_ms);
+    counters.cd.neighborhood_search_time += ms(evc[1], ev[1]);
+    counters.solver.pressure_resolution_time += ms(evc[2], ev[2]);
+    if (prm.solver == SALVA_HIP_SOLVER_DFSPH) counters.custom += ms(evc[3], evc[4]);
+}
+
+// what the kernels of the step flagged (Readback::flags), as the errors the caller sees
+void World::raise_step_flags() {
+    static const struct { uint32_t bit; int code; const char* what; } fatal[] = {
+        {1u, SALVA_HIP_E_NUMERIC, "zero density / boundary denominator or NaN detected (the reference would panic)"},
+        {2u, SALVA_HIP_E_HIP, "internal error: particle outside the cell table"},
+        {8u, SALVA_HIP_E_HIP, "internal error: a third particle mass in a world the host took for a two-mass world"},
+        {16u, SALVA_HIP_E_HIP, "internal error: a referenced halo beyond its bound in a pass that had none"}};
+    for (const auto& f : fatal)
+        if (h_rb->flags & f.bit) {
+            bbox_known = false;  // (the positions are not to be trusted: the next step measures its box itself)
+            throw HipError(f.code, f.what);
+        }
+    if (h_rb->flags & 4u)
+        // k_dist_flags: such a particle was handed to the adjacent rank, which does not own its cells either — it would
+        // never be mirrored as a ghost and its contacts across the next face would be lost
+        throw HipError(SALVA_HIP_E_INVALID, "a particle moved across more than one slab in a single step (slabs too thin for this time step): "
+                                            "results of this step are not reliable");
+}
+
+// the committed pass becomes the world's state: reaction forces, statistics, counters, then the step's flags
+int World::finish_substep(const Pass& p, float dt, SalvaHipStepStats& st) {
+    commit_elastic();
+    // the reaction forces of this substep, summed in fixed point: into boundary.forces, and back to zero
+    if (any_wants_forces && nb) k_bforce_fold<<<nblk(nb), BLOCK, 0, stream>>>(nb, bforce_fx.p, bforce.p, 1.0f / bforce_scale());
+    acc_user = false;
+    // decomposed runs: the contacts whose first particle this rank owns (fluid) / whose first particle lies in its slab
+    // (boundary-boundary, k_boundary_volumes) — the ranks' counts add up to the undivided domain's counters.cd.ncontacts
+    st.ncontacts = comm ? h_rb->ncontacts_own_ff + (nb ? h_rb->ncontacts_own_fb : 0) + ncontacts_bb
+                        : h_rb->ncontacts_ff + (nb ? h_rb->ncontacts_fb : 0) + ncontacts_bb;
+    bbox_known = true;
+    last_ctx = p.c; last_ctx.ctl = nullptr; last_dt = dt; have_last_ctx = true;  // (dt: the substep the solver advanced by)
+    if (p.timers) record_timers(p, st);
+    counters.cd.ncontacts = st.ncontacts;
+    counters.n_divergence_iters = st.n_divergence_iters; counters.n_pressure_iters = st.n_pressure_iters;
+    st.reserved[0] = (float)lds_full.max_halo_fluid;  // (the full box's count, whatever the solver kernels staged: SALVA_HIP_TILE_TRACE prints both)
+    st.reserved[1] = (float)lds.max_halo_boundary; st.reserved[2] = (float)lds.threads;
+    st.reserved[3] = (float)((double)(h_rb->ncontacts_ff + (nb ? h_rb->ncontacts_fb : 0)) / (double)std::max<uint32_t>(n, 1u));  // list entries per local particle
+    st.reserved[4] = (float)(n - owned_count());  // ghosts
+    raise_step_flags();
+    return SALVA_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ substep
+// One substep: the body of the `while` of LiquidWorld::step_with_coupling (liquid_world.rs:85-147).  `dt` comes in as the step's
+// total length and goes out as the substep the solver advanced by.
+int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
+    Pass p;
+    p.timers = prm.enable_timers != 0;
+    if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[0], stream));
+    // (what decides below whether the grid part the previous step enqueued for this one still describes the world)
+    const bool world_touched = tables_dirty || !sorted_valid || !bbox_known || b_dirty;
+    upload_tables();
+    // (the end-of-step publication of the previous step left the flags clear; anything else — the first step, a step that threw —
+    // clears them here)
+    if (!flags_clean) SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));
+    flags_clean = false;
+    prepare_working_set(st);
+    p.gs = choose_grid();
+    // ---- the grid part of this step may be on the device already (world.h PreGrid): adopt the other set of tables, or drop it
+    if (pre.valid) {
+        pre.valid = false;
+        p.adopted = h_rb->pre_ok && !world_touched && !p.timers && !comm && pre.n == n && pre.ncf == p.gs.ncf && pre.ntiles == p.gs.ntiles &&
+                    pre.nslots_bound == p.gs.nslots_bound && pre.split_s == split_s_cur && memcmp(&pre.gf, &gf, sizeof(GridDims)) == 0;
+        if (p.adopted) { gsel ^= 1; ++pre_adopted; ++counters.pregrid_adopted; }
+        else pre_drop();
+    }
+    ensure_slot_tables(p.gs.nslots_bound);
+
+    // ---- One pass over the step.  The sizes of the tile tables (number of non-empty tiles, largest halo, slices) and the
+    // longest neighbour list are results of this step's own kernels; waiting for them costs two host round trips with an
+    // idle GPU.  When nothing forbids it the step is SPECULATIVE: launch shapes, LDS sizes and buffers are taken from the
+    // previous step's totals plus a margin, the kernels clamp themselves to what they were given, and the true totals are
+    // read back once, at the end, with everything else.  If they exceeded the prediction (rare: they change by a few
+    // slots per step) the step is simply run again from the untouched pre-sort buffers with exact sizes.
+    p.has_dyn = has_dynamic_sampling();
+    // a pass can be repeated from the untouched pre-sort buffers iff it has no side effect outside the world's own arrays
+    // (a communicator of one rank exchanges nothing: its passes are as repeatable as the plain world's)
+    const bool solo = comm && !comm->has_lo() && !comm->has_hi();
+    p.can_redo = (!comm || solo) && !any_wants_forces && !has_force(SALVA_HIP_FORCE_CUSTOM) && !p.has_dyn;
+    // (mass_known: the kernels of a pass are chosen by StepCtx::mass_uniform, which a speculative pass — it does not wait for the
+    // publication that carries it — can only inherit; a host edit since the last publication may have changed the masses)
+    p.can_speculate = !spec_off && p.can_redo && !b_dirty && pred_valid && pred_n == n && mass_known;
+    // The neighbour-list capacity check (longest list <= ELL capacity) costs a read-back with an idle GPU in the middle of the
+    // step although it fails about once per run (the capacity follows the longest list seen so far): where the pass can be
+    // repeated (Pass::defer_lists), check at the end of the step with the read-back that happens there anyway, and repeat on
+    // overflow.  It stays in the middle of the step until the capacity has held once for the current set of objects
+    // (`lists_checked`, cleared by every edit of the fluids or boundaries): the first step of a scene — whose lists are longer
+    // than the initial capacity in almost any dense scene — is then not computed twice.
+    const PassSnapshot snap(*this);  // what a discarded pass puts back
+    for (p.attempt = 0; !run_pass(p, snap, dt, g, st); ++p.attempt) {}
+    return finish_substep(p, dt, st);
+}
+
+}  // namespace salva

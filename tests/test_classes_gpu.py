@@ -195,9 +195,9 @@ def test_light_slots_on_the_small_layouts_beside_full_ones_change_nothing(case):
 
 
 def test_the_light_class_when_asked_for_runs_where_many_halos_fit_the_small_layouts_and_some_do_not():
-    """A third of a million particles whose lower 40 % are over-full — too many tiles to cut them all (World::substep keeps tiles
+    """A third of a million particles whose lower 40 % are over-full — too many tiles to cut them all (World::size_pass keeps tiles
     whole when more than a fifth are over-full), and hundreds that are not: with SALVA_HIP_LIGHT=1 those run three per CU again, in
-    launches of their own.  (Opt-in: on the bench scene the second launch per pass costs more than it brings, world.hip.)"""
+    launches of their own.  (Opt-in: on the bench scene the second launch per pass costs more than it brings, World::size_pass.)"""
     sc = _squeezed_column(64, 80, 64, frac=0.4, strays=False)
     os.environ.pop("SALVA_HIP_SPLIT_S", None)
     w0, f0, t0 = _run({"SALVA_HIP_NO_CLASSES": "1"}, sc, 4)

@@ -54,7 +54,7 @@ def run_to(w, k, target):
 def run_to_stable_box(w, fls, k, first, last):
     """Step until the last two steps have left the particles' cell box as they found it, from step `first` on (at most to `last`):
     the step before the last ran on the box its predecessor used, so it enqueued the next step's grid part, and the last one kept
-    the box, so the device opened the gate for it (world.hip, end of substep; world.h PreGrid) — the next step adopts it.  Returns
+    the box, so the device opened the gate for it (world_step.hip, World::publish_end_of_step; world.h PreGrid) — the next step adopts it.  Returns
     the step count.  (Positions read between the steps do not change the path: the twin of
     test_config2_one_step_from_the_long_run.)"""
     hf = np.float32(w.h())

@@ -2,7 +2,7 @@
 SALVA_HIP_FULL_HALO=1 and with SALVA_HIP_REF_HALO=1, and the two runs must agree bit for bit (ref_halo_ab.ab: positions, velocities,
 densities, contact counts, boundary forces, the per-step iteration / contact trace, the fullest box, the exported lists of the
 first, second and last step, entry by entry).  Every case asserts that the second arm kept the referenced slots in EVERY step and
-dropped a slot in some step; the cases where World::substep declines by design are in DECLINES and assert the opposite.
+dropped a slot in some step; the cases where World::size_pass declines by design are in DECLINES and assert the opposite.
 
 Which builder runs: k_nbr_tile_ref<M> (grid.hip) is the V = 1 builder with the compaction behind it; launch_nbr_build takes it for
 every slot of a step that keeps the referenced halo — the slots of a cut tile (SALVA_HIP_SPLIT_S) included: a cut tile is a slot
@@ -21,7 +21,7 @@ from salva_amd import (Becker2009Elasticity, Boundary, DFSPHSolver, Fluid, IISPH
 
 pytestmark = pytest.mark.gpu
 
-# Cases in which `ref_step` (World::substep) is false by design, with the term of its condition they rest on.  No other case may
+# Cases in which `ref_step` (World::size_pass) is false by design, with the term of its condition they rest on.  No other case may
 # assert info[9] == 0 in the kept arm.
 DECLINES = {
     "speculative_first_pass": "!spec  (a speculative pass clamps its tables to the previous step's totals; the repeated pass of a miss keeps)",
