@@ -9,6 +9,8 @@ pub mod dist;
 mod liquid_world;
 #[cfg(feature = "rapier")]
 pub mod coupling;
+#[cfg(feature = "parry")]
+pub mod sampling;
 
 pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};

@@ -1,0 +1,84 @@
+//! `salva3d::sampling::{shape_surface_ray_sample, shape_volume_ray_sample}` (src/sampling/ray_sampling.rs:9-24) over
+//! `salva_hip_sample_shape` / `salva_hip_sample_host_shape`: the reference's two signatures, plus the world that supplies the
+//! device and the stream.  Ball, cuboid, capsule (y) and cylinder (y) are sampled by closed-form casts on the device; every other
+//! parry shape keeps its casts on the host (`cast_local_ray(ray, MAX, false)` per ray, in rounds), and the marked lattice is
+//! expanded on the device.  Points come back in lexicographic lattice order (the reference's order is a HashSet's).
+use crate::ffi;
+use crate::liquid_world::check;
+use crate::{Error, LiquidWorld};
+use parry3d::query::{Ray, RayCast};
+use parry3d::shape::Shape;
+use salva3d::math::{Isometry, Point, Real, Vector};
+
+fn analytic(shape: &dyn Shape) -> Option<ffi::SalvaHipShape> {
+    if let Some(b) = shape.as_ball() {
+        return Some(ffi::SalvaHipShape { kind: ffi::SALVA_HIP_SHAPE_BALL, params: [b.radius, 0.0, 0.0] });
+    }
+    if let Some(c) = shape.as_cuboid() {
+        return Some(ffi::SalvaHipShape { kind: ffi::SALVA_HIP_SHAPE_CUBOID, params: [c.half_extents.x, c.half_extents.y, c.half_extents.z] });
+    }
+    if let Some(c) = shape.as_capsule() {
+        // (only Capsule::new_y: a segment along the local y axis, centred on the origin)
+        if c.segment.a.x == 0.0 && c.segment.a.z == 0.0 && c.segment.b.x == 0.0 && c.segment.b.z == 0.0 && c.segment.a.y == -c.segment.b.y {
+            return Some(ffi::SalvaHipShape { kind: ffi::SALVA_HIP_SHAPE_CAPSULE, params: [c.segment.b.y.abs(), c.radius, 0.0] });
+        }
+    }
+    if let Some(c) = shape.as_cylinder() {
+        return Some(ffi::SalvaHipShape { kind: ffi::SALVA_HIP_SHAPE_CYLINDER, params: [c.half_height, c.radius, 0.0] });
+    }
+    None
+}
+
+unsafe extern "C" fn aabb_thunk(user: *mut std::ffi::c_void, mins: *mut f32, maxs: *mut f32) {
+    let shape = &**(user as *const &dyn Shape);
+    let aabb = shape.compute_aabb(&Isometry::identity());
+    for a in 0..3 {
+        *mins.add(a) = aabb.mins[a];
+        *maxs.add(a) = aabb.maxs[a];
+    }
+}
+
+unsafe extern "C" fn cast_thunk(user: *mut std::ffi::c_void, n: u32, origins: *const f32, axis: i32, toi: *mut f32) {
+    let shape = &**(user as *const &dyn Shape);
+    let mut dir = Vector::zeros();
+    dir[axis as usize] = 1.0;
+    for r in 0..n as usize {
+        let o = Point::new(*origins.add(3 * r), *origins.add(3 * r + 1), *origins.add(3 * r + 2));
+        *toi.add(r) = shape.cast_local_ray(&Ray::new(o, dir), Real::MAX, false).unwrap_or(-1.0);
+    }
+}
+
+fn sample(world: &mut LiquidWorld, shape: &dyn Shape, particle_rad: Real, mode: i32) -> Result<Vec<Point<Real>>, Error> {
+    let raw = world.raw();
+    let analytic = analytic(shape);
+    let user: *const &dyn Shape = &shape;
+    let host = ffi::SalvaHipHostRayShape { user: user as *mut std::ffi::c_void, aabb: Some(aabb_thunk), cast: Some(cast_thunk) };
+    let call = |capacity: u64, out: *mut f32| -> i64 {
+        match &analytic {
+            Some(s) => unsafe { ffi::salva_hip_sample_shape(raw, s, particle_rad, mode, capacity, out) },
+            None => unsafe { ffi::salva_hip_sample_host_shape(raw, &host, particle_rad, mode, capacity, out) },
+        }
+    };
+    let n = call(0, std::ptr::null_mut());
+    if n < 0 {
+        check(n as i32)?;
+    }
+    let mut pts = vec![Point::<Real>::origin(); n as usize];
+    if n > 0 {
+        let m = call(n as u64, pts.as_mut_ptr() as *mut f32);
+        if m < 0 {
+            check(m as i32)?;
+        }
+    }
+    Ok(pts)
+}
+
+/// Samples the surface of `shape` with a method based on ray-casting (ray_sampling.rs:9-15).
+pub fn shape_surface_ray_sample<S: Shape>(world: &mut LiquidWorld, shape: &S, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+    sample(world, shape, particle_rad, ffi::SALVA_HIP_SAMPLE_SURFACE).ok()
+}
+
+/// Samples the volume of `shape` with a method based on ray-casting (ray_sampling.rs:18-24).
+pub fn shape_volume_ray_sample<S: Shape>(world: &mut LiquidWorld, shape: &S, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+    sample(world, shape, particle_rad, ffi::SALVA_HIP_SAMPLE_VOLUME).ok()
+}

@@ -612,6 +612,50 @@ int salva_hip_set_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t
 int64_t salva_hip_get_elasticity_contacts(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets,
                                           uint32_t* j, uint64_t capacity);
 
+/* ---- `sampling::shape_surface_ray_sample` / `shape_volume_ray_sample` (src/sampling/ray_sampling.rs:9-24): the particles every
+ * reference example builds its colliders (surface) and some of its fluids (volume) from.  The lattice has spacing 2 particle_rad and
+ * origin (aabb.mins - 2 r) + r; along every lattice line of every axis a ray is cast from outside; an entry impact is quantised with
+ * ceil, an exit impact with floor (surface mode), or every index from round(entry) to round(exit) is taken (volume mode); after an
+ * impact the reference casts again from impact + s / 10, so a chord shorter than that yields its entry point only (surface) or
+ * nothing (volume).  For the analytic shapes the casts are closed forms evaluated in f32 on the device (for the
+ * capsule and the cylinder, which parry casts with GJK, the closed forms are this library's specification); the result is returned in
+ * lexicographic lattice-index order, x slowest and z fastest (the reference's is a HashSet's).
+ * Both calls return the number of samples (negative on error) and write `out_xyz` (local coordinates) only when `capacity` holds
+ * them all — the convention of salva_hip_particles_intersecting_aabb.  The world supplies the device and the stream; particle_rad is
+ * the argument, as in the reference, and need not be the world's.  A lattice of more than 2^32 points is SALVA_HIP_E_CAPACITY. */
+enum { SALVA_HIP_SAMPLE_SURFACE = 0, SALVA_HIP_SAMPLE_VOLUME = 1 };
+int64_t salva_hip_sample_shape(SalvaHipWorld* world, const SalvaHipShape* shape, float particle_rad, int32_t mode, uint64_t capacity,
+                               float* out_xyz);
+/* The same for ANY other shape (the reference's functions are generic over parry's `Shape`): the casts stay with the host.  The
+ * library calls `aabb` once (`shape.compute_aabb(&Isometry::identity())`) and `cast` once per round and axis with all rays that are
+ * still alive: `toi_out[r] = shape.cast_local_ray(&Ray::new(origins[r], axis unit vector), Real::MAX, false)`, a negative or NaN
+ * value meaning None.  After a hit a ray goes on from origin + toi + s / 10 (ray_sampling.rs:46-52, :109-126), entry and exit
+ * alternating, so concave shapes with several intervals per ray are sampled as the reference samples them.  A ray that still hits
+ * after 64 rounds ends the call with SALVA_HIP_E_INVALID.  The marked lattice is uploaded and expanded on the device as above.
+ * Both callbacks run on the calling thread, inside this call; neither may call back into the world. */
+typedef void (*SalvaHipHostCastFn)(void* user, uint32_t n, const float* origins_xyz, int32_t axis, float* toi_out);
+typedef struct SalvaHipHostRayShape {
+    void* user;
+    SalvaHipHostAabbFn aabb;
+    SalvaHipHostCastFn cast;
+} SalvaHipHostRayShape;
+int64_t salva_hip_sample_host_shape(SalvaHipWorld* world, const SalvaHipHostRayShape* shape, float particle_rad, int32_t mode,
+                                    uint64_t capacity, float* out_xyz);
+/* `fluid.add_particles(&volume_or_surface_samples.transform_by(pose), &[velocity; n])` without the points ever visiting the host: the
+ * shape is sampled at the WORLD's particle radius, posed by `translation` and the unit quaternion `rotation_ijkw` (the device function
+ * salva_hip_update_boundary_pose uses) and appended to fluid `slot` like salva_hip_add_particles — default volume, zero acceleration,
+ * the inherited velocity-change tail.  `velocity` may be NULL (zeros).  Returns the number of particles added (negative on error).
+ * In a RUNNING decomposed world: SALVA_HIP_E_INVALID — sample with salva_hip_sample_shape and add collectively with
+ * salva_hip_add_particles. */
+int64_t salva_hip_add_particles_sampled(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, const float translation[3],
+                                        const float rotation_ijkw[4], int32_t mode, const float velocity[3]);
+/* salva_hip_set_boundary_sampling with the local points = the SURFACE samples of `shape` at the world's particle radius, produced and
+ * kept on the device (`ColliderSampling::StaticSampling(shape_surface_ray_sample(shape, r))`, as every reference example registers its
+ * colliders).  Afterwards boundary `slot` is a StaticSampling boundary like any other.  Returns the number of points (negative on
+ * error).  In a running decomposed world: SALVA_HIP_E_INVALID, as above. */
+int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, uint32_t memberships,
+                                                   uint32_t filter);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

@@ -253,13 +253,25 @@ class Boundary {  // object/boundary.rs
         b.dynamic_host = shape;
         return b;
     }
-    size_t num_particles() const { return dynamic_shape.kind ? dynamic_n_ : (sampling.empty() ? positions.size() : sampling.size()); }
+    // ColliderSampling::StaticSampling(shape_surface_ray_sample(shape, particle_radius)) with the points produced and kept on the
+    // device (salva_hip_set_boundary_sampling_from_shape): afterwards a StaticSampling boundary like any other
+    SalvaHipShape sampled_shape{0, {0, 0, 0}};
+    static Boundary sampled_from_shape(const SalvaHipShape& shape, InteractionGroups groups = {}) {
+        Boundary b({}, groups);
+        b.sampled_shape = shape;
+        return b;
+    }
+    size_t num_particles() const {
+        if (sampled_shape.kind) return sampled_n_;
+        return dynamic_shape.kind ? dynamic_n_ : (sampling.empty() ? positions.size() : sampling.size());
+    }
     void mark_dirty() { dirty_ = true; }
 
   private:
     friend class LiquidWorld;
     bool dirty_ = true;
     size_t dynamic_n_ = 0;  // what the last step emitted
+    size_t sampled_n_ = 0;  // surface samples of sampled_shape, once uploaded
 };
 
 class LiquidWorld;
@@ -387,6 +399,7 @@ class LiquidWorld {  // liquid_world.rs
     std::vector<Fluid>& fluids() { return fluids_; }
     std::vector<Boundary>& boundaries() { return boundaries_; }
     Real h() const { return salva_hip_h(w_); }
+    SalvaHipWorld* handle() const { return w_; }  // for the C entry points this mirror does not wrap
     Real particle_radius() const { return particle_radius_; }
     const SalvaHipStepStats& counters() const { return stats_; }
     // ParticleId of liquid_world.rs:211-280: (is_boundary, handle = slot, particle index)
@@ -615,7 +628,7 @@ class LiquidWorld {  // liquid_world.rs
         b.volumes.resize(b.num_particles());
         if (b.wants_forces) b.forces.resize(b.num_particles());
         check(salva_hip_get_boundary(w_, (uint32_t)h, b.volumes.data(), b.wants_forces ? b.forces[0].data() : nullptr));
-        if (!b.sampling.empty() || b.dynamic_shape.kind) {
+        if (!b.sampling.empty() || b.dynamic_shape.kind || b.sampled_shape.kind) {
             b.positions.resize(b.num_particles()); b.velocities.resize(b.num_particles());
             check(salva_hip_get_boundary_particles(w_, (uint32_t)h, b.positions[0].data(), b.velocities[0].data()));
         }
@@ -639,6 +652,26 @@ class LiquidWorld {  // liquid_world.rs
         b.dynamic_shape = SalvaHipShape{};
         b.dynamic_host = SalvaHipHostShape{nullptr, nullptr, nullptr};
         b.dirty_ = false;  // (the device holds exactly these particles)
+    }
+    // `fluid.add_particles(&shape_volume_ray_sample(shape, r).transform_by(pose), &[velocity; n])` on the device
+    // (salva_hip_add_particles_sampled): sampled at the world's particle radius, posed, appended; the host arrays of the fluid
+    // grow by the same count and are refreshed from the device.  Returns the number of particles added.
+    size_t add_particles_from_shape(FluidHandle h, const SalvaHipShape& shape, const Vec3& translation,
+                                    const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1}, int mode = SALVA_HIP_SAMPLE_VOLUME,
+                                    const Vec3* velocity = nullptr) {
+        upload_new_objects();
+        Fluid& f = fluids_[h];
+        upload(f, (uint32_t)h);
+        const int64_t k = salva_hip_add_particles_sampled(w_, (uint32_t)h, &shape, translation.data(), rotation_ijkw.data(), mode,
+                                                          velocity ? velocity->data() : nullptr);
+        if (k < 0) check((int)k);
+        const size_t n = f.positions.size() + (size_t)k;
+        f.positions.resize(n); f.velocities.resize(n);
+        f.accelerations.resize(n, Vec3{0, 0, 0});
+        f.volumes.resize(n, f.default_particle_volume());
+        f.deleted_.resize(n, false);
+        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        return (size_t)k;
     }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));
@@ -774,6 +807,14 @@ class LiquidWorld {  // liquid_world.rs
             b.dirty_ = false;
             return;
         }
+        if (b.sampled_shape.kind) {
+            const int64_t k = salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, b.interaction_groups.memberships,
+                                                                         b.interaction_groups.filter);
+            if (k < 0) check((int)k);
+            b.sampled_n_ = (size_t)k;
+            b.dirty_ = false;
+            return;
+        }
         if (!b.sampling.empty()) {
             check(salva_hip_set_boundary_sampling(w_, slot, n, b.sampling[0].data(), b.interaction_groups.memberships,
                                                   b.interaction_groups.filter));
@@ -845,5 +886,26 @@ struct FluidsPipeline {
     FluidsPipeline(Real particle_radius, Real smoothing_factor) : liquid_world(DFSPHSolver(), particle_radius, smoothing_factor) {}
     void step(const Vec3& gravity, Real dt) { liquid_world.step_with_coupling(dt, gravity, coupling); }
 };
+
+// sampling/ray_sampling.rs:9-24 for the analytic shapes, on the device (salva_hip_sample_shape; the world supplies the device and the
+// stream); points in lexicographic lattice order
+namespace sampling {
+inline std::vector<Vec3> ray_sample(LiquidWorld& world, const SalvaHipShape& shape, Real particle_rad, int mode) {
+    const int64_t n = salva_hip_sample_shape(world.handle(), &shape, particle_rad, mode, 0, nullptr);
+    if (n < 0) check((int)n);
+    std::vector<Vec3> pts((size_t)n);
+    if (n) {
+        const int64_t m = salva_hip_sample_shape(world.handle(), &shape, particle_rad, mode, (uint64_t)n, pts[0].data());
+        if (m < 0) check((int)m);
+    }
+    return pts;
+}
+inline std::vector<Vec3> shape_surface_ray_sample(LiquidWorld& world, const SalvaHipShape& shape, Real particle_rad) {
+    return ray_sample(world, shape, particle_rad, SALVA_HIP_SAMPLE_SURFACE);
+}
+inline std::vector<Vec3> shape_volume_ray_sample(LiquidWorld& world, const SalvaHipShape& shape, Real particle_rad) {
+    return ray_sample(world, shape, particle_rad, SALVA_HIP_SAMPLE_VOLUME);
+}
+}  // namespace sampling
 
 }  // namespace salva

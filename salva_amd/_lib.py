@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_set_coupling_callback", "salva_hip_get_tile_tables",
     "salva_hip_get_dist_timing", "salva_hip_local_len", "salva_hip_get_local", "salva_hip_get_local_contacts", "salva_hip_force_add_local_accelerations",
     "salva_hip_get_elasticity_state", "salva_hip_set_elasticity_state", "salva_hip_get_elasticity_contacts",
+    "salva_hip_sample_shape", "salva_hip_sample_host_shape", "salva_hip_add_particles_sampled", "salva_hip_set_boundary_sampling_from_shape",
 ]
 
 
@@ -138,6 +139,15 @@ HOST_DISTANCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_float
 class HostQueryShape(C.Structure):
     """SalvaHipHostQueryShape (include/salva_hip.h): a query shape whose geometry stays with the host."""
     _fields_ = [("aabb", HOST_AABB_FN), ("distance", HOST_DISTANCE_FN), ("user", C.c_void_p)]
+
+
+HOST_CAST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float))
+SAMPLE_SURFACE, SAMPLE_VOLUME = 0, 1
+
+
+class HostRayShape(C.Structure):
+    """SalvaHipHostRayShape (include/salva_hip.h): a shape the sampler casts its rays at through the host."""
+    _fields_ = [("user", C.c_void_p), ("aabb", HOST_AABB_FN), ("cast", HOST_CAST_FN)]
 
 
 class HostShape(C.Structure):
@@ -281,6 +291,15 @@ def lib():
     L.salva_hip_set_elasticity_state.argtypes = [vp, u32, u32, u64, fp, fp, fp]
     L.salva_hip_get_elasticity_contacts.argtypes = [vp, u32, u32, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), u64]
     L.salva_hip_get_elasticity_contacts.restype = C.c_int64
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_sample_shape"):
+        L.salva_hip_sample_shape.argtypes = [vp, C.POINTER(Shape), f32, i32, u64, fp]
+        L.salva_hip_sample_shape.restype = C.c_int64
+        L.salva_hip_sample_host_shape.argtypes = [vp, C.POINTER(HostRayShape), f32, i32, u64, fp]
+        L.salva_hip_sample_host_shape.restype = C.c_int64
+        L.salva_hip_add_particles_sampled.argtypes = [vp, u32, C.POINTER(Shape), fp, fp, i32, fp]
+        L.salva_hip_add_particles_sampled.restype = C.c_int64
+        L.salva_hip_set_boundary_sampling_from_shape.argtypes = [vp, u32, C.POINTER(Shape), u32, u32]
+        L.salva_hip_set_boundary_sampling_from_shape.restype = C.c_int64
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

@@ -96,6 +96,15 @@ class StaticSampling:
 
     def __init__(self, points):
         self.points = np.ascontiguousarray(points, F32).reshape(-1, 3)
+        self.shape = None
+
+    @classmethod
+    def from_shape(cls, shape) -> "StaticSampling":
+        """`StaticSampling(shape_surface_ray_sample(shape, particle_radius))` with the points produced and kept on the device
+        (salva_hip_set_boundary_sampling_from_shape); `shape` is what make_shape takes."""
+        self = cls(np.zeros((0, 3), F32))
+        self.shape = shape if isinstance(shape, L.Shape) else make_shape(shape)
+        return self
 
 
 def make_shape(shape) -> "L.Shape":
@@ -239,6 +248,15 @@ class ColliderCouplingSet:
                 b._sampled = b._dynamic = True
                 L.check(world._L.salva_hip_set_boundary_dynamic_sampling(
                     world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                b._dirty = False
+                e.uploaded = True
+            if not e.uploaded and getattr(e.sampling, "shape", None) is not None and isinstance(e.sampling, StaticSampling):
+                b._sampled = True
+                k = int(world._L.salva_hip_set_boundary_sampling_from_shape(
+                    world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                if k < 0:
+                    L.check(k)
+                b._n_sampled = k
                 b._dirty = False
                 e.uploaded = True
             if not e.uploaded:

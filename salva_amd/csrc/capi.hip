@@ -727,6 +727,54 @@ int64_t salva_hip_get_elasticity_contacts(SalvaHipWorld* world, uint32_t slot, u
     return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
+int64_t salva_hip_sample_shape(SalvaHipWorld* world, const SalvaHipShape* shape, float particle_rad, int32_t mode, uint64_t capacity,
+                               float* out_xyz) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        r = world->w->sample_shape(*shape, particle_rad, mode, capacity, out_xyz);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int64_t salva_hip_sample_host_shape(SalvaHipWorld* world, const SalvaHipHostRayShape* shape, float particle_rad, int32_t mode,
+                                    uint64_t capacity, float* out_xyz) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        r = world->w->sample_host_shape(*shape, particle_rad, mode, capacity, out_xyz);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int64_t salva_hip_add_particles_sampled(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, const float translation[3],
+                                        const float rotation_ijkw[4], int32_t mode, const float velocity[3]) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !shape || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        r = world->w->add_particles_sampled(slot, *shape, translation, rotation_ijkw, mode, velocity);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, uint32_t memberships,
+                                                   uint32_t filter) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        r = world->w->set_boundary_sampling_from_shape(slot, *shape, memberships, filter);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

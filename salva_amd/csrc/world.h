@@ -1,6 +1,7 @@
 // world.h — host orchestration of the device-resident fluid world (the body of
 // /root/reference/src/liquid_world.rs:67-158 re-designed around HBM-resident, cell-sorted SoA state).
 #pragma once
+#include <functional>
 #include <string>
 #include <map>
 #include <memory>
@@ -95,7 +96,13 @@ class World {
     uint64_t get_fluid_contacts(uint32_t slot, int boundary, uint64_t* offsets, uint32_t* j_model, uint32_t* j, uint64_t capacity);
     void get_fluid_field(uint32_t slot, int field, float* out);
     void get_boundary(uint32_t slot, float* volumes, float* forces);
-    void set_boundary_sampling(uint32_t slot, uint64_t n, const float* local_points, uint32_t memberships, uint32_t filter);
+    void set_boundary_sampling(uint32_t slot, uint64_t n, const float* local_points, uint32_t memberships, uint32_t filter,
+                               const std::function<void(float4*)>* fill_dev = nullptr);
+    // ---- sampling/ray_sampling.rs on the device (sample.hip)
+    int64_t sample_shape(const SalvaHipShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
+    int64_t sample_host_shape(const SalvaHipHostRayShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
+    int64_t add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel);
+    int64_t set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
     void update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose);
     void set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter);
@@ -161,6 +168,18 @@ class World {
     void upload_tables();
     void build_boundary_grid();
     void resize_boundary_slot(uint32_t slot, uint64_t nn);
+    uint64_t append_particles(uint32_t slot, uint64_t n_add);
+    void set_boundary_from(uint32_t slot, uint64_t n, const float* pos, const float* vel, uint32_t memberships, uint32_t filter,
+                           bool wants_forces, const std::function<void(float4*)>* fill_dev);
+    // the shape sampler's lattice (sample.hip): bit lattice, per-word counts and offsets, the three coordinate arrays, packed output;
+    // sized by what has been asked so far, like the host-shape query's scratch
+    struct SampleLattice;
+    DevBuf<uint32_t> smp_bits, smp_cnt, smp_off;
+    DevBuf<float> smp_coords, smp_out;
+    void sample_lattice(const float mins[3], const float maxs[3], float particle_rad, SampleLattice& L);
+    uint32_t sample_count(const SampleLattice& L);
+    int64_t sample_download(const SampleLattice& L, uint64_t capacity, float* out_xyz);
+    void sample_mark(const SalvaHipShape& shape, float particle_rad, int mode, SampleLattice& L);
     void stamp_fluid_models();
     void stamp_boundary_models();
     bool has_dynamic_sampling() const;

@@ -4,6 +4,7 @@
 #include "world.h"
 #include "dcs.h"
 #include "bbox.h"
+#include "pose.h"
 
 #include <algorithm>
 #include <cmath>
@@ -352,6 +353,23 @@ void World::add_particles(uint32_t slot, uint64_t n_add, const float* pos, const
     if (comm && dist_started) { dist_add_particles(slot, n_add, pos, vel_h); return; }  // (collective, world_dist.hip)
     if (n_add == 0) return;
     if (!pos) throw HipError(SALVA_HIP_E_INVALID, "positions are required");
+    const uint64_t at = append_particles(slot, n_add);
+    scratch_f.ensure(3 * n_add, stream, false, 1.1f);
+    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
+    k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_pos.p + at, 1, 0.0f);
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (vel_h) {
+        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, vel_h, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
+        k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_vel.p + at, 1, 0.0f);
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+}
+
+// The growing half of add_particles: room for n_add particles behind the fluid's last one, filled with the defaults (zero position,
+// velocity and acceleration, default volume, the inherited velocity-change tail).  Returns the staging index of the first new
+// particle; the caller writes positions (and velocities) there — from the host (add_particles) or on the device
+// (add_particles_sampled, sample.hip).
+uint64_t World::append_particles(uint32_t slot, uint64_t n_add) {
     if ((uint64_t)n + n_add >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 fluid particles on one device");
     ensure_staging_current();
     const uint64_t old_n = fluids[slot].n, off = fluid_offset(slot), at = off + old_n, old_total = n, new_total = old_total + n_add;
@@ -382,16 +400,9 @@ void World::add_particles(uint32_t slot, uint64_t n_add, const float* pos, const
         }
     }
     stamp_fluid_models();
-    scratch_f.ensure(3 * n_add, stream, false, 1.1f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
-    k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_pos.p + at, 1, 0.0f);
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    if (vel_h) {
-        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, vel_h, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
-        k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_vel.p + at, 1, 0.0f);
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
     sorted_valid = false; bbox_known = false; tables_dirty = true; have_last_ctx = false;
+    return at;
 }
 
 // Fluid::apply_particles_removal (fluid.rs:88-98) together with the compaction of the solver's velocity_changes
@@ -557,12 +568,19 @@ void World::remove_fluid(uint32_t slot) {
 // ------------------------------------------------------------------------------------------------ boundaries
 void World::set_boundary(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships,
                          uint32_t filter, bool wants_forces) {
+    set_boundary_from(slot, nn, pos, vel_h, memberships, filter, wants_forces, nullptr);
+}
+
+// fill_dev != nullptr: the positions are written on the device — (*fill_dev)(first float4 of the slot), enqueued on the world's
+// stream — instead of uploaded from `pos` (set_boundary_sampling_from_shape, sample.hip)
+void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships, uint32_t filter,
+                              bool wants_forces, const std::function<void(float4*)>* fill_dev) {
     use_device();
     if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
     const bool is_new = slot == bounds.size();
     const uint64_t old_n = is_new ? 0 : bounds[slot].n;
     if ((uint64_t)nb - old_n + nn >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-    if (nn && !pos) throw HipError(SALVA_HIP_E_INVALID, "boundary positions are required");
+    if (nn && !pos && !fill_dev) throw HipError(SALVA_HIP_E_INVALID, "boundary positions are required");
     if (is_new) bounds.emplace_back();
     const uint64_t off = boundary_offset(slot);
     const uint64_t old_total = nb, new_total = old_total - old_n + nn;
@@ -585,8 +603,12 @@ void World::set_boundary(uint32_t slot, uint64_t nn, const float* pos, const flo
     b.vel_zero = true;
     if (nn) {
         scratch_f.ensure(3 * nn, stream, false, 1.1f);
-        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-        k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, bst_pos.p + off, 0, 0.0f);
+        if (fill_dev) {
+            (*fill_dev)(bst_pos.p + off);
+        } else {
+            SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
+            k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, bst_pos.p + off, 0, 0.0f);
+        }
         SALVA_HIP_CHECK(hipStreamSynchronize(stream));
         b.vel_zero = true;
         if (vel_h)
@@ -1480,17 +1502,9 @@ __global__ void k_boundary_pose(uint32_t n, const float4* __restrict__ local, Sa
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 pt = local[i];
-    const float qx = p.rotation[0], qy = p.rotation[1], qz = p.rotation[2], qw = p.rotation[3];
-    // every product is rounded on its own (no FMA contraction): these positions feed the exact d^2 <= h^2 contact test, and
-    // sample points 2r apart make pairs that sit exactly on d = h (found by the literal basic3 scene: 250 boundary-boundary
-    // contacts fewer than the CPU with contracted products)
-    const float tx = (opaque(qy * pt.z) - opaque(qz * pt.y)) * 2.0f, ty = (opaque(qz * pt.x) - opaque(qx * pt.z)) * 2.0f,
-                tz = (opaque(qx * pt.y) - opaque(qy * pt.x)) * 2.0f;
-    const float cx = opaque(qy * tz) - opaque(qz * ty), cy = opaque(qz * tx) - opaque(qx * tz), cz = opaque(qx * ty) - opaque(qy * tx);
     float4 o = pos[i];  // .w (volume slot) untouched
-    o.x = ((opaque(tx * qw) + cx) + pt.x) + p.translation[0];
-    o.y = ((opaque(ty * qw) + cy) + pt.y) + p.translation[1];
-    o.z = ((opaque(tz * qw) + cz) + pt.z) + p.translation[2];
+    pose_point(p.rotation[0], p.rotation[1], p.rotation[2], p.rotation[3], p.translation[0], p.translation[1], p.translation[2], pt.x, pt.y,
+               pt.z, o.x, o.y, o.z);  // (pose.h: shared with the shape sampler's emit kernel)
     pos[i] = o;
     float4 v = vel[i];  // .w carries the boundary's model id
     if (p.has_body) {
@@ -1530,9 +1544,10 @@ __global__ void k_boundary_wrench(uint32_t n, const float4* __restrict__ pos, co
     }
 }
 
-void World::set_boundary_sampling(uint32_t slot, uint64_t nn, const float* local_points, uint32_t memberships, uint32_t filter) {
+void World::set_boundary_sampling(uint32_t slot, uint64_t nn, const float* local_points, uint32_t memberships, uint32_t filter,
+                                  const std::function<void(float4*)>* fill_dev) {
     const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary(slot, nn, local_points, nullptr, memberships, filter, keep_forces);
+    set_boundary_from(slot, nn, local_points, nullptr, memberships, filter, keep_forces, fill_dev);
     auto buf = std::make_shared<DevBuf<float4>>();
     buf->ensure(nn ? nn : 1);
     if (nn) {

@@ -459,6 +459,35 @@ class Fluid:
         self._resized = True
         self._dirty = L.DIRTY_ALL
 
+    def add_particles_from_shape(self, shape, translation=(0.0, 0.0, 0.0), rotation=(0.0, 0.0, 0.0, 1.0), mode: int = 1, velocity=None) -> int:
+        """`add_particles(&shape_volume_ray_sample(shape, r).transform_by(pose), &[velocity; n])` on the device
+        (salva_hip_add_particles_sampled): the shape — what coupling.make_shape takes — is sampled at the world's particle radius
+        (mode 1 = volume, 0 = surface), posed by `translation` and the unit quaternion `rotation` (i, j, k, w) and appended; the
+        points never visit the host.  The fluid must live in a world.  Returns the number of particles added."""
+        from .coupling import make_shape
+
+        w = self._world
+        if w is None:
+            raise ValueError("add_particles_from_shape needs a fluid that was added to a LiquidWorld")
+        w._upload_new_objects()
+        if self._resized or self._dirty:
+            w._sync_fluid(self, apply_removal=False)
+        s = shape if isinstance(shape, L.Shape) else make_shape(shape)
+        t, q = np.ascontiguousarray(translation, F32).reshape(3), np.ascontiguousarray(rotation, F32).reshape(4)
+        v = np.ascontiguousarray(velocity, F32).reshape(3) if velocity is not None else None
+        self._pull()  # (the host copies must be current BEFORE the fluid grows: a read-back fills as many rows as the device holds)
+        k = int(w._L.salva_hip_add_particles_sampled(w._h, self._slot, C.byref(s), _fp(t), _fp(q), int(mode), _fp(v)))
+        if k < 0:
+            L.check(k)
+        if k:  # (the new rows are read back on the next access)
+            self._positions = np.concatenate([self._positions, np.zeros((k, 3), F32)])
+            self._velocities = np.concatenate([self._velocities, np.zeros((k, 3), F32)])
+            self._accelerations = np.concatenate([self._accelerations, np.zeros((k, 3), F32)])
+            self._volumes = np.concatenate([self._volumes, np.full(k, self.default_particle_volume(), F32)])
+            self._deleted = np.concatenate([self._deleted, np.zeros(k, bool)])
+            self._device_newer = True
+        return k
+
     def transform_by(self, rotation: Optional[np.ndarray] = None, translation: Sequence[float] = (0.0, 0.0, 0.0)):
         """`Fluid::transform_by(&Isometry)`: p <- R p + t (fluid.rs:166-168)."""
         self._pull()
