@@ -189,6 +189,9 @@ class World {
     std::vector<float4> dcs_h_f4;
     std::vector<uint8_t> dcs_h_inside;
     DevBuf<uint8_t> dcs_flag;
+    // the particles as they were before the push-outs of a pass that may still end in a FoldRetry (World::run_pass / substep)
+    DevBuf<float4> dcs_undo_pos, dcs_undo_vel;
+    bool dcs_undo = false;
     DevBuf<uint32_t> dcs_num;
     // decomposed run: every rank's emitted points, in rank order (dist_gather_emitted): rows, then one uint32 fluid per row
     DevBuf<unsigned long long> dcs_all;

@@ -800,8 +800,8 @@ void dims_from_bbox(const int32_t* bb, GridDims& g, const FoldRule* fold) {
     const double nc = (double)cells[0] * (double)cells[1] * (double)cells[2];
     if (nc >= 4.0e9) throw HipError(SALVA_HIP_E_CAPACITY, "dense cell table would exceed 2^32 cells; particles are too spread out");
     // The reference's hash grid costs memory per OCCUPIED cell; this table costs 4 bytes per cell of the (folded) bounding box, plus
-    // 8 bytes per tile of 64 cells.  Where folding is not possible (decomposed runs, dynamic contact sampling, a boundary set as wide
-    // as the box) a few stray particles far from the rest cost memory here that they do not cost there: refuse beyond a budget, with
+    // 8 bytes per tile of 64 cells.  Where folding is not possible (the x axis of a decomposed run, a boundary set as wide
+    // as the box, SALVA_HIP_NO_FOLD) a few stray particles far from the rest cost memory here that they do not cost there: refuse beyond a budget, with
     // a message that says what to do, rather than exhaust HBM.
     static const double budget_gib = [] {
         const char* e = getenv("SALVA_HIP_CELL_TABLE_GIB");

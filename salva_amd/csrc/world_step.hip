@@ -976,8 +976,9 @@ World::GridShape World::choose_grid() {
     // sprayed particles falling away from the scene are what this is for (tools/r05/soak.sh: the bench scene's box grows from 1.2 x 10^5
     // to 2.3 x 10^8 cells in a thousand steps).  The periods stay at least 64 cells and at least as long as the boundary grid is wide
     // (a folded fluid tile addresses the boundary cells modulo its own periods: tile.h TileCells::build), so the boundary grid has
-    // to exist first.  Not in decomposed runs (ghost planes are found by absolute cell coordinate) and not with dynamic contact
-    // sampling (dcs.hip decodes cell coordinates from the keys).  SALVA_HIP_NO_FOLD=1: never; SALVA_HIP_FOLD_CELLS=P: every axis
+    // to exist first.  A decomposed run folds y and z only (its ghost planes are found by absolute x-cell); worlds with dynamic contact
+    // sampling fold like any other (dcs.hip decodes cell coordinates from the keys and picks the image by the particle's position:
+    // dcs_unfold).  SALVA_HIP_NO_FOLD=1: never; SALVA_HIP_FOLD_CELLS=P: every axis
     // longer than P cells to exactly P (a power of two >= 8; the tests' way to fold small scenes).
     // (fold_relax: a fold that piled the bulk of the fluid onto itself — the rule below looks at the box, not at where the particles
     // sit — was found out by the tile totals of an earlier attempt, which then threw FoldRetry: every level loosens the fold
@@ -1124,7 +1125,7 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
         // Did the fold pile the fluid onto itself?  (a long sheet of fluid without an enclosing boundary folds onto its
         // own bulk, cells hold several times the particles, and a scene that ran fine on the unfolded table dies of "halo does
         // not fit".)  The totals say so before any solver kernel has run: loosen the fold and run the pass again — the
-        // particle arrays are merely permuted so far.
+        // particle arrays are merely permuted so far (and pushed by DynamicContactSampling: World::substep undoes that).
         ++fold_relax;
         throw FoldRetry{};
     }
@@ -1348,6 +1349,15 @@ bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g
             // (host clock: the pass ends with a read-back of the emitted count, so the stream is drained when it returns)
             if (p.timers) wait_stream();
             const auto t1 = std::chrono::steady_clock::now();
+            // A fold that piles the fluid onto itself is found out behind this point (size_pass: FoldRetry), and the substep then runs
+            // again from the top: the push-outs are not repeatable (a pushed particle projects a few ulps aside the second time, and
+            // its cell is no longer the one it was inserted under), so the particles are kept as they were until that is decided.
+            dcs_undo = n != 0 && gf.folded() && !fold_locked;
+            if (dcs_undo) {
+                dcs_undo_pos.ensure(n, stream, false, 1.1f); dcs_undo_vel.ensure(n, stream, false, 1.1f);
+                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_pos.p, posm[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_vel.p, vel[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            }
             run_dynamic_sampling();
             p.dcs_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
         }
@@ -1524,7 +1534,20 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     // (`lists_checked`, cleared by every edit of the fluids or boundaries): the first step of a scene — whose lists are longer
     // than the initial capacity in almost any dense scene — is then not computed twice.
     const PassSnapshot snap(*this);  // what a discarded pass puts back
-    for (p.attempt = 0; !run_pass(p, snap, dt, g, st); ++p.attempt) {}
+    dcs_undo = false;
+    try {
+        for (p.attempt = 0; !run_pass(p, snap, dt, g, st); ++p.attempt) {}
+    } catch (const FoldRetry&) {
+        if (dcs_undo) {  // (run_pass: DynamicContactSampling had pushed particles already; back to the pre-sort buffers as the substep found them)
+            // (size_pass throws behind reorder_working_set, which has flipped `cur` to the sorted copy of the PUSHED particles: the
+            // snapshot's `cur` is the buffer the kept copies belong to, in their order)
+            snap.restore(*this);
+            SALVA_HIP_CHECK(hipMemcpyAsync(posm[cur].p, dcs_undo_pos.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            SALVA_HIP_CHECK(hipMemcpyAsync(vel[cur].p, dcs_undo_vel.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            dcs_undo = false;
+        }
+        throw;
+    }
     return finish_substep(p, dt, st);
 }
 
