@@ -14,6 +14,7 @@
 #include "dist.h"
 #include "kernels.h"
 #include "elastic.h"
+#include "switches.h"
 
 namespace salva {
 
@@ -191,7 +192,6 @@ class World {
     DevBuf<uint8_t> dcs_flag;
     // the particles as they were before the push-outs of a pass that may still end in a FoldRetry (World::run_pass / substep)
     DevBuf<float4> dcs_undo_pos, dcs_undo_vel;
-    bool dcs_undo = false;
     DevBuf<uint32_t> dcs_num;
     // decomposed run: every rank's emitted points, in rank order (dist_gather_emitted): rows, then one uint32 fluid per row
     DevBuf<unsigned long long> dcs_all;
@@ -206,17 +206,8 @@ class World {
     // Chained steps (device_types.h StepCtx::gate, World::dfsph_solve): both solves of a DFSPH step and everything between and behind
     // them are enqueued without a wait; the end-of-step publication carries their outcome.
     bool chain_allowed() const;
-    SolveCtl pre_init1{};          // the pressure solve's initial control block, written by the divergence solve's k_init_ctl launch
-    bool pre_init1_valid = false;
-    bool chain_off = false;       // SALVA_HIP_NO_CHAIN=1 (A/B, tests)
-    bool chain_pending = false;   // this pass was enqueued that way and its outcome has not been read yet
-    bool chain_div_pending = false;  // ... the divergence solve included (not while its iteration count is rising)
-    int chain_batch[2] = {0, 0};  // iterations enqueued for the divergence / the pressure solve (where a continuation starts)
-    float chain_dt_prev = 0.0f, chain_inv_dt_prev = 0.0f;  // TimestepManager::{dt, inv_dt} as the chained attempt found them
-    uint64_t chain_steps = 0, chain_breaks = 0;  // passes whose chain held / broke (SALVA_HIP_TILE_TRACE prints them)
     DevBuf<float4> w2;            // the second w buffer of speculative divergence applies (dfsph.hip, spec_decide)
     DevBuf<SolveCtl> spec_ring;   // their two alternating control records
-    bool spec_apply_off = false;  // SALVA_HIP_NO_SPEC_APPLY (A/B, tests)
     void wait_stream();  // low-latency wait for the world's stream (spins on an event)
     template <typename Arrived> void spin_until(Arrived&& arrived, const char* drained);  // ... for a host-mapped word (world_step.hip)
     void run_forces(const StepCtx& c);
@@ -228,31 +219,82 @@ class World {
     void dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, int resume = 0);  // dt: in = the step, out = the substep advanced by
     void iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st);
     int substep(float& dt, const float g[3], SalvaHipStepStats& st);  // one pass of the reference's substep loop (liquid_world.rs:85-147)
-    // ---- the phases of a substep, in the order it runs them (world_step.hip).  What they share travels in a Pass; PassSnapshot is
-    // the one place that knows what a discarded pass has to put back.
+    // ---- 2. What belongs to the substep that is running, and to the pass (attempt) of it that is running.  One phase writes it,
+    // the phases behind it, the solvers and make_ctx read it.  World owns the one instance, `pass`, and each lifetime has ONE reset:
+    // `pass = Pass{}` at the top of substep(), `static_cast<Attempt&>(pass) = Attempt{}` at the top of run_pass().  Nothing is reset
+    // at the end: tile_tables, time_kernel and the contact exports read the committed pass's values between steps.  (Not here: the
+    // launch shapes `lds` / `halo_stride`, which every size_pass rewrites whole and the constructor seeds with Switches::ds_level.)
+    // (World::choose_grid: the size of the (folded) cell table, of the dense tile table, and the bound of the compact per-slot tables)
+    struct GridShape { size_t ncf = 0; uint32_t ntiles = 0, nslots_bound = 0; };
+    // What each pass (World::run_pass) decides for the phases behind it.
+    struct Attempt {
+        bool spec = false;          // launch shapes from the previous step's totals (World::substep: "One pass over the step")
+        bool defer_lists = false;   // the list capacity is checked with the end-of-step publication
+        bool have_grid = false;     // keys, sort, tile tables and the totals publication are enqueued already (PreGrid)
+        TileAcc tt{};               // the totals the launch shapes and buffers of this pass are cut for
+        uint32_t nslices = 0;
+        size_t scan_tb = 0;         // temporary bytes of the tile-table scans
+        size_t need_f = 0, need_b = 0;  // entries of the two halo slot tables
+        bool ref_step = false;      // the list build keeps the referenced halo slots only (World::size_pass)
+        RefBuild refb{};
+        StepCtx c{};                // (the committed pass's becomes World::last_ctx)
+        bool check_mass = false;    // this pass's k_cell_keys compares the masses (not while a scene is known to hold different ones)
+        uint32_t nlaunch = 0;       // non-empty tiles of this pass = grid size of the solver kernels (0: not known yet)
+        bool spec_mode = false;     // a speculative pass, and what it lets the kernels use (StepCtx::spec)
+        uint32_t halo_cap = 0xffffffffu, bhalo_cap = 0xffffffffu, nslices_cap = 0xffffffffu;
+        uint64_t halo_len = ~0ull, bhalo_len = ~0ull;
+        uint32_t class_ntiny = 0, class_nlight = 0;  // sparse / light slots of this pass, when they run in launches of their own (0: with the others / the full ones)
+        bool ref_on_cur = false;    // this pass's list build kept the referenced slots only
+        bool ref_bounded = false;   // ... and were cut for the previous step's kept maxima plus a margin (flag 16 = the pass is repeated)
+        // what the next end-of-step publication folds (world_step.hip Epilogue): the list statistics of this pass, the position
+        // update's boxes.  The publication that folds them clears them, so that a second one in the same pass (a broken chain) does not.
+        bool fold_stats = false; uint32_t fold_bbox_blocks = 0; const uint32_t* fold_bbox_gate = nullptr;
+        bool fused_first_divergence = false;  // this pass's density pass also ran the divergence solve's first evaluate (dfsph.hip)
+        bool iisph_dii_fused = false;  // this pass's density pass wrote d_ii (k_density_alpha<true>): iisph_solve skips k_iisph_dii
+        SolveCtl pre_init1{}; bool pre_init1_valid = false;  // the pressure solve's initial control block, written by the divergence solve's k_init_ctl launch
+        bool solve_owes_apply[3] = {false, false, false};  // the apply behind a batch's last test, left to whoever continues the solve
+        hipStream_t spec_dist_stream = nullptr;  // non-null while run_solve launches a decomposed speculative apply: where its kernel goes
+        // this pass was enqueued chained and its outcome has not been read yet / the divergence solve included (not while its count is rising)
+        bool chain_pending = false, chain_div_pending = false;
+        int chain_batch[2] = {0, 0};    // iterations enqueued for the divergence / the pressure solve (where a continuation starts)
+        float chain_dt_prev = 0.0f, chain_inv_dt_prev = 0.0f;  // TimestepManager::{dt, inv_dt} as the chained attempt found them
+    };
+    // ... on top of what the substep decides before its first pass, the same for every attempt
+    struct Pass : Attempt {
+        bool timers = false, has_dyn = false, adopted = false, can_redo = false, can_speculate = false;
+        GridShape gs;
+        double dcs_ms = 0.0;        // host milliseconds of DynamicContactSampling (counters.cd.boundary_update_time)
+        int attempt = 0;            // the pass that runs: 0, or the repeat of a discarded one
+        bool dcs_undo = false;      // dcs_undo_pos / _vel hold the particles as they were before this substep's push-outs
+        uint32_t split_s_cur = 0;   // what this substep's tables are built with (device_types.h StepCtx::split_s)
+        // decide_two_mass: this substep runs the two-mass way, with `nmass` masses, these, ascending, and this class per fluid (two bits each)
+        bool two_mass = false;
+        uint32_t nmass = 0; float mass_classes[4] = {0.0f, 0.0f, 0.0f, 0.0f}; uint64_t mass_cmask = 0;
+        // event pairs of dist_ev in use (dist_time_begin; dist_time_fold consumes them at the end of every pass)
+        size_t dist_ev_used = 0; std::vector<std::pair<size_t, int>> dist_ev_pairs;  // (index of the first event of a pair, 0 = refresh / 1 = test)
+    } pass;
+    // ---- the phases of a substep, in the order it runs them (world_step.hip).  PassSnapshot is the one place that knows what a
+    // discarded pass has to put back.
     struct GridTabs;
-    struct GridShape;
-    struct Attempt;
-    struct Pass;
     struct PassSnapshot;
     void prepare_working_set(SalvaHipStepStats& st);
     GridShape choose_grid();
     void ensure_slot_tables(uint32_t nslots_bound);
-    bool run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st);
+    bool run_pass(const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st);
     void enqueue_grid_keys(GridTabs& T, const GridShape& gs, bool counting, bool mass, const uint32_t* gate);
     void enqueue_grid_sort(GridTabs& T, const GridShape& gs, bool counting, const uint32_t* gate);
     size_t tile_scan_temp(const GridShape& gs);
     uint32_t enqueue_grid_tiles(GridTabs& T, const GridShape& gs, StepCtx c, size_t tb, const uint32_t* gate, bool publish);
     bool predict_totals(const GridShape& gs, TileAcc& tt) const;
     void reorder_working_set(bool timers);
-    void size_pass(Pass& p, uint32_t seq_totals);
-    void fill_tile_tables(Pass& p, bool again);
-    void build_lists(Pass& p);
+    void size_pass(uint32_t seq_totals);
+    void fill_tile_tables(bool again);
+    void build_lists();
     void density_and_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers);
-    void publish_end_of_step(const Pass& p, const PassSnapshot& snap);
+    void publish_end_of_step(const PassSnapshot& snap);
     void adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers);
-    int finish_substep(const Pass& p, float dt, SalvaHipStepStats& st);
-    void record_timers(const Pass& p, SalvaHipStepStats& st);
+    int finish_substep(float dt, SalvaHipStepStats& st);
+    void record_timers(SalvaHipStepStats& st);
     void raise_step_flags();
     bool has_force(int kind) const;                        // some fluid carries a force of this kind
     bool counting_sort_for(size_t ncf, uint32_t np) const;  // the counting sort by cell serves a table of ncf cells over np particles
@@ -273,7 +315,35 @@ class World {
     void refresh_f4(float4* field);
     void ensure_particle_capacity(size_t cap);
     void finalize_solve(SolveCtl* ctl, SolveCtl* pub, uint32_t skipped = 0);
-    bool solve_owes_apply[3] = {false, false, false};  // the apply behind a batch's last test, left to whoever continues the solve
+
+    static constexpr int NUM_SOLVES = 3;  // divergence, pressure, viscosity
+    const Switches sw = Switches::from_env();  // ---- 1. what the environment asked for when the world was made (switches.h)
+    // ---- 3. What one step deliberately hands to the next (with `pre` and `lds` / `halo_stride` further down); PassSnapshot puts
+    // back what a discarded pass has overwritten of it.  Host edits invalidate it where they happen (world.hip).
+    uint32_t last_iters[NUM_SOLVES] = {1u, 1u, 1u};  // iterations of the previous step's divergence / pressure solve (batch sizing)
+    uint32_t prev_iters[NUM_SOLVES] = {1u, 1u, 1u};  // ... and of the step before it (a rising count widens a chained batch)
+    float mass_uniform = 0.0f;  // StepCtx::mass_uniform as the last exact pass found it (0: masses differ, or not known)
+    bool mass_known = false;    // mass_uniform describes the particles as they are (set by a publication, cleared by host edits)
+    bool flags_clean = false;   // d_flags were cleared by the last end-of-step publication and nothing has run since
+    bool lists_checked = false; // the list capacity has held once since the last edit of the objects (upload_tables clears it)
+    uint32_t fold_relax = 0;    // how often a FoldRetry was thrown: the fold rule is loosened eightfold per level, given up at 3
+    bool fold_locked = false;   // the looser fold did not fit the cell-table budget: keep the tighter one
+    bool split_on = false;      // the previous step's totals say: a few tiles are over-full (device_types.h StepCtx::split_s)
+    int32_t bbox_used_last[6] = {0, 0, 0, 0, 0, 0}; bool bbox_used_valid = false;  // the cell box the previous step ran on
+    // speculative sizing (World::substep): the previous step's table totals
+    TileAcc pred_tt{};
+    uint32_t pred_n = 0; bool pred_valid = false;
+    // Referenced-only halo (device_types.h StepCtx::tile_off; World::size_pass / build_lists, world_step.hip)
+    bool ref_pred_valid = false;   // ref_pred = {fluid, fluid + boundary, padded fluid + boundary} maxima of the last step's kept halos
+    uint32_t ref_pred[3] = {0, 0, 0}, ref_pred_n = 0;
+    bool ref_last = false;         // the last step built it, with these caps, on launches cut for lds_full (salva_hip_time_kernel 4)
+    RefCaps ref_last_caps{0xffffffffu, 0xffffffffu, 0xffffffffu};
+    TileLds lds_full;
+    uint32_t ref_last_nslots_bound = 0;
+    // ---- ... and what only ever counts up (SALVA_HIP_TILE_TRACE, salva_hip_get_tile_tables): passes whose chain held / broke, whose
+    // prediction did not hold, that kept the referenced halo only / outgrew its bound, pre-enqueued grids used / dropped.  (The public
+    // `counters` carry cumulative pass counters of their own: World::step names those that survive its `counters = {}`.)
+    struct Tallies { uint64_t chain_steps = 0, chain_breaks = 0, spec_misses = 0, ref_passes = 0, ref_misses = 0, pre_adopted = 0, pre_dropped = 0; } tally;
 
     hipStream_t stream = nullptr;
     // decomposed runs: evaluate passes over interior tiles run here while the ghost exchange is in flight on `stream`
@@ -291,9 +361,6 @@ class World {
     // decomposed solves with speculative applies (World::run_solve): evaluate done -> the apply may start on stream2; apply done ->
     // the main stream may refresh what it wrote
     hipEvent_t ev_spec_eval = nullptr, ev_spec_apply = nullptr;
-    hipStream_t spec_dist_stream = nullptr;  // non-null while run_solve launches such an apply: where its kernel goes
-    bool spec_dist_off = false;              // SALVA_HIP_NO_SPEC_DIST=1 (A/B, tests)
-    bool overlap_exchange = true;   // SALVA_HIP_NO_OVERLAP=1 turns it off (diagnostics)
     template <typename Launch> void evaluate_split(const StepCtx& c, int iteration, Launch&& launch);
     uint32_t n = 0, nb = 0;
 
@@ -306,7 +373,6 @@ class World {
     DevBuf<float4> posm[2], vel[2], dv[2];
     DevBuf<uint32_t> model[2], perm[2];
     int cur = 0;
-    static constexpr int NUM_SOLVES = 3;  // divergence, pressure, viscosity
     DevBuf<float4> acc, w, normal, dii, dijpj, iisph_q, iisph_pr, posmr;
     DevBuf<float> visc_beta, visc_target;  // DFSPHViscosity scratch: betas [36][n], strain-rate targets [6][n]
     DevBuf<float4> visc_u0, visc_u1, visc_va;
@@ -327,10 +393,6 @@ class World {
     GridTabs& G() { return gtab[gsel]; }
     DevBuf<uint4> slot_info;
     DevBuf<uint32_t> d_maxhalo, halo_src, bhalo_src;
-    uint32_t nlaunch = 0;  // non-empty tiles of the current step = grid size of the solver kernels
-    int sched_mode = 0;  // kernel-development builds: 1 = run diag/sched.hip after the list build (SALVA_HIP_SCHED)
-    uint32_t last_iters[NUM_SOLVES] = {1u, 1u, 1u};  // iterations of the previous step's divergence / pressure solve (batch sizing)
-    uint32_t prev_iters[NUM_SOLVES] = {1u, 1u, 1u};  // ... and of the step before it (a rising count widens a chained batch)
     uint32_t halo_stride = 0, bhalo_stride = 0;  // fixed row stride of the slot tables (0 = compact)
     DevBuf<char> tile_list_stats;
     uint32_t cap_ff = 24, cap_fb = 8;  // ELL capacity (dwords per particle), grown on demand
@@ -338,59 +400,25 @@ class World {
     DevBuf<uint32_t> slice_near;   // per slice: a pair closer than 1e-5 h exists (written by k_density_alpha, read by the DFSPH solver kernels)
     DevBuf<int32_t> bbox_partials;
     TileLds lds;
-    float mass_uniform = 0.0f;  // StepCtx::mass_uniform of the current step (0: masses differ, or not known)
     // Two-mass worlds (device_types.h StepCtx::two_mass; BASELINE config 4): every fluid has one particle mass (uniform volumes:
     // FluidSlot::vol_uniform) and exactly two different masses occur.  The plane-layout kernels then serve the whole world in one
     // launch per pass, the heavier class as a tail segment of the lists in the tiles that hold both.
     // Round 6: up to four masses — the third and fourth class as further tail segments (tile_masscd_bits, nffc).
     DevBuf<uint32_t> tile_mass_bits, tile_massb_bits, nffb, nffc;
     DevBuf<uint2> tile_masscd_bits;
-    uint32_t max_masses = 2;      // SALVA_HIP_MAX_MASSES=3 / 4: opt-in — on the one 10^6-particle scene it was measured on (four columns,
-                                  // tools/r06/multi_mass_probe.py) the general kernels are 8-10 % faster than the segments of three and four masses
-    bool two_mass_off = false;    // SALVA_HIP_NO_TWO_MASS=1 (A/B, tests): such a world keeps the general kernels
-    bool fold_off = false;        // SALVA_HIP_NO_FOLD=1: the fluid grid is never folded (device_types.h TileGrid)
-    struct FoldRetry {};          // thrown by World::choose_grid / size_pass when the tile totals show a fold that piled the bulk onto itself (World::step retries)
-    uint32_t fold_relax = 0;      // how often that happened: the fold rule is loosened eightfold per level, given up at 3
-    bool fold_locked = false;     // the looser fold did not fit the cell-table budget: keep the tighter one
-    uint32_t fold_forced = 0;     // SALVA_HIP_FOLD_CELLS=P: every axis longer than P cells is folded to exactly P (tests)
-    bool two_mass = false;        // this step runs that way
-    uint32_t nmass = 0;           // ... with this many masses,
-    float mass_classes[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // these, ascending,
-    uint64_t mass_cmask = 0;      // and this class per fluid (two bits each)
+    struct FoldRetry {};  // thrown by World::choose_grid / size_pass when the tile totals show a fold that piled the bulk onto itself (World::step retries)
     bool decide_two_mass();
     // Decomposed runs, timers enabled (salva_hip_enable_counters): HIP event pairs around every ghost refresh (gather -> exchange ->
     // scatter) and every all-reduced convergence test (sum -> all-reduce -> decide) of a step, folded into `dist_times` at its end:
     // {refresh ms, refreshes, test ms, tests} — what an exchange costs INSIDE a decomposed step, waiting for the neighbour included
     std::vector<hipEvent_t> dist_ev;
-    size_t dist_ev_used = 0;
-    std::vector<std::pair<size_t, int>> dist_ev_pairs;  // (index of the first event of a pair, 0 = refresh / 1 = test)
     double dist_times[4] = {0.0, 0.0, 0.0, 0.0};
     size_t dist_time_begin(int kind);
     void dist_time_end(size_t first);
     void dist_time_fold();
-    bool fused_first_divergence = false;  // this step's density pass also ran the divergence solve's first evaluate (dfsph.hip)
-    bool flags_clean = false;   // d_flags were cleared by the last end-of-step publication and nothing has run since
-    bool check_mass = true;     // this step's k_cell_keys compares the masses (not while a scene is known to hold different ones)
-    bool mass_known = false;    // mass_uniform describes the particles as they are (set by a publication, cleared by host edits)
-    bool tile_trace = false;    // SALVA_HIP_TILE_TRACE=1: one line of tile statistics per step on stderr
-    bool no_fused_div = false;  // SALVA_HIP_NO_FUSED_DIV=1 (A/B): the first divergence evaluate stays a pass of its own
-    bool no_planes = false;     // SALVA_HIP_NO_PLANES=1 (A/B): keep the 32-byte-per-slot evaluate kernels
-    bool iisph_dii_fused = false;  // this step's density pass wrote d_ii (k_density_alpha<true>): iisph_solve skips k_iisph_dii
-    int sort_mode = -1;         // SALVA_HIP_RADIX_SORT: 1 = always the radix sort + k_cell_start, 0 = always the counting sort by cell, unset = by size
 #ifdef SALVA_HIP_DIAG
     PipeCfg pipe;          // launch shape of the persistent pipeline kernels of this step (pipe.h)
 #endif
-    // speculative sizing (World::step): the previous step's table totals, and what the current pass lets the kernels use
-    TileAcc pred_tt{};
-    uint32_t pred_n = 0;
-    bool pred_valid = false, spec_mode = false;
-    uint32_t halo_cap = 0xffffffffu, bhalo_cap = 0xffffffffu, nslices_cap = 0xffffffffu;
-    uint64_t halo_len = ~0ull, bhalo_len = ~0ull;
-    uint64_t spec_misses = 0;  // passes discarded because the prediction did not hold
-    bool trust_cap0 = false;     // SALVA_HIP_LIST_CAP0 (tests)
-    bool lists_checked = false;  // the list capacity has held once since the last edit of the objects (upload_tables clears it)
-    bool defer_off = false;  // SALVA_HIP_NO_DEFER_LISTS: check the list capacity in the middle of the step (read at construction)
-    bool spec_off = true, spec_tight = false;  // SALVA_HIP_SPECULATE / SALVA_HIP_SPEC_TIGHT, read at construction
     int num_cus = 256;
     DevBuf<char> cub_temp;
     DevBuf<float> scratch_f;   // staging for AoS up/downloads and field unsorts
@@ -443,7 +471,6 @@ class World {
         uint32_t split_s = 0;
         GridDims gf;
     } pre;
-    bool pre_off = false;          // SALVA_HIP_NO_PREGRID=1 (A/B, tests)
     // two launch classes per pass (device_types.h StepCtx::slot_order)
     DevBuf<uint32_t> slot_order;
     // scratch of particles_in_host_shape: candidate kinds / indices / positions, kept between queries
@@ -451,36 +478,9 @@ class World {
     DevBuf<uint32_t> hq_kind, hq_index;
     DevBuf<float4> hq_pos;
     uint32_t hq_need = 0;
-    uint32_t class_ntiny = 0;      // sparse slots of this step, when they run in launches of their own (0: with the others)
-    uint32_t class_nlight = 0;     // light slots of this step, when they run in launches of their own (0: with the full ones)
-    bool classes_off = false, classes_forced = false, light_on = false;  // SALVA_HIP_NO_CLASSES=1 / SALVA_HIP_CLASSES=1 / SALVA_HIP_LIGHT=1 (the light class: opt-in, it lost)
-    // splitting of over-full tiles (device_types.h StepCtx::split_s)
-    bool split_off = false;        // SALVA_HIP_NO_SPLIT=1
-    // Referenced-only halo (device_types.h StepCtx::tile_off; World::size_pass / build_lists, world_step.hip)
-    bool ref_off = false, ref_forced = false;  // SALVA_HIP_FULL_HALO=1 (A/B: stage the full box) / SALVA_HIP_REF_HALO=1 (in every step: tests)
-    bool ref_tight = false;        // SALVA_HIP_REF_TIGHT=1 (tests): cut the launches for LESS than the previous step's kept maxima — every such pass misses
-    bool ref_on_cur = false;       // this pass's list build kept the referenced slots only
-    bool ref_bounded = false;      // ... and were cut for the previous step's kept maxima plus a margin (flag 16 = the pass is repeated)
-    bool ref_pred_valid = false;   // ref_pred = {fluid, fluid + boundary, padded fluid + boundary} maxima of the last step's kept halos
-    uint32_t ref_pred[3] = {0, 0, 0}, ref_pred_n = 0;
-    bool ref_last = false;         // the last step built it, with these caps, on launches cut for lds_full (salva_hip_time_kernel 4)
-    RefCaps ref_last_caps{0xffffffffu, 0xffffffffu, 0xffffffffu};
-    TileLds lds_full;
-    uint32_t ref_last_nslots_bound = 0;
-    uint64_t ref_passes = 0, ref_misses = 0;  // (salva_hip_get_tile_tables)
-    uint32_t split_forced = 0;     // SALVA_HIP_SPLIT_S=k: split at k halo particles whatever the statistics say (tests)
-    bool split_on = false;         // the previous step's totals say: a few tiles are over-full
-    uint32_t split_s_cur = 0;      // what this step's tables are built with
-    int32_t bbox_used_last[6] = {0, 0, 0, 0, 0, 0};  // the cell box the previous step ran on
-    bool bbox_used_valid = false;
-    uint64_t pre_adopted = 0, pre_dropped = 0;
     void pre_enqueue_grid(const GridShape& gs);
     void pre_drop();
     void publish_wait(uint32_t seq, bool totals, bool lists, bool end_of_step);
-    // what the next end-of-step publication folds (world_step.hip Epilogue): the list statistics of this pass, the position update's boxes
-    bool fold_stats = false;
-    uint32_t fold_bbox_blocks = 0;
-    const uint32_t* fold_bbox_gate = nullptr;
     void publish_and_wait(const TileAcc* totals, bool lists, bool end_of_step);
     DevBuf<SolveCtl> d_ctl;      // [0] divergence solve, [1] pressure solve, [2] viscosity solve (DFSPHViscosity)
     SolveCtl* h_ctl = nullptr;   // pinned: [0..NUM_SOLVES) read-back, [NUM_SOLVES..2 NUM_SOLVES) initial values
@@ -507,7 +507,6 @@ class World {
     bool have_last_ctx = false;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t evc[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // Counters: fluids in grid, boundaries in grid, densities done, custom on / off
-    uint64_t spec_passes = 0;
     hipEvent_t ev_sync = nullptr;
 
     // ---- multi-GPU slab decomposition (comm.h / dist.h)

@@ -110,6 +110,53 @@ void World::stamp_boundary_models() {  // (boundary model ids ride in bst_vel.w)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ switches
+// The one place where a world looks at the environment (switches.h): a host that calls setenv while a world steps changes nothing.
+Switches Switches::from_env() {
+    Switches s;
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    s.spec_dist_off = on("SALVA_HIP_NO_SPEC_DIST");
+    s.overlap_exchange = !on("SALVA_HIP_NO_OVERLAP");
+    s.spec_off = !on("SALVA_HIP_SPECULATE") || on("SALVA_HIP_NO_SPECULATION");
+    s.spec_tight = on("SALVA_HIP_SPEC_TIGHT");
+    s.defer_off = on("SALVA_HIP_NO_DEFER_LISTS");
+    s.spec_apply_off = on("SALVA_HIP_NO_SPEC_APPLY");
+    s.chain_off = on("SALVA_HIP_NO_CHAIN");
+    s.pre_off = on("SALVA_HIP_NO_PREGRID");
+    s.no_publish = on("SALVA_HIP_NO_PUBLISH");
+    s.split_off = on("SALVA_HIP_NO_SPLIT");
+    s.classes_off = on("SALVA_HIP_NO_CLASSES");
+    s.classes_forced = on("SALVA_HIP_CLASSES");
+    s.light_on = on("SALVA_HIP_LIGHT");
+    s.ref_off = on("SALVA_HIP_FULL_HALO");
+    s.ref_forced = on("SALVA_HIP_REF_HALO");
+    s.ref_tight = on("SALVA_HIP_REF_TIGHT");
+    s.compact_halo = on("SALVA_HIP_COMPACT_HALO");
+    if (const char* e = getenv("SALVA_HIP_SPLIT_S")) s.split_forced = (uint32_t)std::max(atoi(e), 1);
+    s.no_planes = on("SALVA_HIP_NO_PLANES");
+    s.two_mass_off = on("SALVA_HIP_NO_TWO_MASS");
+    if (const char* e = getenv("SALVA_HIP_MAX_MASSES")) s.max_masses = (uint32_t)std::min(std::max(atoi(e), 2), 4);  // (2 = round 5's rule, the default)
+    s.fold_off = on("SALVA_HIP_NO_FOLD");
+    if (const char* e = getenv("SALVA_HIP_FOLD_CELLS")) {
+        const long v = atol(e);
+        if (v >= 8 && v <= (1 << 20) && (v & (v - 1)) == 0) s.fold_forced = (uint32_t)v;
+    }
+    s.tile_trace = on("SALVA_HIP_TILE_TRACE");
+    s.dist_trace = on("SALVA_HIP_DIST_TRACE");
+    s.no_fused_div = on("SALVA_HIP_NO_FUSED_DIV");
+    if (const char* e = getenv("SALVA_HIP_RADIX_SORT")) s.sort_mode = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("SALVA_HIP_DS_LEVEL")) s.ds_level = (uint32_t)std::max(0, atoi(e));
+    if (const char* e = getenv("SALVA_HIP_LIST_CAP0")) { s.list_cap0 = std::max<uint32_t>(LIST_REGS, ((uint32_t)atoi(e) + 3u) & ~3u); s.trust_cap0 = true; }
+#ifdef SALVA_HIP_DIAG
+    if (const char* e = getenv("SALVA_HIP_SCHED")) s.sched_mode = atoi(e);
+    if (const char* e = getenv("SALVA_HIP_TILE_THREADS")) { s.tile_threads = (uint32_t)atoi(e); s.tile_threads_set = true; }
+    s.no_pipeline = on("SALVA_HIP_NO_PIPELINE");
+    if (const char* e = getenv("SALVA_HIP_PIPE_WAVES")) s.pipe_waves = std::min<uint32_t>(std::max(atoi(e), 1), PIPE_MAX_WAVES);
+    s.tile_timing = on("SALVA_HIP_TILE_TIMING");
+#endif
+    return s;
+}
+
 // ------------------------------------------------------------------------------------------------ ctor / dtor
 World::World(const SalvaHipParams& p) : prm(p) {
     if (!(p.particle_radius > 0.0f) || !(p.smoothing_factor > 0.0f))
@@ -135,43 +182,8 @@ World::World(const SalvaHipParams& p) : prm(p) {
     SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev_interior, hipEventDisableTiming));
     SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev_spec_eval, hipEventDisableTiming));
     SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev_spec_apply, hipEventDisableTiming));
-    spec_dist_off = getenv("SALVA_HIP_NO_SPEC_DIST") != nullptr;
-    overlap_exchange = getenv("SALVA_HIP_NO_OVERLAP") == nullptr;
-    // Speculative sizing is OFF unless asked for (SALVA_HIP_SPECULATE=1).  Measured on the bench scene (10^6 particles): it
-    // removes two ~20 us host round trips from a ~0.9 ms free-fall step (-2 %), but a failed prediction costs a whole extra
-    // step, and at the impact — where the halo and the lists grow for a dozen steps in a row — two passes in twenty were
-    // discarded, 2.25 ms per step against 1.88 ms without speculation.  Kept as an option for steady flows.
-    spec_off = getenv("SALVA_HIP_SPECULATE") == nullptr || getenv("SALVA_HIP_NO_SPECULATION") != nullptr;
-    spec_tight = getenv("SALVA_HIP_SPEC_TIGHT") != nullptr;
-    defer_off = getenv("SALVA_HIP_NO_DEFER_LISTS") != nullptr;
-    spec_apply_off = getenv("SALVA_HIP_NO_SPEC_APPLY") != nullptr;
-    chain_off = getenv("SALVA_HIP_NO_CHAIN") != nullptr;
-    pre_off = getenv("SALVA_HIP_NO_PREGRID") != nullptr;
-    split_off = getenv("SALVA_HIP_NO_SPLIT") != nullptr;
-    classes_off = getenv("SALVA_HIP_NO_CLASSES") != nullptr;
-    classes_forced = getenv("SALVA_HIP_CLASSES") != nullptr;
-    light_on = getenv("SALVA_HIP_LIGHT") != nullptr;
-    ref_off = getenv("SALVA_HIP_FULL_HALO") != nullptr;
-    ref_forced = getenv("SALVA_HIP_REF_HALO") != nullptr;
-    ref_tight = getenv("SALVA_HIP_REF_TIGHT") != nullptr;
-    if (const char* e = getenv("SALVA_HIP_SPLIT_S")) split_forced = (uint32_t)std::max(atoi(e), 1);
-    no_planes = getenv("SALVA_HIP_NO_PLANES") != nullptr;
-    two_mass_off = getenv("SALVA_HIP_NO_TWO_MASS") != nullptr;
-    if (const char* e = getenv("SALVA_HIP_MAX_MASSES")) max_masses = (uint32_t)std::min(std::max(atoi(e), 2), 4);  // (2 = round 5's rule, the default)
-    fold_off = getenv("SALVA_HIP_NO_FOLD") != nullptr;
-    if (const char* e = getenv("SALVA_HIP_FOLD_CELLS")) {
-        const long v = atol(e);
-        if (v >= 8 && v <= (1 << 20) && (v & (v - 1)) == 0) fold_forced = (uint32_t)v;
-    }
-    tile_trace = getenv("SALVA_HIP_TILE_TRACE") != nullptr;
-    no_fused_div = getenv("SALVA_HIP_NO_FUSED_DIV") != nullptr;
-    if (const char* e = getenv("SALVA_HIP_RADIX_SORT")) sort_mode = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("SALVA_HIP_DS_LEVEL")) lds.ds_level = (uint32_t)std::max(0, atoi(e));  // (tests: pairs.h pick_ds*)
-#ifdef SALVA_HIP_DIAG
-    if (const char* e = getenv("SALVA_HIP_SCHED")) sched_mode = atoi(e);
-#endif
-    // (tests: force an overflow — the given capacity also counts as checked, so that the very first step takes the deferred path)
-    if (const char* e = getenv("SALVA_HIP_LIST_CAP0")) { cap_ff = std::max<uint32_t>(LIST_REGS, ((uint32_t)atoi(e) + 3u) & ~3u); trust_cap0 = true; }
+    lds.ds_level = sw.ds_level;
+    if (sw.trust_cap0) cap_ff = sw.list_cap0;
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device) == hipSuccess && cus > 0) num_cus = cus;
@@ -658,7 +670,7 @@ static inline bool groups_test(uint32_t m1, uint32_t f1, uint32_t m2, uint32_t f
 
 void World::upload_tables() {
     if (!tables_dirty) return;
-    lists_checked = trust_cap0;  // the objects changed: the next step checks the list capacity before it solves (World::step)
+    lists_checked = sw.trust_cap0;  // the objects changed: the next step checks the list capacity before it solves (World::step)
     const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1), nbm = (uint32_t)std::max<size_t>(bounds.size(), 1);
     std::vector<float> r0(nm, 1000.0f);
     std::vector<uint32_t> counts(nm, 0);
@@ -709,7 +721,7 @@ StepCtx World::make_ctx() {
     c.sc = sc;
     {   // groups of 64 slots (what one XCD's 32 CUs hold at a time), fewer for launches of less than 1024 tiles
         uint32_t lg = 1u;
-        while (lg < 7u && (16u << lg) <= nlaunch) ++lg;
+        while (lg < 7u && (16u << lg) <= pass.nlaunch) ++lg;
         c.xcd = lg;
     }
     c.n = n;
@@ -723,11 +735,11 @@ StepCtx World::make_ctx() {
     c.tile_off = G().tile_off.p; c.halo_src = halo_src.p; c.bhalo_src = bhalo_src.p;
     c.halo_stride = halo_stride; c.bhalo_stride = bhalo_stride;
     c.ntiles = (uint32_t)gf.ntiles();
-    c.split_s = split_s_cur;
-    c.slot_order = (class_ntiny || class_nlight) ? slot_order.p : nullptr; c.slot_base = 0u; c.ntiny = class_ntiny; c.nlight = class_nlight;
-    c.tile_ids = G().tile_ids.p; c.tile_rank = G().tile_rank.p; c.nlaunch = nlaunch; c.slot_desc = G().slot_desc.p; c.slot_info = slot_info.p;
-    c.spec = spec_mode ? 1u : 0u; c.halo_cap = halo_cap; c.bhalo_cap = bhalo_cap; c.nslices_cap = nslices_cap;
-    c.halo_len = halo_len; c.bhalo_len = bhalo_len;
+    c.split_s = pass.split_s_cur;
+    c.slot_order = (pass.class_ntiny || pass.class_nlight) ? slot_order.p : nullptr; c.slot_base = 0u; c.ntiny = pass.class_ntiny; c.nlight = pass.class_nlight;
+    c.tile_ids = G().tile_ids.p; c.tile_rank = G().tile_rank.p; c.nlaunch = pass.nlaunch; c.slot_desc = G().slot_desc.p; c.slot_info = slot_info.p;
+    c.spec = pass.spec_mode ? 1u : 0u; c.halo_cap = pass.halo_cap; c.bhalo_cap = pass.bhalo_cap; c.nslices_cap = pass.nslices_cap;
+    c.halo_len = pass.halo_len; c.bhalo_len = pass.bhalo_len;
     c.gf = gf.device(G().cell_start_f.p);
     c.stale_keys = has_dynamic_sampling() ? G().keys[1].p : nullptr;
     c.nb = nb;
@@ -740,14 +752,14 @@ StepCtx World::make_ctx() {
     c.nmodels = (uint32_t)std::max<size_t>(fluids.size(), 1);
     c.nbmodels = (uint32_t)std::max<size_t>(bounds.size(), 1);
     c.mass_uniform = mass_uniform;
-    c.two_mass = two_mass ? 1u : 0u;
-    c.nmass = two_mass ? nmass : 0u; c.cmask = mass_cmask;
-    for (int k = 0; k < 4; ++k) c.class_mass[k] = mass_classes[k];
-    c.tile_mass_bits = two_mass ? tile_mass_bits.p : nullptr;
-    c.tile_massb_bits = two_mass ? tile_massb_bits.p : nullptr;
-    c.tile_masscd_bits = (two_mass && nmass > 2u) ? tile_masscd_bits.p : nullptr;
-    c.nffb = two_mass ? nffb.p : nullptr;
-    c.nffc = (two_mass && nmass > 2u) ? nffc.p : nullptr;
+    c.two_mass = pass.two_mass ? 1u : 0u;
+    c.nmass = pass.two_mass ? pass.nmass : 0u; c.cmask = pass.mass_cmask;
+    for (int k = 0; k < 4; ++k) c.class_mass[k] = pass.mass_classes[k];
+    c.tile_mass_bits = pass.two_mass ? tile_mass_bits.p : nullptr;
+    c.tile_massb_bits = pass.two_mass ? tile_massb_bits.p : nullptr;
+    c.tile_masscd_bits = (pass.two_mass && pass.nmass > 2u) ? tile_masscd_bits.p : nullptr;
+    c.nffb = pass.two_mass ? nffb.p : nullptr;
+    c.nffc = (pass.two_mass && pass.nmass > 2u) ? nffc.p : nullptr;
     c.bvel_zero = 1u;  // no boundary particle moves: the passes that subtract a boundary velocity need not stage it
     for (const BoundarySlot& b : bounds) if (b.n && (!b.vel_zero || b.sampling || b.dyn_kind)) c.bvel_zero = 0u;
     c.rho0_tab = rho0_tab.p; c.rho0_single = fluids.empty() ? 1000.0f : fluids[0].density0; c.ff_ok = ff_ok.p; c.fb_ok = fb_ok.p; c.bb_ok = bb_ok.p;
@@ -1938,7 +1950,7 @@ float World::time_pred_density(int reps) {
     if (!have_last_ctx || !sorted_valid || n == 0) throw HipError(SALVA_HIP_E_INVALID, "no completed step to time");
     if (reps < 1) reps = 1;
 #ifdef SALVA_HIP_DIAG
-    if (getenv("SALVA_HIP_TILE_TIMING")) tile_timing_report();
+    if (sw.tile_timing) tile_timing_report();
 #endif
     flags_clean = false;  // (a between-step launch may raise an error flag: the next step clears them itself — ADVICE r04)
     launch_pred_density(last_ctx, lds, last_dt, stream);  // warm-up
@@ -1970,7 +1982,7 @@ void World::tile_tables(uint32_t slot, uint32_t* info, uint32_t* halo_row, uint3
     memset(info, 0, 16 * sizeof(uint32_t));
     info[0] = c.nlaunch; info[1] = desc.y; info[2] = desc.z; info[3] = S; info[4] = SB;
     info[5] = lds.max_halo_fluid; info[6] = lds.raw_slots(); info[7] = lds.sum_slots(); info[8] = lds_full.max_halo_fluid;
-    info[9] = ref_last ? 1u : 0u; info[10] = (uint32_t)ref_passes; info[11] = (uint32_t)ref_misses;
+    info[9] = ref_last ? 1u : 0u; info[10] = (uint32_t)tally.ref_passes; info[11] = (uint32_t)tally.ref_misses;
     if (halo_row && cap_row && S)
         SALVA_HIP_CHECK(hipMemcpy(halo_row, c.halo_src + hoff, (size_t)std::min(S, cap_row) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (!own_n) return;

@@ -331,14 +331,14 @@ void World::dist_build_lists() {
 // ---- event pairs around the exchanges of a step (world.h dist_times); only while the stage timers are on
 size_t World::dist_time_begin(int kind) {
     if (!prm.enable_timers) return (size_t)-1;
-    if (dist_ev_used + 2 > dist_ev.size()) {
+    if (pass.dist_ev_used + 2 > dist_ev.size()) {
         const size_t old = dist_ev.size();
         dist_ev.resize(old + 64, nullptr);
         for (size_t k = old; k < dist_ev.size(); ++k) SALVA_HIP_CHECK(hipEventCreate(&dist_ev[k]));
     }
-    const size_t first = dist_ev_used;
-    dist_ev_used += 2;
-    dist_ev_pairs.emplace_back(first, kind);
+    const size_t first = pass.dist_ev_used;
+    pass.dist_ev_used += 2;
+    pass.dist_ev_pairs.emplace_back(first, kind);
     SALVA_HIP_CHECK(hipEventRecord(dist_ev[first], stream));
     return first;
 }
@@ -347,14 +347,14 @@ void World::dist_time_end(size_t first) {
 }
 void World::dist_time_fold() {
     dist_times[0] = dist_times[1] = dist_times[2] = dist_times[3] = 0.0;
-    for (const auto& pr : dist_ev_pairs) {
+    for (const auto& pr : pass.dist_ev_pairs) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, dist_ev[pr.first], dist_ev[pr.first + 1]) != hipSuccess) { (void)hipGetLastError(); continue; }
         dist_times[2 * pr.second] += ms;
         dist_times[2 * pr.second + 1] += 1.0;
     }
-    dist_ev_pairs.clear();
-    dist_ev_used = 0;
+    pass.dist_ev_pairs.clear();
+    pass.dist_ev_used = 0;
 }
 
 void World::refresh_f32(float* field) {
@@ -388,7 +388,7 @@ void World::refresh_f4(float4* field) {
 
 // Error reduction + break test of an iterative solve; with a transport the per-fluid sums are all-reduced first.
 void World::finalize_solve(SolveCtl* ctl, SolveCtl* pub, uint32_t skipped) {
-    const unsigned ntiles = nlaunch;  // one partial per launched (non-empty) tile
+    const unsigned ntiles = pass.nlaunch;  // one partial per launched (non-empty) tile
     const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
     if (!comm || comm->size() == 1) {
         // (folding this into the evaluate kernels through a last-workgroup reduction was measured 7x slower: the

@@ -150,10 +150,10 @@ void World::spin_until(Arrived&& arrived, const char* drained) {
 uint32_t World::publish_enqueue(const TileAcc* totals, bool lists, bool end_of_step, const PrePub* pre, const uint32_t* gate) {
     const uint32_t seq = ++hostpub_seq;
     Epilogue ep{nullptr, 0u, 0, nullptr, 0u, nullptr};
-    if (end_of_step) {  // what this step left for the publication to fold (World::build_lists and the solvers set them, one publication consumes them)
-        if (fold_stats) { ep.ts = reinterpret_cast<const TileListStats*>(tile_list_stats.p); ep.nts = nlaunch; ep.own = comm ? 1 : 0; }
-        if (fold_bbox_blocks) { ep.bbox_partials = bbox_partials.p; ep.nbb = fold_bbox_blocks; ep.chain_gate = fold_bbox_gate; }
-        fold_stats = false; fold_bbox_blocks = 0u; fold_bbox_gate = nullptr;
+    if (end_of_step) {  // what this pass left for the publication to fold (World::build_lists and the solvers set them, one publication consumes them)
+        if (pass.fold_stats) { ep.ts = reinterpret_cast<const TileListStats*>(tile_list_stats.p); ep.nts = pass.nlaunch; ep.own = comm ? 1 : 0; }
+        if (pass.fold_bbox_blocks) { ep.bbox_partials = bbox_partials.p; ep.nbb = pass.fold_bbox_blocks; ep.chain_gate = pass.fold_bbox_gate; }
+        pass.fold_stats = false; pass.fold_bbox_blocks = 0u; pass.fold_bbox_gate = nullptr;
     }
     const unsigned threads = (ep.ts || ep.bbox_partials) ? BLOCK : WAVE;
     k_publish_readback<<<1, threads, 0, stream>>>(d_rb.p, totals, lists ? 1 : 0, end_of_step ? 1 : 0, mass_slots.p, &h_hostpub->rb, &h_hostpub->seq, seq,
@@ -215,8 +215,7 @@ World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_ite
     // Every convergence test publishes its outcome to host-mapped memory (k_finalize_error; in a decomposed run k_decide,
     // behind the all-reduce), and the host waits for the test count it enqueued — it then decides (and enqueues what
     // follows) while the batch's last apply pass is still running.
-    static const bool no_publish = getenv("SALVA_HIP_NO_PUBLISH") != nullptr;  // (diagnostics: A/B against the copy + wait)
-    SolveCtl* const pub = no_publish ? nullptr : h_pub + which;
+    SolveCtl* const pub = sw.no_publish ? nullptr : h_pub + which;
     c.ctl = d_ctl.p + which;
     if (from == 0) {
         SolveCtl& init = h_ctl[NUM_SOLVES + which];
@@ -224,14 +223,14 @@ World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_ite
         h_ctl[which] = init;
         // (one tiny kernel with the record as its argument instead of up to three copies from pageable host memory, each of which
         // stalls the host until its staging copy is done; the first solve of a chained step also opens the chain)
-        const bool have = which == 1 && pre_init1_valid && memcmp(&pre_init1, &init, sizeof(SolveCtl)) == 0 && !chain_open;
+        const bool have = which == 1 && pass.pre_init1_valid && memcmp(&pass.pre_init1, &init, sizeof(SolveCtl)) == 0 && !chain_open;
         if (!have) {
-            const bool both = which == 0 && pre_init1_valid;  // (World::dfsph_solve has said what the pressure solve will start from)
+            const bool both = which == 0 && pass.pre_init1_valid;  // (World::dfsph_solve has said what the pressure solve will start from)
             k_init_ctl<<<1, 1, 0, stream>>>(d_ctl.p + which, spec_apply ? spec_ring.p : nullptr, init, chain_open ? &d_rb.p->chain_ok : nullptr,
-                                            both ? d_ctl.p + 1 : nullptr, both ? pre_init1 : init);
+                                            both ? d_ctl.p + 1 : nullptr, both ? pass.pre_init1 : init);
             SALVA_HIP_CHECK(hipGetLastError());
         }
-        if (which == 1) pre_init1_valid = false;
+        if (which == 1) pass.pre_init1_valid = false;
         if (pub) { pub->done = 0u; pub->iters = 0u; pub->err = 0.0f; __atomic_store_n(&pub->seq, 0u, __ATOMIC_RELEASE); }
     }
     // First batch: what the previous step's solve needed (iters applies + the converged evaluate) — consecutive steps
@@ -250,12 +249,11 @@ World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_ite
     uint32_t skipped = 0u;
     auto test = [&](int it, bool last_of_batch, const uint32_t* gate, uint32_t* close, uint32_t stage) {
         if (it < min_iter && it + 1 < max_iter && !last_of_batch) { ++skipped; return; }
-        if (!multi) launch_finalize_error(partials.p, nlaunch, (uint32_t)std::max<size_t>(fluids.size(), 1), model_counts.p, d_ctl.p + which, pub, stream, gate, close, stage, skipped);
+        if (!multi) launch_finalize_error(partials.p, pass.nlaunch, (uint32_t)std::max<size_t>(fluids.size(), 1), model_counts.p, d_ctl.p + which, pub, stream, gate, close, stage, skipped);
         else finalize_solve(d_ctl.p + which, pub, skipped);
         skipped = 0u;
     };
-    if (from > 0 && solve_owes_apply[which]) apply(c, from - 1);  // (the apply the batch before left to its successor)
-    solve_owes_apply[which] = false;
+    if (from > 0 && pass.solve_owes_apply[which]) { apply(c, from - 1); pass.solve_owes_apply[which] = false; }  // (the apply the batch before left to its successor)
     if (chain_stage) {
         // Chained (device_types.h StepCtx::gate): ONE batch and no wait.  The batch is what the previous step needed plus, while the
         // count is rising (the impact: 2, 4, 14, 18, 30 ... iterations in consecutive steps), what it rose by last time — a surplus
@@ -269,10 +267,10 @@ World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_ite
             eval(c, k);
             const bool closes = k == nbatch - 1 && nbatch < max_iter;
             test(k, k == nbatch - 1, c.gate, closes ? &d_rb.p->chain_ok : nullptr, (uint32_t)chain_stage);
-            if (closes && lazy_apply) solve_owes_apply[which] = true;  // (only a continuation needs it)
+            if (closes && lazy_apply) pass.solve_owes_apply[which] = true;  // (only a continuation needs it)
             else apply(c, k);
         }
-        chain_batch[which] = nbatch;
+        pass.chain_batch[which] = nbatch;
         return SolveResult{0u, 0.0f};  // (pending: World::adopt_chain_outcome reads it from the end-of-step publication)
     }
     if (from > 0) batch = (from <= 2) ? 4 : 8;
@@ -291,13 +289,13 @@ World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_ite
                 eval(c, it);
                 SALVA_HIP_CHECK(hipEventRecord(ev_spec_eval, stream));
                 SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_spec_eval, 0));
-                spec_dist_stream = stream2;
+                pass.spec_dist_stream = stream2;
                 apply(c, it);  // (the kernel only: World::dfsph_solve's lambda leaves the refresh to the lines below)
-                spec_dist_stream = nullptr;
+                pass.spec_dist_stream = nullptr;
                 SALVA_HIP_CHECK(hipEventRecord(ev_spec_apply, stream2));
                 const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
                 const size_t tm = dist_time_begin(1);
-                launch_sum_partials(partials.p, nlaunch, nm, spec_ring.p + (it & 1), d_sums.p, stream);
+                launch_sum_partials(partials.p, pass.nlaunch, nm, spec_ring.p + (it & 1), d_sums.p, stream);
                 comm->allreduce_sum_f32(d_sums.p, (int)nm, stream);
                 launch_decide_ring(d_sums.p, nm, model_counts.p, spec_ring.p, it, pub, stream);
                 dist_time_end(tm);
@@ -416,7 +414,7 @@ void World::run_forces(const StepCtx& c) {
 template <typename Launch>
 void World::evaluate_split(const StepCtx& c, int iteration, Launch&& launch) {
     // (nothing to overlap with when no ghost is refreshed: a one-rank communicator, or a rank whose faces hold no particle)
-    if (!comm || !overlap_exchange || iteration == 0 || nghost_lo + nghost_hi + nborder_lo + nborder_hi == 0) { launch(c, stream); return; }
+    if (!comm || !sw.overlap_exchange || iteration == 0 || nghost_lo + nghost_hi + nborder_lo + nborder_hi == 0) { launch(c, stream); return; }
     StepCtx ci = c, cb = c;
     ci.phase = 1; cb.phase = 2;
     SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_pre_refresh, 0));
@@ -430,9 +428,7 @@ void World::evaluate_split(const StepCtx& c, int iteration, Launch&& launch) {
 // non-empty fluid has one particle mass (FluidSlot::vol_uniform x density0, the product launch_stage_to_sorted forms) and two, three
 // or four different masses occur — BASELINE config 4 has two.  Sets mass_classes / mass_cmask / nmass.
 bool World::decide_two_mass() {
-    mass_cmask = 0ull; nmass = 0u;
-    for (float& m : mass_classes) m = 0.0f;
-    if (two_mass_off || no_planes || comm || prm.solver != SALVA_HIP_SOLVER_DFSPH || prm.kernel_density != 0 || prm.kernel_gradient != 0) return false;
+    if (sw.two_mass_off || sw.no_planes || comm || prm.solver != SALVA_HIP_SOLVER_DFSPH || prm.kernel_density != 0 || prm.kernel_gradient != 0) return false;
     if (fluids.size() < 2 || fluids.size() > 32 || bounds.size() > 32) return false;
     float ms[4];
     uint32_t distinct = 0;
@@ -443,19 +439,19 @@ bool World::decide_two_mass() {
         bool seen = false;
         for (uint32_t k = 0; k < distinct; ++k) seen |= ms[k] == m;
         if (seen) continue;
-        if (distinct == max_masses) return false;  // one mass too many: the general kernels
+        if (distinct == sw.max_masses) return false;  // one mass too many: the general kernels
         ms[distinct++] = m;
     }
     if (distinct < 2) return false;
     std::sort(ms, ms + distinct);
-    for (uint32_t k = 0; k < distinct; ++k) mass_classes[k] = ms[k];
+    for (uint32_t k = 0; k < distinct; ++k) pass.mass_classes[k] = ms[k];
     for (uint32_t f = 0; f < fluids.size(); ++f) {
         if (!fluids[f].n) continue;  // (an empty fluid has no particle whose class could be asked for)
         const float m = fluids[f].vol_uniform * fluids[f].density0;
         for (uint32_t k = 0; k < distinct; ++k)
-            if (ms[k] == m) mass_cmask |= (uint64_t)k << (2u * f);
+            if (ms[k] == m) pass.mass_cmask |= (uint64_t)k << (2u * f);
     }
-    nmass = distinct;
+    pass.nmass = distinct;
     return true;
 }
 
@@ -521,7 +517,7 @@ float World::choose_substep(const StepCtx& c) {
 // to be a kernel that honours the gate and needs no host decision: a single domain, no CFL choice (a read-back inside the solver), no
 // host force callback, no force with a solve of its own (DFSPHViscosity).  SALVA_HIP_NO_CHAIN=1 switches it off (A/B, tests).
 bool World::chain_allowed() const {
-    if (chain_off || comm || cfl_mode || spec_mode || prm.solver != SALVA_HIP_SOLVER_DFSPH) return false;
+    if (sw.chain_off || comm || cfl_mode || pass.spec_mode || prm.solver != SALVA_HIP_SOLVER_DFSPH) return false;
     if (has_force(SALVA_HIP_FORCE_CUSTOM) || has_force(SALVA_HIP_FORCE_DFSPH_VISCOSITY)) return false;
     if (elastic_stale()) return false;  // (the rest build reads its contact total back)
     return true;
@@ -576,8 +572,8 @@ void World::commit_elastic() {
 // if one did not, calls again with resume = 1 (continue the divergence solve, then everything behind it) or 2 (continue the pressure
 // solve, then the position update) — the classic way, one wait per batch.
 void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, int resume) {
-    if (resume) { dt_prev = chain_dt_prev; inv_dt_prev = chain_inv_dt_prev; }  // (TimestepManager's state as the chained attempt found it)
-    chain_dt_prev = dt_prev; chain_inv_dt_prev = inv_dt_prev;
+    if (resume) { dt_prev = pass.chain_dt_prev; inv_dt_prev = pass.chain_inv_dt_prev; }  // (TimestepManager's state as the chained attempt found it)
+    pass.chain_dt_prev = dt_prev; pass.chain_inv_dt_prev = inv_dt_prev;
     // divergence_solve (:466-503).  NOTE the dt lag: inv_dt is still the previous step's here (0 on the first step).
     const float inv_dt_lag = inv_dt_prev;
     const bool timers = prm.enable_timers != 0;
@@ -589,8 +585,8 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     // Decomposed runs (round 6): the same double buffer lets the apply run BESIDE the all-reduced test instead of behind it
     // (World::run_solve); there the wasted apply is cheaper than the all-reduces it hides from four iterations on.
     const bool multi_rank = comm && comm->size() > 1;
-    const bool spec_apply = !resume && !spec_apply_off && !any_wants_forces &&
-                            (multi_rank ? (!spec_dist_off && last_iters[0] >= 4u) : (!comm && last_iters[0] >= 16u));
+    const bool spec_apply = !resume && !sw.spec_apply_off && !any_wants_forces &&
+                            (multi_rank ? (!sw.spec_dist_off && last_iters[0] >= 4u) : (!comm && last_iters[0] >= 16u));
     if (spec_apply) { w2.ensure(n, stream, false, 1.1f); spec_ring.ensure(2); c.w2 = w2.p; c.spec_ring = spec_ring.p; }
     // Chained: neither solve is waited for (the w / w2 swap below is a host decision on the iteration count: not with speculative applies)
     const bool chain = !resume && !spec_apply && chain_allowed();
@@ -602,29 +598,27 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     if (chain) cg.gate = &d_rb.p->chain_ok;
     const StepCtx& ca = chain_div ? cg : c;  // ... which the kernels between the two solves are only when the first one is chained
     auto div_eval = [&](const StepCtx& cc, int it) {
-        if (it == 0 && fused_first_divergence) return;  // (k_density_alpha_div_p3 wrote kappa and the error partials already)
+        if (it == 0 && pass.fused_first_divergence) return;  // (k_density_alpha_div_p3 wrote kappa and the error partials already)
         evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_divergence(cs, lds, s); });
     };
     auto div_apply = [&](const StepCtx& cc, int) {
         // decomposed runs: kappa of the inner ghost plane was computed here from refreshed w — the applies of the
         // owned particles read nothing else, so only w travels, once per iteration
-        launch_divergence_apply(cc, lds, inv_dt_lag, spec_dist_stream ? spec_dist_stream : stream);
-        if (comm && !spec_dist_stream) refresh_f4(w.p);  // (a speculative decomposed apply: run_solve refreshes the buffer it wrote)
+        launch_divergence_apply(cc, lds, inv_dt_lag, pass.spec_dist_stream ? pass.spec_dist_stream : stream);
+        if (comm && !pass.spec_dist_stream) refresh_f4(w.p);  // (a speculative decomposed apply: run_solve refreshes the buffer it wrote)
     };
     const float div_tol = prm.max_divergence_error * inv_dt_prev * 0.01f;
     SolveResult rd{0u, 0.0f};
     // (the pressure solve's control block is initialised by the divergence solve's launch — unless that solve has to open the chain)
-    pre_init1_valid = false;
     if (resume == 0 && (!chain || chain_div)) {
-        pre_init1 = SolveCtl{0u, 0u, 0.0f, 0u, prm.max_density_error, (uint32_t)std::max(prm.min_pressure_iter, 0), 0u, 0u};
-        pre_init1_valid = true;
+        pass.pre_init1 = SolveCtl{0u, 0u, 0.0f, 0u, prm.max_density_error, (uint32_t)std::max(prm.min_pressure_iter, 0), 0u, 0u};
+        pass.pre_init1_valid = true;
     }
     if (resume <= 1) {
         rd = run_solve(c, 0, div_tol, prm.min_divergence_iter, prm.max_divergence_iter, 0u, div_eval, div_apply, spec_apply, chain_div ? 1 : 0,
-                       resume == 1 ? chain_batch[0] : 0, chain_div);
+                       resume == 1 ? pass.chain_batch[0] : 0, chain_div);
         if (spec_apply && multi_rank) {
-            static const bool trace = getenv("SALVA_HIP_DIST_TRACE") != nullptr;
-            if (trace) fprintf(stderr, "salva_hip dist[%d]: divergence solve with applies beside the all-reduce, %u iterations\n", comm->rank(), rd.iters);
+            if (sw.dist_trace) fprintf(stderr, "salva_hip dist[%d]: divergence solve with applies beside the all-reduce, %u iterations\n", comm->rank(), rd.iters);
         }
         if (spec_apply && (rd.iters & 1u)) {  // an odd number of committed applies: w lives in the second buffer
             std::swap(w.p, w2.p); std::swap(w.cap, w2.cap);
@@ -650,15 +644,15 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
         [&](const StepCtx& cc, int) {
             launch_pressure_apply(cc, lds, inv_dt, stream);
             if (comm) refresh_f4(w.p);
-        }, false, chain ? 2 : 0, resume == 2 ? chain_batch[1] : 0, chain && !chain_div);
+        }, false, chain ? 2 : 0, resume == 2 ? pass.chain_batch[1] : 0, chain && !chain_div);
     st.n_pressure_iters = (int32_t)rp.iters;
     st.density_error = rp.err;
     launch_update_positions(cg, dt, bbox_partials.p, nullptr, stream);  // (the per-block boxes are folded by the end-of-step publication)
-    fold_bbox_blocks = n ? num_blocks(n) : 0u; fold_bbox_gate = cg.gate;
+    pass.fold_bbox_blocks = n ? num_blocks(n) : 0u; pass.fold_bbox_gate = cg.gate;
     dt_prev = dt;
     inv_dt_prev = inv_dt;
-    chain_pending = chain;
-    chain_div_pending = chain_div;
+    pass.chain_pending = chain;
+    pass.chain_div_pending = chain_div;
 }
 
 // IISPHSolver::step (iisph_solver.rs:643-711)
@@ -671,10 +665,10 @@ void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     const float inv_dt = (dt == 0.0f) ? 0.0f : 1.0f / dt;
     launch_integrate(c, dt, stream);
     if (comm) refresh_f4(w.p);             // a ghost's own forces were summed over an incomplete neighbourhood
-    if (!iisph_dii_fused) launch_iisph_dii(c, lds, dt, stream);  // also p = 0.5 * p_prev (a per-particle operation: right for ghosts too)
+    if (!pass.iisph_dii_fused) launch_iisph_dii(c, lds, dt, stream);  // also p = 0.5 * p_prev (a per-particle operation: right for ghosts too)
     // (d_ii depends on positions only: right on the inner ghost plane without an exchange)
     launch_iisph_pred_density(c, lds, dt, stream);
-    if (!iisph_dii_fused) launch_iisph_aii(c, lds, dt, stream);  // (fused: a_ii came out of the density pass with d_ii)
+    if (!pass.iisph_dii_fused) launch_iisph_aii(c, lds, dt, stream);  // (fused: a_ii came out of the density pass with d_ii)
     float* const pa = kappa.p;
     float* const pb = kappa2.p;
     const float omega = 0.5f;  // :53
@@ -694,7 +688,7 @@ void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     const float* p = (rp.iters & 1u) ? pb : pa;
     launch_iisph_velocity_changes(c, lds, dt, p, stream);
     launch_iisph_finish(c, dt, p, bbox_partials.p, nullptr, stream);  // (the per-block boxes are folded by the end-of-step publication)
-    fold_bbox_blocks = n ? num_blocks(n) : 0u; fold_bbox_gate = nullptr;
+    pass.fold_bbox_blocks = n ? num_blocks(n) : 0u; pass.fold_bbox_gate = nullptr;
     dt_prev = dt;
     inv_dt_prev = inv_dt;
 }
@@ -704,7 +698,8 @@ int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
     use_device();
     SalvaHipStepStats st{};
     st.nparticles = n;
-    {   // self.counters.reset() (liquid_world.rs:73); the pass counters of this implementation are cumulative
+    {   // self.counters.reset() (liquid_world.rs:73); the pass counters of this implementation are cumulative, like World::tally:
+        // a counter added to SalvaHipCounters that is to survive the step is named here
         const SalvaHipCounters last = counters;
         counters = SalvaHipCounters{};
         counters.speculative_passes = last.speculative_passes; counters.discarded_passes = last.discarded_passes;
@@ -769,39 +764,17 @@ void World::call_coupling(int phase, float dt) {
 }
 
 // ------------------------------------------------------------------------------------------------ substep: what its phases share
-// What World::choose_grid settles for a substep: the size of the (folded) cell table, of the dense tile table, and the bound of the
-// compact per-slot tables.
-struct World::GridShape { size_t ncf = 0; uint32_t ntiles = 0, nslots_bound = 0; };
-
-// What each pass (World::run_pass) decides for the phases behind it: reset at the top of every attempt.
-struct World::Attempt {
-    bool spec = false;          // launch shapes from the previous step's totals (World::substep: "One pass over the step")
-    bool defer_lists = false;   // the list capacity is checked with the end-of-step publication
-    bool have_grid = false;     // keys, sort, tile tables and the totals publication are enqueued already (world.h PreGrid)
-    TileAcc tt{};               // the totals the launch shapes and buffers of this pass are cut for
-    uint32_t nslices = 0;
-    size_t scan_tb = 0;         // temporary bytes of the tile-table scans
-    size_t need_f = 0, need_b = 0;  // entries of the two halo slot tables
-    bool ref_step = false;      // the list build keeps the referenced halo slots only (World::size_pass)
-    RefBuild refb{};
-    StepCtx c{};                // (the committed pass's becomes World::last_ctx)
-};
-// ... on top of what the substep decides before its first pass, the same for every attempt
-struct World::Pass : World::Attempt {
-    bool timers = false, has_dyn = false, adopted = false, can_redo = false, can_speculate = false;
-    GridShape gs;
-    double dcs_ms = 0.0;        // host milliseconds of DynamicContactSampling (counters.cd.boundary_update_time)
-    int attempt = 0;            // the pass that runs: 0, or the repeat of a discarded one
-};
-
-// State a pass touches, and where a discarded pass leaves it (extend this list — and restore() — with every new side effect, or
-// exclude the feature in can_redo):
+// State a pass touches, and where a discarded pass leaves it.  What a pass or a substep decides for its own phases lives in
+// World::pass (world.h Attempt / Pass) and starts from a fresh object at the top of every run_pass / substep: a discarded pass, and a
+// step that threw (World::step's catch paths need nothing extra), can leave nothing of it armed.  What remains to be listed here — and
+// in restore(), or excluded in can_redo — is a new side effect on the state that is CARRIED from step to step:
 //   particle arrays of buffer cur^1 (the sort's output: positions, velocities, dv / pressures, models, permutation) ....
 //       recomputed by the repeated pass; buffer `cur` (the pre-sort state) is read-only until the pass commits
 //   cur, dt_prev / inv_dt_prev, h_rb->bbox, last_iters / prev_iters ........ snapshot here, restored on discard
 //   the next step's pre-enqueued grid (world.h PreGrid) ........ dropped on discard: it was built from the discarded positions
 //   per-step scratch (acc, w, rho, alpha, kappa, lists, tables, partials, control blocks) ........ rewritten from the start
 //   d_flags ........ cleared at the top of every attempt
+//   World::tally ........ counts discarded passes too
 //   counters / stats ........ filled after the loop; discarded_passes counts the discards
 //   boundary force accumulators, host force callbacks, DynamicContactSampling push-outs, ghost exchanges ........ not
 //       repeatable: can_redo is false for worlds that have them
@@ -836,7 +809,7 @@ bool World::has_force(int kind) const {
 // with k_cell_start writes it once: a bounding box blown up by a few strays (4 x 10^8 cells around 25 k particles) keeps
 // the radix sort.  SALVA_HIP_RADIX_SORT=1 / 0 forces one or the other.
 bool World::counting_sort_for(size_t ncf, uint32_t n) const {
-    return ncf + 1 < 0x7fffffffull && (sort_mode == 0 || (sort_mode < 0 && ncf <= 16ull * n + (1ull << 20)));
+    return ncf + 1 < 0x7fffffffull && (sw.sort_mode == 0 || (sw.sort_mode < 0 && ncf <= 16ull * n + (1ull << 20)));
 }
 
 // a list was cut at the ELL capacity: room for the longest list seen, and a quarter to spare
@@ -895,7 +868,7 @@ size_t World::tile_scan_temp(const GridShape& gs) {
 // tile tables: per-tile halo sizes / slice counts -> prefix.  `c`: the step's context, pointed at the tables of T here.  Returns the
 // sequence number of the totals' publication (publish: somebody will wait for it).
 uint32_t World::enqueue_grid_tiles(GridTabs& T, const GridShape& gs, StepCtx c, size_t tb, const uint32_t* gate, bool publish) {
-    launch_tile_slots(gf.device(T.cell_start_f.p), gs.ntiles, T.tile_flags.p, T.tile_rank.p, T.tile_ids.p, cub_temp.p, tb, stream, gate, split_s_cur);
+    launch_tile_slots(gf.device(T.cell_start_f.p), gs.ntiles, T.tile_flags.p, T.tile_rank.p, T.tile_ids.p, cub_temp.p, tb, stream, gate, pass.split_s_cur);
     // (k_tile_count zeroes the entries of its surplus workgroups and the scan's extra element itself: no memset —
     // unless there is no workgroup at all, a rank that holds no particle)
     if (gs.nslots_bound == 0) SALVA_HIP_CHECK(hipMemsetAsync(T.tile_cnt.p, 0, sizeof(TileAcc), stream));
@@ -917,12 +890,12 @@ void World::pre_enqueue_grid(const GridShape& gs) {
     enqueue_grid_keys(T, gs, true, pre.check_mass, gate);
     enqueue_grid_sort(T, gs, true, gate);
     pre.seq = enqueue_grid_tiles(T, gs, make_ctx(), tile_scan_temp(gs), gate, true);
-    pre.n = n; pre.ncf = gs.ncf; pre.ntiles = gs.ntiles; pre.nslots_bound = gs.nslots_bound; pre.gf = gf; pre.split_s = split_s_cur;
+    pre.n = n; pre.ncf = gs.ncf; pre.ntiles = gs.ntiles; pre.nslots_bound = gs.nslots_bound; pre.gf = gf; pre.split_s = pass.split_s_cur;
     pre.valid = true;
 }
 // The next step could not use it.  If its launches ran (the gate was open) they have raised flags and mass marks that belong to no step.
 void World::pre_drop() {
-    ++pre_dropped; ++counters.pregrid_dropped;
+    ++tally.pre_dropped; ++counters.pregrid_dropped;
     if (!h_rb->pre_ok) return;
     SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));
     SALVA_HIP_CHECK(hipMemsetAsync(mass_slots.p, 0, MASS_SLOTS * sizeof(uint32_t), stream));
@@ -956,9 +929,9 @@ void World::prepare_working_set(SalvaHipStepStats& st) {
     if (has_force(SALVA_HIP_FORCE_AKINCI2013)) normal.ensure(n, stream, false, 1.1f);
     if (prm.solver == SALVA_HIP_SOLVER_IISPH) { kappa2.ensure(n); rho_star.ensure(n); aii.ensure(n); dii.ensure(n); dijpj.ensure(n); iisph_q.ensure(n); iisph_pr.ensure(n); }
     bbox_partials.ensure(6 * std::max<size_t>(std::max<size_t>(num_blocks(n), bbox_blocks(n)), 1024));
-    two_mass = decide_two_mass();
-    if (two_mass) nffb.ensure(n, stream, false, 1.1f);
-    if (two_mass && nmass > 2u) nffc.ensure(n, stream, false, 1.1f);
+    pass.two_mass = decide_two_mass();
+    if (pass.two_mass) nffb.ensure(n, stream, false, 1.1f);
+    if (pass.two_mass && pass.nmass > 2u) nffc.ensure(n, stream, false, 1.1f);
 }
 
 // The fluid grid of this substep: gf from the cell bounding box (known from the previous step's position update unless the host
@@ -983,11 +956,11 @@ World::GridShape World::choose_grid() {
     // (fold_relax: a fold that piled the bulk of the fluid onto itself — the rule below looks at the box, not at where the particles
     // sit — was found out by the tile totals of an earlier attempt, which then threw FoldRetry: every level loosens the fold
     // eightfold, the third gives it up.  Sticky for the world.)
-    const uint32_t forced = fold_forced ? fold_forced << (2u * std::min(fold_relax, 3u)) : 0u;
+    const uint32_t forced = sw.fold_forced ? sw.fold_forced << (2u * std::min(fold_relax, 3u)) : 0u;
     constexpr bool tiles_pow2 = (TX & (TX - 1)) == 0 && (TY & (TY - 1)) == 0 && (TZ & (TZ - 1)) == 0;  // (a period is a whole number of tiles)
     // (a decomposed run finds its ghost planes by absolute x-cell: it folds y and z only.  Dynamically sampled colliders read cells
     // back from the keys: dcs.hip picks the image by the particle's position.)
-    const bool can_fold = tiles_pow2 && !fold_off && fold_relax < 3u;
+    const bool can_fold = tiles_pow2 && !sw.fold_off && fold_relax < 3u;
     if (can_fold && nb && b_dirty) build_boundary_grid();
     // (once it folds, it folds tight — to half a cell per particle if the periods allow: the particles that have left the scene
     // then land on the tiles of the bulk instead of owning a tile each; a tile with one particle costs a quarter of a full one)
@@ -1016,10 +989,9 @@ World::GridShape World::choose_grid() {
     // Splitting of over-full tiles (device_types.h StepCtx::split_s): where the plane layouts run (one or two particle masses, single
     // domain), and while the tiles beyond the three-per-CU layouts are a minority — decided from the totals of the step before
     // (split_on, World::size_pass).  SALVA_HIP_NO_SPLIT=1: never; SALVA_HIP_SPLIT_S=k: always, at k halo particles (tests).
-    split_s_cur = 0u;
-    if (split_forced) split_s_cur = split_forced;
-    else if (!split_off && split_on && !comm && spec_off && mass_known && (mass_uniform != 0.0f || two_mass)) split_s_cur = TILE_SPLIT_S;
-    gs.nslots_bound = (uint32_t)std::min<uint64_t>((uint64_t)gs.ntiles * (split_s_cur ? (uint64_t)TX : 1ull), n);
+    if (sw.split_forced) pass.split_s_cur = sw.split_forced;
+    else if (!sw.split_off && split_on && !comm && sw.spec_off && mass_known && (mass_uniform != 0.0f || pass.two_mass)) pass.split_s_cur = TILE_SPLIT_S;
+    gs.nslots_bound = (uint32_t)std::min<uint64_t>((uint64_t)gs.ntiles * (pass.split_s_cur ? (uint64_t)TX : 1ull), n);
     return gs;
 }
 
@@ -1030,10 +1002,10 @@ void World::ensure_slot_tables(uint32_t nslots_bound) {
     d_maxhalo.ensure(4);
     partials.ensure((size_t)nslots * std::max<size_t>(fluids.size(), 1), stream, false, 1.5f);
     tile_list_stats.ensure(tile_list_stats_bytes(nslots), stream, false, 1.5f);
-    if (two_mass) {  // (per slot; Tile::setup reads them in every tile kernel, k_nbr_tile writes them)
+    if (pass.two_mass) {  // (per slot; Tile::setup reads them in every tile kernel, k_nbr_tile writes them)
         tile_mass_bits.ensure(nslots, stream, false, 1.5f);
         tile_massb_bits.ensure(nslots, stream, false, 1.5f);
-        if (nmass > 2u) tile_masscd_bits.ensure(nslots, stream, false, 1.5f);
+        if (pass.nmass > 2u) tile_masscd_bits.ensure(nslots, stream, false, 1.5f);
     }
 }
 
@@ -1052,7 +1024,7 @@ void World::reorder_working_set(bool timers) {
 bool World::predict_totals(const GridShape& gs, TileAcc& tt) const {
     const TileAcc& l = pred_tt;
     tt = l;
-    const uint32_t m = spec_tight ? 0u : 1u;  // (SALVA_HIP_SPEC_TIGHT: no margin at all — the tests' way to force misses)
+    const uint32_t m = sw.spec_tight ? 0u : 1u;  // (SALVA_HIP_SPEC_TIGHT: no margin at all — the tests' way to force misses)
     tt.nonempty = std::min<uint32_t>(gs.nslots_bound, l.nonempty + m * std::max<uint32_t>(16u, l.nonempty / 16u));
     tt.max_s = (l.max_s + m * std::max<uint32_t>(32u, l.max_s / 16u) + m * 63u) & ~(m * 63u);
     tt.max_sb = nb ? ((l.max_sb + m * std::max<uint32_t>(32u, l.max_sb / 8u) + m * 63u) & ~(m * 63u)) : 0u;
@@ -1064,28 +1036,29 @@ bool World::predict_totals(const GridShape& gs, TileAcc& tt) const {
 // Everything that turns a TileAcc into launch shapes: the totals themselves (waited for — `seq_totals` is their publication — or
 // predicted: p.tt holds the prediction), the lds fields, the workgroup size, the halo tables' stride and size, the launch classes,
 // the referenced halo's caps.  Enqueues the reorder.  Throws FoldRetry when the exact totals show a fold that piled the fluid up.
-void World::size_pass(Pass& p, uint32_t seq_totals) {
+void World::size_pass(uint32_t seq_totals) {
+    Pass& p = pass;
     TileAcc& tt = p.tt;
     const bool spec = p.spec;
     reorder_working_set(p.timers);  // (the host waits for the totals while the GPU moves the particles)
     if (!spec) {  // (else mass_uniform: what the last exact pass found — nothing has touched the particles since, see can_speculate)
         publish_wait(seq_totals, true, false, false);
         tt = h_rb->tile_total;
-        if (check_mass) {  // every particle of the working set has the same mass: the evaluate kernels stage 24 bytes per halo slot
+        if (p.check_mass) {  // every particle of the working set has the same mass: the evaluate kernels stage 24 bytes per halo slot
             float m;
             memcpy(&m, &h_rb->mass_mm[0], sizeof(m));
-            mass_uniform = (h_rb->mass_mm[0] == h_rb->mass_mm[1] && m > 0.0f && std::isfinite(m) && !no_planes) ? m : 0.0f;
+            mass_uniform = (h_rb->mass_mm[0] == h_rb->mass_mm[1] && m > 0.0f && std::isfinite(m) && !sw.no_planes) ? m : 0.0f;
             mass_known = true;
         }
     }
-    nlaunch = tt.nonempty;
+    p.nlaunch = tt.nonempty;
     lds.max_halo_fluid = tt.max_s; lds.max_halo_boundary = tt.max_sb;
     lds.max_sum = spec ? 0u : tt.max_sum;  // (a speculative pass knows the two maxima only: TileLds::sum_slots falls back to their sum)
     lds.max_raw = spec ? 0u : tt.max_raw;
-    if (tile_trace)
+    if (sw.tile_trace)
         fprintf(stderr, "salva_hip tiles: nonempty %u max_s %u max_sb %u max_sum %u max_raw %u heavy %u light %u tiny %u split_s %u mass_uniform %g | chained %llu breaks %llu pregrid %llu dropped %llu | fold %u %u %u\n",
-                tt.nonempty, tt.max_s, tt.max_sb, tt.max_sum, tt.max_raw, tt.heavy, tt.nlight, tt.ntiny, split_s_cur, (double)mass_uniform,
-                (unsigned long long)chain_steps, (unsigned long long)chain_breaks, (unsigned long long)pre_adopted, (unsigned long long)pre_dropped,
+                tt.nonempty, tt.max_s, tt.max_sb, tt.max_sum, tt.max_raw, tt.heavy, tt.nlight, tt.ntiny, p.split_s_cur, (double)mass_uniform,
+                (unsigned long long)tally.chain_steps, (unsigned long long)tally.chain_breaks, (unsigned long long)tally.pre_adopted, (unsigned long long)tally.pre_dropped,
                 gf.mask[0] + 1u, gf.mask[1] + 1u, gf.mask[2] + 1u);  // fold: period of each axis in cells, 0 = not folded
     if (!spec) {
         // next step's splitting: on while the over-full tiles are few (each costs a second workgroup and a third more staging, and
@@ -1119,7 +1092,7 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
 #endif
     lds.threads = WAVE * std::min<uint32_t>(std::max<uint32_t>(std::max<uint32_t>((avg + WAVE - 1) / WAVE, weighted), lo), hi);
 #ifdef SALVA_HIP_DIAG
-    if (const char* e = getenv("SALVA_HIP_TILE_THREADS")) lds.threads = (uint32_t)atoi(e);
+    if (sw.tile_threads_set) lds.threads = sw.tile_threads;
 #endif
     if (gf.folded() && !fold_locked && !spec && !halo_fits(tt, tt.max_sum)) {
         // Did the fold pile the fluid onto itself?  (a long sheet of fluid without an enclosing boundary folds onto its
@@ -1136,27 +1109,27 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
     // slot tables: one fixed-stride row per tile when that costs at most ~3x the compact size (dense scenes), so
     // that a tile kernel can fetch its rows before it knows its sizes; compact rows otherwise (sparse scenes)
     const uint64_t st_f = (lds.max_halo_fluid + 63u) & ~63u, st_b = nb ? ((lds.max_halo_boundary + 63u) & ~63u) : 0u;
-    const uint64_t strided = (uint64_t)nlaunch * (st_f + st_b), compact = tt.s + tt.sb;
-    const bool use = strided <= 3 * compact + (1u << 20) && !getenv("SALVA_HIP_COMPACT_HALO");
+    const uint64_t strided = (uint64_t)p.nlaunch * (st_f + st_b), compact = tt.s + tt.sb;
+    const bool use = strided <= 3 * compact + (1u << 20) && !sw.compact_halo;
     halo_stride = use ? (uint32_t)st_f : 0u; bhalo_stride = use ? (uint32_t)st_b : 0u;
 #ifdef SALVA_HIP_DIAG
     // persistent pipeline kernels (pipe.h): one wave per slice of the fullest tile, at most PIPE_MAX_WAVES
-    pipe.enabled = halo_stride > 0 && !getenv("SALVA_HIP_NO_PIPELINE");
+    pipe.enabled = halo_stride > 0 && !sw.no_pipeline;
     pipe.scap = halo_stride; pipe.sbcap = bhalo_stride;
-    pipe.num_cus = (uint32_t)num_cus; pipe.nlaunch = nlaunch;
+    pipe.num_cus = (uint32_t)num_cus; pipe.nlaunch = p.nlaunch;
     uint32_t waves = std::min<uint32_t>(std::max<uint32_t>(tt.max_nsl, 4u), (uint32_t)PIPE_MAX_WAVES);
-    if (const char* e = getenv("SALVA_HIP_PIPE_WAVES")) waves = std::min<uint32_t>(std::max(atoi(e), 1), PIPE_MAX_WAVES);
+    if (sw.pipe_waves) waves = sw.pipe_waves;
     pipe.threads = waves * WAVE;
 #endif
-    p.need_f = halo_stride ? (size_t)nlaunch * halo_stride : (size_t)tt.s;
-    p.need_b = halo_stride ? (size_t)nlaunch * bhalo_stride : (size_t)tt.sb;
+    p.need_f = halo_stride ? (size_t)p.nlaunch * halo_stride : (size_t)tt.s;
+    p.need_b = halo_stride ? (size_t)p.nlaunch * bhalo_stride : (size_t)tt.sb;
     halo_src.ensure(p.need_f ? p.need_f : 1, stream, false, 1.2f);
     bhalo_src.ensure(p.need_b ? p.need_b : 1, stream, false, 1.2f);
     p.nslices = tt.nsl;
     if (spec) {  // what the kernels clamp themselves to (StepCtx::spec)
-        spec_mode = true;
-        halo_cap = lds.max_halo_fluid; bhalo_cap = lds.max_halo_boundary; nslices_cap = p.nslices;
-        halo_len = p.need_f; bhalo_len = p.need_b;
+        p.spec_mode = true;
+        p.halo_cap = lds.max_halo_fluid; p.bhalo_cap = lds.max_halo_boundary; p.nslices_cap = p.nslices;
+        p.halo_len = p.need_f; p.bhalo_len = p.need_b;
     }
     // Launch classes (device_types.h StepCtx::slot_order).  Sparse slots: worth a launch of their own per pass once they are many —
     // a thousand of them hold a CU's LDS for a round and a third of the chip each pass.  Light slots: the class the round-5 review
@@ -1168,17 +1141,16 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
     // are >= 256).  SALVA_HIP_NO_CLASSES=1: no class ever; SALVA_HIP_CLASSES=1: both, whenever there is a slot of the kind and
     // one outside it (tests).
     const bool beyond3 = tt.max_s > P3_DS_THREE || tt.max_raw > P2_DS_THREE || tt.max_sum > FIXED_DS_SMALL;
-    class_ntiny = class_nlight = 0u;
-    if (!spec && !classes_off) {
-        if (tt.ntiny > 0u && tt.ntiny < tt.nonempty && (classes_forced || tt.ntiny >= 512u)) class_ntiny = tt.ntiny;
+    if (!spec && !sw.classes_off) {
+        if (tt.ntiny > 0u && tt.ntiny < tt.nonempty && (sw.classes_forced || tt.ntiny >= 512u)) p.class_ntiny = tt.ntiny;
         const uint32_t nfull = tt.nonempty - tt.nlight - tt.ntiny;
-        if (tt.nlight > 0u && nfull > 0u && (classes_forced || (light_on && beyond3 && tt.nlight >= 256u))) class_nlight = tt.nlight;
+        if (tt.nlight > 0u && nfull > 0u && (sw.classes_forced || (sw.light_on && beyond3 && tt.nlight >= 256u))) p.class_nlight = tt.nlight;
         // (sparse slots without a launch of their own are light ones — tile_is_light holds for them — when the light class runs)
-        if (class_nlight && !class_ntiny) class_nlight += tt.ntiny;
+        if (p.class_nlight && !p.class_ntiny) p.class_nlight += tt.ntiny;
     }
-    if (class_ntiny || class_nlight) slot_order.ensure(nlaunch, stream, false, 1.5f);
-    if (class_nlight) ++counters.light_class_passes;
-    if (class_ntiny) ++counters.sparse_class_passes;
+    if (p.class_ntiny || p.class_nlight) slot_order.ensure(p.nlaunch, stream, false, 1.5f);
+    if (p.class_nlight) ++counters.light_class_passes;
+    if (p.class_ntiny) ++counters.sparse_class_passes;
 
     // Referenced-only halo (device_types.h StepCtx::tile_off): the list builder drops the halo slots no list names — a seventh of
     // the 6x6x6 box lies further than h from the own cube — and the solver kernels stage what is left.  It runs where that can
@@ -1190,15 +1162,14 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
     // are sized by the PREVIOUS step's kept maxima plus a margin, never beyond the full box's: the builder holds every tile to
     // those caps, raises flag 16 where one does not fit, and the pass is repeated with the full box's bounds — the way a list
     // longer than the capacity is handled.
-    p.ref_step = !ref_off && !spec && n > 0 && halo_stride > 0u && p.c.nmodels <= 32u && p.c.nbmodels <= 32u && (ref_forced || beyond3);
+    p.ref_step = !sw.ref_off && !spec && n > 0 && halo_stride > 0u && p.c.nmodels <= 32u && p.c.nbmodels <= 32u && (sw.ref_forced || beyond3);
     p.refb = RefBuild{halo_src.p, slot_info.p, G().tile_off.p, RefCaps{0xffffffffu, 0xffffffffu, 0xffffffffu}, d_rb.p->max_ref};
-    ref_bounded = false;
     if (p.ref_step && p.defer_lists && ref_pred_valid && ref_pred_n == n) {
         // (the fullest kept halo moves by a few slots per step in a settled fluid and by a layer of particles — a hundred — when one
         // crosses a tile face: an eighth of room, which costs LDS bytes only where no layout is at stake; a bound just above a
         // three-per-CU layout is held to that layout while the prediction leaves it eight slots)
         auto bound = [&](uint32_t pred, uint32_t full, uint32_t layout) {
-            if (ref_tight) return std::min(pred - pred / 8u, full);  // (tests: a bound every fullest tile outgrows)
+            if (sw.ref_tight) return std::min(pred - pred / 8u, full);  // (tests: a bound every fullest tile outgrows)
             uint32_t b = pred + std::max<uint32_t>(96u, pred / 8u);
             if (b > layout && pred + 8u <= layout) b = layout;
             return std::min(b, full);
@@ -1206,34 +1177,34 @@ void World::size_pass(Pass& p, uint32_t seq_totals) {
         p.refb.cap.s = bound(ref_pred[0], tt.max_s, P3_DS_THREE);
         p.refb.cap.raw = std::max(bound(ref_pred[1], tt.max_raw, P2_DS_THREE), tt.max_sb);
         p.refb.cap.sum = std::max(bound(ref_pred[2], tt.max_sum, FIXED_DS_SMALL), tt.max_sb);
-        ref_bounded = true;
+        p.ref_bounded = true;
     }
 }
 
 // flat halo slot tables (again: behind a list build that kept the referenced slots only — tile_off back to the full box's counts first)
-void World::fill_tile_tables(Pass& p, bool again) {
-    const uint32_t keep_t = class_ntiny, keep_l = class_nlight;
-    class_ntiny = class_nlight = 0u;  // (the table builder itself runs over every slot in one launch)
-    p.c = make_ctx();
+void World::fill_tile_tables(bool again) {
+    const Pass& p = pass;
+    StepCtx c = make_ctx();
+    c.slot_order = nullptr; c.ntiny = c.nlight = 0u;  // (the table builder itself runs over every slot in one launch)
     if (again) scan_tiles(cub_temp.p, p.scan_tb, G().tile_cnt.p, G().tile_off.p, p.gs.nslots_bound + 1, stream);
-    launch_tile_halo_fill(p.c, halo_src.p, bhalo_src.p, slot_info.p, stream, (keep_t || keep_l) ? slot_order.p : nullptr, keep_l, keep_t);
-    class_ntiny = keep_t; class_nlight = keep_l;
+    launch_tile_halo_fill(c, halo_src.p, bhalo_src.p, slot_info.p, stream, (p.class_ntiny || p.class_nlight) ? slot_order.p : nullptr, p.class_nlight, p.class_ntiny);
 }
 
 // The halo slot tables and the neighbour lists   (compute_contacts, contacts.rs:154-252): one pass into fixed-capacity ELL rows; if a
 // list turns out longer than the capacity the pass is repeated with room to spare (rare: the capacity follows the
 // longest list seen so far).  Speculative passes and those that defer the check look at the end of the step instead.
-void World::build_lists(Pass& p) {
-    fill_tile_tables(p, false);
+void World::build_lists() {
+    Pass& p = pass;
+    fill_tile_tables(false);
     for (int nattempt = 0;; ++nattempt) {
-        if (nattempt > 0 && p.ref_step) fill_tile_tables(p, true);  // (the first build compacted the slot tables in place)
+        if (nattempt > 0 && p.ref_step) fill_tile_tables(true);  // (the first build compacted the slot tables in place)
         nbr_ff.ensure((size_t)p.nslices * cap_ff * WAVE + 1, stream, false, 1.1f);
         nbr_fb.ensure(nb ? (size_t)p.nslices * cap_fb * WAVE + 1 : 1, stream, false, 1.1f);
         slice_near.ensure((size_t)p.nslices + 1, stream, false, 1.1f);
         p.c = make_ctx();
         // (a pass whose list statistics are only looked at with the end-of-step publication lets that publication fold them)
-        fold_stats = (p.spec || p.defer_lists) && n > 0;
-        launch_nbr_build(p.c, lds, tile_list_stats.p, fold_stats ? nullptr : reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff),
+        p.fold_stats = (p.spec || p.defer_lists) && n > 0;
+        launch_nbr_build(p.c, lds, tile_list_stats.p, p.fold_stats ? nullptr : reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_ff),
                          &d_rb.p->max_cnt_ff, comm ? reinterpret_cast<unsigned long long*>(&d_rb.p->ncontacts_own_ff) : nullptr, stream,
                          p.ref_step ? &p.refb : nullptr);
         if (p.spec || p.defer_lists) break;
@@ -1248,27 +1219,27 @@ void World::build_lists(Pass& p) {
     if (p.ref_step) {
         // from here on the tiles hold their kept slots only, and the launches are cut for them
         if (!p.defer_lists) { lds.max_halo_fluid = std::max<uint32_t>(h_rb->max_ref[0], 1u); lds.max_raw = h_rb->max_ref[1]; lds.max_sum = h_rb->max_ref[2]; }
-        else if (ref_bounded) { lds.max_halo_fluid = p.refb.cap.s; lds.max_raw = p.refb.cap.raw; lds.max_sum = p.refb.cap.sum; }
-        ref_on_cur = true;
-        ++ref_passes;
-        if (tile_trace && !p.defer_lists)
+        else if (p.ref_bounded) { lds.max_halo_fluid = p.refb.cap.s; lds.max_raw = p.refb.cap.raw; lds.max_sum = p.refb.cap.sum; }
+        p.ref_on_cur = true;
+        ++tally.ref_passes;
+        if (sw.tile_trace && !p.defer_lists)
             fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (exact)\n",
                     p.tt.max_s, p.tt.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid);
     }
 #ifdef SALVA_HIP_DIAG
     // kernel-development builds: bank-conflict-aware list order (diag/sched.hip), SALVA_HIP_SCHED=1
-    if (sched_mode > 0) launch_list_schedule(p.c, lds, stream);
+    if (sw.sched_mode > 0) launch_list_schedule(p.c, lds, stream);
 #endif
 }
 
 // solver   (evaluate_kernels + compute_densities + solver.step, liquid_world.rs:123-144)
 void World::density_and_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers) {
     // (DFSPH: the first evaluate of the divergence solve rides in the density pass when the plane layout applies, dfsph.hip)
-    fused_first_divergence = prm.solver == SALVA_HIP_SOLVER_DFSPH && !no_fused_div && launch_density_alpha_div(c, lds, stream);
+    pass.fused_first_divergence = prm.solver == SALVA_HIP_SOLVER_DFSPH && !sw.no_fused_div && launch_density_alpha_div(c, lds, stream);
     // (single-domain IISPH: d_ii rides in the density pass, dfsph.hip k_density_alpha<true>)
     // (not with CFL sub-stepping: d_ii carries dt^2, and the substep is only chosen inside the solver)
-    iisph_dii_fused = prm.solver == SALVA_HIP_SOLVER_IISPH && !comm && !no_fused_div && !cfl_mode;
-    if (!fused_first_divergence) launch_density_alpha(c, lds, iisph_dii_fused ? dt : 0.0f, stream);
+    pass.iisph_dii_fused = prm.solver == SALVA_HIP_SOLVER_IISPH && !comm && !sw.no_fused_div && !cfl_mode;
+    if (!pass.fused_first_divergence) launch_density_alpha(c, lds, pass.iisph_dii_fused ? dt : 0.0f, stream);
     if (comm) {
         refresh_f32(rho.p);
         // (the density pass wrote posmr.w = m / rho from each rank's OWN sum; a ghost's rho has just been replaced by its owner's,
@@ -1283,13 +1254,14 @@ void World::density_and_solve(StepCtx& c, float& dt, const float g[3], SalvaHipS
 // end of step: next bbox + flags (+ in a speculative pass: the true table totals and list statistics), published and waited for.
 // The next step's grid part rides behind this step's publication when the cell box has been standing still (world.h PreGrid):
 // the device compares the box this step's position update found with the one this step ran on, and opens the gate if equal.
-void World::publish_end_of_step(const Pass& p, const PassSnapshot& snap) {
+void World::publish_end_of_step(const PassSnapshot& snap) {
+    const Pass& p = pass;
     static_assert(offsetof(Readback, bbox) == offsetof(Readback, flags) + sizeof(uint32_t), "flags and bbox travel in one copy");
     const bool stable = bbox_used_valid && memcmp(bbox_used_last, snap.bbox, sizeof(snap.bbox)) == 0;
-    const bool want_pre = !pre_off && p.attempt == 0 && !p.spec && !comm && !p.timers && !p.has_dyn && !has_force(SALVA_HIP_FORCE_CUSTOM) && !cfl_mode &&
+    const bool want_pre = !sw.pre_off && p.attempt == 0 && !p.spec && !comm && !p.timers && !p.has_dyn && !has_force(SALVA_HIP_FORCE_CUSTOM) && !cfl_mode &&
                           counting_sort_for(p.gs.ncf, n) && stable && n > 0 && p.gs.nslots_bound > 0;
     memcpy(bbox_used_last, snap.bbox, sizeof(snap.bbox)); bbox_used_valid = true;
-    PrePub pp{want_pre ? 1 : 0, chain_pending ? 1 : 0, {snap.bbox[0], snap.bbox[1], snap.bbox[2], snap.bbox[3], snap.bbox[4], snap.bbox[5]}};
+    PrePub pp{want_pre ? 1 : 0, p.chain_pending ? 1 : 0, {snap.bbox[0], snap.bbox[1], snap.bbox[2], snap.bbox[3], snap.bbox[4], snap.bbox[5]}};
     const uint32_t seq_end = publish_enqueue(p.spec ? G().tile_off.p + p.gs.nslots_bound : nullptr, p.spec || p.defer_lists, true, &pp);
     if (want_pre) pre_enqueue_grid(p.gs);
     publish_wait(seq_end, p.spec, p.spec || p.defer_lists, true);
@@ -1298,7 +1270,7 @@ void World::publish_end_of_step(const Pass& p, const PassSnapshot& snap) {
 
 // A chained step (World::dfsph_solve): the publication says whether both solves converged within the batches they were given.
 void World::adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHipStepStats& st, bool timers) {
-    chain_pending = false;
+    pass.chain_pending = false;
     auto adopt = [&](int which) {  // the outcome of a solve nobody waited for
         prev_iters[which] = last_iters[which];
         last_iters[which] = h_rb->solve[which][1];
@@ -1307,17 +1279,17 @@ void World::adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHi
     };
     uint32_t stage = h_rb->chain_ok ? 0u : h_rb->chain_stage;
     if (stage == 0u) {
-        if (chain_div_pending) adopt(0);
+        if (pass.chain_div_pending) adopt(0);
         adopt(1);
-        ++chain_steps; ++counters.chained_passes;
+        ++tally.chain_steps; ++counters.chained_passes;
     } else {
         // one of them fell short: every kernel behind it returned at once.  Continue that solve the classic way (batches with a
         // wait each) and run what follows it; the flags raised so far were published (and cleared) by the first publication.
         if (stage != 1u && stage != 2u) throw HipError(SALVA_HIP_E_HIP, "internal error: a chained step broke at an unknown stage");
-        ++chain_breaks; ++counters.chain_breaks;
+        ++tally.chain_breaks; ++counters.chain_breaks;
         pre.valid = false;  // (its gate stayed shut: Readback::pre_ok needs the chain)
         const uint32_t flags0 = h_rb->flags;
-        if (stage == 2u && chain_div_pending) adopt(0);
+        if (stage == 2u && pass.chain_div_pending) adopt(0);
         dfsph_solve(c, dt, g, st, (int)stage);
         if (timers) SALVA_HIP_CHECK(hipEventRecord(ev[2], stream));  // (the solver's part of the step ends here, not at the first publication)
         publish_and_wait(nullptr, false, true);
@@ -1330,21 +1302,20 @@ void World::adopt_chain_outcome(StepCtx& c, float& dt, const float g[3], SalvaHi
 // One attempt at the substep: grid -> launch shapes -> lists -> solver -> end-of-step publication.  True: the pass committed.
 // False: the publication showed that it ran on too little room (a list cut at the capacity, a kept halo or a predicted total
 // outgrown); `snap` has put the world back and the pass is to be repeated, with p.attempt + 1.
-bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st) {
+bool World::run_pass(const PassSnapshot& snap, float& dt, const float g[3], SalvaHipStepStats& st) {
+    Pass& p = pass;
     const GridShape& gs = p.gs;
-    static_cast<Attempt&>(p) = Attempt{};
+    static_cast<Attempt&>(p) = Attempt{};  // (the one reset of what belongs to a pass: world.h)
     p.spec = p.can_speculate && p.attempt == 0;
-    chain_pending = false;
-    ref_on_cur = false;
-    p.defer_lists = p.can_redo && !defer_off && p.attempt == 0 && lists_checked;
+    p.defer_lists = p.can_redo && !sw.defer_off && p.attempt == 0 && lists_checked;
     if (p.attempt > 0) SALVA_HIP_CHECK(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), stream));  // (whatever the discarded pass flagged)
     p.have_grid = p.adopted && p.attempt == 0;
     // (a scene known to hold different masses — two fluids of different density0 — is not asked again until the host edits the
     // particles: every wave of the lighter fluid would raise a flag, 71 us per launch at 2 x 10^6 particles)
-    check_mass = p.have_grid ? pre.check_mass : !(mass_known && mass_uniform == 0.0f);
+    p.check_mass = p.have_grid ? pre.check_mass : !(mass_known && mass_uniform == 0.0f);
     const bool counting = counting_sort_for(gs.ncf, n);
     if (!p.have_grid) {
-        enqueue_grid_keys(G(), gs, counting, check_mass, nullptr);
+        enqueue_grid_keys(G(), gs, counting, p.check_mass, nullptr);
         if (p.has_dyn) {  // coupling.update_boundaries (liquid_world.rs:94-103): may push particles, cells stay
             // (host clock: the pass ends with a read-back of the emitted count, so the stream is drained when it returns)
             if (p.timers) wait_stream();
@@ -1352,8 +1323,8 @@ bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g
             // A fold that piles the fluid onto itself is found out behind this point (size_pass: FoldRetry), and the substep then runs
             // again from the top: the push-outs are not repeatable (a pushed particle projects a few ulps aside the second time, and
             // its cell is no longer the one it was inserted under), so the particles are kept as they were until that is decided.
-            dcs_undo = n != 0 && gf.folded() && !fold_locked;
-            if (dcs_undo) {
+            p.dcs_undo = n != 0 && gf.folded() && !fold_locked;
+            if (p.dcs_undo) {
                 dcs_undo_pos.ensure(n, stream, false, 1.1f); dcs_undo_vel.ensure(n, stream, false, 1.1f);
                 SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_pos.p, posm[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
                 SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_vel.p, vel[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
@@ -1366,39 +1337,37 @@ bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g
     build_boundary_grid();  // insert_boundaries_to_grid (liquid_world.rs:106) + boundary volumes, only when dirty
     if (p.timers) SALVA_HIP_CHECK(hipEventRecord(evc[1], stream));
 
-    nlaunch = 0;  // not known yet
-    spec_mode = false; halo_cap = bhalo_cap = 0xffffffffu; nslices_cap = 0xffffffffu; halo_len = bhalo_len = ~0ull;
-    p.c = make_ctx();
+    p.c = make_ctx();  // (nlaunch is not known yet)
     p.scan_tb = tile_scan_temp(gs);
     if (p.spec) p.spec = predict_totals(gs, p.tt);
     uint32_t seq_totals = pre.seq;  // (an adopted grid published its totals already)
     if (!p.have_grid) seq_totals = enqueue_grid_tiles(G(), gs, p.c, p.scan_tb, nullptr, !p.spec);
-    size_pass(p, seq_totals);
-    build_lists(p);
+    size_pass(seq_totals);
+    build_lists();
     if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[1], stream));
 
     density_and_solve(p.c, dt, g, st, p.timers);
     if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[2], stream));
-    publish_end_of_step(p, snap);
+    publish_end_of_step(snap);
     if (comm && prm.enable_timers) dist_time_fold();  // (the stream has drained up to the publication: every pair has completed)
 
     const uint32_t need_ff = (h_rb->max_cnt_ff + 1) / 2, need_fb = (h_rb->max_cnt_fb + 1) / 2;  // (where the publication carried them)
     bool miss = false;
     if (p.defer_lists && !p.spec) {
         // (flag 16: a tile kept more halo slots than the launches of this pass were cut for — k_nbr_tile's REF part)
-        const bool ref_miss = ref_bounded && (h_rb->flags & 16u) != 0u;
-        if (ref_miss) { ref_pred_valid = false; ++ref_misses; }
-        if (ref_on_cur && tile_trace)
+        const bool ref_miss = p.ref_bounded && (h_rb->flags & 16u) != 0u;
+        if (ref_miss) { ref_pred_valid = false; ++tally.ref_misses; }
+        if (p.ref_on_cur && sw.tile_trace)
             fprintf(stderr, "salva_hip halo: full max_s %u max_raw %u | referenced max_s %u max_raw %u max_sum %u | staged bound %u (%s)%s\n",
                     lds_full.max_halo_fluid, lds_full.max_raw, h_rb->max_ref[0], h_rb->max_ref[1], h_rb->max_ref[2], lds.max_halo_fluid,
-                    ref_bounded ? "previous step + margin" : "full box", ref_miss ? " MISS: pass repeated" : "");
+                    p.ref_bounded ? "previous step + margin" : "full box", ref_miss ? " MISS: pass repeated" : "");
         miss = need_ff > cap_ff || need_fb > cap_fb || ref_miss;  // a list was cut at the capacity, or a kept halo at its bound
     }
     if (p.spec) {
         const TileAcc& a = h_rb->tile_total;
         miss = !(a.nonempty <= p.tt.nonempty && a.max_s <= p.tt.max_s && a.max_sb <= p.tt.max_sb && a.nsl <= p.tt.nsl &&
                  (halo_stride || (a.s <= p.tt.s && a.sb <= p.tt.sb)) && need_ff <= cap_ff && need_fb <= cap_fb);
-        if (miss) ++spec_misses;  // the prediction did not hold
+        if (miss) ++tally.spec_misses;  // the prediction did not hold
         ++counters.speculative_passes;
     }
     if (miss) {
@@ -1407,16 +1376,17 @@ bool World::run_pass(Pass& p, const PassSnapshot& snap, float& dt, const float g
         grow_list_caps(need_ff, need_fb);
         return false;
     }
-    if (chain_pending) adopt_chain_outcome(p.c, dt, g, st, p.timers);
+    if (p.chain_pending) adopt_chain_outcome(p.c, dt, g, st, p.timers);
     pred_tt = h_rb->tile_total; pred_n = n; pred_valid = true;
-    if (ref_on_cur) { memcpy(ref_pred, h_rb->max_ref, sizeof(ref_pred)); ref_pred_n = n; ref_pred_valid = true; }
+    if (p.ref_on_cur) { memcpy(ref_pred, h_rb->max_ref, sizeof(ref_pred)); ref_pred_n = n; ref_pred_valid = true; }
     else ref_pred_valid = false;
     lists_checked = true;  // (every path to here has compared the longest lists with the capacity)
     return true;
 }
 
 // ------------------------------------------------------------------------------------------------ substep: its tails
-void World::record_timers(const Pass& p, SalvaHipStepStats& st) {
+void World::record_timers(SalvaHipStepStats& st) {
+    const Pass& p = pass;
     // ev[2] was recorded before the end-of-step publication, whose arrival the host has seen through host-mapped memory — which
     // says nothing about the EVENT's completion signal: without the synchronisation hipEventElapsedTime can still answer
     // hipErrorNotReady (it did, on a fresh box: VERDICT r04).  Every other event of the step precedes ev[2] on the stream.
@@ -1465,7 +1435,8 @@ void World::raise_step_flags() {
 }
 
 // the committed pass becomes the world's state: reaction forces, statistics, counters, then the step's flags
-int World::finish_substep(const Pass& p, float dt, SalvaHipStepStats& st) {
+int World::finish_substep(float dt, SalvaHipStepStats& st) {
+    const Pass& p = pass;
     commit_elastic();
     // the reaction forces of this substep, summed in fixed point: into boundary.forces, and back to zero
     if (any_wants_forces && nb) k_bforce_fold<<<nblk(nb), BLOCK, 0, stream>>>(nb, bforce_fx.p, bforce.p, 1.0f / bforce_scale());
@@ -1476,7 +1447,7 @@ int World::finish_substep(const Pass& p, float dt, SalvaHipStepStats& st) {
                         : h_rb->ncontacts_ff + (nb ? h_rb->ncontacts_fb : 0) + ncontacts_bb;
     bbox_known = true;
     last_ctx = p.c; last_ctx.ctl = nullptr; last_dt = dt; have_last_ctx = true;  // (dt: the substep the solver advanced by)
-    if (p.timers) record_timers(p, st);
+    if (p.timers) record_timers(st);
     counters.cd.ncontacts = st.ncontacts;
     counters.n_divergence_iters = st.n_divergence_iters; counters.n_pressure_iters = st.n_pressure_iters;
     st.reserved[0] = (float)lds_full.max_halo_fluid;  // (the full box's count, whatever the solver kernels staged: SALVA_HIP_TILE_TRACE prints both)
@@ -1491,7 +1462,8 @@ int World::finish_substep(const Pass& p, float dt, SalvaHipStepStats& st) {
 // One substep: the body of the `while` of LiquidWorld::step_with_coupling (liquid_world.rs:85-147).  `dt` comes in as the step's
 // total length and goes out as the substep the solver advanced by.
 int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
-    Pass p;
+    pass = Pass{};  // (the one reset of what belongs to a substep: world.h)
+    Pass& p = pass;
     p.timers = prm.enable_timers != 0;
     if (p.timers) SALVA_HIP_CHECK(hipEventRecord(ev[0], stream));
     // (what decides below whether the grid part the previous step enqueued for this one still describes the world)
@@ -1507,8 +1479,8 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     if (pre.valid) {
         pre.valid = false;
         p.adopted = h_rb->pre_ok && !world_touched && !p.timers && !comm && pre.n == n && pre.ncf == p.gs.ncf && pre.ntiles == p.gs.ntiles &&
-                    pre.nslots_bound == p.gs.nslots_bound && pre.split_s == split_s_cur && memcmp(&pre.gf, &gf, sizeof(GridDims)) == 0;
-        if (p.adopted) { gsel ^= 1; ++pre_adopted; ++counters.pregrid_adopted; }
+                    pre.nslots_bound == p.gs.nslots_bound && pre.split_s == p.split_s_cur && memcmp(&pre.gf, &gf, sizeof(GridDims)) == 0;
+        if (p.adopted) { gsel ^= 1; ++tally.pre_adopted; ++counters.pregrid_adopted; }
         else pre_drop();
     }
     ensure_slot_tables(p.gs.nslots_bound);
@@ -1526,7 +1498,7 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     p.can_redo = (!comm || solo) && !any_wants_forces && !has_force(SALVA_HIP_FORCE_CUSTOM) && !p.has_dyn;
     // (mass_known: the kernels of a pass are chosen by StepCtx::mass_uniform, which a speculative pass — it does not wait for the
     // publication that carries it — can only inherit; a host edit since the last publication may have changed the masses)
-    p.can_speculate = !spec_off && p.can_redo && !b_dirty && pred_valid && pred_n == n && mass_known;
+    p.can_speculate = !sw.spec_off && p.can_redo && !b_dirty && pred_valid && pred_n == n && mass_known;
     // The neighbour-list capacity check (longest list <= ELL capacity) costs a read-back with an idle GPU in the middle of the
     // step although it fails about once per run (the capacity follows the longest list seen so far): where the pass can be
     // repeated (Pass::defer_lists), check at the end of the step with the read-back that happens there anyway, and repeat on
@@ -1534,21 +1506,19 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     // (`lists_checked`, cleared by every edit of the fluids or boundaries): the first step of a scene — whose lists are longer
     // than the initial capacity in almost any dense scene — is then not computed twice.
     const PassSnapshot snap(*this);  // what a discarded pass puts back
-    dcs_undo = false;
     try {
-        for (p.attempt = 0; !run_pass(p, snap, dt, g, st); ++p.attempt) {}
+        for (p.attempt = 0; !run_pass(snap, dt, g, st); ++p.attempt) {}
     } catch (const FoldRetry&) {
-        if (dcs_undo) {  // (run_pass: DynamicContactSampling had pushed particles already; back to the pre-sort buffers as the substep found them)
+        if (p.dcs_undo) {  // (run_pass: DynamicContactSampling had pushed particles already; back to the pre-sort buffers as the substep found them)
             // (size_pass throws behind reorder_working_set, which has flipped `cur` to the sorted copy of the PUSHED particles: the
             // snapshot's `cur` is the buffer the kept copies belong to, in their order)
             snap.restore(*this);
             SALVA_HIP_CHECK(hipMemcpyAsync(posm[cur].p, dcs_undo_pos.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
             SALVA_HIP_CHECK(hipMemcpyAsync(vel[cur].p, dcs_undo_vel.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-            dcs_undo = false;
         }
         throw;
     }
-    return finish_substep(p, dt, st);
+    return finish_substep(dt, st);
 }
 
 }  // namespace salva
