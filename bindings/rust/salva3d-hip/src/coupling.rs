@@ -21,6 +21,10 @@ pub enum ColliderSampling {
     /// device; every other parry shape through `salva_hip_set_boundary_dynamic_sampling_host`: the loop on the device, the
     /// shape's `compute_aabb` / `project_point_and_get_feature` called back here once per step).
     DynamicContactSampling,
+    /// The same for a collider whose shape is a triangle mesh or height field that lives on the device
+    /// (`crate::sampling::Mesh::id`, `salva_hip_set_boundary_dynamic_sampling_mesh`): the projection runs there as well, no
+    /// callback.  The collider's pose places the mesh.
+    DynamicContactSamplingMesh(u32),
 }
 
 /// What the host-shape callbacks see: the collider's shape and its pose as of this step's `update_boundaries`.
@@ -240,6 +244,9 @@ impl FluidsPipeline {
                     ColliderSampling::StaticSampling(points) => check(unsafe {
                         ffi::salva_hip_set_boundary_sampling(raw, slot, points.len() as u64, points.as_ptr() as *const f32, groups.memberships.bits(), groups.filter.bits())
                     })?,
+                    ColliderSampling::DynamicContactSamplingMesh(mesh) => {
+                        check(unsafe { ffi::salva_hip_set_boundary_dynamic_sampling_mesh(raw, slot, *mesh, groups.memberships.bits(), groups.filter.bits()) })?
+                    }
                     ColliderSampling::DynamicContactSampling => {
                         let builtin = if let Some(b) = collider.shape().as_ball() {
                             Some(ffi::SalvaHipShape { kind: ffi::SALVA_HIP_SHAPE_BALL, params: [b.radius, 0.0, 0.0] })

@@ -82,3 +82,65 @@ pub fn shape_surface_ray_sample<S: Shape>(world: &mut LiquidWorld, shape: &S, pa
 pub fn shape_volume_ray_sample<S: Shape>(world: &mut LiquidWorld, shape: &S, particle_rad: Real) -> Option<Vec<Point<Real>>> {
     sample(world, shape, particle_rad, ffi::SALVA_HIP_SAMPLE_VOLUME).ok()
 }
+
+/// A triangle mesh (parry `TriMesh`) or height field (parry `HeightField`) on the device (`salva_hip_create_mesh` /
+/// `salva_hip_create_heightfield`).  Belongs to the world it was created in; `destroy` hands it back (refused while a
+/// dynamically sampled boundary still uses it), and the world's end releases whatever is left.
+pub struct Mesh {
+    id: u32,
+}
+
+impl Mesh {
+    /// `oriented`: the mesh is closed and wound counter-clockwise seen from outside (only such a mesh has an inside).
+    pub fn new(world: &mut LiquidWorld, vertices: &[Point<Real>], indices: &[[u32; 3]], oriented: bool) -> Result<Mesh, Error> {
+        let mut id = 0u32;
+        let flags = if oriented { ffi::SALVA_HIP_MESH_ORIENTED as u32 } else { 0 };
+        check(unsafe {
+            ffi::salva_hip_create_mesh(world.raw(), vertices.as_ptr() as *const f32, vertices.len() as u32, indices.as_ptr() as *const u32, indices.len() as u32, flags, &mut id)
+        })?;
+        Ok(Mesh { id })
+    }
+
+    /// `HeightField::new(heights, scale)`: `heights` row-major, rows along z.
+    pub fn heightfield(world: &mut LiquidWorld, heights: &[Real], nrows: u32, ncols: u32, scale: Vector<Real>) -> Result<Mesh, Error> {
+        assert_eq!(heights.len(), nrows as usize * ncols as usize);
+        let mut id = 0u32;
+        let s = [scale.x, scale.y, scale.z];
+        check(unsafe { ffi::salva_hip_create_heightfield(world.raw(), heights.as_ptr(), nrows, ncols, s.as_ptr(), &mut id) })?;
+        Ok(Mesh { id })
+    }
+
+    pub fn id(&self) -> u32 {
+        self.id
+    }
+
+    pub fn destroy(self, world: &mut LiquidWorld) -> Result<(), Error> {
+        check(unsafe { ffi::salva_hip_destroy_mesh(world.raw(), self.id) })
+    }
+}
+
+fn sample_mesh(world: &mut LiquidWorld, mesh: &Mesh, particle_rad: Real, mode: i32) -> Result<Vec<Point<Real>>, Error> {
+    let raw = world.raw();
+    let n = unsafe { ffi::salva_hip_sample_mesh(raw, mesh.id, particle_rad, mode, 0, std::ptr::null_mut()) };
+    if n < 0 {
+        check(n as i32)?;
+    }
+    let mut pts = vec![Point::<Real>::origin(); n as usize];
+    if n > 0 {
+        let m = unsafe { ffi::salva_hip_sample_mesh(raw, mesh.id, particle_rad, mode, n as u64, pts.as_mut_ptr() as *mut f32) };
+        if m < 0 {
+            check(m as i32)?;
+        }
+    }
+    Ok(pts)
+}
+
+/// `shape_surface_ray_sample` for a mesh on the device: one thread per ray, no host casts.
+pub fn mesh_surface_ray_sample(world: &mut LiquidWorld, mesh: &Mesh, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+    sample_mesh(world, mesh, particle_rad, ffi::SALVA_HIP_SAMPLE_SURFACE).ok()
+}
+
+/// `shape_volume_ray_sample` for a mesh on the device.
+pub fn mesh_volume_ray_sample(world: &mut LiquidWorld, mesh: &Mesh, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+    sample_mesh(world, mesh, particle_rad, ffi::SALVA_HIP_SAMPLE_VOLUME).ok()
+}

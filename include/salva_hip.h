@@ -446,6 +446,7 @@ enum {
     SALVA_HIP_SHAPE_CUBOID = 2,    /* params = half extents */
     SALVA_HIP_SHAPE_CAPSULE = 3,   /* parry Capsule::new_y: params[0] = half height of the segment along the local y axis, params[1] = radius */
     SALVA_HIP_SHAPE_CYLINDER = 4,  /* parry Cylinder (axis = local y): params[0] = half height, params[1] = radius */
+    SALVA_HIP_SHAPE_MESH = 5,      /* a triangle mesh or height field of this world (salva_hip_create_mesh below); never passed in a SalvaHipShape */
     SALVA_HIP_SHAPE_HOST = 100     /* any other shape: its geometry stays with the host (SalvaHipHostShape below); never passed in a SalvaHipShape */
 };
 typedef struct SalvaHipShape {
@@ -655,6 +656,39 @@ int64_t salva_hip_add_particles_sampled(SalvaHipWorld* world, uint32_t slot, con
  * error).  In a running decomposed world: SALVA_HIP_E_INVALID, as above. */
 int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, uint32_t memberships,
                                                    uint32_t filter);
+
+/* ---- Triangle meshes and height fields on the device: what the reference's examples hand to the sampler and register
+ * as colliders when the collider is not a primitive (examples3d/heightfield3.rs).  A mesh belongs to the world that created it and
+ * lives until salva_hip_destroy_mesh or the world's end; `*mesh_out` is its handle.  Vertices are packed xyz, `indices` holds three
+ * vertex indices per triangle.  SALVA_HIP_MESH_ORIENTED states that the mesh is closed and wound consistently (counter-clockwise
+ * seen from outside): such a mesh gets pseudo-normals and tells inside from outside; any other mesh is a surface with no inside.
+ * SALVA_HIP_E_INVALID: an index >= nv, nt == 0, a non-finite vertex, nrows < 2 or ncols < 2, destroying a mesh that is still the
+ * collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it).
+ * A height field is parry 0.18's HeightField as triangles: vertex (i, j) = ((j / (ncols - 1) - 0.5) sx, heights[i][j] sy,
+ * (i / (nrows - 1) - 0.5) sz), two triangles per cell, (p00, p10, p11) and (p00, p11, p01) with pab the corner in row i + a, column
+ * j + b; never oriented. */
+enum { SALVA_HIP_MESH_ORIENTED = 1 };
+int salva_hip_create_mesh(SalvaHipWorld* world, const float* vertices_xyz, uint32_t nv, const uint32_t* indices, uint32_t nt,
+                          uint32_t flags, uint32_t* mesh_out);
+int salva_hip_create_heightfield(SalvaHipWorld* world, const float* heights, uint32_t nrows, uint32_t ncols, const float scale[3],
+                                 uint32_t* mesh_out);
+int salva_hip_destroy_mesh(SalvaHipWorld* world, uint32_t mesh);
+/* salva_hip_sample_shape, salva_hip_add_particles_sampled and salva_hip_set_boundary_sampling_from_shape with a mesh in place of the
+ * shape: one thread per ray casts against the triangles in closed form (f32; edges and vertices belong to both neighbours, a hit
+ * shared by two triangles counts once), entry and exit alternating along the ray, so concave meshes and open surfaces are sampled as
+ * the reference's loop samples them.  A ray with more than 64 accepted hits ends the call with SALVA_HIP_E_CAPACITY.  The last two
+ * are refused in a running decomposed world, like their shape twins. */
+int64_t salva_hip_sample_mesh(SalvaHipWorld* world, uint32_t mesh, float particle_rad, int32_t mode, uint64_t capacity, float* out_xyz);
+int64_t salva_hip_add_particles_sampled_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, const float translation[3],
+                                             const float rotation_ijkw[4], int32_t mode, const float velocity[3]);
+int64_t salva_hip_set_boundary_sampling_from_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
+                                                  uint32_t filter);
+/* salva_hip_set_boundary_dynamic_sampling for a mesh collider, entirely on the device: the host arm's pass with the projection —
+ * the closest point over all triangles, ties to the lowest triangle index — done by one thread per candidate.  The pose given to
+ * salva_hip_update_boundary_pose places the mesh.  is_inside is false for a mesh without SALVA_HIP_MESH_ORIENTED (parry's answer for
+ * a height field): such a collider samples contacts and pushes nothing out.  Not available in a running decomposed world. */
+int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
+                                                 uint32_t filter);
 
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);

@@ -202,6 +202,34 @@ class Fluid {  // object/fluid.rs
     bool structural_ = true;        // the whole fluid must be (re)uploaded: new fluid, or edits that the device cannot replay
 };
 
+// A triangle mesh (parry TriMesh) or height field (parry HeightField) on the device (salva_hip_create_mesh /
+// salva_hip_create_heightfield): RAII over the handle.  Accepted where a SalvaHipShape is — the ray samplers,
+// LiquidWorld::add_particles_from_shape, Boundary::sampled_from_mesh, Boundary::dynamic_mesh.  Belongs to the world it was created in
+// and must be destroyed before it; a mesh that is still the collider of a dynamically sampled boundary stays alive in the library
+// until that boundary lets go of it.
+class Mesh {
+  public:
+    // `oriented`: closed and wound counter-clockwise seen from outside — only such a mesh has an inside to push particles out of
+    Mesh(LiquidWorld& world, const std::vector<Vec3>& vertices, const std::vector<std::array<uint32_t, 3>>& triangles, bool oriented = false);
+    // heights[i * ncols + j] over a grid of scale[0] x scale[2] centred at the origin, rows along z, columns along x
+    static Mesh heightfield(LiquidWorld& world, const std::vector<Real>& heights, uint32_t nrows, uint32_t ncols, const Vec3& scale);
+    Mesh(Mesh&& o) noexcept : w_(o.w_), id_(o.id_) { o.w_ = nullptr; }
+    Mesh& operator=(Mesh&& o) noexcept {
+        if (this != &o) { release(); w_ = o.w_; id_ = o.id_; o.w_ = nullptr; }
+        return *this;
+    }
+    Mesh(const Mesh&) = delete;
+    Mesh& operator=(const Mesh&) = delete;
+    ~Mesh() { release(); }
+    uint32_t id() const { return id_; }
+
+  private:
+    Mesh() = default;
+    void release() { if (w_) (void)salva_hip_destroy_mesh(w_, id_); w_ = nullptr; }
+    SalvaHipWorld* w_ = nullptr;
+    uint32_t id_ = 0;
+};
+
 class Boundary {  // object/boundary.rs
   public:
     std::vector<Vec3> positions, velocities;
@@ -253,9 +281,24 @@ class Boundary {  // object/boundary.rs
         b.dynamic_host = shape;
         return b;
     }
+    // ... and for a triangle mesh or height field of the world, with the projection on the device as well
+    // (salva_hip_set_boundary_dynamic_sampling_mesh)
+    uint32_t mesh_id = 0;  // with dynamic_shape.kind / sampled_shape.kind == SALVA_HIP_SHAPE_MESH
+    static Boundary dynamic_mesh(const Mesh& mesh, InteractionGroups groups = {}) {
+        Boundary b({}, groups);
+        b.dynamic_shape = SalvaHipShape{SALVA_HIP_SHAPE_MESH, {0, 0, 0}};
+        b.mesh_id = mesh.id();
+        return b;
+    }
     // ColliderSampling::StaticSampling(shape_surface_ray_sample(shape, particle_radius)) with the points produced and kept on the
-    // device (salva_hip_set_boundary_sampling_from_shape): afterwards a StaticSampling boundary like any other
+    // device (salva_hip_set_boundary_sampling_from_shape / _from_mesh): afterwards a StaticSampling boundary like any other
     SalvaHipShape sampled_shape{0, {0, 0, 0}};
+    static Boundary sampled_from_mesh(const Mesh& mesh, InteractionGroups groups = {}) {
+        Boundary b({}, groups);
+        b.sampled_shape = SalvaHipShape{SALVA_HIP_SHAPE_MESH, {0, 0, 0}};
+        b.mesh_id = mesh.id();
+        return b;
+    }
     static Boundary sampled_from_shape(const SalvaHipShape& shape, InteractionGroups groups = {}) {
         Boundary b({}, groups);
         b.sampled_shape = shape;
@@ -673,6 +716,23 @@ class LiquidWorld {  // liquid_world.rs
         if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
         return (size_t)k;
     }
+    size_t add_particles_from_shape(FluidHandle h, const Mesh& mesh, const Vec3& translation,
+                                    const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1}, int mode = SALVA_HIP_SAMPLE_VOLUME,
+                                    const Vec3* velocity = nullptr) {
+        upload_new_objects();
+        Fluid& f = fluids_[h];
+        upload(f, (uint32_t)h);
+        const int64_t k = salva_hip_add_particles_sampled_mesh(w_, (uint32_t)h, mesh.id(), translation.data(), rotation_ijkw.data(), mode,
+                                                               velocity ? velocity->data() : nullptr);
+        if (k < 0) check((int)k);
+        const size_t n = f.positions.size() + (size_t)k;
+        f.positions.resize(n); f.velocities.resize(n);
+        f.accelerations.resize(n, Vec3{0, 0, 0});
+        f.volumes.resize(n, f.default_particle_volume());
+        f.deleted_.resize(n, false);
+        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        return (size_t)k;
+    }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));
     }
@@ -801,6 +861,11 @@ class LiquidWorld {  // liquid_world.rs
             b.dirty_ = false;
             return;
         }
+        if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_MESH) {
+            check(salva_hip_set_boundary_dynamic_sampling_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter));
+            b.dirty_ = false;
+            return;
+        }
         if (b.dynamic_shape.kind) {
             check(salva_hip_set_boundary_dynamic_sampling(w_, slot, &b.dynamic_shape, b.interaction_groups.memberships,
                                                           b.interaction_groups.filter));
@@ -808,8 +873,10 @@ class LiquidWorld {  // liquid_world.rs
             return;
         }
         if (b.sampled_shape.kind) {
-            const int64_t k = salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, b.interaction_groups.memberships,
-                                                                         b.interaction_groups.filter);
+            const int64_t k = b.sampled_shape.kind == SALVA_HIP_SHAPE_MESH
+                                  ? salva_hip_set_boundary_sampling_from_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter)
+                                  : salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, b.interaction_groups.memberships,
+                                                                               b.interaction_groups.filter);
             if (k < 0) check((int)k);
             b.sampled_n_ = (size_t)k;
             b.dirty_ = false;
@@ -906,6 +973,36 @@ inline std::vector<Vec3> shape_surface_ray_sample(LiquidWorld& world, const Salv
 inline std::vector<Vec3> shape_volume_ray_sample(LiquidWorld& world, const SalvaHipShape& shape, Real particle_rad) {
     return ray_sample(world, shape, particle_rad, SALVA_HIP_SAMPLE_VOLUME);
 }
+inline std::vector<Vec3> ray_sample(LiquidWorld& world, const Mesh& mesh, Real particle_rad, int mode) {
+    const int64_t n = salva_hip_sample_mesh(world.handle(), mesh.id(), particle_rad, mode, 0, nullptr);
+    if (n < 0) check((int)n);
+    std::vector<Vec3> pts((size_t)n);
+    if (n) {
+        const int64_t m = salva_hip_sample_mesh(world.handle(), mesh.id(), particle_rad, mode, (uint64_t)n, pts[0].data());
+        if (m < 0) check((int)m);
+    }
+    return pts;
+}
+inline std::vector<Vec3> shape_surface_ray_sample(LiquidWorld& world, const Mesh& mesh, Real particle_rad) {
+    return ray_sample(world, mesh, particle_rad, SALVA_HIP_SAMPLE_SURFACE);
+}
+inline std::vector<Vec3> shape_volume_ray_sample(LiquidWorld& world, const Mesh& mesh, Real particle_rad) {
+    return ray_sample(world, mesh, particle_rad, SALVA_HIP_SAMPLE_VOLUME);
+}
 }  // namespace sampling
+
+inline Mesh::Mesh(LiquidWorld& world, const std::vector<Vec3>& vertices, const std::vector<std::array<uint32_t, 3>>& triangles, bool oriented) {
+    check(salva_hip_create_mesh(world.handle(), vertices.empty() ? nullptr : vertices[0].data(), (uint32_t)vertices.size(),
+                                triangles.empty() ? nullptr : triangles[0].data(), (uint32_t)triangles.size(),
+                                oriented ? (uint32_t)SALVA_HIP_MESH_ORIENTED : 0u, &id_));
+    w_ = world.handle();
+}
+inline Mesh Mesh::heightfield(LiquidWorld& world, const std::vector<Real>& heights, uint32_t nrows, uint32_t ncols, const Vec3& scale) {
+    if (heights.size() != (size_t)nrows * ncols) throw std::invalid_argument("Mesh::heightfield: heights must hold nrows x ncols values");
+    Mesh m;
+    check(salva_hip_create_heightfield(world.handle(), heights.data(), nrows, ncols, scale.data(), &m.id_));
+    m.w_ = world.handle();
+    return m;
+}
 
 }  // namespace salva

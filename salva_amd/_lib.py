@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     "salva_hip_get_dist_timing", "salva_hip_local_len", "salva_hip_get_local", "salva_hip_get_local_contacts", "salva_hip_force_add_local_accelerations",
     "salva_hip_get_elasticity_state", "salva_hip_set_elasticity_state", "salva_hip_get_elasticity_contacts",
     "salva_hip_sample_shape", "salva_hip_sample_host_shape", "salva_hip_add_particles_sampled", "salva_hip_set_boundary_sampling_from_shape",
+    "salva_hip_create_mesh", "salva_hip_create_heightfield", "salva_hip_destroy_mesh", "salva_hip_sample_mesh",
+    "salva_hip_add_particles_sampled_mesh", "salva_hip_set_boundary_sampling_from_mesh", "salva_hip_set_boundary_dynamic_sampling_mesh",
 ]
 
 
@@ -143,6 +145,7 @@ class HostQueryShape(C.Structure):
 
 HOST_CAST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float))
 SAMPLE_SURFACE, SAMPLE_VOLUME = 0, 1
+MESH_ORIENTED = 1
 
 
 class HostRayShape(C.Structure):
@@ -300,6 +303,18 @@ def lib():
         L.salva_hip_add_particles_sampled.restype = C.c_int64
         L.salva_hip_set_boundary_sampling_from_shape.argtypes = [vp, u32, C.POINTER(Shape), u32, u32]
         L.salva_hip_set_boundary_sampling_from_shape.restype = C.c_int64
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_create_mesh"):
+        up = C.POINTER(u32)
+        L.salva_hip_create_mesh.argtypes = [vp, fp, u32, up, u32, u32, up]
+        L.salva_hip_create_heightfield.argtypes = [vp, fp, u32, u32, fp, up]
+        L.salva_hip_destroy_mesh.argtypes = [vp, u32]
+        L.salva_hip_sample_mesh.argtypes = [vp, u32, f32, i32, u64, fp]
+        L.salva_hip_sample_mesh.restype = C.c_int64
+        L.salva_hip_add_particles_sampled_mesh.argtypes = [vp, u32, u32, fp, fp, i32, fp]
+        L.salva_hip_add_particles_sampled_mesh.restype = C.c_int64
+        L.salva_hip_set_boundary_sampling_from_mesh.argtypes = [vp, u32, u32, u32, u32]
+        L.salva_hip_set_boundary_sampling_from_mesh.restype = C.c_int64
+        L.salva_hip_set_boundary_dynamic_sampling_mesh.argtypes = [vp, u32, u32, u32, u32]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

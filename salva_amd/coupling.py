@@ -101,9 +101,12 @@ class StaticSampling:
     @classmethod
     def from_shape(cls, shape) -> "StaticSampling":
         """`StaticSampling(shape_surface_ray_sample(shape, particle_radius))` with the points produced and kept on the device
-        (salva_hip_set_boundary_sampling_from_shape); `shape` is what make_shape takes."""
+        (salva_hip_set_boundary_sampling_from_shape); `shape` is what make_shape takes, or a
+        sampling.Mesh (salva_hip_set_boundary_sampling_from_mesh)."""
+        from .sampling import Mesh
+
         self = cls(np.zeros((0, 3), F32))
-        self.shape = shape if isinstance(shape, L.Shape) else make_shape(shape)
+        self.shape = shape if isinstance(shape, (L.Shape, Mesh)) else make_shape(shape)
         return self
 
 
@@ -128,10 +131,14 @@ class DynamicContactSampling:
     """ColliderSampling::DynamicContactSampling (fluids_pipeline.rs:42-43) for a collider of shape ("ball", radius),
     ("cuboid", (hx, hy, hz)), ("capsule", half_height, radius) (parry Capsule::new_y) or ("cylinder", half_height, radius) (axis = local
     y): the boundary's particles are the projections of the nearby fluid particles onto the collider, recomputed inside every step
-    on the device (salva_hip_set_boundary_dynamic_sampling)."""
+    on the device (salva_hip_set_boundary_dynamic_sampling).  A sampling.Mesh — triangle mesh or height field — is projected onto on
+    the device as well (salva_hip_set_boundary_dynamic_sampling_mesh); only an oriented mesh pushes particles out."""
 
     def __init__(self, shape):
-        self.shape = make_shape(shape)
+        from .sampling import Mesh
+
+        self.mesh = shape if isinstance(shape, Mesh) else None
+        self.shape = None if self.mesh is not None else make_shape(shape)
 
 
 class HostShapeSampling:
@@ -246,14 +253,22 @@ class ColliderCouplingSet:
                 e.uploaded = True
             if not e.uploaded and isinstance(e.sampling, DynamicContactSampling):
                 b._sampled = b._dynamic = True
-                L.check(world._L.salva_hip_set_boundary_dynamic_sampling(
-                    world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                if e.sampling.mesh is not None:
+                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling_mesh(
+                        world._h, b._slot, e.sampling.mesh.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
+                else:
+                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling(
+                        world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
                 b._dirty = False
                 e.uploaded = True
             if not e.uploaded and getattr(e.sampling, "shape", None) is not None and isinstance(e.sampling, StaticSampling):
                 b._sampled = True
-                k = int(world._L.salva_hip_set_boundary_sampling_from_shape(
-                    world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                if isinstance(e.sampling.shape, L.Shape):
+                    k = int(world._L.salva_hip_set_boundary_sampling_from_shape(
+                        world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                else:
+                    k = int(world._L.salva_hip_set_boundary_sampling_from_mesh(
+                        world._h, b._slot, e.sampling.shape.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
                 if k < 0:
                     L.check(k)
                 b._n_sampled = k

@@ -775,6 +775,81 @@ int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_
     return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
+int salva_hip_create_mesh(SalvaHipWorld* world, const float* vertices_xyz, uint32_t nv, const uint32_t* indices, uint32_t nt,
+                          uint32_t flags, uint32_t* mesh_out) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !mesh_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        *mesh_out = world->w->create_mesh(vertices_xyz, nv, indices, nt, flags);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_create_heightfield(SalvaHipWorld* world, const float* heights, uint32_t nrows, uint32_t ncols, const float scale[3],
+                                 uint32_t* mesh_out) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !mesh_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        *mesh_out = world->w->create_heightfield(heights, nrows, ncols, scale);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_destroy_mesh(SalvaHipWorld* world, uint32_t mesh) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        world->w->destroy_mesh(mesh);
+        return SALVA_HIP_OK;
+    });
+}
+
+int64_t salva_hip_sample_mesh(SalvaHipWorld* world, uint32_t mesh, float particle_rad, int32_t mode, uint64_t capacity,
+                              float* out_xyz) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        r = world->w->sample_mesh(mesh, particle_rad, mode, capacity, out_xyz);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int64_t salva_hip_add_particles_sampled_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, const float translation[3],
+                                             const float rotation_ijkw[4], int32_t mode, const float velocity[3]) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        r = world->w->add_particles_sampled_mesh(slot, mesh, translation, rotation_ijkw, mode, velocity);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int64_t salva_hip_set_boundary_sampling_from_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
+                                                  uint32_t filter) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        r = world->w->set_boundary_sampling_from_mesh(slot, mesh, memberships, filter);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
+                                                 uint32_t filter) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        world->w->set_boundary_dynamic_sampling_mesh(slot, mesh, memberships, filter);
+        return SALVA_HIP_OK;
+    });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

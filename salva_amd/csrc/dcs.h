@@ -35,6 +35,11 @@ void launch_dcs_gather(uint32_t n, const float4* posm, const float4* vel, const 
                        uint8_t* flag, hipStream_t st);
 void launch_dcs_apply(uint32_t cnt, const float4* pred, const float4* proj, float4* posm, float4* vel, const uint32_t* perm,
                       const uint32_t* gtag, const DcsParams& s, float4* cand, uint8_t* flag, hipStream_t st);
+// mesh arm (salva_hip_set_boundary_dynamic_sampling_mesh): the same two kernels around a projection on the device — per compacted
+// candidate (predicted position) the closest point of the posed mesh and is_inside, in the layout launch_dcs_apply reads
+struct MeshDev;
+DcsParams dcs_params_mesh(const float mins[3], const float maxs[3], const SalvaHipRigidPose& pose, float h, float particle_radius, float dt);
+void launch_dcs_project_mesh(uint32_t cnt, const float4* pred, const MeshDev& mesh, const DcsParams& s, float4* proj, hipStream_t st);
 // decomposed run: compacted rows (point, sorted index) -> (point, global id of the source particle), fluid of the source
 void launch_dcs_pack(uint32_t cnt, const float4* rows, const uint32_t* gid, const uint32_t* model, float4* out_rows, uint32_t* out_models,
                      hipStream_t st);

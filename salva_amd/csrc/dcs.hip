@@ -28,6 +28,7 @@
 // This file is compiled with -ffp-contract=off (see Makefile): Rust never fuses a*b+c, and the emitted points feed the
 // exact d^2 <= h^2 contact test.
 #include "dcs.h"
+#include "mesh.h"
 #include "dist.h"
 #include "tile.h"
 #include <cmath>
@@ -220,6 +221,26 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_apply(uint32_t cnt, const float4*
     if (keep) cand[k] = make_float4(w.x, w.y, w.z, __uint_as_float(gtag ? i : perm[i]));
 }
 
+// The mesh arm (salva_hip_set_boundary_dynamic_sampling_mesh): the host arm's pass with the host taken out of it.  Between
+// k_dcs_gather and k_dcs_apply one thread per compacted candidate projects its predicted position onto the posed mesh —
+// m^-1 pt as in k_dcs_project, the closest point over all triangles (mesh.h), carried back by the pose — and writes what the host's
+// callback would have written: (projection, is_inside ? 1 : 0).
+__global__ __launch_bounds__(BLOCK) void k_dcs_project_mesh(uint32_t cnt, const float4* __restrict__ pred, MeshDev mesh, DcsParams s,
+                                                            float4* __restrict__ proj) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= cnt) return;
+    const float4 pr = pred[k];
+    float lx, ly, lz;
+    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], pr.x - s.t[0], pr.y - s.t[1], pr.z - s.t[2], lx, ly, lz);
+    float jx, jy, jz;
+    bool inside;
+    mesh_project_point(mesh, lx, ly, lz, jx, jy, jz, inside);
+    float wx, wy, wz;
+    quat_rot(s.q[0], s.q[1], s.q[2], s.q[3], jx, jy, jz, wx, wy, wz);
+    wx += s.t[0]; wy += s.t[1]; wz += s.t[2];
+    proj[k] = make_float4(wx, wy, wz, inside ? 1.0f : 0.0f);
+}
+
 // Decomposed run: this rank's compacted rows (point, sorted index of the source particle) -> its section of the table every
 // rank assembles (World::dist_gather_emitted): (point, global id of the source) and the source's fluid.
 __global__ __launch_bounds__(BLOCK) void k_dcs_pack(uint32_t cnt, const float4* __restrict__ rows, const uint32_t* __restrict__ gid,
@@ -322,6 +343,29 @@ DcsParams dcs_params_host(const float mins[3], const float maxs[3], float h, flo
     return s;
 }
 
+// the mesh arm: parry's Aabb::transform_by — the local box's centre posed by the collider's pose, -+ |R| half_extents (the matrix
+// form of shape_world_extent)
+DcsParams dcs_params_mesh(const float mins[3], const float maxs[3], const SalvaHipRigidPose& pose, float h, float particle_radius, float dt) {
+    const float* q = pose.rotation;
+    SalvaHipShape box{};
+    box.kind = SALVA_HIP_SHAPE_CUBOID;
+    float c[3], ext[3];
+    for (int a = 0; a < 3; ++a) { c[a] = (mins[a] + maxs[a]) * 0.5f; box.params[a] = (maxs[a] - mins[a]) * 0.5f; }
+    shape_world_extent(box, q, ext);
+    // quat_rot on the host
+    const float tx = (q[1] * c[2] - q[2] * c[1]) * 2.0f, ty = (q[2] * c[0] - q[0] * c[2]) * 2.0f, tz = (q[0] * c[1] - q[1] * c[0]) * 2.0f;
+    const float cx = q[1] * tz - q[2] * ty, cy = q[2] * tx - q[0] * tz, cz = q[0] * ty - q[1] * tx;
+    const float w[3] = {((tx * q[3] + cx) + c[0]) + pose.translation[0], ((ty * q[3] + cy) + c[1]) + pose.translation[1],
+                        ((tz * q[3] + cz) + c[2]) + pose.translation[2]};
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) { lo[a] = w[a] - ext[a]; hi[a] = w[a] + ext[a]; }
+    DcsParams s = dcs_params_host(lo, hi, h, particle_radius, dt);
+    s.kind = SALVA_HIP_SHAPE_MESH;
+    for (int a = 0; a < 3; ++a) s.t[a] = pose.translation[a];
+    for (int a = 0; a < 4; ++a) s.q[a] = pose.rotation[a];
+    return s;
+}
+
 void launch_dcs_project(uint32_t n, float4* posm, float4* vel, const uint32_t* keys, const uint32_t* perm, const uint32_t* gtag, TileGrid g,
                         const DcsParams& s, float4* cand, uint8_t* flag, hipStream_t st) {
     if (n == 0) return;
@@ -338,6 +382,11 @@ void launch_dcs_apply(uint32_t cnt, const float4* pred, const float4* proj, floa
                       const uint32_t* gtag, const DcsParams& s, float4* cand, uint8_t* flag, hipStream_t st) {
     if (cnt == 0) return;
     k_dcs_apply<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, pred, proj, posm, vel, perm, gtag, s, cand, flag);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
+void launch_dcs_project_mesh(uint32_t cnt, const float4* pred, const MeshDev& mesh, const DcsParams& s, float4* proj, hipStream_t st) {
+    if (cnt == 0) return;
+    k_dcs_project_mesh<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, pred, mesh, s, proj);
     SALVA_HIP_CHECK(hipGetLastError());
 }
 void launch_dcs_pack(uint32_t cnt, const float4* rows, const uint32_t* gid, const uint32_t* model, float4* out_rows, uint32_t* out_models,

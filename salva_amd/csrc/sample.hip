@@ -19,6 +19,7 @@
 
 #include "world.h"
 #include "dcs.h"
+#include "mesh.h"
 #include "pose.h"
 
 // (the Makefile's -ffp-contract=off already says so; the sampler's bit-for-bit specification must not depend on a build flag)
@@ -155,6 +156,57 @@ __global__ __launch_bounds__(BLOCK) void k_sample_mark(SampleGrid g, SalvaHipSha
     } else {
         if (q0 < ni) atomicOr(&bits[base + q0 * stride], bit);
         if (q1 < ni && q1 != q0) atomicOr(&bits[base + q1 * stride], bit);
+    }
+}
+
+// The same for a triangle mesh: every accepted hit is one walk of the hierarchy (mesh.h mesh_next_hit), the loop around it is the host
+// arm's (World::sample_host_shape) for one ray — toi = hit - origin, impact = origin + toi, the next origin = origin + (toi + s / 10),
+// entry and exit alternating; a 65th accepted hit raises *err.
+__device__ __forceinline__ void mark_bit(const SampleGrid& g, int axis, uint32_t qi, uint32_t qj, uint32_t qk, uint32_t* __restrict__ bits) {
+    // axis 0: (x, y, z) = (qi, qj, qk); axis 1: (z, x) = (qj, qk); axis 2: (x, y) = (qj, qk)
+    const uint32_t qx = sel3(axis, qi, qk, qj), qy = sel3(axis, qj, qi, qk), qz = sel3(axis, qk, qj, qi);
+    atomicOr(&bits[word_of(g, qx, qy, qz)], 1u << (qz & 31u));
+}
+
+__global__ __launch_bounds__(BLOCK) void k_sample_mesh_mark(SampleGrid g, MeshDev mesh, int volume, uint32_t* __restrict__ bits,
+                                                            uint32_t* __restrict__ err) {
+    uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const uint64_t r0 = (uint64_t)g.ny * g.nz, r1 = (uint64_t)g.nz * g.nx, r2 = (uint64_t)g.nx * g.ny;
+    int axis;
+    if (t < r0) axis = 0;
+    else if (t < r0 + r1) { axis = 1; t -= r0; }
+    else if (t < r0 + r1 + r2) { axis = 2; t -= r0 + r1; }
+    else return;
+    const uint32_t ni = sel3(axis, g.nx, g.ny, g.nz), nj = sel3(axis, g.ny, g.nz, g.nx), nk = sel3(axis, g.nz, g.nx, g.ny);
+    const float oi = sel3(axis, g.ox, g.oy, g.oz), oj = sel3(axis, g.oy, g.oz, g.ox), ok = sel3(axis, g.oz, g.ox, g.oy);
+    const float* lj = sel3(axis, g.cy, g.cz, g.cx);
+    const float* lk = sel3(axis, g.cz, g.cx, g.cy);
+    const uint32_t aj = (uint32_t)(t / nk), ak = (uint32_t)(t % nk);  // aj < nj: t < nj * nk
+    const float cj = lj[aj], ck = lk[ak];
+    const uint32_t qj = sat_u32(roundf((cj - oj) / g.s)), qk = sat_u32(roundf((ck - ok) / g.s));
+    if (qj >= nj || qk >= nk) return;  // (outside the lattice: never written)
+    const float step = g.s / 10.0f;
+    float o = oi, prev = 0.0f;
+    bool entry = true, has_prev = false;
+    for (int hits = 0;; ++hits) {
+        const float h = mesh_next_hit(mesh, axis, cj, ck, o);
+        if (!(h < __builtin_inff())) break;
+        if (hits == MESH_MAX_HITS) { atomicOr(err, 1u); break; }
+        const float toi = h - o, impact = o + toi;
+        if (!volume) {
+            const float f = (impact - oi) / g.s;
+            const uint32_t q = sat_u32(entry ? ceilf(f) : floorf(f));
+            if (q < ni) mark_bit(g, axis, q, qj, qk, bits);
+            entry = !entry;
+        } else if (has_prev) {
+            const uint32_t q0 = sat_u32(roundf((prev - oi) / g.s)), qe = sat_u32(roundf((impact - oi) / g.s));
+            const uint32_t q1 = qe < ni - 1u ? qe : ni - 1u;
+            for (uint32_t q = q0; q <= q1 && q < ni; ++q) mark_bit(g, axis, q, qj, qk, bits);
+            has_prev = false;
+        } else {
+            prev = impact; has_prev = true;
+        }
+        o = o + (toi + step);
     }
 }
 
@@ -389,14 +441,14 @@ static const char* const kDecomposedSampling =
 
 // Fluid::add_particles of the posed samples, one velocity for all: the positions go from the bit lattice straight into the staging
 // array.
-int64_t World::add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel_h) {
-    use_device();
+void World::check_add_sampled(uint32_t slot, const float t[3], const float q[4]) const {
     if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
     if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
     for (int a = 0; a < 4; ++a)
         if (!std::isfinite(q[a]) || (a < 3 && !std::isfinite(t[a]))) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
-    SampleLattice L;
-    sample_mark(shape, prm.particle_radius, mode, L);
+}
+
+int64_t World::append_sampled(uint32_t slot, const SampleLattice& L, const float t[3], const float q[4], const float* vel_h) {
     const uint32_t total = sample_count(L);
     if (!total) return 0;
     const uint64_t at = append_particles(slot, total);
@@ -414,13 +466,16 @@ int64_t World::add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, 
     return total;
 }
 
-// salva_hip_set_boundary_sampling with the surface samples at the world's particle radius as the local points, kept on the device
-int64_t World::set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter) {
+int64_t World::add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel_h) {
     use_device();
-    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
+    check_add_sampled(slot, t, q);
     SampleLattice L;
-    sample_mark(shape, prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
+    sample_mark(shape, prm.particle_radius, mode, L);
+    return append_sampled(slot, L, t, q, vel_h);
+}
+
+// salva_hip_set_boundary_sampling with the surface samples at the world's particle radius as the local points, kept on the device
+int64_t World::boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint32_t memberships, uint32_t filter) {
     const uint32_t total = sample_count(L);
     const std::function<void(float4*)> fill = [&](float4* dst) {
         SampleEmit e{};
@@ -430,6 +485,55 @@ int64_t World::set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipSha
     };
     set_boundary_sampling(slot, total, nullptr, memberships, filter, &fill);
     return total;
+}
+
+int64_t World::set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter) {
+    use_device();
+    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
+    SampleLattice L;
+    sample_mark(shape, prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
+    return boundary_from_sampled(slot, L, memberships, filter);
+}
+
+// ---- the same three for a triangle mesh (mesh.h): a second mark kernel, everything behind it shared
+void World::sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L) {
+    check_sample_args(particle_rad, mode);
+    sample_lattice(mesh.mins, mesh.maxs, particle_rad, L);
+    const SampleGrid& g = L.g;
+    const uint64_t rays = (uint64_t)g.ny * g.nz + (uint64_t)g.nz * g.nx + (uint64_t)g.nx * g.ny;
+    smp_err.ensure(1);
+    SALVA_HIP_CHECK(hipMemsetAsync(smp_err.p, 0, sizeof(uint32_t), stream));
+    k_sample_mesh_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, mesh.dev(), mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0, smp_bits.p, smp_err.p);
+    SALVA_HIP_CHECK(hipGetLastError());
+    uint32_t err = 0;
+    SALVA_HIP_CHECK(hipMemcpyAsync(&err, smp_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (err) throw HipError(SALVA_HIP_E_CAPACITY, "mesh sampling: a ray crosses the mesh more than 64 times");
+}
+
+int64_t World::sample_mesh(uint32_t mesh, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
+    use_device();
+    SampleLattice L;
+    sample_mark_mesh(*mesh_at(mesh), particle_rad, mode, L);
+    return sample_download(L, capacity, out_xyz);
+}
+
+int64_t World::add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel_h) {
+    use_device();
+    check_add_sampled(slot, t, q);
+    SampleLattice L;
+    sample_mark_mesh(*mesh_at(mesh), prm.particle_radius, mode, L);
+    return append_sampled(slot, L, t, q, vel_h);
+}
+
+int64_t World::set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter) {
+    use_device();
+    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
+    SampleLattice L;
+    sample_mark_mesh(*mesh_at(mesh), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
+    return boundary_from_sampled(slot, L, memberships, filter);
 }
 
 }  // namespace salva

@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "elastic.h"
 #include "switches.h"
+#include "mesh.h"
 
 namespace salva {
 
@@ -46,6 +47,7 @@ struct BoundarySlot {
     SalvaHipShape dyn_shape{};
     SalvaHipHostShape dyn_host{};  // dyn_kind == SALVA_HIP_SHAPE_HOST: the host's compute_aabb / project_point callbacks
     SalvaHipRigidPose dyn_pose{};
+    std::shared_ptr<MeshRes> dyn_mesh;  // dyn_kind == SALVA_HIP_SHAPE_MESH: the collider's mesh (kept alive: salva_hip_destroy_mesh refuses)
     std::shared_ptr<DevBuf<uint32_t>> dyn_src, dyn_src_model;
 };
 
@@ -104,6 +106,14 @@ class World {
     int64_t sample_host_shape(const SalvaHipHostRayShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
     int64_t add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel);
     int64_t set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
+    // ---- triangle meshes and height fields (mesh.hip): the world's table, the sampler and DynamicContactSampling on one
+    uint32_t create_mesh(const float* vertices_xyz, uint32_t nv, const uint32_t* indices, uint32_t nt, uint32_t flags);
+    uint32_t create_heightfield(const float* heights, uint32_t nrows, uint32_t ncols, const float scale[3]);
+    void destroy_mesh(uint32_t mesh);
+    int64_t sample_mesh(uint32_t mesh, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
+    int64_t add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel);
+    int64_t set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
+    void set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
     void update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose);
     void set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter);
@@ -181,6 +191,13 @@ class World {
     uint32_t sample_count(const SampleLattice& L);
     int64_t sample_download(const SampleLattice& L, uint64_t capacity, float* out_xyz);
     void sample_mark(const SalvaHipShape& shape, float particle_rad, int mode, SampleLattice& L);
+    void sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L);
+    DevBuf<uint32_t> smp_err;  // k_sample_mesh_mark: a ray with more than 64 accepted hits
+    void check_add_sampled(uint32_t slot, const float t[3], const float q[4]) const;
+    int64_t append_sampled(uint32_t slot, const SampleLattice& L, const float t[3], const float q[4], const float* vel);
+    int64_t boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint32_t memberships, uint32_t filter);
+    std::vector<std::shared_ptr<MeshRes>> meshes;  // by handle; a destroyed mesh leaves a free entry
+    const std::shared_ptr<MeshRes>& mesh_at(uint32_t mesh) const;
     void stamp_fluid_models();
     void stamp_boundary_models();
     bool has_dynamic_sampling() const;

@@ -612,6 +612,7 @@ void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, cons
     BoundarySlot& b = bounds[slot];
     b.n = nn; b.memberships = memberships; b.filter = filter; b.wants_forces = wants_forces;
     b.dyn_kind = 0;  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
+    b.dyn_mesh.reset();
     b.vel_zero = true;
     if (nn) {
         scratch_f.ensure(3 * nn, stream, false, 1.1f);
@@ -1630,6 +1631,23 @@ void World::set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHost
     b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
 }
 
+// The same arm for a collider that is a triangle mesh or a height field of this world (mesh.hip): gather, projection and apply all
+// stay on the device, and the pose handed to salva_hip_update_boundary_pose places the mesh.
+void World::set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter) {
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
+    const std::shared_ptr<MeshRes> m = mesh_at(mesh);
+    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
+    set_boundary(slot, 0, nullptr, nullptr, memberships, filter, keep_forces);
+    BoundarySlot& b = bounds[slot];
+    b.sampling.reset();
+    b.dyn_kind = SALVA_HIP_SHAPE_MESH;
+    b.dyn_shape = SalvaHipShape{};
+    b.dyn_mesh = m;
+    b.dyn_pose = SalvaHipRigidPose{};
+    b.dyn_pose.rotation[3] = 1.0f;
+    b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
+}
+
 // unregister_coupling (fluids_pipeline.rs:116-125): the boundary stays, with the particles it holds now, as a plain boundary;
 // nothing of the sampling method — in particular no host callback or user pointer — is kept
 void World::clear_boundary_sampling(uint32_t slot) {
@@ -1639,6 +1657,7 @@ void World::clear_boundary_sampling(uint32_t slot) {
     b.dyn_kind = 0;
     b.dyn_shape = SalvaHipShape{};
     b.dyn_host = SalvaHipHostShape{};
+    b.dyn_mesh.reset();
     b.dyn_src.reset(); b.dyn_src_model.reset();
     // the particles keep the velocities k_boundary_pose / k_dcs_emit wrote for the moving collider (the reference keeps them after
     // unregister_coupling too): from now on make_ctx must not take the upload's "at rest" for them
@@ -1704,13 +1723,20 @@ void World::run_dynamic_sampling() {
         HipError local_error(SALVA_HIP_E_INVALID, "");
         bool local_failed = false;
         try {
-        if (n && b.dyn_kind == SALVA_HIP_SHAPE_HOST) {
-            // the host's shape: box tests on the device, the projections on the host, the rest of the loop body on the device
-            float mins[3], maxs[3];
-            b.dyn_host.aabb(b.dyn_host.user, mins, maxs);
-            for (int a = 0; a < 3; ++a)
-                if (!(mins[a] <= maxs[a])) throw HipError(SALVA_HIP_E_INVALID, "host shape: the aabb callback returned an empty or NaN box");
-            const DcsParams prm_d = dcs_params_host(mins, maxs, sc.h, prm.particle_radius, dt_prev);
+        if (n && (b.dyn_kind == SALVA_HIP_SHAPE_HOST || b.dyn_kind == SALVA_HIP_SHAPE_MESH)) {
+            // the host's shape: box tests on the device, the projections on the host, the rest of the loop body on the device;
+            // a mesh: the same pass with the projections on the device as well (k_dcs_project_mesh)
+            const bool on_host = b.dyn_kind == SALVA_HIP_SHAPE_HOST;
+            DcsParams prm_d;
+            if (on_host) {
+                float mins[3], maxs[3];
+                b.dyn_host.aabb(b.dyn_host.user, mins, maxs);
+                for (int a = 0; a < 3; ++a)
+                    if (!(mins[a] <= maxs[a])) throw HipError(SALVA_HIP_E_INVALID, "host shape: the aabb callback returned an empty or NaN box");
+                prm_d = dcs_params_host(mins, maxs, sc.h, prm.particle_radius, dt_prev);
+            } else {
+                prm_d = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
+            }
             dcs_cand.ensure(n, stream, false, 1.1f); dcs_out.ensure(n, stream, false, 1.1f); dcs_flag.ensure(n, stream, false, 1.1f);
             dcs_num.ensure(1);
             launch_dcs_gather(n, posm[cur].p, vel[cur].p, G().keys[0].p, gv, prm_d, dcs_cand.p, dcs_flag.p, stream);
@@ -1721,15 +1747,19 @@ void World::run_dynamic_sampling() {
             wait_stream();
             const uint32_t ng = h_rb->dcs_count;
             if (ng) {
-                dcs_h_f4.resize(ng); dcs_h_pts.resize(3 * (size_t)ng); dcs_h_proj.assign(3 * (size_t)ng, 0.0f); dcs_h_inside.assign(ng, 0);
-                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_h_f4.data(), dcs_out.p, (size_t)ng * sizeof(float4), hipMemcpyDeviceToHost, stream));
-                wait_stream();
-                for (uint32_t k = 0; k < ng; ++k) { dcs_h_pts[3 * k] = dcs_h_f4[k].x; dcs_h_pts[3 * k + 1] = dcs_h_f4[k].y; dcs_h_pts[3 * k + 2] = dcs_h_f4[k].z; }
-                b.dyn_host.project(b.dyn_host.user, ng, dcs_h_pts.data(), dcs_h_proj.data(), dcs_h_inside.data());
-                for (uint32_t k = 0; k < ng; ++k)
-                    dcs_h_f4[k] = make_float4(dcs_h_proj[3 * k], dcs_h_proj[3 * k + 1], dcs_h_proj[3 * k + 2], dcs_h_inside[k] ? 1.0f : 0.0f);
                 dcs_proj.ensure(ng, stream, false, 1.5f); dcs_cand2.ensure(ng, stream, false, 1.5f);
-                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_proj.p, dcs_h_f4.data(), (size_t)ng * sizeof(float4), hipMemcpyHostToDevice, stream));
+                if (on_host) {
+                    dcs_h_f4.resize(ng); dcs_h_pts.resize(3 * (size_t)ng); dcs_h_proj.assign(3 * (size_t)ng, 0.0f); dcs_h_inside.assign(ng, 0);
+                    SALVA_HIP_CHECK(hipMemcpyAsync(dcs_h_f4.data(), dcs_out.p, (size_t)ng * sizeof(float4), hipMemcpyDeviceToHost, stream));
+                    wait_stream();
+                    for (uint32_t k = 0; k < ng; ++k) { dcs_h_pts[3 * k] = dcs_h_f4[k].x; dcs_h_pts[3 * k + 1] = dcs_h_f4[k].y; dcs_h_pts[3 * k + 2] = dcs_h_f4[k].z; }
+                    b.dyn_host.project(b.dyn_host.user, ng, dcs_h_pts.data(), dcs_h_proj.data(), dcs_h_inside.data());
+                    for (uint32_t k = 0; k < ng; ++k)
+                        dcs_h_f4[k] = make_float4(dcs_h_proj[3 * k], dcs_h_proj[3 * k + 1], dcs_h_proj[3 * k + 2], dcs_h_inside[k] ? 1.0f : 0.0f);
+                    SALVA_HIP_CHECK(hipMemcpyAsync(dcs_proj.p, dcs_h_f4.data(), (size_t)ng * sizeof(float4), hipMemcpyHostToDevice, stream));
+                } else {
+                    launch_dcs_project_mesh(ng, dcs_out.p, b.dyn_mesh->dev(), prm_d, dcs_proj.p, stream);
+                }
                 // (dcs_out holds the gathered candidates; its compaction goes back into dcs_cand, which is free again)
                 launch_dcs_apply(ng, dcs_out.p, dcs_proj.p, posm[cur].p, vel[cur].p, perm[cur].p, comm ? gtag[cur].p : nullptr, prm_d,
                                  dcs_cand2.p, dcs_flag.p, stream);

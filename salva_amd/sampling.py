@@ -1,6 +1,7 @@
 """sampling/ray_sampling.rs: `shape_surface_ray_sample` / `shape_volume_ray_sample` on the device (salva_hip_sample_shape,
 DESIGN.md §13).  A shape is what salva_amd.coupling.make_shape takes — ("ball", r), ("cuboid", (hx, hy, hz)), ("capsule", hh, r),
-("cylinder", hh, r) — or a HostRayShape for anything else."""
+("cylinder", hh, r) — a Mesh (triangle mesh or height field, cast at on the device: DESIGN.md §14), or a HostRayShape for anything
+else."""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,6 +49,57 @@ class HostRayShape:
         self.shape = L.HostRayShape(None, self._thunks[0], self._thunks[1])
 
 
+class Mesh:
+    """A triangle mesh (parry `TriMesh`) or, through `Mesh.heightfield`, a height field (parry `HeightField`) that lives on the
+    device (salva_hip_create_mesh / salva_hip_create_heightfield).  `oriented=True` states that the mesh is closed and wound
+    counter-clockwise seen from outside: only such a mesh has an inside for DynamicContactSampling to push particles out of.
+    Accepted wherever a shape is: shape_surface_ray_sample / shape_volume_ray_sample, Fluid.add_particles_from_shape,
+    StaticSampling.from_shape and DynamicContactSampling.  The device copy belongs to a world and is made on first use there."""
+
+    def __init__(self, vertices, indices, oriented: bool = False):
+        self.vertices = np.ascontiguousarray(vertices, F32).reshape(-1, 3)
+        self.indices = np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+        self.oriented = bool(oriented)
+        self._heights = self._scale = None
+
+    @classmethod
+    def heightfield(cls, heights, scale) -> "Mesh":
+        """parry `HeightField::new(heights, scale)`: heights[i][j] over a grid of `scale[0]` x `scale[2]` centred at the origin,
+        rows along z, columns along x, two triangles per cell."""
+        self = cls(np.zeros((0, 3), F32), np.zeros((0, 3), np.uint32))
+        self._heights = np.ascontiguousarray(heights, F32)
+        if self._heights.ndim != 2:
+            raise ValueError("heights: a 2D array, rows along z")
+        self._scale = np.ascontiguousarray(scale, F32).reshape(3)
+        return self
+
+    def handle(self, world) -> int:
+        """The mesh's handle in `world`, created on first use."""
+        table = world.__dict__.setdefault("_mesh_handles", {})
+        hit = table.get(id(self))
+        if hit is not None:
+            return hit[1]
+        h = C.c_uint32()
+        fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        if self._heights is not None:
+            L.check(world._L.salva_hip_create_heightfield(world._h, self._heights.ctypes.data_as(fp), self._heights.shape[0],
+                                                          self._heights.shape[1], self._scale.ctypes.data_as(fp), C.byref(h)))
+        else:
+            L.check(world._L.salva_hip_create_mesh(world._h, self.vertices.ctypes.data_as(fp), len(self.vertices),
+                                                   self.indices.ctypes.data_as(up), len(self.indices),
+                                                   L.MESH_ORIENTED if self.oriented else 0, C.byref(h)))
+        table[id(self)] = (self, h.value)  # (keeps the mesh alive, so that its id stays its own)
+        return h.value
+
+    def destroy(self, world):
+        """salva_hip_destroy_mesh: refused while a dynamically sampled boundary of `world` still uses the mesh."""
+        table = world.__dict__.get("_mesh_handles", {})
+        hit = table.get(id(self))
+        if hit is not None:
+            L.check(world._L.salva_hip_destroy_mesh(world._h, hit[1]))
+            del table[id(self)]
+
+
 def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
     from .coupling import make_shape
     from .world import DFSPHSolver, LiquidWorld
@@ -61,6 +113,9 @@ def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
             if err is not None:
                 raise err
             return n
+    elif isinstance(shape, Mesh):
+        def call(cap, out):
+            return w._L.salva_hip_sample_mesh(w._h, shape.handle(w), float(particle_rad), mode, cap, out)
     else:
         s = shape if isinstance(shape, L.Shape) else make_shape(shape)
 
