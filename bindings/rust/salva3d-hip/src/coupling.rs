@@ -301,24 +301,35 @@ impl FluidsPipeline {
                 pose.has_body = 1;
                 pose.is_dynamic = b.is_dynamic() as i32;
             }
-            check(unsafe { ffi::salva_hip_update_boundary_pose(raw, slot, &pose) })?;
             poses.push((slot, pose, body.map(|(p, _)| p)));
+        }
+        // all poses with one call, in the order of the entries (salva_hip_update_boundary_poses)
+        if !poses.is_empty() {
+            let slots: Vec<u32> = poses.iter().map(|p| p.0).collect();
+            let raw_poses: Vec<ffi::SalvaHipRigidPose> = poses.iter().map(|p| p.1).collect();
+            check(unsafe { ffi::salva_hip_update_boundary_poses(raw, slots.len() as u32, slots.as_ptr(), raw_poses.as_ptr()) })?;
         }
         Ok(poses)
     }
 
     /// `transmit_forces` (fluids_pipeline.rs:266-287): sum_i apply_impulse_at_point(f_i dt, x_i) = apply_impulse(F dt) + apply_torque_impulse(T dt)
     fn transmit_forces(&mut self, poses: &[Pose], bodies: &mut RigidBodySet, dt: Real) -> Result<(), Error> {
-        for (slot, pose, parent) in poses.iter().copied() {
-            let Some(parent) = parent else { continue };
-            if pose.is_dynamic == 0 {
-                continue;
-            }
-            let (mut f, mut t) = ([0.0f32; 3], [0.0f32; 3]);
-            check(unsafe { ffi::salva_hip_get_boundary_wrench(self.liquid_world.raw(), slot, pose.world_com.as_ptr(), f.as_mut_ptr(), t.as_mut_ptr()) })?;
-            if let Some(body) = bodies.get_mut(parent) {
-                body.apply_impulse(Vector::new(f[0], f[1], f[2]) * dt, true);
-                body.apply_torque_impulse(Vector::new(t[0], t[1], t[2]) * dt, true);
+        // one launch, one copy and one wait for every dynamic body's boundary (salva_hip_get_boundary_wrenches); the impulses are
+        // applied in the order of the entries
+        let live: Vec<_> = poses.iter().copied().filter_map(|(slot, pose, parent)| parent.filter(|_| pose.is_dynamic != 0).map(|p| (slot, pose, p))).collect();
+        if live.is_empty() {
+            return Ok(());
+        }
+        let slots: Vec<u32> = live.iter().map(|e| e.0).collect();
+        let points: Vec<f32> = live.iter().flat_map(|e| e.1.world_com).collect();
+        let (mut f, mut t) = (vec![0.0f32; 3 * live.len()], vec![0.0f32; 3 * live.len()]);
+        check(unsafe {
+            ffi::salva_hip_get_boundary_wrenches(self.liquid_world.raw(), live.len() as u32, slots.as_ptr(), points.as_ptr(), f.as_mut_ptr(), t.as_mut_ptr())
+        })?;
+        for (k, (_, _, parent)) in live.iter().enumerate() {
+            if let Some(body) = bodies.get_mut(*parent) {
+                body.apply_impulse(Vector::new(f[3 * k], f[3 * k + 1], f[3 * k + 2]) * dt, true);
+                body.apply_torque_impulse(Vector::new(t[3 * k], t[3 * k + 1], t[3 * k + 2]) * dt, true);
             }
         }
         Ok(())

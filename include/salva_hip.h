@@ -253,6 +253,10 @@ int salva_hip_set_boundary_sampling(SalvaHipWorld* world, uint32_t slot, uint64_
  * world_com) — the reference passes the LOCAL point there (:183), reproduced as written; forces are cleared.
  * Call before salva_hip_step (the reference calls it at the top of the substep, liquid_world.rs:93-101). */
 int salva_hip_update_boundary_pose(SalvaHipWorld* world, uint32_t slot, const SalvaHipRigidPose* pose);
+/* `n` calls of salva_hip_update_boundary_pose, entry k for boundary slots[k] with poses[k], in order and with the same result bit
+ * for bit — but validated as a whole before anything changes (any invalid entry: SALVA_HIP_E_INVALID, nothing done), and with the
+ * statically sampled boundaries posed, and their forces cleared, by one launch over all their particles.  A slot may appear twice. */
+int salva_hip_update_boundary_poses(SalvaHipWorld* world, uint32_t n, const uint32_t* slots, const SalvaHipRigidPose* poses);
 /* Reads `boundary.positions` / `boundary.velocities` (object/boundary.rs:13-15) back, e.g. after a pose update.  Any pointer may be NULL. */
 int salva_hip_get_boundary_particles(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz);
 /* ColliderCouplingManager::transmit_forces (fluids_pipeline.rs:266-287) applies `force_i * dt` at `position_i` for every
@@ -260,6 +264,12 @@ int salva_hip_get_boundary_particles(SalvaHipWorld* world, uint32_t slot, float*
  *   force = sum_i f_i,  torque = sum_i (x_i - point) x f_i   ->  body.apply_impulse(force*dt), apply_torque_impulse(torque*dt)
  * with point = body.center_of_mass().  Zero when the boundary does not receive forces. */
 int salva_hip_get_boundary_wrench(SalvaHipWorld* world, uint32_t slot, const float point[3], float force[3], float torque[3]);
+/* `n` calls of salva_hip_get_boundary_wrench — entry k: boundary slots[k] about points_xyz[3k..], into forces_xyz[3k..] and
+ * torques_xyz[3k..] — with one launch, one copy and one wait for all of them.  Every boundary is summed exactly as the single call
+ * sums it, so the results are the same bit for bit.  A slot may appear twice; a slot out of range is SALVA_HIP_E_INVALID and leaves
+ * the outputs untouched. */
+int salva_hip_get_boundary_wrenches(SalvaHipWorld* world, uint32_t n, const uint32_t* slots, const float* points_xyz, float* forces_xyz,
+                                    float* torques_xyz);
 
 /* ---- User-defined `NonPressureForce`s (solver/nonpressure_force.rs:10-30; examples3d/custom_forces3.rs:67-90).
  * A SALVA_HIP_FORCE_CUSTOM entry in a fluid's force list makes salva_hip_step call `cb` in the middle of the substep, at the
@@ -523,6 +533,11 @@ int salva_hip_get_boundary_sources(SalvaHipWorld* world, uint32_t slot, uint32_t
  * times include waiting for the neighbour's data: they are what an exchange costs inside a real step, not the transport alone
  * (salva_hip_comm_time).  Zeros without a domain or with the timers off. */
 int salva_hip_get_dist_timing(const SalvaHipWorld* world, double out4[4]);
+/* What DynamicContactSampling did inside the LAST salva_hip_step: out4 = {passes over the fluid particles, host waits, colliders
+ * that went through a batched pass, boundary particles emitted}.  Consecutive dynamically sampled boundaries whose collider shape is
+ * on the device (built-in shapes, meshes, height fields) share ONE pass and ONE wait per step; a host shape between them splits the
+ * run.  SALVA_HIP_NO_DCS_BATCH=1 (read when the world is created) gives every collider a pass of its own, as do decomposed worlds. */
+int salva_hip_get_dcs_stats(const SalvaHipWorld* world, uint64_t out4[4]);
 
 /* ---- The working set as it is ("local view"): every fluid particle this world holds — in a decomposed run the particles the
  * rank owns AND its ghosts — in the order of the last step's cell sort, with global ids.  This is the per-rank form of what

@@ -682,6 +682,16 @@ class LiquidWorld {  // liquid_world.rs
         if (pose.has_body) boundaries_[h].wants_forces = pose.is_dynamic != 0;
         check(salva_hip_update_boundary_pose(w_, (uint32_t)h, &pose));
     }
+    // ... for many boundaries with one call (salva_hip_update_boundary_poses): entry k poses boundary hs[k], in order
+    void update_boundary_poses(const std::vector<BoundaryHandle>& hs, const std::vector<SalvaHipRigidPose>& poses) {
+        std::vector<uint32_t> slots(hs.size());
+        for (size_t k = 0; k < hs.size(); ++k) {
+            upload(boundaries_[hs[k]], (uint32_t)hs[k]);
+            if (poses[k].has_body) boundaries_[hs[k]].wants_forces = poses[k].is_dynamic != 0;
+            slots[k] = (uint32_t)hs[k];
+        }
+        if (!hs.empty()) check(salva_hip_update_boundary_poses(w_, (uint32_t)hs.size(), slots.data(), poses.data()));
+    }
     // `unregister_coupling` as the library sees it (salva_hip_clear_boundary_sampling): the boundary keeps the particles it holds
     // and becomes a plain boundary; call it before the memory behind Boundary::dynamic_host's callbacks / user pointer goes away
     void clear_boundary_sampling(BoundaryHandle h) {
@@ -735,6 +745,17 @@ class LiquidWorld {  // liquid_world.rs
     }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));
+    }
+    // DynamicContactSampling inside the last step: {passes over the fluid, host waits, colliders batched, boundary particles emitted}
+    void dcs_stats(uint64_t out[4]) const { check(salva_hip_get_dcs_stats(w_, out)); }
+    // ... of many boundaries with one launch, one copy and one wait (salva_hip_get_boundary_wrenches)
+    void boundary_wrenches(const std::vector<BoundaryHandle>& hs, const std::vector<Vec3>& points, std::vector<Vec3>& forces,
+                           std::vector<Vec3>& torques) {
+        std::vector<uint32_t> slots(hs.size());
+        for (size_t k = 0; k < hs.size(); ++k) slots[k] = (uint32_t)hs[k];
+        forces.assign(hs.size(), Vec3{0, 0, 0}); torques.assign(hs.size(), Vec3{0, 0, 0});
+        if (!hs.empty())
+            check(salva_hip_get_boundary_wrenches(w_, (uint32_t)hs.size(), slots.data(), points[0].data(), forces[0].data(), torques[0].data()));
     }
 
   private:
@@ -924,19 +945,27 @@ class ColliderCouplingSet : public CouplingManager {
     }
     void update_boundaries(LiquidWorld& world) override {
         poses_.clear();
+        std::vector<BoundaryHandle> hs;
         for (Entry& e : entries_) {
             poses_.push_back(e.pose());
-            world.update_boundary_pose(e.boundary, poses_.back());
+            hs.push_back(e.boundary);
         }
+        world.update_boundary_poses(hs, poses_);
     }
     void transmit_forces(LiquidWorld& world, Real dt) override {
+        std::vector<size_t> live;
+        std::vector<BoundaryHandle> hs;
+        std::vector<Vec3> points, f, t;
         for (size_t k = 0; k < entries_.size(); ++k) {
             const SalvaHipRigidPose& p = poses_[k];
             if (!entries_[k].apply || !p.has_body || !p.is_dynamic) continue;
-            Vec3 f{0, 0, 0}, t{0, 0, 0};
-            world.boundary_wrench(entries_[k].boundary, Vec3{p.world_com[0], p.world_com[1], p.world_com[2]}, f, t);
-            entries_[k].apply(Vec3{f[0] * dt, f[1] * dt, f[2] * dt}, Vec3{t[0] * dt, t[1] * dt, t[2] * dt});
+            live.push_back(k);
+            hs.push_back(entries_[k].boundary);
+            points.push_back(Vec3{p.world_com[0], p.world_com[1], p.world_com[2]});
         }
+        world.boundary_wrenches(hs, points, f, t);
+        for (size_t j = 0; j < live.size(); ++j)
+            entries_[live[j]].apply(Vec3{f[j][0] * dt, f[j][1] * dt, f[j][2] * dt}, Vec3{t[j][0] * dt, t[j][1] * dt, t[j][2] * dt});
     }
 
   private:

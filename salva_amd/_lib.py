@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_sample_shape", "salva_hip_sample_host_shape", "salva_hip_add_particles_sampled", "salva_hip_set_boundary_sampling_from_shape",
     "salva_hip_create_mesh", "salva_hip_create_heightfield", "salva_hip_destroy_mesh", "salva_hip_sample_mesh",
     "salva_hip_add_particles_sampled_mesh", "salva_hip_set_boundary_sampling_from_mesh", "salva_hip_set_boundary_dynamic_sampling_mesh",
+    "salva_hip_update_boundary_poses", "salva_hip_get_boundary_wrenches", "salva_hip_get_dcs_stats",
 ]
 
 
@@ -234,6 +235,9 @@ def lib():
     L.salva_hip_get_boundary_sources.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.salva_hip_get_boundary_particles.argtypes = [vp, u32, fp, fp]
     L.salva_hip_get_boundary_wrench.argtypes = [vp, u32, fp, fp, fp]
+    L.salva_hip_update_boundary_poses.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(RigidPose)]
+    L.salva_hip_get_boundary_wrenches.argtypes = [vp, u32, C.POINTER(u32), fp, fp, fp]
+    L.salva_hip_get_dcs_stats.argtypes = [vp, C.POINTER(u64)]
     L.salva_hip_set_force_callback.argtypes = [vp, FORCE_CALLBACK, vp]
     L.salva_hip_set_coupling_callback.argtypes = [vp, COUPLING_CALLBACK, vp]
     L.salva_hip_force_get_state.argtypes = [vp, u32, fp, fp, fp]

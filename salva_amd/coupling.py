@@ -241,6 +241,7 @@ class ColliderCouplingSet:
 
     # CouplingManager::update_boundaries (:146-264), StaticSampling arm
     def update_boundaries(self, world):
+        slots, poses = [], []  # all poses go in with one call, in the order of the entries (salva_hip_update_boundary_poses)
         for e in self.entries.values():
             b = e.boundary
             if b._world is not world:
@@ -288,22 +289,29 @@ class ColliderCouplingSet:
             else:
                 pose = L.RigidPose()
                 pose.rotation[3] = 1.0
-            L.check(world._L.salva_hip_update_boundary_pose(world._h, b._slot, C.byref(pose)))
+            slots.append(b._slot)
+            poses.append(pose)
+        if slots:
+            L.check(world._L.salva_hip_update_boundary_poses(world._h, len(slots), (C.c_uint32 * len(slots))(*slots),
+                                                             (L.RigidPose * len(poses))(*poses)))
 
     # CouplingManager::transmit_forces (:266-287)
     def transmit_forces(self, world, dt: float):
-        for e in self.entries.values():
-            b = e.boundary
-            if b._world is not world or e.body is None or not b.wants_forces or b.num_particles() == 0:
-                continue
-            com = e.body.center_of_mass()
-            f = np.zeros(3, F32)
-            t = np.zeros(3, F32)
-            fp = C.POINTER(C.c_float)
-            L.check(world._L.salva_hip_get_boundary_wrench(world._h, b._slot, com.ctypes.data_as(fp), f.ctypes.data_as(fp),
-                                                           t.ctypes.data_as(fp)))
-            e.body.apply_impulse(f * F32(dt))
-            e.body.apply_torque_impulse(t * F32(dt))
+        live = [e for e in self.entries.values()
+                if e.boundary._world is world and e.body is not None and e.boundary.wants_forces and e.boundary.num_particles() != 0]
+        if not live:
+            return
+        # one launch, one copy and one wait for all of them (salva_hip_get_boundary_wrenches); the impulses in the order of the entries
+        slots = (C.c_uint32 * len(live))(*[e.boundary._slot for e in live])
+        coms = np.ascontiguousarray([e.body.center_of_mass() for e in live], F32)
+        f = np.zeros((len(live), 3), F32)
+        t = np.zeros((len(live), 3), F32)
+        fp = C.POINTER(C.c_float)
+        L.check(world._L.salva_hip_get_boundary_wrenches(world._h, len(live), slots, coms.ctypes.data_as(fp), f.ctypes.data_as(fp),
+                                                         t.ctypes.data_as(fp)))
+        for k, e in enumerate(live):
+            e.body.apply_impulse(f[k] * F32(dt))
+            e.body.apply_torque_impulse(t[k] * F32(dt))
 
 
 class FluidsPipeline:

@@ -199,6 +199,16 @@ int salva_hip_update_boundary_pose(SalvaHipWorld* world, uint32_t slot, const Sa
     });
 }
 
+int salva_hip_update_boundary_poses(SalvaHipWorld* world, uint32_t n, const uint32_t* slots, const SalvaHipRigidPose* poses) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        if (n && (!slots || !poses)) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        world->w->update_boundary_poses(n, slots, poses);
+        return SALVA_HIP_OK;
+    });
+}
+
 int salva_hip_set_boundary_dynamic_sampling(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* collider_shape,
                                             uint32_t memberships, uint32_t filter) { WorldLock _lk(world);
     return guarded([&]() -> int {
@@ -387,6 +397,24 @@ int salva_hip_get_boundary_wrench(SalvaHipWorld* world, uint32_t slot, const flo
         if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
         if (!point || !force || !torque) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
         world->w->get_boundary_wrench(slot, point, force, torque);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_get_boundary_wrenches(SalvaHipWorld* world, uint32_t n, const uint32_t* slots, const float* points_xyz, float* forces_xyz,
+                                    float* torques_xyz) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        if (n && (!slots || !points_xyz || !forces_xyz || !torques_xyz)) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        world->w->get_boundary_wrenches(n, slots, points_xyz, forces_xyz, torques_xyz);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_get_dcs_stats(const SalvaHipWorld* world, uint64_t out4[4]) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !out4) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        world->w->get_dcs_stats(out4);
         return SALVA_HIP_OK;
     });
 }

@@ -63,6 +63,39 @@ struct DevBuf {
     size_t bytes() const { return cap * sizeof(T); }
 };
 
+// Pinned host staging for the small tables that go to, and the small results that come from, the device without the copy making
+// the host wait (a pageable source or destination does).  acquire() waits for whatever was enqueued when release() was last
+// called — by then long done — before the memory is written again, and grows.
+struct PinnedStage {
+    char* p = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    PinnedStage() = default;
+    PinnedStage(const PinnedStage&) = delete;
+    PinnedStage& operator=(const PinnedStage&) = delete;
+    ~PinnedStage() {
+        if (ev) { if (pending) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+        if (p) (void)hipHostFree(p);
+    }
+    char* acquire(size_t bytes) {
+        if (pending) { SALVA_HIP_CHECK(hipEventSynchronize(ev)); pending = false; }
+        if (bytes > cap) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr; cap = 0;
+            const size_t ncap = bytes + bytes / 2 + 256;
+            SALVA_HIP_CHECK(hipHostMalloc((void**)&p, ncap, hipHostMallocDefault));
+            cap = ncap;
+        }
+        return p;
+    }
+    void release(hipStream_t stream) {
+        if (!ev) SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        SALVA_HIP_CHECK(hipEventRecord(ev, stream));
+        pending = true;
+    }
+};
+
 // The kernel sources (dfsph.hip, iisph.hip, forces.hip, visc.hip) are compiled twice: as they are (namespace salva, the cubic
 // spline everywhere) and with -DSALVA_OTHER_KERNELS into namespace salva_ok, where sph_math.h also knows the reference's
 // other kernels.  Every launcher that ends in a kernel evaluation starts with SALVA_OK_DISPATCH: a world whose solver was

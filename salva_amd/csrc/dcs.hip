@@ -66,8 +66,8 @@ __device__ __forceinline__ bool dcs_in_cells(uint32_t k, const TileGrid& g, cons
 
 // :219-243 from the projection on: dpt = particle_pos - proj.point; a particle inside the shape is pushed out along dpt by
 // depth + margin and loses its velocity along it; one outside and farther than h + prediction emits nothing (false).
-__device__ __forceinline__ bool dcs_finish(uint32_t i, float4 p, float4 v, float px, float py, float pz, float wx, float wy, float wz,
-                                           bool inside, const DcsParams& s, float4* __restrict__ posm, float4* __restrict__ vel) {
+__device__ __forceinline__ bool dcs_finish_reg(float4& p, float4& v, float px, float py, float pz, float wx, float wy, float wz, bool inside,
+                                               const DcsParams& s, bool& moved, bool& slowed) {
     const float dx = px - wx, dy = py - wy, dz = pz - wz;
     const float sq = (dx * dx + dy * dy) + dz * dz;
     if (sq > s.eps * s.eps) {  // Unit::try_new_and_get(dpt, f32::EPSILON)
@@ -76,11 +76,11 @@ __device__ __forceinline__ bool dcs_finish(uint32_t i, float4 p, float4 v, float
         if (inside) {
             const float m = depth + s.margin;
             p.x -= nx * m; p.y -= ny * m; p.z -= nz * m;
-            posm[i] = p;
+            moved = true;
             const float vel_err = (nx * v.x + ny * v.y) + nz * v.z;
             if (vel_err > 0.0f) {
                 v.x -= nx * vel_err; v.y -= ny * vel_err; v.z -= nz * vel_err;
-                vel[i] = v;
+                slowed = true;
             }
         } else if (depth > s.reach) {
             return false;
@@ -88,24 +88,20 @@ __device__ __forceinline__ bool dcs_finish(uint32_t i, float4 p, float4 v, float
     }
     return true;
 }
+// ... on the particle in memory (the per-collider kernels); the batched kernel keeps it in registers (k_dcsb_project)
+__device__ __forceinline__ bool dcs_finish(uint32_t i, float4 p, float4 v, float px, float py, float pz, float wx, float wy, float wz,
+                                           bool inside, const DcsParams& s, float4* __restrict__ posm, float4* __restrict__ vel) {
+    bool moved = false, slowed = false;
+    const bool keep = dcs_finish_reg(p, v, px, py, pz, wx, wy, wz, inside, s, moved, slowed);
+    if (moved) posm[i] = p;
+    if (slowed) vel[i] = v;
+    return keep;
+}
 
-__global__ __launch_bounds__(BLOCK) void k_dcs_project(uint32_t n, float4* __restrict__ posm, float4* __restrict__ vel,
-                                                       const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm,
-                                                       const uint32_t* __restrict__ gtag, TileGrid g, DcsParams s,
-                                                       float4* __restrict__ cand, uint8_t* __restrict__ flag) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    flag[i] = 0;
-    float4 p = posm[i];
-    if (!dcs_in_cells(keys[i], g, s, p)) return;
-    float4 v = vel[i];
-    const float px = p.x + v.x * s.dt, py = p.y + v.y * s.dt, pz = p.z + v.z * s.dt;  // :206-207
-    if (px < s.lo[0] || px > s.hi[0] || py < s.lo[1] || py > s.hi[1] || pz < s.lo[2] || pz > s.hi[2]) return;  // NaN: passes, as `<` / `>` do
-    // m^-1 * pt
-    float lx, ly, lz;
-    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], px - s.t[0], py - s.t[1], pz - s.t[2], lx, ly, lz);
-    float jx, jy, jz;
-    bool inside;
+// project_local of the built-in shapes (see the header of this file) on a collider-local point: the projection and is_inside.
+// The one copy of this arithmetic: k_dcs_project and k_dcsb_project both call it.
+__device__ __forceinline__ void dcs_project_local(const DcsParams& s, float lx, float ly, float lz, float& jx, float& jy, float& jz,
+                                                  bool& inside) {
     if (s.kind == SALVA_HIP_SHAPE_BALL) {
         const float r = s.p[0], d2 = (lx * lx + ly * ly) + lz * lz;
         inside = d2 <= r * r;
@@ -176,9 +172,44 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_project(uint32_t n, float4* __res
         }
         jx = l3[0] + shift[0]; jy = l3[1] + shift[1]; jz = l3[2] + shift[2];
     }
-    float wx, wy, wz;
+}
+
+// project_point_and_get_feature(m, pt) of a built-in shape: m^-1 * pt, project_local, carried back by m
+__device__ __forceinline__ void dcs_project_world(const DcsParams& s, float px, float py, float pz, float& wx, float& wy, float& wz,
+                                                  bool& inside) {
+    float lx, ly, lz;
+    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], px - s.t[0], py - s.t[1], pz - s.t[2], lx, ly, lz);
+    float jx, jy, jz;
+    dcs_project_local(s, lx, ly, lz, jx, jy, jz, inside);
     quat_rot(s.q[0], s.q[1], s.q[2], s.q[3], jx, jy, jz, wx, wy, wz);
     wx += s.t[0]; wy += s.t[1]; wz += s.t[2];
+}
+// ... of a posed mesh: the closest point over all triangles (mesh.h) in place of project_local
+__device__ __forceinline__ void dcs_project_mesh_world(const MeshDev& mesh, const DcsParams& s, float px, float py, float pz, float& wx,
+                                                       float& wy, float& wz, bool& inside) {
+    float lx, ly, lz;
+    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], px - s.t[0], py - s.t[1], pz - s.t[2], lx, ly, lz);
+    float jx, jy, jz;
+    mesh_project_point(mesh, lx, ly, lz, jx, jy, jz, inside);
+    quat_rot(s.q[0], s.q[1], s.q[2], s.q[3], jx, jy, jz, wx, wy, wz);
+    wx += s.t[0]; wy += s.t[1]; wz += s.t[2];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_dcs_project(uint32_t n, float4* __restrict__ posm, float4* __restrict__ vel,
+                                                       const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm,
+                                                       const uint32_t* __restrict__ gtag, TileGrid g, DcsParams s,
+                                                       float4* __restrict__ cand, uint8_t* __restrict__ flag) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    flag[i] = 0;
+    float4 p = posm[i];
+    if (!dcs_in_cells(keys[i], g, s, p)) return;
+    float4 v = vel[i];
+    const float px = p.x + v.x * s.dt, py = p.y + v.y * s.dt, pz = p.z + v.z * s.dt;  // :206-207
+    if (px < s.lo[0] || px > s.hi[0] || py < s.lo[1] || py > s.hi[1] || pz < s.lo[2] || pz > s.hi[2]) return;  // NaN: passes, as `<` / `>` do
+    float wx, wy, wz;
+    bool inside;
+    dcs_project_world(s, px, py, pz, wx, wy, wz, inside);
     if (dcs_finish(i, p, v, px, py, pz, wx, wy, wz, inside, s, posm, vel)) {
         // decomposed run (gtag != nullptr): a ghost is pushed like its owner — same inputs, same arithmetic — but only the owner
         // emits; the row then carries the SORTED index (k_dcs_pack turns it into global id + fluid)
@@ -230,14 +261,9 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_project_mesh(uint32_t cnt, const 
     const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
     if (k >= cnt) return;
     const float4 pr = pred[k];
-    float lx, ly, lz;
-    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], pr.x - s.t[0], pr.y - s.t[1], pr.z - s.t[2], lx, ly, lz);
-    float jx, jy, jz;
-    bool inside;
-    mesh_project_point(mesh, lx, ly, lz, jx, jy, jz, inside);
     float wx, wy, wz;
-    quat_rot(s.q[0], s.q[1], s.q[2], s.q[3], jx, jy, jz, wx, wy, wz);
-    wx += s.t[0]; wy += s.t[1]; wz += s.t[2];
+    bool inside;
+    dcs_project_mesh_world(mesh, s, pr.x, pr.y, pr.z, wx, wy, wz, inside);
     proj[k] = make_float4(wx, wy, wz, inside ? 1.0f : 0.0f);
 }
 
@@ -254,12 +280,9 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_pack(uint32_t cnt, const float4* 
     out_models[k] = model[i];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_dcs_emit(uint32_t cnt, const float4* __restrict__ cand, SalvaHipRigidPose pose, uint32_t slot,
-                                                    float4* __restrict__ pos, float4* __restrict__ vel, uint32_t* __restrict__ src) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= cnt) return;
-    const float4 c = cand[i];
-    pos[i] = make_float4(c.x, c.y, c.z, 0.0f);  // boundary.volumes.push(0) :249
+// one boundary row from one accepted projection (the one copy: k_dcs_emit and k_dcsb_emit)
+__device__ __forceinline__ void dcs_emit_row(const float4 c, const SalvaHipRigidPose& pose, uint32_t slot, float4& pos, float4& vel, uint32_t& src) {
+    pos = make_float4(c.x, c.y, c.z, 0.0f);  // boundary.volumes.push(0) :249
     float vx = 0.0f, vy = 0.0f, vz = 0.0f;
     if (pose.has_body) {  // body.velocity_at_point(&proj.point) :241-242 (the WORLD point here, unlike the static arm)
         const float rx = c.x - pose.world_com[0], ry = c.y - pose.world_com[1], rz = c.z - pose.world_com[2];
@@ -267,8 +290,99 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_emit(uint32_t cnt, const float4* 
         vy = pose.linvel[1] + (pose.angvel[2] * rx - pose.angvel[0] * rz);
         vz = pose.linvel[2] + (pose.angvel[0] * ry - pose.angvel[1] * rx);
     }
-    vel[i] = make_float4(vx, vy, vz, __uint_as_float(slot));
-    src[i] = __float_as_uint(c.w);
+    vel = make_float4(vx, vy, vz, __uint_as_float(slot));
+    src = __float_as_uint(c.w);
+}
+__global__ __launch_bounds__(BLOCK) void k_dcs_emit(uint32_t cnt, const float4* __restrict__ cand, SalvaHipRigidPose pose, uint32_t slot,
+                                                    float4* __restrict__ pos, float4* __restrict__ vel, uint32_t* __restrict__ src) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= cnt) return;
+    dcs_emit_row(cand[i], pose, slot, pos[i], vel[i], src[i]);
+}
+
+// ------------------------------------------------------------------------------------------------ batched runs
+// A run of consecutive device-shape colliders in ONE pass over the fluid.  What collider c does to particle i depends on particle
+// i's own state and on collider c alone, so a thread that keeps its particle in registers and goes through the colliders in slot
+// order computes what C passes of k_dcs_project / k_dcs_gather + k_dcs_project_mesh + k_dcs_apply compute, operation for operation
+// (the same device functions).  The pass itself writes no particle: accepted projections are appended to a record buffer, pushed
+// particles to a push list, both through one wave-aggregated atomic each; when the record buffer was too small the host grows it and
+// repeats the pass from the unmodified state (World::run_dynamic_sampling_batch).  Keys (collider << shift | sorted index) are
+// unique, so the radix sort behind the pass gives one order whatever order the atomics ran in: by slot, then by sorted index — the
+// order of the per-collider stable selects.
+// counts: [0, ncol) records per collider, [ncol] all records, [ncol + 1] pushed particles
+__device__ __forceinline__ uint32_t dcsb_append(bool mine, unsigned long long* total, unsigned long long* per_collider) {
+    const unsigned long long m = __ballot(mine);
+    if (m == 0ull) return 0xffffffffu;
+    const int lane = (int)(threadIdx.x & (WAVE - 1)), leader = __ffsll((long long)m) - 1;
+    unsigned long long base = 0ull;
+    if (lane == leader) {
+        base = atomicAdd(total, (unsigned long long)__popcll(m));
+        if (per_collider) atomicAdd(per_collider, (unsigned long long)__popcll(m));
+    }
+    base = __shfl(base, leader, WAVE);
+    const unsigned long long k = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+    return (mine && k < 0xffffffffull) ? (uint32_t)k : 0xffffffffu;
+}
+__global__ __launch_bounds__(BLOCK) void k_dcsb_project(uint32_t n, const float4* __restrict__ posm, const float4* __restrict__ vel,
+                                                        const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm, TileGrid g,
+                                                        const DcsbEntry* __restrict__ tab, uint32_t ncol, uint32_t cap, uint32_t shift,
+                                                        unsigned long long* __restrict__ counts, unsigned long long* __restrict__ rec_key,
+                                                        uint32_t* __restrict__ rec_idx, float4* __restrict__ rec,
+                                                        uint32_t* __restrict__ push_idx, float4* __restrict__ push_pos,
+                                                        float4* __restrict__ push_vel) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = i < n;  // (every lane stays to the end: the appends are wave-wide)
+    float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v = p;
+    uint32_t key = 0u;
+    if (live) { p = posm[i]; key = keys[i]; }
+    bool have_v = false, moved = false, slowed = false;
+#pragma unroll 1
+    for (uint32_t c = 0; c < ncol; ++c) {  // (c is wave-uniform: the table comes through the scalar cache)
+        const DcsParams& s = tab[c].s;
+        bool accept = false;
+        float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+        if (live && dcs_in_cells(key, g, s, p)) {
+            if (!have_v) { v = vel[i]; have_v = true; }
+            const float px = p.x + v.x * s.dt, py = p.y + v.y * s.dt, pz = p.z + v.z * s.dt;  // :206-207
+            if (!(px < s.lo[0] || px > s.hi[0] || py < s.lo[1] || py > s.hi[1] || pz < s.lo[2] || pz > s.hi[2])) {
+                bool inside;
+                if (s.kind == SALVA_HIP_SHAPE_MESH) dcs_project_mesh_world(tab[c].mesh, s, px, py, pz, wx, wy, wz, inside);
+                else dcs_project_world(s, px, py, pz, wx, wy, wz, inside);
+                accept = dcs_finish_reg(p, v, px, py, pz, wx, wy, wz, inside, s, moved, slowed);
+            }
+        }
+        const uint32_t k = dcsb_append(accept, counts + ncol, counts + c);
+        if (k < cap) {
+            rec_key[k] = ((unsigned long long)c << shift) | (unsigned long long)i;
+            rec_idx[k] = k;
+            rec[k] = make_float4(wx, wy, wz, __uint_as_float(perm[i]));
+        }
+    }
+    // (a pushed particle has an accepted record: pushes <= records, so the push list fits whenever the records do)
+    const uint32_t k = dcsb_append(moved, counts + ncol + 1, nullptr);
+    if (k < cap) { push_idx[k] = i; push_pos[k] = p; push_vel[k] = v; }
+}
+// the pushes of a pass whose records fitted (a velocity that no collider changed is written back as it was read)
+__global__ __launch_bounds__(BLOCK) void k_dcsb_push(uint32_t cnt, const uint32_t* __restrict__ push_idx, const float4* __restrict__ push_pos,
+                                                     const float4* __restrict__ push_vel, float4* __restrict__ posm, float4* __restrict__ vel) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t i = push_idx[k];
+    posm[i] = push_pos[k];
+    vel[i] = push_vel[k];
+}
+// sorted records -> the rows of their boundaries (DcsbEntry::row0 / rec0: first boundary row / first sorted record of the collider),
+// forces cleared (clear_forces(true) :262)
+__global__ __launch_bounds__(BLOCK) void k_dcsb_emit(uint32_t cnt, const unsigned long long* __restrict__ skey, const uint32_t* __restrict__ sidx,
+                                                     const float4* __restrict__ rec, const DcsbEntry* __restrict__ tab, uint32_t shift,
+                                                     float4* __restrict__ pos, float4* __restrict__ vel, float4* __restrict__ force) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t c = (uint32_t)(skey[k] >> shift);
+    const DcsbEntry& e = tab[c];
+    const uint32_t j = k - e.rec0, row = e.row0 + j;
+    dcs_emit_row(rec[sidx[k]], e.pose, e.slot, pos[row], vel[row], e.src[j]);
+    force[row] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // half extents of the posed shape's AABB about the pose's translation (parry compute_aabb, see the header of this file)
@@ -399,6 +513,28 @@ void launch_dcs_emit(uint32_t cnt, const float4* cand, const SalvaHipRigidPose& 
                      uint32_t* src, hipStream_t st) {
     if (cnt == 0) return;
     k_dcs_emit<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, cand, pose, slot, pos, vel, src);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
+
+void launch_dcsb_project(uint32_t n, const float4* posm, const float4* vel, const uint32_t* keys, const uint32_t* perm, TileGrid g,
+                         const DcsbEntry* tab, uint32_t ncol, uint32_t cap, uint32_t shift, unsigned long long* counts,
+                         unsigned long long* rec_key, uint32_t* rec_idx, float4* rec, uint32_t* push_idx, float4* push_pos, float4* push_vel,
+                         hipStream_t st) {
+    if (n == 0) return;
+    k_dcsb_project<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, posm, vel, keys, perm, g, tab, ncol, cap, shift, counts, rec_key, rec_idx, rec, push_idx,
+                                                       push_pos, push_vel);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
+void launch_dcsb_push(uint32_t cnt, const uint32_t* push_idx, const float4* push_pos, const float4* push_vel, float4* posm, float4* vel,
+                      hipStream_t st) {
+    if (cnt == 0) return;
+    k_dcsb_push<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, push_idx, push_pos, push_vel, posm, vel);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
+void launch_dcsb_emit(uint32_t cnt, const unsigned long long* skey, const uint32_t* sidx, const float4* rec, const DcsbEntry* tab,
+                      uint32_t shift, float4* pos, float4* vel, float4* force, hipStream_t st) {
+    if (cnt == 0) return;
+    k_dcsb_emit<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, skey, sidx, rec, tab, shift, pos, vel, force);
     SALVA_HIP_CHECK(hipGetLastError());
 }
 

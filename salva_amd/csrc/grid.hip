@@ -163,6 +163,17 @@ void sort_pairs(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t
                 uint32_t* idx_out, uint32_t n, int end_bit, hipStream_t s) {
     SALVA_HIP_CHECK(sort_dispatch(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out, n, end_bit, s));
 }
+// 64-bit keys (the batched DynamicContactSampling records: collider << shift | sorted index, dcs.hip), rocPRIM's own configuration
+size_t sort_pairs_u64_temp_bytes(uint32_t n, int end_bit) {
+    size_t bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr,
+                                    (uint32_t*)nullptr, (size_t)n, 0u, (unsigned)end_bit, (hipStream_t) nullptr);
+    return bytes;
+}
+void sort_pairs_u64(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, const uint32_t* idx_in,
+                    uint32_t* idx_out, uint32_t n, int end_bit, hipStream_t s) {
+    SALVA_HIP_CHECK(rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)n, 0u, (unsigned)end_bit, s));
+}
 size_t select_flagged_temp_bytes(uint32_t n) {
     size_t b = 0;
     (void)hipcub::DeviceSelect::Flagged(nullptr, b, (const float4*)nullptr, (const uint8_t*)nullptr, (float4*)nullptr, (uint32_t*)nullptr, (int)n);

@@ -70,6 +70,9 @@ struct RefCaps { uint32_t s, raw, sum; };
 struct RefBuild { uint32_t* halo_src; uint4* slot_info; TileAcc* tile_off; RefCaps cap; uint32_t* maxima3; };
 void launch_nbr_build(const StepCtx& c, const TileLds& L, void* tile_stats, unsigned long long* totals2, uint32_t* maxima2,
                       unsigned long long* own2, hipStream_t s, const RefBuild* ref = nullptr);
+size_t sort_pairs_u64_temp_bytes(uint32_t n, int end_bit);
+void sort_pairs_u64(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out, const uint32_t* idx_in,
+                    uint32_t* idx_out, uint32_t n, int end_bit, hipStream_t s);
 size_t select_flagged_temp_bytes(uint32_t n);
 void select_flagged_f4(void* temp, size_t temp_bytes, const float4* in, const uint8_t* flags, float4* out, uint32_t* num_selected,
                        uint32_t n, hipStream_t s);

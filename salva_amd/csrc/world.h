@@ -19,6 +19,8 @@
 
 namespace salva {
 
+struct DcsbEntry;  // dcs.h
+
 struct FluidSlot {
     uint64_t n = 0;
     float density0 = 1000.0f;
@@ -115,6 +117,7 @@ class World {
     int64_t set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
     void update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose);
+    void update_boundary_poses(uint32_t count, const uint32_t* slots, const SalvaHipRigidPose* poses);
     void set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter);
     void clear_boundary_sampling(uint32_t slot);
@@ -138,6 +141,9 @@ class World {
     void set_timestep(float dt, float inv_dt) { dt_prev = dt; inv_dt_prev = inv_dt; }
     void get_boundary_particles(uint32_t slot, float* positions, float* velocities);
     void get_boundary_wrench(uint32_t slot, const float point[3], float force[3], float torque[3]);
+    void get_boundary_wrenches(uint32_t count, const uint32_t* slots, const float* points, float* forces, float* torques);
+    // DynamicContactSampling of the last step: passes over the fluid, host waits, colliders that went through a batch, records emitted
+    void get_dcs_stats(uint64_t out[4]) const { for (int k = 0; k < 4; ++k) out[k] = dcs_stats[k]; }
     void clear_boundary_forces(uint32_t slot);
     uint64_t device_bytes() const;
     // multi-GPU: this world owns the cell planes [lo, hi] along x; neighbours are rank-1 / rank+1 of `transport`
@@ -201,6 +207,20 @@ class World {
     void stamp_fluid_models();
     void stamp_boundary_models();
     bool has_dynamic_sampling() const;
+    // ... in one pass over the fluid for a run of device-shape colliders (dcs.hip "batched runs")
+    static constexpr size_t DCS_BATCH_MIN_RUN = 2;
+    void run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv);
+    void run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const TileGrid& gv);
+    void relayout_boundaries(const std::vector<uint32_t>& run, const uint64_t* counts);
+    DevBuf<DcsbEntry> dcsb_tab;
+    DevBuf<unsigned long long> dcsb_counts, dcsb_key[2];
+    DevBuf<uint32_t> dcsb_idx[2], dcsb_push_idx;
+    DevBuf<float4> dcsb_rec, dcsb_push_pos, dcsb_push_vel;
+    uint32_t dcsb_cap = 0;  // records the buffers above are cut for (0: not yet)
+    PinnedStage dcsb_stage, pose_stage, wrench_stage;
+    DevBuf<char> pose_tab, wrench_tab;  // salva_hip_update_boundary_poses / _get_boundary_wrenches: their entry tables
+    DevBuf<double> wrenches_partial;
+    uint64_t dcs_stats[4] = {0, 0, 0, 0};
     void run_dynamic_sampling();   // between the cell keys and the sort (fluids_pipeline.rs:193-259 inside liquid_world.rs:94-103)
     DevBuf<float4> dcs_cand, dcs_out, dcs_proj, dcs_cand2;  // (_proj, _cand2: the host-shape arm)
     std::vector<float> dcs_h_pts, dcs_h_proj;

@@ -144,6 +144,8 @@ Switches Switches::from_env() {
     s.tile_trace = on("SALVA_HIP_TILE_TRACE");
     s.dist_trace = on("SALVA_HIP_DIST_TRACE");
     s.no_fused_div = on("SALVA_HIP_NO_FUSED_DIV");
+    s.dcs_batch_off = on("SALVA_HIP_NO_DCS_BATCH");
+    if (const char* e = getenv("SALVA_HIP_DCSB_CAP0")) s.dcsb_cap0 = (uint32_t)std::max(atoi(e), 1);
     if (const char* e = getenv("SALVA_HIP_RADIX_SORT")) s.sort_mode = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("SALVA_HIP_DS_LEVEL")) s.ds_level = (uint32_t)std::max(0, atoi(e));
     if (const char* e = getenv("SALVA_HIP_LIST_CAP0")) { s.list_cap0 = std::max<uint32_t>(LIST_REGS, ((uint32_t)atoi(e) + 3u) & ~3u); s.trust_cap0 = true; }
@@ -1510,16 +1512,12 @@ void World::get_boundary(uint32_t slot, float* volumes, float* forces) {
 // ------------------------------------------------------------------------------------------------ rigid-body coupling
 // integrations/rapier/fluids_pipeline.rs, StaticSampling arm.  q * v of nalgebra's UnitQuaternion (geometry/
 // quaternion_ops.rs): t = 2 q.vec x v; v' = v + w t + q.vec x t.
-__global__ void k_boundary_pose(uint32_t n, const float4* __restrict__ local, SalvaHipRigidPose p, float4* __restrict__ pos,
-                                float4* __restrict__ vel) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 pt = local[i];
-    float4 o = pos[i];  // .w (volume slot) untouched
+__device__ __forceinline__ void boundary_pose_row(const float4 pt, const SalvaHipRigidPose& p, float4& pos_io, float4& vel_io) {
+    float4 o = pos_io;  // .w (volume slot) untouched
     pose_point(p.rotation[0], p.rotation[1], p.rotation[2], p.rotation[3], p.translation[0], p.translation[1], p.translation[2], pt.x, pt.y,
                pt.z, o.x, o.y, o.z);  // (pose.h: shared with the shape sampler's emit kernel)
-    pos[i] = o;
-    float4 v = vel[i];  // .w carries the boundary's model id
+    pos_io = o;
+    float4 v = vel_io;  // .w carries the boundary's model id
     if (p.has_body) {
         // body.velocity_at_point(pt) with the local point, as the reference writes it (:183)
         const float dx = pt.x - p.world_com[0], dy = pt.y - p.world_com[1], dz = pt.z - p.world_com[2];
@@ -1529,14 +1527,35 @@ __global__ void k_boundary_pose(uint32_t n, const float4* __restrict__ local, Sa
     } else {
         v.x = v.y = v.z = 0.0f;
     }
-    vel[i] = v;
+    vel_io = v;
+}
+__global__ void k_boundary_pose(uint32_t n, const float4* __restrict__ local, SalvaHipRigidPose p, float4* __restrict__ pos,
+                                float4* __restrict__ vel) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    boundary_pose_row(local[i], p, pos[i], vel[i]);
+}
+// salva_hip_update_boundary_poses: the statically sampled boundaries of one call as one launch over their concatenated rows
+// (`first`: the entry's first row in that concatenation, ascending); the force rows are cleared on the way (clear_forces(true) :262)
+struct PoseEntry { SalvaHipRigidPose pose; const float4* local; uint32_t first, n, off, pad; };
+__global__ void k_boundary_poses(uint32_t total, uint32_t nent, const PoseEntry* __restrict__ ent, float4* __restrict__ pos,
+                                 float4* __restrict__ vel, float4* __restrict__ force) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    uint32_t lo = 0, hi = nent;  // the last entry with first <= i
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) / 2u; if (ent[mid].first <= i) lo = mid; else hi = mid; }
+    const PoseEntry& e = ent[lo];
+    const uint32_t j = i - e.first, row = e.off + j;
+    boundary_pose_row(e.local[j], e.pose, pos[row], vel[row]);
+    force[row] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 // per-block partial sums of f and (x - c) x f in f64 (6 doubles per block)
-__global__ void k_boundary_wrench(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ force, float cx, float cy,
-                                  float cz, double* __restrict__ partial) {
+// block `lb` of `nblocks` over one boundary's rows (grid stride): the one copy of k_boundary_wrench / k_boundary_wrenches
+__device__ __forceinline__ void boundary_wrench_block(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ force, float cx,
+                                                      float cy, float cz, uint32_t lb, uint32_t nblocks, double* __restrict__ partial) {
     double a[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    for (uint32_t i = lb * blockDim.x + threadIdx.x; i < n; i += nblocks * blockDim.x) {
         const float4 p = pos[i], f = force[i];
         const float rx = p.x - cx, ry = p.y - cy, rz = p.z - cz;
         a[0] += f.x; a[1] += f.y; a[2] += f.z;
@@ -1553,8 +1572,22 @@ __global__ void k_boundary_wrench(uint32_t n, const float4* __restrict__ pos, co
     if (threadIdx.x < 6) {
         double v = 0;
         for (uint32_t w = 0; w < blockDim.x / WAVE; ++w) v += sh[w][threadIdx.x];
-        partial[blockIdx.x * 6 + threadIdx.x] = v;
+        partial[threadIdx.x] = v;
     }
+}
+__global__ void k_boundary_wrench(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ force, float cx, float cy,
+                                  float cz, double* __restrict__ partial) {
+    boundary_wrench_block(n, pos, force, cx, cy, cz, blockIdx.x, gridDim.x, partial + (size_t)blockIdx.x * 6);
+}
+// salva_hip_get_boundary_wrenches: every listed boundary keeps the partition of k_boundary_wrench — its own min(nblk(n), 256) blocks,
+// `block0` the first of them in this launch (ascending) — so that its partial sums are the single call's, bit for bit
+struct WrenchEntry { uint32_t off, n, block0, nblocks; float c[3]; uint32_t pad; };
+__global__ void k_boundary_wrenches(uint32_t nent, const WrenchEntry* __restrict__ ent, const float4* __restrict__ pos,
+                                    const float4* __restrict__ force, double* __restrict__ partial) {
+    uint32_t lo = 0, hi = nent;  // the last entry with block0 <= blockIdx.x
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) / 2u; if (ent[mid].block0 <= blockIdx.x) lo = mid; else hi = mid; }
+    const WrenchEntry e = ent[lo];
+    boundary_wrench_block(e.n, pos + e.off, force + e.off, e.c[0], e.c[1], e.c[2], blockIdx.x - e.block0, e.nblocks, partial + (size_t)blockIdx.x * 6);
 }
 
 void World::set_boundary_sampling(uint32_t slot, uint64_t nn, const float* local_points, uint32_t memberships, uint32_t filter,
@@ -1597,6 +1630,51 @@ void World::update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose) {
         SALVA_HIP_CHECK(hipMemsetAsync(bforce.p + off, 0, b.n * sizeof(float4), stream));  // boundary.clear_forces(true) :262
     }
     b_dirty = true; have_last_ctx = false;
+}
+
+// `count` calls of update_boundary_pose in order, validated as a whole before anything changes: the dynamically sampled slots store
+// their pose, the statically sampled ones share one launch (a slot listed twice: its last pose is the one that stays, as in order)
+void World::update_boundary_poses(uint32_t count, const uint32_t* slots, const SalvaHipRigidPose* poses) {
+    use_device();
+    for (uint32_t k = 0; k < count; ++k) {
+        if (slots[k] >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
+        const BoundarySlot& b = bounds[slots[k]];
+        if (!b.sampling && !b.dyn_kind)
+            throw HipError(SALVA_HIP_E_INVALID, "boundary has no sampling method (salva_hip_set_boundary_sampling / _dynamic_sampling)");
+        for (int a = 0; a < 4; ++a)
+            if (!std::isfinite(poses[k].rotation[a])) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
+    }
+    std::vector<uint32_t> launch;  // the entries that write rows
+    for (uint32_t k = 0; k < count; ++k) {
+        BoundarySlot& b = bounds[slots[k]];
+        const SalvaHipRigidPose& pose = poses[k];
+        if (pose.has_body) {
+            const bool wants = pose.is_dynamic != 0;
+            if (wants != b.wants_forces) { b.wants_forces = wants; tables_dirty = true; }
+        }
+        if (b.dyn_kind) { b.dyn_pose = pose; continue; }  // the projection itself runs inside the step, where the reference runs it
+        b_dirty = true; have_last_ctx = false;
+        if (!b.n) continue;
+        bool last = true;
+        for (uint32_t j = k + 1; j < count; ++j) if (slots[j] == slots[k]) last = false;
+        if (last) launch.push_back(k);
+    }
+    if (launch.empty()) return;
+    PoseEntry* ent_h = reinterpret_cast<PoseEntry*>(pose_stage.acquire(launch.size() * sizeof(PoseEntry)));
+    uint64_t total = 0;
+    for (size_t e = 0; e < launch.size(); ++e) {
+        const uint32_t k = launch[e];
+        const BoundarySlot& b = bounds[slots[k]];
+        ent_h[e] = PoseEntry{poses[k], b.sampling->p, (uint32_t)total, (uint32_t)b.n, (uint32_t)boundary_offset(slots[k]), 0u};
+        total += b.n;
+    }
+    if (total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
+    pose_tab.ensure(launch.size() * sizeof(PoseEntry), stream, false, 1.5f);
+    SALVA_HIP_CHECK(hipMemcpyAsync(pose_tab.p, ent_h, launch.size() * sizeof(PoseEntry), hipMemcpyHostToDevice, stream));
+    k_boundary_poses<<<nblk(total), BLOCK, 0, stream>>>((uint32_t)total, (uint32_t)launch.size(), reinterpret_cast<const PoseEntry*>(pose_tab.p),
+                                                        bst_pos.p, bst_vel.p, bforce.p);
+    SALVA_HIP_CHECK(hipGetLastError());
+    pose_stage.release(stream);
 }
 
 // ------------------------------------------------------------------------------------------------ DynamicContactSampling
@@ -1712,10 +1790,31 @@ void World::resize_boundary_slot(uint32_t slot, uint64_t nn) {
 // insertion, liquid_world.rs:90-91), the boundaries are not in the grid yet (:106).  Works on the sorted working set of the
 // previous step (posm[cur] / vel[cur], G().keys[0] = this step's keys in that order).
 void World::run_dynamic_sampling() {
-    TileGrid gv = gf.device(nullptr);
-    for (uint32_t slot = 0; slot < bounds.size(); ++slot) {
+    const TileGrid gv = gf.device(nullptr);
+    // Maximal runs of consecutive dynamically sampled slots whose shape is on the device go through ONE pass over the fluid
+    // (run_dynamic_sampling_batch).  Slots that are not dynamically sampled do not break a run; a host shape does, and
+    // runs at its place in slot order, so that the pushes keep their order.  A run of one, an empty fluid and every decomposed world
+    // (whose emitted rows go through a collective per collider) take the per-collider path.
+    std::vector<uint32_t> run;
+    for (uint32_t slot = 0; slot < bounds.size();) {
+        if (!bounds[slot].dyn_kind) { ++slot; continue; }
+        run.clear();
+        if (!comm && !sw.dcs_batch_off && n)
+            for (uint32_t s = slot; s < bounds.size() && bounds[s].dyn_kind != SALVA_HIP_SHAPE_HOST; ++s)
+                if (bounds[s].dyn_kind) run.push_back(s);
+        if (run.size() >= DCS_BATCH_MIN_RUN) {
+            run_dynamic_sampling_batch(run, gv);
+            slot = run.back() + 1;
+        } else {
+            run_dynamic_sampling_slot(slot, gv);
+            ++slot;
+        }
+    }
+}
+
+void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
+    {
         BoundarySlot& b = bounds[slot];
-        if (!b.dyn_kind) continue;
         uint32_t cnt = 0;
         const float4* emit_src = nullptr;  // the compacted (projection, source particle) rows
         // (decomposed run: a failure of the rank-local part must not leave the other ranks waiting in the collective below —
@@ -1740,18 +1839,19 @@ void World::run_dynamic_sampling() {
             dcs_cand.ensure(n, stream, false, 1.1f); dcs_out.ensure(n, stream, false, 1.1f); dcs_flag.ensure(n, stream, false, 1.1f);
             dcs_num.ensure(1);
             launch_dcs_gather(n, posm[cur].p, vel[cur].p, G().keys[0].p, gv, prm_d, dcs_cand.p, dcs_flag.p, stream);
+            ++dcs_stats[0];
             const size_t tb = select_flagged_temp_bytes(n);
             ensure_cub_temp(tb);
             select_flagged_f4(cub_temp.p, tb, dcs_cand.p, dcs_flag.p, dcs_out.p, dcs_num.p, n, stream);
             SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            wait_stream();
+            wait_stream(); ++dcs_stats[1];
             const uint32_t ng = h_rb->dcs_count;
             if (ng) {
                 dcs_proj.ensure(ng, stream, false, 1.5f); dcs_cand2.ensure(ng, stream, false, 1.5f);
                 if (on_host) {
                     dcs_h_f4.resize(ng); dcs_h_pts.resize(3 * (size_t)ng); dcs_h_proj.assign(3 * (size_t)ng, 0.0f); dcs_h_inside.assign(ng, 0);
                     SALVA_HIP_CHECK(hipMemcpyAsync(dcs_h_f4.data(), dcs_out.p, (size_t)ng * sizeof(float4), hipMemcpyDeviceToHost, stream));
-                    wait_stream();
+                    wait_stream(); ++dcs_stats[1];
                     for (uint32_t k = 0; k < ng; ++k) { dcs_h_pts[3 * k] = dcs_h_f4[k].x; dcs_h_pts[3 * k + 1] = dcs_h_f4[k].y; dcs_h_pts[3 * k + 2] = dcs_h_f4[k].z; }
                     b.dyn_host.project(b.dyn_host.user, ng, dcs_h_pts.data(), dcs_h_proj.data(), dcs_h_inside.data());
                     for (uint32_t k = 0; k < ng; ++k)
@@ -1765,7 +1865,7 @@ void World::run_dynamic_sampling() {
                                  dcs_cand2.p, dcs_flag.p, stream);
                 select_flagged_f4(cub_temp.p, tb, dcs_cand2.p, dcs_flag.p, dcs_cand.p, dcs_num.p, ng, stream);
                 SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                wait_stream();  // (also: dcs_h_f4 has been read)
+                wait_stream(); ++dcs_stats[1];  // (also: dcs_h_f4 has been read)
                 cnt = h_rb->dcs_count;
                 emit_src = dcs_cand.p;
             }
@@ -1775,11 +1875,12 @@ void World::run_dynamic_sampling() {
             dcs_num.ensure(1);
             launch_dcs_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, comm ? gtag[cur].p : nullptr, gv, prm_d, dcs_cand.p,
                                dcs_flag.p, stream);
+            ++dcs_stats[0];
             const size_t tb = select_flagged_temp_bytes(n);
             ensure_cub_temp(tb);
             select_flagged_f4(cub_temp.p, tb, dcs_cand.p, dcs_flag.p, dcs_out.p, dcs_num.p, n, stream);
             SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            wait_stream();
+            wait_stream(); ++dcs_stats[1];
             cnt = h_rb->dcs_count;
             emit_src = dcs_out.p;
         }
@@ -1800,6 +1901,7 @@ void World::run_dynamic_sampling() {
         if (comm) cnt = dist_gather_emitted(emit_src, cnt, &emit_src, &emit_models, local_failed ? &local_error : nullptr);
         resize_boundary_slot(slot, cnt);
         b_dirty = true;  // same count, new positions
+        dcs_stats[3] += cnt;
         if (cnt) {
             const uint64_t off = boundary_offset(slot);
             b.dyn_src->ensure(cnt, stream, false, 1.5f);
@@ -1812,6 +1914,122 @@ void World::run_dynamic_sampling() {
             SALVA_HIP_CHECK(hipMemsetAsync(bforce.p + off, 0, (size_t)cnt * sizeof(float4), stream));  // clear_forces(true) :262
         }
     }
+}
+
+// One run of device-shape colliders (`run`: their slots, ascending, at least two) in one pass over the fluid; dcs.hip "batched runs".
+//   table up -> k_dcsb_project (writes records, the push list and the counts; no particle) -> counts down, ONE wait
+//   -> too small: grow, repeat from the unmodified state -> k_dcsb_push -> sort the record keys -> lay the boundary arrays out once
+//   -> table up again (first row / first record / source array per collider) -> k_dcsb_emit
+void World::run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const TileGrid& gv) {
+    const uint32_t ncol = (uint32_t)run.size();
+    const size_t tab_bytes = (size_t)ncol * sizeof(DcsbEntry), cnt_bytes = ((size_t)ncol + 2) * sizeof(unsigned long long);
+    // (pinned: neither copy makes the host wait; the previous batch's second upload is long done — acquire() checks)
+    char* stage = dcsb_stage.acquire(tab_bytes + cnt_bytes);
+    DcsbEntry* tab_h = reinterpret_cast<DcsbEntry*>(stage);
+    const unsigned long long* cnt_h = reinterpret_cast<const unsigned long long*>(stage + tab_bytes);
+    for (uint32_t c = 0; c < ncol; ++c) {
+        const BoundarySlot& b = bounds[run[c]];
+        DcsbEntry e{};
+        if (b.dyn_kind == SALVA_HIP_SHAPE_MESH) {
+            e.s = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
+            e.mesh = b.dyn_mesh->dev();
+        } else {
+            e.s = dcs_params(b.dyn_shape, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
+        }
+        e.pose = b.dyn_pose;
+        e.slot = run[c];
+        tab_h[c] = e;
+    }
+    dcsb_tab.ensure(ncol, stream, false, 1.5f);
+    dcsb_counts.ensure((size_t)ncol + 2, stream, false, 1.5f);
+    SALVA_HIP_CHECK(hipMemcpyAsync(dcsb_tab.p, tab_h, tab_bytes, hipMemcpyHostToDevice, stream));
+    int nbits = 1;
+    while (nbits < 32 && ((uint64_t)1 << nbits) < (uint64_t)n) ++nbits;
+    int cbits = 1;
+    while (((uint64_t)1 << cbits) < (uint64_t)ncol) ++cbits;
+    const uint32_t shift = (uint32_t)nbits;
+    // the first capacity is a guess (an eighth of the fluid, or SALVA_HIP_DCSB_CAP0 for the tests); afterwards what the fullest pass
+    // so far needed, with half as much again
+    if (dcsb_cap == 0) dcsb_cap = sw.dcsb_cap0 ? sw.dcsb_cap0 : std::max<uint32_t>(n / 8u, 4096u);
+    uint64_t total = 0, npush = 0;
+    for (;;) {
+        for (int k = 0; k < 2; ++k) { dcsb_key[k].ensure(dcsb_cap, stream); dcsb_idx[k].ensure(dcsb_cap, stream); }
+        dcsb_rec.ensure(dcsb_cap, stream); dcsb_push_idx.ensure(dcsb_cap, stream); dcsb_push_pos.ensure(dcsb_cap, stream); dcsb_push_vel.ensure(dcsb_cap, stream);
+        SALVA_HIP_CHECK(hipMemsetAsync(dcsb_counts.p, 0, cnt_bytes, stream));
+        launch_dcsb_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, dcsb_cap, shift, dcsb_counts.p,
+                            dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, stream);
+        SALVA_HIP_CHECK(hipMemcpyAsync(stage + tab_bytes, dcsb_counts.p, cnt_bytes, hipMemcpyDeviceToHost, stream));
+        wait_stream();
+        ++dcs_stats[0]; ++dcs_stats[1];
+        total = cnt_h[ncol]; npush = cnt_h[ncol + 1];
+        if (total <= dcsb_cap) break;
+        // nothing has been written but the scratch of this pass: a larger buffer, the same pass again
+        if (total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
+        dcsb_cap = (uint32_t)std::min<uint64_t>(total + total / 2, 0xfffffff0ull);
+    }
+    launch_dcsb_push((uint32_t)npush, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, posm[cur].p, vel[cur].p, stream);
+    std::vector<uint64_t> counts(ncol);
+    for (uint32_t c = 0; c < ncol; ++c) counts[c] = cnt_h[c];
+    relayout_boundaries(run, counts.data());
+    b_dirty = true;  // same counts, new positions
+    dcs_stats[2] += ncol; dcs_stats[3] += total;
+    if (total) {
+        const size_t tb = sort_pairs_u64_temp_bytes((uint32_t)total, nbits + cbits);
+        ensure_cub_temp(tb);
+        sort_pairs_u64(cub_temp.p, tb, dcsb_key[0].p, dcsb_key[1].p, dcsb_idx[0].p, dcsb_idx[1].p, (uint32_t)total, nbits + cbits, stream);
+        uint64_t rec0 = 0;
+        for (uint32_t c = 0; c < ncol; ++c) {
+            BoundarySlot& b = bounds[run[c]];
+            if (counts[c]) b.dyn_src->ensure(counts[c], stream, false, 1.5f);
+            tab_h[c].row0 = (uint32_t)boundary_offset(run[c]);
+            tab_h[c].rec0 = (uint32_t)rec0;
+            tab_h[c].src = b.dyn_src->p;
+            rec0 += counts[c];
+        }
+        SALVA_HIP_CHECK(hipMemcpyAsync(dcsb_tab.p, tab_h, tab_bytes, hipMemcpyHostToDevice, stream));
+        launch_dcsb_emit((uint32_t)total, dcsb_key[1].p, dcsb_idx[1].p, dcsb_rec.p, dcsb_tab.p, shift, bst_pos.p, bst_vel.p, bforce.p, stream);
+    }
+    dcsb_stage.release(stream);
+}
+
+// New particle counts for the slots of `run` (ascending) in one go: every other boundary's rows move at most once, through scratch;
+// the run's own rows are left for the caller to fill.  (resize_boundary_slot, once per collider, moves the tail once per collider.)
+void World::relayout_boundaries(const std::vector<uint32_t>& run, const uint64_t* counts) {
+    const size_t ns = bounds.size();
+    std::vector<uint64_t> old_off(ns + 1, 0), new_off(ns + 1, 0);
+    std::vector<uint8_t> in_run(ns, 0);
+    for (size_t c = 0; c < run.size(); ++c) in_run[run[c]] = 1;
+    bool changed = false;
+    for (size_t s = 0, c = 0; s < ns; ++s) {
+        const uint64_t nn = in_run[s] ? counts[c++] : bounds[s].n;
+        if (nn != bounds[s].n) changed = true;
+        old_off[s + 1] = old_off[s] + bounds[s].n;
+        new_off[s + 1] = new_off[s] + nn;
+    }
+    if (!changed) return;
+    const uint64_t old_total = old_off[ns], new_total = new_off[ns];
+    if (new_total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
+    // segments of consecutive slots outside the run that move (they stay contiguous): (source, destination, length)
+    struct Seg { uint64_t src, dst, len; };
+    std::vector<Seg> segs;
+    for (size_t s = run[0]; s < ns; ++s) {
+        if (in_run[s] || !bounds[s].n || old_off[s] == new_off[s]) continue;
+        if (!segs.empty() && segs.back().src + segs.back().len == old_off[s] && segs.back().dst + segs.back().len == new_off[s]) segs.back().len += bounds[s].n;
+        else segs.push_back(Seg{old_off[s], new_off[s], bounds[s].n});
+    }
+    const uint64_t tail_src = old_off[run[0]], tail_len = old_total - tail_src;
+    DevBuf<float4>* bufs[3] = {&bst_pos, &bst_vel, &bforce};
+    for (DevBuf<float4>* buf : bufs) {
+        buf->ensure(std::max<uint64_t>(new_total, 1), stream, true, 1.5f);
+        if (segs.empty()) continue;
+        scratch_f4.ensure(tail_len, stream, false, 1.5f);
+        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f4.p, buf->p + tail_src, tail_len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        for (const Seg& g : segs)
+            SALVA_HIP_CHECK(hipMemcpyAsync(buf->p + g.dst, scratch_f4.p + (g.src - tail_src), g.len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+    }
+    for (size_t c = 0; c < run.size(); ++c) bounds[run[c]].n = counts[c];
+    nb = (uint32_t)new_total;
+    b_dirty = true; have_last_ctx = false;
 }
 
 // (fluid slot, index) of the fluid particle each point of a dynamically sampled boundary was projected from
@@ -1942,6 +2160,49 @@ void World::get_boundary_wrench(uint32_t slot, const float point[3], float force
     for (uint32_t k = 0; k < nblocks; ++k)
         for (int j = 0; j < 6; ++j) acc[j] += h[(size_t)k * 6 + j];
     for (int k = 0; k < 3; ++k) { force[k] = (float)acc[k]; torque[k] = (float)acc[3 + k]; }
+}
+
+// `count` calls of get_boundary_wrench with one launch, one copy and one wait (points / forces / torques: 3 floats per entry)
+void World::get_boundary_wrenches(uint32_t count, const uint32_t* slots, const float* points, float* forces, float* torques) {
+    use_device();
+    for (uint32_t k = 0; k < count; ++k)
+        if (slots[k] >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
+    std::vector<uint32_t> live;  // the entries with something to sum
+    uint64_t nblocks = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        const BoundarySlot& b = bounds[slots[k]];
+        for (int a = 0; a < 3; ++a) forces[3 * (size_t)k + a] = torques[3 * (size_t)k + a] = 0.0f;
+        if (!b.n || !b.wants_forces) continue;
+        live.push_back(k);
+        nblocks += std::min<uint64_t>(nblk(b.n), 256);
+    }
+    if (live.empty()) return;
+    const size_t ent_bytes = live.size() * sizeof(WrenchEntry), part_bytes = (size_t)nblocks * 6 * sizeof(double);
+    char* stage = wrench_stage.acquire(ent_bytes + part_bytes);
+    WrenchEntry* ent_h = reinterpret_cast<WrenchEntry*>(stage);
+    uint32_t block0 = 0;
+    for (size_t e = 0; e < live.size(); ++e) {
+        const uint32_t k = live[e];
+        const BoundarySlot& b = bounds[slots[k]];
+        const uint32_t nbk = (uint32_t)std::min<uint64_t>(nblk(b.n), 256);
+        ent_h[e] = WrenchEntry{(uint32_t)boundary_offset(slots[k]), (uint32_t)b.n, block0, nbk, {points[3 * (size_t)k], points[3 * (size_t)k + 1], points[3 * (size_t)k + 2]}, 0u};
+        block0 += nbk;
+    }
+    wrench_tab.ensure(ent_bytes, stream, false, 1.5f);
+    wrenches_partial.ensure((size_t)nblocks * 6, stream, false, 1.5f);
+    SALVA_HIP_CHECK(hipMemcpyAsync(wrench_tab.p, ent_h, ent_bytes, hipMemcpyHostToDevice, stream));
+    k_boundary_wrenches<<<(uint32_t)nblocks, BLOCK, 0, stream>>>((uint32_t)live.size(), reinterpret_cast<const WrenchEntry*>(wrench_tab.p), bst_pos.p,
+                                                                 bforce.p, wrenches_partial.p);
+    SALVA_HIP_CHECK(hipGetLastError());
+    SALVA_HIP_CHECK(hipMemcpyAsync(stage + ent_bytes, wrenches_partial.p, part_bytes, hipMemcpyDeviceToHost, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    const double* h = reinterpret_cast<const double*>(stage + ent_bytes);
+    for (size_t e = 0; e < live.size(); ++e) {
+        double acc[6] = {0, 0, 0, 0, 0, 0};
+        for (uint32_t k = 0; k < ent_h[e].nblocks; ++k)
+            for (int j = 0; j < 6; ++j) acc[j] += h[(size_t)(ent_h[e].block0 + k) * 6 + j];
+        for (int a = 0; a < 3; ++a) { forces[3 * (size_t)live[e] + a] = (float)acc[a]; torques[3 * (size_t)live[e] + a] = (float)acc[3 + a]; }
+    }
 }
 
 void World::clear_boundary_forces(uint32_t slot) {

@@ -698,6 +698,7 @@ int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
     use_device();
     SalvaHipStepStats st{};
     st.nparticles = n;
+    for (uint64_t& v : dcs_stats) v = 0;
     {   // self.counters.reset() (liquid_world.rs:73); the pass counters of this implementation are cumulative, like World::tally:
         // a counter added to SalvaHipCounters that is to survive the step is named here
         const SalvaHipCounters last = counters;
