@@ -99,6 +99,53 @@ impl<KD: GpuKernel, KG: GpuKernel> salva3d::solver::NonPressureForce for Becker2
     }
 }
 
+/// Any other `impl NonPressureForce` written as a kernel (`SALVA_HIP_FORCE_DEVICE`, include/salva_hip.h): `entry` is an
+/// `extern "C"` function of a HIP object the crate links ("Linking a HIP object") that enqueues its kernel on
+/// `view.stream` and returns 0.  It is called in the middle of the substep, at the force's place in the list, without a wait; the
+/// pointers of the view are valid for work enqueued on that stream during the call only.  `needs`: `SALVA_HIP_DEVICE_NEEDS_*` bits;
+/// `params` reach the kernel as `view.params[1..]`.  Add it with `LiquidWorld::push_device_force`, which also records the entry.
+pub struct DeviceForce {
+    pub needs: u32,
+    pub params: [f32; 6],
+    pub entry: unsafe extern "C" fn(user: *mut std::ffi::c_void, view: *const ffi::SalvaHipDeviceView) -> i32,
+    pub user: *mut std::ffi::c_void,
+}
+// (the user data is the caller's to keep valid and thread-safe, as with every C callback of this crate)
+unsafe impl Send for DeviceForce {}
+unsafe impl Sync for DeviceForce {}
+
+impl salva3d::solver::NonPressureForce for DeviceForce {
+    fn solve(
+        &mut self,
+        _timestep: &salva3d::TimestepManager,
+        _kernel_radius: Real,
+        _fluid_fluid_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid_boundaries_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid: &mut Fluid,
+        _boundaries: &[Boundary],
+        _densities: &[Real],
+    ) {
+        unreachable!("a DeviceForce runs on the device (LiquidWorld::step)")
+    }
+
+    fn gpu_desc(&self) -> Option<(i32, [f32; 7])> {
+        let p = self.params;
+        Some((ffi::SALVA_HIP_FORCE_DEVICE, [self.needs as f32, p[0], p[1], p[2], p[3], p[4], p[5]]))
+    }
+}
+
+/// (fluid slot, force index) -> the entry to call: what the world-level device callback dispatches through
+type DeviceForceTable = Vec<(u32, u32, unsafe extern "C" fn(*mut std::ffi::c_void, *const ffi::SalvaHipDeviceView) -> i32, *mut std::ffi::c_void)>;
+
+unsafe extern "C" fn device_force_trampoline(user: *mut std::ffi::c_void, _world: *mut ffi::SalvaHipWorld, view: *const ffi::SalvaHipDeviceView) -> i32 {
+    let table = &*(user as *const DeviceForceTable);
+    let v = &*view;
+    match table.iter().find(|e| e.0 == v.fluid_slot && e.1 == v.force_index) {
+        Some(e) => (e.2)(e.3, view),
+        None => 1,
+    }
+}
+
 impl<KD: GpuKernel, KG: GpuKernel> GpuPressureSolver for DFSPHSolver<KD, KG> {
     fn params(&self, particle_radius: Real, smoothing_factor: Real) -> ffi::SalvaHipParams {
         let mut p = default_params();
@@ -152,6 +199,7 @@ pub struct LiquidWorld {
     decomposed: bool,    // set_domain was called (dist.rs): particles are read with owned()
     last_stats: ffi::SalvaHipStepStats,
     cfl_mode: i32,       // what set_cfl_substepping was last called with (coupling.rs: the manager's calls move into the substep loop)
+    device_forces: Box<DeviceForceTable>,  // boxed: the C side holds its address as the device callback's user pointer
 }
 
 // Send: the C side keeps no thread-affine state — every entry point selects the world's device and stream itself, and the
@@ -217,7 +265,37 @@ impl LiquidWorld {
             decomposed: false,
             last_stats: unsafe { std::mem::zeroed() },
             cfl_mode: 0,
+            device_forces: Box::new(Vec::new()),
         })
+    }
+
+    /// `fluid.nonpressure_forces.push(Box::new(force))` for a `DeviceForce`: also records its entry point under the place it takes in
+    /// the list, and registers the world's one device callback the first time.  (Removing or reordering the fluid's forces, or
+    /// removing a fluid, afterwards is the caller's to mirror with `clear_device_forces` and new pushes.)
+    pub fn push_device_force(&mut self, handle: FluidHandle, force: DeviceForce) -> Result<(), Error> {
+        // the fluid's dense index = its slot on the C side (the upload loop of `sync` numbers the fluids the same way)
+        let no_fluid = || Error { code: ffi::SALVA_HIP_E_INVALID, message: "no such fluid".into() };
+        let target = self.fluids.get(handle).ok_or_else(no_fluid)? as *const Fluid;
+        let slot = self.fluids.as_slice().iter().position(|f| std::ptr::eq(f, target)).ok_or_else(no_fluid)? as u32;
+        if self.device_forces.is_empty() {
+            let user = &*self.device_forces as *const DeviceForceTable as *mut std::ffi::c_void;
+            check(unsafe { ffi::salva_hip_set_device_force_callback(self.raw, Some(device_force_trampoline), user) })?;
+        }
+        let fluid = self.fluids.get_mut(handle).ok_or_else(no_fluid)?;
+        let index = fluid.nonpressure_forces.len() as u32;
+        self.device_forces.push((slot, index, force.entry, force.user));
+        fluid.nonpressure_forces.push(Box::new(force));
+        self.host_dirty = true;
+        Ok(())
+    }
+    pub fn clear_device_forces(&mut self) {
+        self.device_forces.clear();
+    }
+    /// {device callbacks, contact-table builds, bytes of contact tables written, host waits} of the last step.
+    pub fn device_force_stats(&self) -> Result<[u64; 4], Error> {
+        let mut out = [0u64; 4];
+        check(unsafe { ffi::salva_hip_get_device_force_stats(self.raw, out.as_mut_ptr()) })?;
+        Ok(out)
     }
 
     pub fn set_auto_sync(&mut self, on: bool) {

@@ -80,9 +80,19 @@ enum {
     SALVA_HIP_FORCE_HE2014 = 5,      /* solver::He2014SurfaceTension::new(fluid_tension, boundary_tension), he2014_surface_tension.rs:21-29 */
     SALVA_HIP_FORCE_WCSPH_TENSION = 6, /* solver::WCSPHSurfaceTension::new(fluid_tension, boundary_tension), wcsph_surface_tension.rs:22-28 */
     SALVA_HIP_FORCE_CUSTOM = 7,      /* any other `impl NonPressureForce` (nonpressure_force.rs:10-30): runs on the host through
-                                        the callback of salva_hip_set_force_callback, at its place in the list */
-    SALVA_HIP_FORCE_BECKER2009 = 8   /* solver::Becker2009Elasticity::new(young_modulus, poisson_ratio, nonlinear_strain),
+                                        the callback of salva_hip_set_force_callback, at its place in the list.  A user with a
+                                        kernel of their own takes SALVA_HIP_FORCE_DEVICE instead: nothing crosses PCIe */
+    SALVA_HIP_FORCE_BECKER2009 = 8,  /* solver::Becker2009Elasticity::new(young_modulus, poisson_ratio, nonlinear_strain),
                                         becker2009_elasticity.rs:66-82: corotated SPH elasticity with a rest state of its own */
+    SALVA_HIP_FORCE_DEVICE = 9       /* any other `impl NonPressureForce` written as a kernel: the callback of
+                                        salva_hip_set_device_force_callback enqueues it on the world's stream, on the state where
+                                        it lies in device memory (SalvaHipDeviceView below), at its place in the list */
+};
+/* p[0] of a SALVA_HIP_FORCE_DEVICE entry: what the force needs besides the particles, as a sum of these (stored exactly in the float) */
+enum {
+    SALVA_HIP_DEVICE_NEEDS_FF = 1,      /* the fluid-fluid contact lists */
+    SALVA_HIP_DEVICE_NEEDS_FB = 2,      /* the fluid-boundary contact lists */
+    SALVA_HIP_DEVICE_NEEDS_KERNEL = 4   /* W_ij and grad W_ij of every contact of the lists asked for */
 };
 typedef struct SalvaHipForceDesc {
     int32_t kind;
@@ -98,7 +108,9 @@ typedef struct SalvaHipForceDesc {
      *                  (SALVA_HIP_KERNEL_*, 0 = CubicSplineKernel: the force's own type parameters).  The entry keeps its state
      *                  (rest positions, rest lists, volumes0, rotations) across salva_hip_set_fluid_forces calls that give entry k the
      *                  same kind and bit-identical p[]; any other entry k starts empty.  Not available in decomposed worlds
-     *                  (salva_hip_set_domain): the rest lists cross slabs. */
+     *                  (salva_hip_set_domain): the rest lists cross slabs.
+     * DEVICE:     p[0] SALVA_HIP_DEVICE_NEEDS_* bits (0 ... 7); p[1..6] are the user's and reach the kernel in SalvaHipDeviceView::params.
+     *                  Not available in decomposed worlds: ghost rows and ownership are not part of the view. */
     float p[7];
 } SalvaHipForceDesc;
 
@@ -287,6 +299,74 @@ int salva_hip_set_force_callback(SalvaHipWorld* world, SalvaHipForceCallback cb,
 int salva_hip_force_get_state(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz, float* densities);
 /* `fluid.accelerations[i] += acc[i]` */
 int salva_hip_force_add_accelerations(SalvaHipWorld* world, uint32_t slot, const float* accelerations_xyz);
+
+/* ---- User-defined `NonPressureForce`s on the device.  A SALVA_HIP_FORCE_DEVICE entry makes salva_hip_step call `cb` at the same
+ * point of the substep as the host arm above, but WITHOUT waiting for the stream: the library says where the substep's state lies in
+ * device memory and on which stream it is working, the callback enqueues its kernels there and returns.  Nothing crosses PCIe and
+ * nobody waits.  include/salva_hip_device.h holds what such a kernel needs (the kernels, the boundary reaction force).
+ *
+ * Lifetime: every pointer of the view may be used only by work enqueued on `stream` during the call; the arrays are the solver's own
+ * and are rewritten by the kernels the library enqueues next.  `acc` is the only fluid array a user kernel may write (add to it:
+ * gravity and the forces listed earlier are in it); `bforce_fx` only through atomic adds in the library's fixed-point unit.
+ * The working set holds the particles of ALL fluids in the order of this substep's cell sort; a kernel filters by `model`.
+ * `id[i]` is the particle's index over all fluids in host order (fluid 0's particles, then fluid 1's ...): what a user's own
+ * per-particle array is indexed by.  4-vectors are packed (16-byte aligned): row i at [4 i .. 4 i + 3].
+ * Contact tables (NULL unless a force of this substep asked for them in p[0]) are CSR over all n rows: row i holds entries
+ * [off[i], off[i + 1]); an entry is the SORTED index of the neighbour (a row of posm / vel / rho, or of bposv / bvel), the self
+ * contact included in ff as in the reference, neighbours of other fluids included.  ff_kern / fb_kern hold, per entry, the
+ * reference's Contact::gradient (x, y, z) and Contact::weight (w) for the world's kernel pair.  The tables are built once per
+ * substep, by the first force that asks, for the union of what the substep's device forces ask for.
+ * A world with such a force runs like one with a host force: its steps are not chained, speculated or pre-enqueued.
+ * A non-zero return aborts the step with SALVA_HIP_E_INVALID; an entry without a callback does the same. */
+#define SALVA_HIP_DEVICE_VIEW_VERSION 1
+#define SALVA_HIP_DEVICE_VIEW_BYTES 240
+typedef struct SalvaHipDeviceView {
+    uint32_t struct_size;            /* SALVA_HIP_DEVICE_VIEW_BYTES */
+    uint32_t version;                /* SALVA_HIP_DEVICE_VIEW_VERSION */
+    /* -- launch context */
+    void* stream;                    /* the world's hipStream_t */
+    uint32_t fluid_slot, force_index; /* whose force list, which entry */
+    float dt, inv_dt;                /* timestep.dt() / inv_dt() at this point: the previous substep's, as the host callback gets them */
+    float h, particle_radius;
+    int32_t kernel_density, kernel_gradient; /* SALVA_HIP_KERNEL_* */
+    float params[7];                 /* the entry's p[] */
+    uint32_t needs;                  /* p[0] as an integer */
+    /* -- the working set of all fluids, n rows in the order of this substep's cell sort */
+    uint32_t n, nfluids;
+    const float* posm;               /* 4 n: x, y, z, mass */
+    const float* vel;                /* 4 n: v + dv (what salva_hip_force_get_state hands out); the fourth component is not for users */
+    float* acc;                      /* 4 n: x, y, z, unused — writable */
+    const float* rho;                /* n: densities of this substep */
+    const uint32_t* model;           /* n: fluid slot of each row */
+    const uint32_t* id;              /* n: index over all fluids in host order */
+    const float* rho0;               /* nfluids: density0 of each fluid */
+    /* -- the boundary particles of all boundaries in their sorted order, nb rows */
+    uint32_t nb;
+    float bforce_scale;              /* force -> fixed point */
+    const float* bposv;              /* 4 nb: x, y, z, V_b */
+    const float* bvel;               /* 4 nb: x, y, z, the boundary slot as the BITS of the fourth float */
+    const uint32_t* bid;             /* nb: index over all boundaries in host order = row of bforce_fx */
+    uint64_t* bforce_fx;             /* 3 per boundary particle, host order: this step's reaction forces in fixed point; NULL when no
+                                        boundary wants forces */
+    const uint8_t* bwants;           /* per boundary slot: forces requested? */
+    /* -- contacts */
+    const uint64_t* ff_off;          /* n + 1 */
+    const uint32_t* ff_j;            /* sorted fluid index */
+    const uint64_t* fb_off;          /* n + 1 */
+    const uint32_t* fb_j;            /* sorted boundary index */
+    const float* ff_kern;            /* 4 per entry of ff_j: grad W_ij (x, y, z), W_ij */
+    const float* fb_kern;            /* 4 per entry of fb_j */
+} SalvaHipDeviceView;
+typedef int (*SalvaHipDeviceForceCallback)(void* user, SalvaHipWorld* world, const SalvaHipDeviceView* view);
+int salva_hip_set_device_force_callback(SalvaHipWorld* world, SalvaHipDeviceForceCallback cb, void* user);
+/* Inside the device callback only (SALVA_HIP_E_INVALID elsewhere): copies `bytes` bytes from device memory — a pointer of the view,
+ * or the user's own — to the host behind everything enqueued on the world's stream so far, and waits.  For debugging a user force
+ * and for tests; a production force does not call it.  The read-only getters of the local view (salva_hip_local_len,
+ * salva_hip_get_local, salva_hip_get_local_contacts) may be called there too and wait for the stream themselves. */
+int salva_hip_device_view_read(SalvaHipWorld* world, const void* device_src, void* host_dst, uint64_t bytes);
+/* What the device forces of the LAST salva_hip_step cost: out4 = {device callbacks made, contact-table builds, bytes of contact
+ * tables written, host waits made by the force loop on behalf of device forces (a table buffer that had to be released to grow)}. */
+int salva_hip_get_device_force_stats(const SalvaHipWorld* world, uint64_t out4[4]);
 
 /* ---- `CouplingManager` inside the substep loop (coupling_manager.rs:9-28; liquid_world.rs:85-147).
  * `LiquidWorld::step_with_coupling` calls `coupling.update_boundaries(&timestep, h, r, &hgrid, fluids, boundaries)` at the top of

@@ -108,6 +108,22 @@ struct DFSPHViscosity : NonPressureForce {  // viscosity/dfsph_viscosity.rs:85-1
     }
 };
 
+// Any other `impl NonPressureForce` written as a kernel (SALVA_HIP_FORCE_DEVICE, include/salva_hip.h): `solve` is called in the middle
+// of the substep, at the force's place in the list, with the substep's state where it lies in device memory; it enqueues its kernel
+// on view.stream (include/salva_hip_device.h) and returns 0.  `needs` = SALVA_HIP_DEVICE_NEEDS_* bits; `params` reach the kernel as
+// view.params[1..6].  This header stays free of HIP: the kernel and its launch live in the user's own HIP translation unit.
+struct DeviceForce : NonPressureForce {
+    uint32_t needs;
+    std::array<Real, 6> params{};
+    std::function<int(const SalvaHipDeviceView&)> solve;
+    DeviceForce(uint32_t needs_, std::function<int(const SalvaHipDeviceView&)> solve_, std::array<Real, 6> params_ = {})
+        : needs(needs_), params(params_), solve(std::move(solve_)) {}
+    SalvaHipForceDesc desc() const override {
+        SalvaHipForceDesc d{SALVA_HIP_FORCE_DEVICE, {(Real)needs, params[0], params[1], params[2], params[3], params[4], params[5]}};
+        return d;
+    }
+};
+
 // ---- pressure solvers: only the pub tuning fields exist on the host, the passes run on the device
 struct PressureSolver {
     int kind = SALVA_HIP_SOLVER_DFSPH;
@@ -871,8 +887,24 @@ class LiquidWorld {  // liquid_world.rs
         }
         std::vector<SalvaHipForceDesc> descs;
         for (auto& np : f.nonpressure_forces) descs.push_back(np->desc());
+        for (const SalvaHipForceDesc& d : descs)
+            if (d.kind == SALVA_HIP_FORCE_DEVICE && !device_force_installed_) {
+                check(salva_hip_set_device_force_callback(w_, &LiquidWorld::device_force_trampoline, this));
+                device_force_installed_ = true;
+            }
         check(salva_hip_set_fluid_forces(w_, slot, descs.data(), (uint32_t)descs.size()));
     }
+    // one callback for the world: the view says whose force it is (an exception must not cross the C boundary: it becomes an error code)
+    static int device_force_trampoline(void* user, SalvaHipWorld*, const SalvaHipDeviceView* view) {
+        try {
+            LiquidWorld& self = *static_cast<LiquidWorld*>(user);
+            auto* force = dynamic_cast<DeviceForce*>(self.fluids_.at(view->fluid_slot).nonpressure_forces.at(view->force_index).get());
+            return (force && force->solve) ? force->solve(*view) : 1;
+        } catch (...) {
+            return 1;
+        }
+    }
+    bool device_force_installed_ = false;
     void upload(Boundary& b, uint32_t slot) {
         if (!b.dirty_) return;
         const size_t n = b.num_particles();

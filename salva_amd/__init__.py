@@ -15,12 +15,14 @@ from .world import (  # noqa: F401
     CubicSplineKernel,
     DFSPHSolver,
     DFSPHViscosity,
+    DeviceForce,
     Fluid,
     He2014SurfaceTension,
     IISPHSolver,
     InteractionGroups,
     LiquidWorld,
     NonPressureForce,
+    PluginForce,
     Poly6Kernel,
     SpikyKernel,
     ViscosityKernel,
@@ -29,8 +31,8 @@ from .world import (  # noqa: F401
 )
 
 __all__ = [
-    "Akinci2013SurfaceTension", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "Fluid", "He2014SurfaceTension", "IISPHSolver",
-    "InteractionGroups", "LiquidWorld", "NonPressureForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "dist", "sampling", "scenes", "HostRayShape", "shape_surface_ray_sample", "shape_volume_ray_sample",
+    "Akinci2013SurfaceTension", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "DeviceForce", "Fluid", "He2014SurfaceTension", "IISPHSolver",
+    "InteractionGroups", "LiquidWorld", "NonPressureForce", "PluginForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "dist", "sampling", "scenes", "HostRayShape", "shape_surface_ray_sample", "shape_volume_ray_sample",
 ]
 
 

@@ -18,7 +18,8 @@ if os.environ.get("SALVA_HIP_LIB_VARIANT"):  # kernel experiments only (tools/va
 OK, E_HIP, E_INVALID, E_NUMERIC, E_CAPACITY = 0, -1, -2, -3, -4
 SOLVER_DFSPH, SOLVER_IISPH = 0, 1
 (FORCE_XSPH, FORCE_ARTIFICIAL, FORCE_AKINCI2013, FORCE_DFSPH_VISCOSITY, FORCE_HE2014, FORCE_WCSPH_TENSION, FORCE_CUSTOM,
- FORCE_BECKER2009) = 1, 2, 3, 4, 5, 6, 7, 8
+ FORCE_BECKER2009, FORCE_DEVICE) = 1, 2, 3, 4, 5, 6, 7, 8, 9
+DEVICE_NEEDS_FF, DEVICE_NEEDS_FB, DEVICE_NEEDS_KERNEL = 1, 2, 4  # p[0] of a FORCE_DEVICE entry
 DIRTY_POSITIONS, DIRTY_VELOCITIES, DIRTY_VOLUMES, DIRTY_ACCELERATIONS, DIRTY_ALL = 1, 2, 4, 8, 15
 (FIELD_DENSITY, FIELD_ALPHA, FIELD_NUM_FLUID_CONTACTS, FIELD_NUM_BOUNDARY_CONTACTS, FIELD_VELOCITY_CHANGE,
  FIELD_PRESSURE, FIELD_VOLUME, FIELD_ACCELERATION) = range(8)
@@ -49,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_create_mesh", "salva_hip_create_heightfield", "salva_hip_destroy_mesh", "salva_hip_sample_mesh",
     "salva_hip_add_particles_sampled_mesh", "salva_hip_set_boundary_sampling_from_mesh", "salva_hip_set_boundary_dynamic_sampling_mesh",
     "salva_hip_update_boundary_poses", "salva_hip_get_boundary_wrenches", "salva_hip_get_dcs_stats",
+    "salva_hip_set_device_force_callback", "salva_hip_device_view_read", "salva_hip_get_device_force_stats",
 ]
 
 
@@ -79,6 +81,25 @@ class ForceDesc(C.Structure):
 FORCE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float)
 # SalvaHipCouplingCallback: (user, world, phase, dt)
 COUPLING_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_float)
+
+
+class DeviceView(C.Structure):
+    """SalvaHipDeviceView (include/salva_hip.h): where the substep's state lies in device memory, for a FORCE_DEVICE entry."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32),
+                ("stream", C.c_void_p), ("fluid_slot", C.c_uint32), ("force_index", C.c_uint32), ("dt", C.c_float), ("inv_dt", C.c_float),
+                ("h", C.c_float), ("particle_radius", C.c_float), ("kernel_density", C.c_int32), ("kernel_gradient", C.c_int32),
+                ("params", C.c_float * 7), ("needs", C.c_uint32),
+                ("n", C.c_uint32), ("nfluids", C.c_uint32), ("posm", C.c_void_p), ("vel", C.c_void_p), ("acc", C.c_void_p),
+                ("rho", C.c_void_p), ("model", C.c_void_p), ("id", C.c_void_p), ("rho0", C.c_void_p),
+                ("nb", C.c_uint32), ("bforce_scale", C.c_float), ("bposv", C.c_void_p), ("bvel", C.c_void_p), ("bid", C.c_void_p),
+                ("bforce_fx", C.c_void_p), ("bwants", C.c_void_p),
+                ("ff_off", C.c_void_p), ("ff_j", C.c_void_p), ("fb_off", C.c_void_p), ("fb_j", C.c_void_p),
+                ("ff_kern", C.c_void_p), ("fb_kern", C.c_void_p)]
+
+
+DEVICE_VIEW_BYTES, DEVICE_VIEW_VERSION = 240, 1  # SALVA_HIP_DEVICE_VIEW_BYTES / _VERSION
+# SalvaHipDeviceForceCallback: (user, world, view)
+DEVICE_FORCE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DeviceView))
 
 
 class RigidPose(C.Structure):
@@ -240,6 +261,10 @@ def lib():
     L.salva_hip_get_dcs_stats.argtypes = [vp, C.POINTER(u64)]
     L.salva_hip_set_force_callback.argtypes = [vp, FORCE_CALLBACK, vp]
     L.salva_hip_set_coupling_callback.argtypes = [vp, COUPLING_CALLBACK, vp]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_set_device_force_callback"):
+        L.salva_hip_set_device_force_callback.argtypes = [vp, DEVICE_FORCE_CALLBACK, vp]
+        L.salva_hip_device_view_read.argtypes = [vp, vp, vp, u64]
+        L.salva_hip_get_device_force_stats.argtypes = [vp, C.POINTER(u64)]
     L.salva_hip_force_get_state.argtypes = [vp, u32, fp, fp, fp]
     L.salva_hip_force_add_accelerations.argtypes = [vp, u32, fp]
     L.salva_hip_set_fluid_field.argtypes = [vp, u32, i32, fp]

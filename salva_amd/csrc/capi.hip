@@ -335,6 +335,30 @@ int salva_hip_set_force_callback(SalvaHipWorld* world, SalvaHipForceCallback cb,
     });
 }
 
+int salva_hip_set_device_force_callback(SalvaHipWorld* world, SalvaHipDeviceForceCallback cb, void* user) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        world->w->set_device_force_callback(cb, user, world);
+        return SALVA_HIP_OK;
+    });
+}
+static_assert(sizeof(SalvaHipDeviceView) == SALVA_HIP_DEVICE_VIEW_BYTES, "SalvaHipDeviceView: the header's size constant is what the mirrors check");
+int salva_hip_device_view_read(SalvaHipWorld* world, const void* device_src, void* host_dst, uint64_t bytes) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        world->w->device_view_read(device_src, host_dst, bytes);
+        return SALVA_HIP_OK;
+    });
+}
+int salva_hip_get_device_force_stats(const SalvaHipWorld* world, uint64_t out4[4]) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !out4) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        world->w->get_device_force_stats(out4);
+        return SALVA_HIP_OK;
+    });
+}
+
 int salva_hip_set_coupling_callback(SalvaHipWorld* world, SalvaHipCouplingCallback cb, void* user) { WorldLock _lk(world);
     return guarded([&]() -> int {
         if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");

@@ -412,21 +412,10 @@ __global__ __launch_bounds__(BLOCK) void k_export_contacts(StepCtx c, const uint
     if (i >= c.n || c.model[i] != slot) return;
     const uint32_t host_local = c.perm[i] - model_off[slot];
     uint64_t o = offsets[host_local];
-    const uint32_t cnt = boundary ? c.nfb[i] : c.nff[i];
-    const uint32_t tile = keys[i] / TCELLS;
-    // (the slot that owns particle i: the tile's only one, or — a split tile, tile.h Tile::part — the part whose range holds it)
-    uint32_t slot_t = c.tile_rank[tile];
-    for (const uint32_t last = c.tile_rank[tile + 1]; slot_t + 1 < last && i >= c.slot_desc[slot_t].z; ++slot_t) {}
-    const uint32_t own_begin = c.slot_desc[slot_t].y;
-    const TileAcc a0 = c.tile_off[slot_t];
-    const uint32_t gs = a0.nsl + (i - own_begin) / WAVE, lane = (i - own_begin) % WAVE;
-    const uint32_t cap = boundary ? c.cap_fb : c.cap_ff;
-    const uint32_t* __restrict__ p = (boundary ? c.nbr_fb : c.nbr_ff) + (size_t)gs * cap * WAVE + 4u * lane;
-    const uint64_t hoff = boundary ? (c.halo_stride ? (uint64_t)slot_t * c.bhalo_stride : a0.sb)
-                                   : (c.halo_stride ? (uint64_t)slot_t * c.halo_stride : a0.s);
-    for (uint32_t k = 0; k < cnt; ++k) {
-        const uint32_t d = p[ellq(k >> 1)];
-        const uint32_t s = (k & 1u) ? (d >> 16) : (d & 0xffffu);
+    const ContactRow row = contact_row(c, keys, i, boundary);  // (tile.h: the one walk from a particle to its list)
+    const uint64_t hoff = row.hoff;
+    for (uint32_t k = 0; k < row.cnt; ++k) {
+        const uint32_t s = contact_row_entry(row.p, k);
         if (boundary) {
             const uint32_t g = c.bhalo_src[hoff + s];
             const uint32_t bm = __float_as_uint(c.bvel[g].w);
@@ -448,21 +437,10 @@ __global__ __launch_bounds__(BLOCK) void k_export_contacts_local(StepCtx c, cons
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= c.n) return;
     uint64_t o = offsets[i];
-    const uint32_t cnt = boundary ? c.nfb[i] : c.nff[i];
-    const uint32_t tile = keys[i] / TCELLS;
-    // (the slot that owns particle i: the tile's only one, or — a split tile, tile.h Tile::part — the part whose range holds it)
-    uint32_t slot_t = c.tile_rank[tile];
-    for (const uint32_t last = c.tile_rank[tile + 1]; slot_t + 1 < last && i >= c.slot_desc[slot_t].z; ++slot_t) {}
-    const uint32_t own_begin = c.slot_desc[slot_t].y;
-    const TileAcc a0 = c.tile_off[slot_t];
-    const uint32_t gs = a0.nsl + (i - own_begin) / WAVE, lane = (i - own_begin) % WAVE;
-    const uint32_t cap = boundary ? c.cap_fb : c.cap_ff;
-    const uint32_t* __restrict__ p = (boundary ? c.nbr_fb : c.nbr_ff) + (size_t)gs * cap * WAVE + 4u * lane;
-    const uint64_t hoff = boundary ? (c.halo_stride ? (uint64_t)slot_t * c.bhalo_stride : a0.sb)
-                                   : (c.halo_stride ? (uint64_t)slot_t * c.halo_stride : a0.s);
-    for (uint32_t k = 0; k < cnt; ++k) {
-        const uint32_t d = p[ellq(k >> 1)];
-        const uint32_t s = (k & 1u) ? (d >> 16) : (d & 0xffffu);
+    const ContactRow row = contact_row(c, keys, i, boundary);  // (tile.h: the one walk from a particle to its list)
+    const uint64_t hoff = row.hoff;
+    for (uint32_t k = 0; k < row.cnt; ++k) {
+        const uint32_t s = contact_row_entry(row.p, k);
         if (boundary) {
             const uint32_t g = c.bhalo_src[hoff + s];
             const uint32_t bm = __float_as_uint(c.bvel[g].w);

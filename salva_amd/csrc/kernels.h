@@ -42,6 +42,12 @@ void launch_export_contacts(const StepCtx& c, const uint32_t* keys, uint32_t slo
                             const uint32_t* model_off, const uint32_t* bmodel_off, uint32_t* out_model, uint32_t* out_j, hipStream_t s);
 void launch_export_contacts_local(const StepCtx& c, const uint32_t* keys, int boundary, const uint64_t* offsets, const uint32_t* bmodel_off,
                                   uint32_t* out_model, uint32_t* out_j, hipStream_t s);
+// userforce.hip: the contact tables of device forces (SalvaHipDeviceView).  off[0 .. n] = exclusive scan of counts (the scan's temporary
+// storage: scan_temp_bytes(n + 1)); then per entry the neighbour's sorted index and, with out_kern, (grad W_ij, W_ij).  Entries at or
+// beyond `capacity` are not written.
+void launch_contact_offsets(uint32_t n, const uint32_t* counts, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s);
+void launch_contact_tables(const StepCtx& c, const uint32_t* keys, int boundary, const uint64_t* off, uint64_t capacity, uint32_t* out_j,
+                           float4* out_kern, hipStream_t s);
 void launch_unsort_u32(uint32_t n, const uint32_t* perm, const uint32_t* in, uint32_t* out, hipStream_t s);
 void launch_unsort_u32_as_f32(uint32_t n, const uint32_t* perm, const uint32_t* in, float* out, hipStream_t s);
 void launch_unsort_f4(uint32_t n, const uint32_t* perm, const float4* in, float4* out, hipStream_t s);

@@ -1154,5 +1154,35 @@ __device__ __forceinline__ uint32_t boundary_sorted_of_slot(const StepCtx& c, co
     return c.bhalo_src[t.hboff + slot];
 }
 
+// The walk from a sorted particle index to its contact list, for the kernels that do not run over tiles (the contact exports of
+// grid.hip, the contact tables of userforce.hip): the slot that owns particle i, its slice and lane there, and the row of the slot
+// table its entries index.  Entry k of the list is halo slot contact_row_entry(r, k); (b)halo_src[r.hoff + that] is the sorted index
+// of the neighbour.  Split tiles, fixed-stride rows and the referenced-only halo are all in here and nowhere else.
+struct ContactRow {
+    const uint32_t* p;   // the particle's first list dword (dword q: p[ellq(q)])
+    uint64_t hoff;       // first entry of its slot's row of halo_src / bhalo_src
+    uint32_t cnt;        // entries
+};
+__device__ __forceinline__ ContactRow contact_row(const StepCtx& c, const uint32_t* __restrict__ keys, uint32_t i, int boundary) {
+    const uint32_t tile = keys[i] / TCELLS;
+    // (the slot that owns particle i: the tile's only one, or — a split tile, Tile::part — the part whose range holds it)
+    uint32_t slot_t = c.tile_rank[tile];
+    for (const uint32_t last = c.tile_rank[tile + 1]; slot_t + 1 < last && i >= c.slot_desc[slot_t].z; ++slot_t) {}
+    const uint32_t own_begin = c.slot_desc[slot_t].y;
+    const TileAcc a0 = c.tile_off[slot_t];
+    const uint32_t gs = a0.nsl + (i - own_begin) / WAVE, lane = (i - own_begin) % WAVE;
+    const uint32_t cap = boundary ? c.cap_fb : c.cap_ff;
+    ContactRow r;
+    r.p = (boundary ? c.nbr_fb : c.nbr_ff) + (size_t)gs * cap * WAVE + 4u * lane;
+    r.hoff = boundary ? (c.halo_stride ? (uint64_t)slot_t * c.bhalo_stride : a0.sb)
+                      : (c.halo_stride ? (uint64_t)slot_t * c.halo_stride : a0.s);
+    r.cnt = boundary ? c.nfb[i] : c.nff[i];
+    return r;
+}
+__device__ __forceinline__ uint32_t contact_row_entry(const uint32_t* __restrict__ p, uint32_t k) {
+    const uint32_t d = p[ellq(k >> 1)];
+    return (k & 1u) ? (d >> 16) : (d & 0xffffu);
+}
+
 #endif  // __HIPCC__
 }  // namespace salva

@@ -134,6 +134,10 @@ class World {
     void force_get_state(uint32_t slot, float* positions, float* velocities, float* densities);
     void force_add_accelerations(uint32_t slot, const float* acc);
     bool in_force_callback() const { return in_force_cb; }
+    // user-defined forces as kernels (SALVA_HIP_FORCE_DEVICE; userforce.hip)
+    void set_device_force_callback(SalvaHipDeviceForceCallback cb, void* user, SalvaHipWorld* owner) { dforce_cb = cb; dforce_user = user; dforce_owner = owner; }
+    void device_view_read(const void* device_src, void* host_dst, uint64_t bytes);
+    void get_device_force_stats(uint64_t out[4]) const { for (int k = 0; k < 4; ++k) out[k] = dforce_stats[k]; }
     // CouplingManager::update_boundaries / transmit_forces inside the substep loop (include/salva_hip.h, salva_hip_set_coupling_callback)
     void set_coupling_callback(SalvaHipCouplingCallback cb, void* user, SalvaHipWorld* owner) { coupling_cb = cb; coupling_user = user; coupling_owner = owner; }
     void set_fluid_field(uint32_t slot, int field, const float* data);
@@ -249,6 +253,9 @@ class World {
     template <typename Arrived> void spin_until(Arrived&& arrived, const char* drained);  // ... for a host-mapped word (world_step.hip)
     void run_forces(const StepCtx& c);
     void run_elasticity(const StepCtx& c, uint32_t slot, uint32_t force);
+    void run_device_force(const StepCtx& c, uint32_t slot, uint32_t force);
+    void build_contact_tables(const StepCtx& c, uint32_t needs);
+    bool has_user_force() const { return has_force(SALVA_HIP_FORCE_CUSTOM) || has_force(SALVA_HIP_FORCE_DEVICE); }  // a force the library cannot see into
     ElasticState& elastic_state(uint32_t slot, uint32_t force);
     bool elastic_stale() const;  // some Becker2009Elasticity entry (re)builds its rest state in the next step
     bool has_elastic() const;
@@ -295,6 +302,7 @@ class World {
         bool chain_pending = false, chain_div_pending = false;
         int chain_batch[2] = {0, 0};    // iterations enqueued for the divergence / the pressure solve (where a continuation starts)
         float chain_dt_prev = 0.0f, chain_inv_dt_prev = 0.0f;  // TimestepManager::{dt, inv_dt} as the chained attempt found them
+        uint32_t dforce_tables = 0;  // SALVA_HIP_DEVICE_NEEDS_* the contact tables hold for this pass's lists (0: not built)
     };
     // ... on top of what the substep decides before its first pass, the same for every attempt
     struct Pass : Attempt {
@@ -534,6 +542,13 @@ class World {
     void* force_user = nullptr;
     SalvaHipWorld* force_owner = nullptr;
     bool in_force_cb = false;
+    SalvaHipDeviceForceCallback dforce_cb = nullptr;
+    void* dforce_user = nullptr;
+    SalvaHipWorld* dforce_owner = nullptr;
+    bool in_dforce_cb = false;
+    uint64_t dforce_stats[4] = {0, 0, 0, 0};  // of the last step: callbacks, table builds, table bytes written, host waits
+    // the contact tables of device forces (SalvaHipDeviceView::ff_off ...): CSR over the working set, built at most once per pass
+    struct ContactTables { DevBuf<uint64_t> off[2]; DevBuf<uint32_t> j[2]; DevBuf<float4> kern[2]; } dtab;  // [0] fluid-fluid, [1] fluid-boundary
     SalvaHipCouplingCallback coupling_cb = nullptr;
     void* coupling_user = nullptr;
     SalvaHipWorld* coupling_owner = nullptr;

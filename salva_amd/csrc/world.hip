@@ -483,8 +483,15 @@ uint64_t World::delete_particles(uint32_t slot, const uint8_t* mask) {
 void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
     if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
     for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_BECKER2009)
+        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_DEVICE)
             throw HipError(SALVA_HIP_E_INVALID, "unknown non-pressure force kind (only built-ins run on the device)");
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_DEVICE) {
+            if (comm)  // ghost rows and the local view's ownership rules are not part of SalvaHipDeviceView
+                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE is not available in a decomposed world (salva_hip_set_domain)");
+            if (!(f[k].p[0] >= 0.0f && f[k].p[0] <= 7.0f && f[k].p[0] == (float)(uint32_t)f[k].p[0]))
+                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE: p[0] must be a sum of SALVA_HIP_DEVICE_NEEDS_* bits (0 ... 7)");
+        }
     for (uint32_t k = 0; k < nf; ++k)
         if (f[k].kind == SALVA_HIP_FORCE_BECKER2009) {
             if (comm)  // the rest lists cross slabs and have no ghost protocol

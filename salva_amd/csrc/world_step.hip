@@ -394,6 +394,7 @@ void World::run_forces(const StepCtx& c) {
                     break;
                 }
                 case SALVA_HIP_FORCE_BECKER2009: run_elasticity(c, f, (uint32_t)(&d - fluids[f].forces.data())); break;
+                case SALVA_HIP_FORCE_DEVICE: run_device_force(c, f, (uint32_t)(&d - fluids[f].forces.data())); break;
                 case SALVA_HIP_FORCE_AKINCI2013:
                     launch_akinci_normals(c, lds, f, stream);
                     // (normals of the inner ghost plane are complete: rho was refreshed on both planes)
@@ -518,7 +519,7 @@ float World::choose_substep(const StepCtx& c) {
 // host force callback, no force with a solve of its own (DFSPHViscosity).  SALVA_HIP_NO_CHAIN=1 switches it off (A/B, tests).
 bool World::chain_allowed() const {
     if (sw.chain_off || comm || cfl_mode || pass.spec_mode || prm.solver != SALVA_HIP_SOLVER_DFSPH) return false;
-    if (has_force(SALVA_HIP_FORCE_CUSTOM) || has_force(SALVA_HIP_FORCE_DFSPH_VISCOSITY)) return false;
+    if (has_user_force() || has_force(SALVA_HIP_FORCE_DFSPH_VISCOSITY)) return false;  // (a user's kernel cannot honour the gate either)
     if (elastic_stale()) return false;  // (the rest build reads its contact total back)
     return true;
 }
@@ -699,6 +700,7 @@ int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
     SalvaHipStepStats st{};
     st.nparticles = n;
     for (uint64_t& v : dcs_stats) v = 0;
+    for (uint64_t& v : dforce_stats) v = 0;
     {   // self.counters.reset() (liquid_world.rs:73); the pass counters of this implementation are cumulative, like World::tally:
         // a counter added to SalvaHipCounters that is to survive the step is named here
         const SalvaHipCounters last = counters;
@@ -1259,7 +1261,7 @@ void World::publish_end_of_step(const PassSnapshot& snap) {
     const Pass& p = pass;
     static_assert(offsetof(Readback, bbox) == offsetof(Readback, flags) + sizeof(uint32_t), "flags and bbox travel in one copy");
     const bool stable = bbox_used_valid && memcmp(bbox_used_last, snap.bbox, sizeof(snap.bbox)) == 0;
-    const bool want_pre = !sw.pre_off && p.attempt == 0 && !p.spec && !comm && !p.timers && !p.has_dyn && !has_force(SALVA_HIP_FORCE_CUSTOM) && !cfl_mode &&
+    const bool want_pre = !sw.pre_off && p.attempt == 0 && !p.spec && !comm && !p.timers && !p.has_dyn && !has_user_force() && !cfl_mode &&
                           counting_sort_for(p.gs.ncf, n) && stable && n > 0 && p.gs.nslots_bound > 0;
     memcpy(bbox_used_last, snap.bbox, sizeof(snap.bbox)); bbox_used_valid = true;
     PrePub pp{want_pre ? 1 : 0, p.chain_pending ? 1 : 0, {snap.bbox[0], snap.bbox[1], snap.bbox[2], snap.bbox[3], snap.bbox[4], snap.bbox[5]}};
@@ -1496,7 +1498,7 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
     // a pass can be repeated from the untouched pre-sort buffers iff it has no side effect outside the world's own arrays
     // (a communicator of one rank exchanges nothing: its passes are as repeatable as the plain world's)
     const bool solo = comm && !comm->has_lo() && !comm->has_hi();
-    p.can_redo = (!comm || solo) && !any_wants_forces && !has_force(SALVA_HIP_FORCE_CUSTOM) && !p.has_dyn;
+    p.can_redo = (!comm || solo) && !any_wants_forces && !has_user_force() && !p.has_dyn;  // (a user's force may keep state of its own)
     // (mass_known: the kernels of a pass are chosen by StepCtx::mass_uniform, which a speculative pass — it does not wait for the
     // publication that carries it — can only inherit; a host edit since the last publication may have changed the masses)
     p.can_speculate = !sw.spec_off && p.can_redo && !b_dirty && pred_valid && pred_n == n && mass_known;

@@ -77,6 +77,45 @@ class NonPressureForce:
         return d
 
 
+class DeviceForce(NonPressureForce):
+    """Any other `impl NonPressureForce` written as a kernel (include/salva_hip.h, SALVA_HIP_FORCE_DEVICE): `solve_device(view)` is
+    called in the middle of the substep, at the force's place in the list, WITHOUT a wait; `view` is a `_lib.DeviceView` — where the
+    substep's state lies in device memory and the stream it is being worked on.  The method enqueues its kernel there (through a
+    library of the user's: see PluginForce) and returns 0 or None; any other return value, or an exception, aborts the step.
+    `needs`: `_lib.DEVICE_NEEDS_*` bits — the contact tables the kernel wants; `params`: up to six floats, view.params[1:]."""
+
+    def __init__(self, needs: int = 0, params: Sequence[float] = ()):
+        if not 0 <= int(needs) <= 7 or len(params) > 6:
+            raise ValueError("needs is a sum of DEVICE_NEEDS_* bits (0..7); at most six parameters")
+        self.needs, self.params = int(needs), [float(x) for x in params]
+
+    def solve_device(self, view: "L.DeviceView"):
+        raise NotImplementedError("a DeviceForce must implement solve_device(view)")
+
+    def _desc(self):
+        d = L.ForceDesc()
+        d.kind = L.FORCE_DEVICE
+        d.p[0] = float(self.needs)
+        for k, x in enumerate(self.params):
+            d.p[1 + k] = x
+        return d
+
+
+class PluginForce(DeviceForce):
+    """The ready-made DeviceForce: `int symbol(const SalvaHipDeviceView*)` of a shared library built with hipcc against
+    include/salva_hip_device.h (examples/device_forces3.hip -> examples/libdevice_forces3.so)."""
+
+    def __init__(self, path: str, symbol: str, needs: int = 0, params: Sequence[float] = ()):
+        super().__init__(needs, params)
+        self.path, self.symbol = path, symbol
+        self._fn = getattr(C.CDLL(path), symbol)
+        self._fn.argtypes = [C.POINTER(L.DeviceView)]
+        self._fn.restype = C.c_int
+
+    def solve_device(self, view):
+        return self._fn(C.byref(view))
+
+
 class TimestepView:
     """The two TimestepManager getters forces use (timestep_manager.rs:60-72)."""
 
@@ -906,6 +945,8 @@ class LiquidWorld:
             descs[k] = force._desc()
             if descs[k].kind == L.FORCE_CUSTOM:
                 self._install_force_callback()
+            if descs[k].kind == L.FORCE_DEVICE:
+                self._install_device_force_callback()
         if f._resized or f._dirty:
             n = f.num_particles()
             dirty = L.DIRTY_ALL if f._resized else f._dirty
@@ -1061,6 +1102,39 @@ class LiquidWorld:
         self._force_cb = L.FORCE_CALLBACK(callback)
         self._force_cb_error = None
         L.check(self._L.salva_hip_set_force_callback(self._h, self._force_cb, None))
+
+    # ---- NonPressureForce::solve as a kernel of the user's (SALVA_HIP_FORCE_DEVICE): one trampoline for the world
+    def _install_device_force_callback(self):
+        if getattr(self, "_device_force_cb", None) is not None:
+            return
+
+        def callback(_user, _world, view):
+            try:
+                v = view.contents
+                f = next(x for x in self._fluids if x._slot == v.fluid_slot)
+                rc = f.nonpressure_forces[v.force_index].solve_device(v)
+                return int(rc or 0)
+            except BaseException as e:  # noqa: BLE001 - reported through the step's error
+                self._force_cb_error = e
+                return 1
+
+        self._device_force_cb = L.DEVICE_FORCE_CALLBACK(callback)
+        self._force_cb_error = getattr(self, "_force_cb_error", None)
+        L.check(self._L.salva_hip_set_device_force_callback(self._h, self._device_force_cb, None))
+
+    def device_view_read(self, device_ptr, dtype, count) -> np.ndarray:
+        """Inside DeviceForce.solve_device only: `count` elements of `dtype` from device memory (a pointer of the view), copied behind
+        the world's stream, waited for.  For debugging a device force and for tests."""
+        out = np.zeros(int(count), dtype)
+        if out.nbytes:
+            L.check(self._L.salva_hip_device_view_read(self._h, device_ptr, out.ctypes.data, out.nbytes))
+        return out
+
+    def device_force_stats(self):
+        """(device callbacks, contact-table builds, bytes of contact tables written, host waits) of the last step."""
+        out = (C.c_uint64 * 4)()
+        L.check(self._L.salva_hip_get_device_force_stats(self._h, out))
+        return tuple(int(x) for x in out)
 
     # ---- the working set as it is (include/salva_hip.h "local view"): what a rank of a decomposed run can look at
     def local_view(self):
