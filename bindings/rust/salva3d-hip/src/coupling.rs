@@ -25,6 +25,9 @@ pub enum ColliderSampling {
     /// (`crate::sampling::Mesh::id`, `salva_hip_set_boundary_dynamic_sampling_mesh`): the projection runs there as well, no
     /// callback.  The collider's pose places the mesh.
     DynamicContactSamplingMesh(u32),
+    /// The same for a collider whose shape is a compound that lives on the device (`crate::sampling::Compound::id`,
+    /// `salva_hip_set_boundary_dynamic_sampling_compound`).  The collider's pose places the compound.
+    DynamicContactSamplingCompound(u32),
 }
 
 /// What the host-shape callbacks see: the collider's shape and its pose as of this step's `update_boundaries`.
@@ -246,6 +249,9 @@ impl FluidsPipeline {
                     })?,
                     ColliderSampling::DynamicContactSamplingMesh(mesh) => {
                         check(unsafe { ffi::salva_hip_set_boundary_dynamic_sampling_mesh(raw, slot, *mesh, groups.memberships.bits(), groups.filter.bits()) })?
+                    }
+                    ColliderSampling::DynamicContactSamplingCompound(compound) => {
+                        check(unsafe { ffi::salva_hip_set_boundary_dynamic_sampling_compound(raw, slot, *compound, groups.memberships.bits(), groups.filter.bits()) })?
                     }
                     ColliderSampling::DynamicContactSampling => {
                         let builtin = if let Some(b) = collider.shape().as_ball() {

@@ -119,6 +119,48 @@ impl Mesh {
     }
 }
 
+/// One part of a [`Compound`]: a built-in shape (`ffi::SalvaHipShape`: ball, cuboid, capsule (y), cylinder) or a [`Mesh`] of the same
+/// world, with its pose in the compound's frame.
+pub enum CompoundPartShape<'a> {
+    Shape(ffi::SalvaHipShape),
+    Mesh(&'a Mesh),
+}
+
+/// parry's `Compound` on the device (`salva_hip_create_compound`): 1 to 64 posed parts.  From a parry compound: one
+/// part per `(part_pos, shape)` of `compound.shapes()`, a convex part handed over as the oriented triangle mesh of its hull.  Belongs
+/// to the world it was created in; `destroy` hands it back (refused while a dynamically sampled boundary still uses it).  Ray
+/// sampling of a compound is not on the device.
+pub struct Compound {
+    id: u32,
+}
+
+impl Compound {
+    pub fn new(world: &mut LiquidWorld, parts: &[(CompoundPartShape, Isometry<Real>)]) -> Result<Compound, Error> {
+        let raw: Vec<ffi::SalvaHipCompoundPart> = parts
+            .iter()
+            .map(|(shape, pos)| {
+                let (kind, params, mesh) = match shape {
+                    CompoundPartShape::Shape(s) => (s.kind, s.params, 0),
+                    CompoundPartShape::Mesh(m) => (ffi::SALVA_HIP_SHAPE_MESH, [0.0; 3], m.id()),
+                };
+                let q = pos.rotation.coords;
+                ffi::SalvaHipCompoundPart { kind, params, mesh, translation: [pos.translation.x, pos.translation.y, pos.translation.z], rotation_ijkw: [q.x, q.y, q.z, q.w] }
+            })
+            .collect();
+        let mut id = 0u32;
+        check(unsafe { ffi::salva_hip_create_compound(world.raw(), raw.as_ptr(), raw.len() as u32, &mut id) })?;
+        Ok(Compound { id })
+    }
+
+    pub fn id(&self) -> u32 {
+        self.id
+    }
+
+    pub fn destroy(self, world: &mut LiquidWorld) -> Result<(), Error> {
+        check(unsafe { ffi::salva_hip_destroy_compound(world.raw(), self.id) })
+    }
+}
+
 fn sample_mesh(world: &mut LiquidWorld, mesh: &Mesh, particle_rad: Real, mode: i32) -> Result<Vec<Point<Real>>, Error> {
     let raw = world.raw();
     let n = unsafe { ffi::salva_hip_sample_mesh(raw, mesh.id, particle_rad, mode, 0, std::ptr::null_mut()) };

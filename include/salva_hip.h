@@ -577,7 +577,8 @@ int64_t salva_hip_particles_intersecting_host_shape(SalvaHipWorld* world, const 
  * wrench on the collider is the sum of the ranks' salva_hip_get_boundary_wrench. */
 int salva_hip_set_boundary_dynamic_sampling(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* collider_shape,
                                             uint32_t memberships, uint32_t filter);
-/* The same arm for every other parry shape (triangle mesh, height field, convex polyhedron, compound, ...): the loop is the
+/* The same arm for every other parry shape (convex polyhedron, round shapes, ...; meshes, height fields and compounds have device
+ * arms of their own below): the loop is the
  * same, the two calls into parry stay on the host.  Inside every salva_hip_step, on the calling thread and at the same point
  * of the step, the library calls `aabb` once (`collider.shape().compute_aabb(collider.position())`), copies the predicted
  * positions of the fluid particles that pass the reference's two box tests (fluids_pipeline.rs:204-211) to the host, calls
@@ -615,7 +616,7 @@ int salva_hip_get_boundary_sources(SalvaHipWorld* world, uint32_t slot, uint32_t
 int salva_hip_get_dist_timing(const SalvaHipWorld* world, double out4[4]);
 /* What DynamicContactSampling did inside the LAST salva_hip_step: out4 = {passes over the fluid particles, host waits, colliders
  * that went through a batched pass, boundary particles emitted}.  Consecutive dynamically sampled boundaries whose collider shape is
- * on the device (built-in shapes, meshes, height fields) share ONE pass and ONE wait per step; a host shape between them splits the
+ * on the device (built-in shapes, meshes, height fields, compounds) share ONE pass and ONE wait per step; a host shape between them splits the
  * run.  SALVA_HIP_NO_DCS_BATCH=1 (read when the world is created) gives every collider a pass of its own, as do decomposed worlds. */
 int salva_hip_get_dcs_stats(const SalvaHipWorld* world, uint64_t out4[4]);
 
@@ -758,7 +759,7 @@ int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_
  * vertex indices per triangle.  SALVA_HIP_MESH_ORIENTED states that the mesh is closed and wound consistently (counter-clockwise
  * seen from outside): such a mesh gets pseudo-normals and tells inside from outside; any other mesh is a surface with no inside.
  * SALVA_HIP_E_INVALID: an index >= nv, nt == 0, a non-finite vertex, nrows < 2 or ncols < 2, destroying a mesh that is still the
- * collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it).
+ * collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it) or a part of a compound.
  * A height field is parry 0.18's HeightField as triangles: vertex (i, j) = ((j / (ncols - 1) - 0.5) sx, heights[i][j] sy,
  * (i / (nrows - 1) - 0.5) sz), two triangles per cell, (p00, p10, p11) and (p00, p11, p01) with pab the corner in row i + a, column
  * j + b; never oriented. */
@@ -784,6 +785,47 @@ int64_t salva_hip_set_boundary_sampling_from_mesh(SalvaHipWorld* world, uint32_t
  * a height field): such a collider samples contacts and pushes nothing out.  Not available in a running decomposed world. */
 int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
                                                  uint32_t filter);
+
+/* ---- Compound colliders on the device: parry's `Compound`, which is what a dynamic body that is neither a primitive
+ * nor a mesh usually is in rapier - a hull of cuboids, a ring of slabs, a convex decomposition handed over as oriented meshes.  A
+ * compound is a list of 1 .. 64 posed parts; a part is a ball, a cuboid, a capsule, a cylinder (params as in SalvaHipShape) or a mesh
+ * or height field of the same world (`mesh`: its handle; params are ignored).  It belongs to the world that created it, shares
+ * ownership of its meshes the way a boundary slot does, and lives until salva_hip_destroy_compound or the world's end.
+ * The projection is a reading of parry 0.18's Compound::project_local_point_and_get_feature with solid = false: every part projects
+ * the point on its own boundary (point -> part frame -> projection -> compound frame), the nearest projection wins, ties go to the
+ * lowest part index, and is_inside is that part's alone: a point deep inside part A but nearer to the surface of a part B it lies
+ * outside of is reported outside, on B.
+ * SALVA_HIP_E_INVALID: nparts == 0 or > SALVA_HIP_COMPOUND_MAX_PARTS; a part kind other than the five above (no nesting, no host
+ * parts); non-positive or non-finite params; a non-finite translation or a rotation that is not unit within 1e-3; an unknown mesh
+ * handle; destroying a mesh that a compound still names; destroying a compound that is still the collider of a dynamically sampled
+ * boundary (salva_hip_clear_boundary_sampling, a re-registration or the boundary's removal release it).
+ * Out of scope: ray sampling of a compound (rays are axis-aligned in the compound's frame, not in a rotated part's: it stays with
+ * salva_hip_sample_host_shape), decomposed worlds, nested compounds, convex-hull construction (hand the hull over as an oriented mesh). */
+enum { SALVA_HIP_SHAPE_COMPOUND = 6 };            /* never passed in a SalvaHipShape */
+enum { SALVA_HIP_COMPOUND_MAX_PARTS = 64 };
+typedef struct SalvaHipCompoundPart {
+    int32_t kind;            /* BALL, CUBOID, CAPSULE, CYLINDER or MESH */
+    float params[3];         /* as SalvaHipShape; ignored for MESH */
+    uint32_t mesh;           /* handle of salva_hip_create_mesh / _create_heightfield when kind == MESH */
+    float translation[3];    /* the part's pose in the compound's frame */
+    float rotation_ijkw[4];
+} SalvaHipCompoundPart;
+int salva_hip_create_compound(SalvaHipWorld* world, const SalvaHipCompoundPart* parts, uint32_t nparts, uint32_t* compound_out);
+int salva_hip_destroy_compound(SalvaHipWorld* world, uint32_t compound);
+/* salva_hip_set_boundary_dynamic_sampling for a compound collider, entirely on the device; the pose given to
+ * salva_hip_update_boundary_pose places the compound.  In a batched run (salva_hip_get_dcs_stats) a compound counts like any device
+ * shape.  Not available in a running decomposed world or inside a force callback. */
+int salva_hip_set_boundary_dynamic_sampling_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
+                                                     uint32_t filter);
+/* salva_hip_particles_intersecting_shape for a posed compound and for a posed mesh, entirely on the device.  A compound's solid
+ * distance is the smallest of its parts'; an oriented mesh's is 0 inside and the distance to the closest point outside.  A mesh
+ * without SALVA_HIP_MESH_ORIENTED has no solid distance: SALVA_HIP_E_INVALID for it and for a compound with such a part - those go
+ * through salva_hip_particles_intersecting_host_shape.  Not available in a running decomposed world or inside a force callback. */
+int64_t salva_hip_particles_intersecting_compound(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
+                                                  uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                                                  uint32_t* indices);
+int64_t salva_hip_particles_intersecting_mesh(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
+                                              uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices);
 
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);

@@ -246,6 +246,39 @@ class Mesh {
     uint32_t id_ = 0;
 };
 
+// parry's Compound on the device (salva_hip_create_compound): a list of 1 .. 64 posed parts, each a ball, a cuboid, a
+// capsule, a cylinder or a Mesh of the same world; RAII over the handle.  Accepted by Boundary::dynamic_compound and
+// LiquidWorld::particles_intersecting_shape.  Belongs to the world it was created in and must be destroyed before it and before the
+// meshes it names; a compound that is still the collider of a dynamically sampled boundary stays alive in the library until that
+// boundary lets go of it.  Ray sampling of a compound is not on the device (salva_hip_sample_host_shape).
+class Compound {
+  public:
+    struct Part {
+        SalvaHipCompoundPart c;
+        Part(const SalvaHipShape& shape, const Vec3& translation, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1})
+            : c{shape.kind, {shape.params[0], shape.params[1], shape.params[2]}, 0u, {translation[0], translation[1], translation[2]},
+                {rotation_ijkw[0], rotation_ijkw[1], rotation_ijkw[2], rotation_ijkw[3]}} {}
+        Part(const Mesh& mesh, const Vec3& translation, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1})
+            : c{SALVA_HIP_SHAPE_MESH, {0, 0, 0}, mesh.id(), {translation[0], translation[1], translation[2]},
+                {rotation_ijkw[0], rotation_ijkw[1], rotation_ijkw[2], rotation_ijkw[3]}} {}
+    };
+    Compound(LiquidWorld& world, const std::vector<Part>& parts);
+    Compound(Compound&& o) noexcept : w_(o.w_), id_(o.id_) { o.w_ = nullptr; }
+    Compound& operator=(Compound&& o) noexcept {
+        if (this != &o) { release(); w_ = o.w_; id_ = o.id_; o.w_ = nullptr; }
+        return *this;
+    }
+    Compound(const Compound&) = delete;
+    Compound& operator=(const Compound&) = delete;
+    ~Compound() { release(); }
+    uint32_t id() const { return id_; }
+
+  private:
+    void release() { if (w_) (void)salva_hip_destroy_compound(w_, id_); w_ = nullptr; }
+    SalvaHipWorld* w_ = nullptr;
+    uint32_t id_ = 0;
+};
+
 class Boundary {  // object/boundary.rs
   public:
     std::vector<Vec3> positions, velocities;
@@ -304,6 +337,14 @@ class Boundary {  // object/boundary.rs
         Boundary b({}, groups);
         b.dynamic_shape = SalvaHipShape{SALVA_HIP_SHAPE_MESH, {0, 0, 0}};
         b.mesh_id = mesh.id();
+        return b;
+    }
+    // ... and for a compound of the world (salva_hip_set_boundary_dynamic_sampling_compound)
+    uint32_t compound_id = 0;  // with dynamic_shape.kind == SALVA_HIP_SHAPE_COMPOUND
+    static Boundary dynamic_compound(const Compound& compound, InteractionGroups groups = {}) {
+        Boundary b({}, groups);
+        b.dynamic_shape = SalvaHipShape{SALVA_HIP_SHAPE_COMPOUND, {0, 0, 0}};
+        b.compound_id = compound.id();
         return b;
     }
     // ColliderSampling::StaticSampling(shape_surface_ray_sample(shape, particle_radius)) with the points produced and kept on the
@@ -476,6 +517,20 @@ class LiquidWorld {  // liquid_world.rs
         sync_for_query();
         return run_query([&](uint64_t cap, uint32_t* k, uint32_t* s, uint32_t* i) {
             return salva_hip_particles_intersecting_shape(w_, translation.data(), rotation_ijkw.data(), &shape, cap, k, s, i);
+        });
+    }
+    // ... for a compound and for an oriented mesh of this world, on the device as well
+    std::vector<ParticleId> particles_intersecting_shape(const Vec3& translation, const std::array<Real, 4>& rotation_ijkw,
+                                                         const Compound& compound) {
+        sync_for_query();
+        return run_query([&](uint64_t cap, uint32_t* k, uint32_t* s, uint32_t* i) {
+            return salva_hip_particles_intersecting_compound(w_, translation.data(), rotation_ijkw.data(), compound.id(), cap, k, s, i);
+        });
+    }
+    std::vector<ParticleId> particles_intersecting_shape(const Vec3& translation, const std::array<Real, 4>& rotation_ijkw, const Mesh& mesh) {
+        sync_for_query();
+        return run_query([&](uint64_t cap, uint32_t* k, uint32_t* s, uint32_t* i) {
+            return salva_hip_particles_intersecting_mesh(w_, translation.data(), rotation_ijkw.data(), mesh.id(), cap, k, s, i);
         });
     }
     // ... and for any other shape (the reference's query is generic over parry's `Shape`): `compute_aabb()` = shape.compute_aabb(pos)
@@ -914,6 +969,12 @@ class LiquidWorld {  // liquid_world.rs
             b.dirty_ = false;
             return;
         }
+        if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_COMPOUND) {
+            check(salva_hip_set_boundary_dynamic_sampling_compound(w_, slot, b.compound_id, b.interaction_groups.memberships,
+                                                                   b.interaction_groups.filter));
+            b.dirty_ = false;
+            return;
+        }
         if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_MESH) {
             check(salva_hip_set_boundary_dynamic_sampling_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter));
             b.dirty_ = false;
@@ -1056,6 +1117,12 @@ inline Mesh::Mesh(LiquidWorld& world, const std::vector<Vec3>& vertices, const s
     check(salva_hip_create_mesh(world.handle(), vertices.empty() ? nullptr : vertices[0].data(), (uint32_t)vertices.size(),
                                 triangles.empty() ? nullptr : triangles[0].data(), (uint32_t)triangles.size(),
                                 oriented ? (uint32_t)SALVA_HIP_MESH_ORIENTED : 0u, &id_));
+    w_ = world.handle();
+}
+inline Compound::Compound(LiquidWorld& world, const std::vector<Part>& parts) {
+    std::vector<SalvaHipCompoundPart> raw;
+    for (const Part& p : parts) raw.push_back(p.c);
+    check(salva_hip_create_compound(world.handle(), raw.data(), (uint32_t)raw.size(), &id_));
     w_ = world.handle();
 }
 inline Mesh Mesh::heightfield(LiquidWorld& world, const std::vector<Real>& heights, uint32_t nrows, uint32_t ncols, const Vec3& scale) {

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = [
     "salva_hip_add_particles_sampled_mesh", "salva_hip_set_boundary_sampling_from_mesh", "salva_hip_set_boundary_dynamic_sampling_mesh",
     "salva_hip_update_boundary_poses", "salva_hip_get_boundary_wrenches", "salva_hip_get_dcs_stats",
     "salva_hip_set_device_force_callback", "salva_hip_device_view_read", "salva_hip_get_device_force_stats",
+    "salva_hip_create_compound", "salva_hip_destroy_compound", "salva_hip_set_boundary_dynamic_sampling_compound",
+    "salva_hip_particles_intersecting_compound", "salva_hip_particles_intersecting_mesh",
 ]
 
 
@@ -150,8 +152,15 @@ class Shape(C.Structure):
     _fields_ = [("kind", C.c_int32), ("params", C.c_float * 3)]
 
 
+class CompoundPart(C.Structure):
+    """SalvaHipCompoundPart (include/salva_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("params", C.c_float * 3), ("mesh", C.c_uint32), ("translation", C.c_float * 3),
+                ("rotation_ijkw", C.c_float * 4)]
+
+
 KERNEL_CUBIC_SPLINE, KERNEL_POLY6, KERNEL_SPIKY, KERNEL_VISCOSITY = 0, 1, 2, 3
-SHAPE_BALL, SHAPE_CUBOID, SHAPE_CAPSULE, SHAPE_CYLINDER = 1, 2, 3, 4
+SHAPE_BALL, SHAPE_CUBOID, SHAPE_CAPSULE, SHAPE_CYLINDER, SHAPE_MESH, SHAPE_COMPOUND = 1, 2, 3, 4, 5, 6
+COMPOUND_MAX_PARTS = 64
 
 HOST_AABB_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float))
 HOST_PROJECT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8))
@@ -344,6 +353,15 @@ def lib():
         L.salva_hip_set_boundary_sampling_from_mesh.argtypes = [vp, u32, u32, u32, u32]
         L.salva_hip_set_boundary_sampling_from_mesh.restype = C.c_int64
         L.salva_hip_set_boundary_dynamic_sampling_mesh.argtypes = [vp, u32, u32, u32, u32]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_create_compound"):
+        up = C.POINTER(u32)
+        L.salva_hip_create_compound.argtypes = [vp, C.POINTER(CompoundPart), u32, up]
+        L.salva_hip_destroy_compound.argtypes = [vp, u32]
+        L.salva_hip_set_boundary_dynamic_sampling_compound.argtypes = [vp, u32, u32, u32, u32]
+        L.salva_hip_particles_intersecting_compound.argtypes = [vp, fp, fp, u32, u64, up, up, up]
+        L.salva_hip_particles_intersecting_compound.restype = C.c_int64
+        L.salva_hip_particles_intersecting_mesh.argtypes = [vp, fp, fp, u32, u64, up, up, up]
+        L.salva_hip_particles_intersecting_mesh.restype = C.c_int64
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

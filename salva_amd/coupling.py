@@ -132,18 +132,21 @@ class DynamicContactSampling:
     ("cuboid", (hx, hy, hz)), ("capsule", half_height, radius) (parry Capsule::new_y) or ("cylinder", half_height, radius) (axis = local
     y): the boundary's particles are the projections of the nearby fluid particles onto the collider, recomputed inside every step
     on the device (salva_hip_set_boundary_dynamic_sampling).  A sampling.Mesh — triangle mesh or height field — is projected onto on
-    the device as well (salva_hip_set_boundary_dynamic_sampling_mesh); only an oriented mesh pushes particles out."""
+    the device as well (salva_hip_set_boundary_dynamic_sampling_mesh); only an oriented mesh pushes particles out.  So is a
+    sampling.Compound (salva_hip_set_boundary_dynamic_sampling_compound)."""
 
     def __init__(self, shape):
-        from .sampling import Mesh
+        from .sampling import Compound, Mesh
 
         self.mesh = shape if isinstance(shape, Mesh) else None
-        self.shape = None if self.mesh is not None else make_shape(shape)
+        self.compound = shape if isinstance(shape, Compound) else None
+        self.shape = None if self.mesh is not None or self.compound is not None else make_shape(shape)
 
 
 class HostShapeSampling:
-    """ColliderSampling::DynamicContactSampling for a collider whose shape the library has no code for (triangle mesh, height
-    field, convex polyhedron, compound, ...): the loop of fluids_pipeline.rs:193-259 runs on the device, its two calls into the shape
+    """ColliderSampling::DynamicContactSampling for a collider whose shape the library has no code for (a convex polyhedron, a round
+    shape, a nested compound, ...; triangle meshes, height fields and compounds of primitives and meshes have device arms, see
+    DynamicContactSampling): the loop of fluids_pipeline.rs:193-259 runs on the device, its two calls into the shape
     come back to the host once per step (salva_hip_set_boundary_dynamic_sampling_host):
 
       aabb()              -> (mins, maxs)               `collider.shape().compute_aabb(collider.position())`
@@ -254,7 +257,10 @@ class ColliderCouplingSet:
                 e.uploaded = True
             if not e.uploaded and isinstance(e.sampling, DynamicContactSampling):
                 b._sampled = b._dynamic = True
-                if e.sampling.mesh is not None:
+                if e.sampling.compound is not None:
+                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling_compound(
+                        world._h, b._slot, e.sampling.compound.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
+                elif e.sampling.mesh is not None:
                     L.check(world._L.salva_hip_set_boundary_dynamic_sampling_mesh(
                         world._h, b._slot, e.sampling.mesh.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
                 else:

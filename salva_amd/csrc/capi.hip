@@ -902,6 +902,59 @@ int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t 
     });
 }
 
+int salva_hip_create_compound(SalvaHipWorld* world, const SalvaHipCompoundPart* parts, uint32_t nparts, uint32_t* compound_out) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !compound_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        *compound_out = world->w->create_compound(parts, nparts);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_destroy_compound(SalvaHipWorld* world, uint32_t compound) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        world->w->destroy_compound(compound);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_set_boundary_dynamic_sampling_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
+                                                     uint32_t filter) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        world->w->set_boundary_dynamic_sampling_compound(slot, compound, memberships, filter);
+        return SALVA_HIP_OK;
+    });
+}
+
+int64_t salva_hip_particles_intersecting_compound(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
+                                                  uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                                                  uint32_t* indices) { WorldLock _lk(world);
+    int64_t total = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        total = (int64_t)world->w->particles_in_compound(translation, rotation_ijkw, compound, capacity, kinds, slots, indices);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
+}
+
+int64_t salva_hip_particles_intersecting_mesh(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
+                                              uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices) { WorldLock _lk(world);
+    int64_t total = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        total = (int64_t)world->w->particles_in_mesh(translation, rotation_ijkw, mesh, capacity, kinds, slots, indices);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -28,22 +28,13 @@
 // This file is compiled with -ffp-contract=off (see Makefile): Rust never fuses a*b+c, and the emitted points feed the
 // exact d^2 <= h^2 contact test.
 #include "dcs.h"
+#include "compound.h"
 #include "mesh.h"
 #include "dist.h"
 #include "tile.h"
 #include <cmath>
 
 namespace salva {
-
-// nalgebra UnitQuaternion * Vector3: t = 2 q.vec x v; v' = t w + q.vec x t + v
-__device__ __forceinline__ void quat_rot(float qx, float qy, float qz, float qw, float vx, float vy, float vz, float& ox, float& oy,
-                                         float& oz) {
-    const float tx = (qy * vz - qz * vy) * 2.0f, ty = (qz * vx - qx * vz) * 2.0f, tz = (qx * vy - qy * vx) * 2.0f;
-    const float cx = qy * tz - qz * ty, cy = qz * tx - qx * tz, cz = qx * ty - qy * tx;
-    ox = (tx * qw + cx) + vx;
-    oy = (ty * qw + cy) + vy;
-    oz = (tz * qw + cz) + vz;
-}
 
 // the cell the particle was inserted under (hgrid.rs:122-133 filters CELLS by the box, then :211 tests the prediction)
 // On a FOLDED grid (device_types.h TileGrid; round 6: worlds with dynamically sampled colliders fold too) the key names the cell modulo
@@ -96,82 +87,6 @@ __device__ __forceinline__ bool dcs_finish(uint32_t i, float4 p, float4 v, float
     if (moved) posm[i] = p;
     if (slowed) vel[i] = v;
     return keep;
-}
-
-// project_local of the built-in shapes (see the header of this file) on a collider-local point: the projection and is_inside.
-// The one copy of this arithmetic: k_dcs_project and k_dcsb_project both call it.
-__device__ __forceinline__ void dcs_project_local(const DcsParams& s, float lx, float ly, float lz, float& jx, float& jy, float& jz,
-                                                  bool& inside) {
-    if (s.kind == SALVA_HIP_SHAPE_BALL) {
-        const float r = s.p[0], d2 = (lx * lx + ly * ly) + lz * lz;
-        inside = d2 <= r * r;
-        const float f = __fdiv_rn(r, sqrtf(d2));
-        jx = lx * f; jy = ly * f; jz = lz * f;
-    } else if (s.kind == SALVA_HIP_SHAPE_CAPSULE) {
-        const float hh = s.p[0], r = s.p[1];
-        // a = (0, -hh, 0), ab = (0, hh - (-hh), 0), ap = p - a; dots as ((x0 y0 + x1 y1) + x2 y2)
-        const float aby = hh - (-hh);
-        const float apx = lx, apy = ly - (-hh), apz = lz;
-        const float ab_ap = (0.0f * apx + aby * apy) + 0.0f * apz;
-        const float sqnab = (0.0f * 0.0f + aby * aby) + 0.0f * 0.0f;
-        float sx = 0.0f, sy, sz = 0.0f;
-        if (ab_ap <= 0.0f) sy = -hh;
-        else if (ab_ap >= sqnab) sy = hh;
-        else { const float u = __fdiv_rn(ab_ap, sqnab); sx = 0.0f + 0.0f * u; sy = -hh + aby * u; sz = 0.0f + 0.0f * u; }
-        const float ex = lx - sx, ey = ly - sy, ez = lz - sz;
-        const float sq = (ex * ex + ey * ey) + ez * ez;
-        if (sq > s.eps * s.eps) {
-            const float dist = sqrtf(sq);
-            inside = dist <= r;
-            jx = sx + __fdiv_rn(ex, dist) * r; jy = sy + __fdiv_rn(ey, dist) * r; jz = sz + __fdiv_rn(ez, dist) * r;
-        } else {
-            inside = true;
-            jx = sx + 1.0f * r; jy = sy + 0.0f * r; jz = sz + 0.0f * r;
-        }
-    } else if (s.kind == SALVA_HIP_SHAPE_CYLINDER) {
-        const float hh = s.p[0], r = s.p[1];
-        const float planar = sqrtf(lx * lx + lz * lz);
-        float dx2 = __fdiv_rn(lx, planar), dz2 = __fdiv_rn(lz, planar);
-        if (planar <= s.eps) { dx2 = 1.0f; dz2 = 0.0f; }
-        const float qx = dx2 * r, qz = dz2 * r;
-        if (ly >= -hh && ly <= hh && planar <= r) {
-            inside = true;
-            const float top = hh - ly, bottom = ly - (-hh), side = r - planar;
-            if (top < bottom && top < side) { jx = lx; jy = hh; jz = lz; }
-            else if (bottom < top && bottom < side) { jx = lx; jy = -hh; jz = lz; }
-            else { jx = qx; jy = ly; jz = qz; }
-        } else {
-            inside = false;
-            if (ly > hh) { jy = hh; if (planar <= r) { jx = lx; jz = lz; } else { jx = qx; jz = qz; } }
-            else if (ly < -hh) { jy = -hh; if (planar <= r) { jx = lx; jz = lz; } else { jx = qx; jz = qz; } }
-            else { jx = qx; jy = ly; jz = qz; }
-        }
-    } else {
-        const float l3[3] = {lx, ly, lz};
-        float mins_pt[3], pt_maxs[3], shift[3];
-        inside = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mins_pt[a] = -s.p[a] - l3[a];
-            pt_maxs[a] = l3[a] - s.p[a];
-            shift[a] = fmaxf(mins_pt[a], 0.0f) - fmaxf(pt_maxs[a], 0.0f);
-            if (shift[a] != 0.0f) inside = false;
-        }
-        if (inside) {
-            float best = -3.402823466e+38f;
-            bool is_mins = false;
-            int best_id = 0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                if (mins_pt[a] < pt_maxs[a]) {
-                    if (pt_maxs[a] > best) { best_id = a; is_mins = false; best = pt_maxs[a]; }
-                } else if (mins_pt[a] > best) { best_id = a; is_mins = true; best = mins_pt[a]; }
-            }
-            const float sh = is_mins ? best : -best;
-            shift[0] = best_id == 0 ? sh : 0.0f; shift[1] = best_id == 1 ? sh : 0.0f; shift[2] = best_id == 2 ? sh : 0.0f;
-        }
-        jx = l3[0] + shift[0]; jy = l3[1] + shift[1]; jz = l3[2] + shift[2];
-    }
 }
 
 // project_point_and_get_feature(m, pt) of a built-in shape: m^-1 * pt, project_local, carried back by m
@@ -267,6 +182,21 @@ __global__ __launch_bounds__(BLOCK) void k_dcs_project_mesh(uint32_t cnt, const 
     proj[k] = make_float4(wx, wy, wz, inside ? 1.0f : 0.0f);
 }
 
+// The compound arm (salva_hip_set_boundary_dynamic_sampling_compound; compound.h): the mesh arm's pass with the walk over
+// the compound's parts in place of the walk over one mesh.  The part index is wave-uniform, so the table is read through the scalar
+// cache.
+__global__ __launch_bounds__(BLOCK) void k_dcs_compound_project(uint32_t cnt, const float4* __restrict__ pred,
+                                                                const CompoundPartDev* __restrict__ parts, uint32_t nparts, DcsParams s,
+                                                                float4* __restrict__ proj) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= cnt) return;
+    const float4 pr = pred[k];
+    float wx, wy, wz;
+    bool inside;
+    dcs_project_compound_world(parts, nparts, s, pr.x, pr.y, pr.z, wx, wy, wz, inside);
+    proj[k] = make_float4(wx, wy, wz, inside ? 1.0f : 0.0f);
+}
+
 // Decomposed run: this rank's compacted rows (point, sorted index of the source particle) -> its section of the table every
 // rank assembles (World::dist_gather_emitted): (point, global id of the source) and the source's fluid.
 __global__ __launch_bounds__(BLOCK) void k_dcs_pack(uint32_t cnt, const float4* __restrict__ rows, const uint32_t* __restrict__ gid,
@@ -323,6 +253,38 @@ __device__ __forceinline__ uint32_t dcsb_append(bool mine, unsigned long long* t
     const unsigned long long k = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
     return (mine && k < 0xffffffffull) ? (uint32_t)k : 0xffffffffu;
 }
+// What collider c of the table does to the particle a thread holds in registers, and the record it appends.  COMPOUND picks the
+// projection at compile time: false — a built-in shape or a mesh, the arithmetic of k_dcs_project / k_dcs_project_mesh; true — the walk
+// over a compound's parts (compound.h).  The two never share a kernel: with the walk in it k_dcsb_project would need 106 VGPRs and
+// lose its fifth wave, so a run that holds compounds goes through k_dcsb_segment below, one launch per stretch of
+// colliders of one class.
+template <bool COMPOUND>
+__device__ __forceinline__ void dcsb_collider(uint32_t c, uint32_t i, bool live, uint32_t key, float4& p, float4& v, bool& have_v, bool& moved,
+                                              bool& slowed, const float4* __restrict__ vel, const uint32_t* __restrict__ perm, const TileGrid& g,
+                                              const DcsbEntry* __restrict__ tab, uint32_t ncol, uint32_t cap, uint32_t shift,
+                                              unsigned long long* __restrict__ counts, unsigned long long* __restrict__ rec_key,
+                                              uint32_t* __restrict__ rec_idx, float4* __restrict__ rec) {
+    const DcsParams& s = tab[c].s;
+    bool accept = false;
+    float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+    if (live && dcs_in_cells(key, g, s, p)) {
+        if (!have_v) { v = vel[i]; have_v = true; }
+        const float px = p.x + v.x * s.dt, py = p.y + v.y * s.dt, pz = p.z + v.z * s.dt;  // :206-207
+        if (!(px < s.lo[0] || px > s.hi[0] || py < s.lo[1] || py > s.hi[1] || pz < s.lo[2] || pz > s.hi[2])) {
+            bool inside;
+            if (COMPOUND) dcs_project_compound_world(tab[c].parts, tab[c].nparts, s, px, py, pz, wx, wy, wz, inside);
+            else if (s.kind == SALVA_HIP_SHAPE_MESH) dcs_project_mesh_world(tab[c].mesh, s, px, py, pz, wx, wy, wz, inside);
+            else dcs_project_world(s, px, py, pz, wx, wy, wz, inside);
+            accept = dcs_finish_reg(p, v, px, py, pz, wx, wy, wz, inside, s, moved, slowed);
+        }
+    }
+    const uint32_t k = dcsb_append(accept, counts + ncol, counts + c);
+    if (k < cap) {
+        rec_key[k] = ((unsigned long long)c << shift) | (unsigned long long)i;
+        rec_idx[k] = k;
+        rec[k] = make_float4(wx, wy, wz, __uint_as_float(perm[i]));
+    }
+}
 __global__ __launch_bounds__(BLOCK) void k_dcsb_project(uint32_t n, const float4* __restrict__ posm, const float4* __restrict__ vel,
                                                         const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm, TileGrid g,
                                                         const DcsbEntry* __restrict__ tab, uint32_t ncol, uint32_t cap, uint32_t shift,
@@ -337,30 +299,45 @@ __global__ __launch_bounds__(BLOCK) void k_dcsb_project(uint32_t n, const float4
     if (live) { p = posm[i]; key = keys[i]; }
     bool have_v = false, moved = false, slowed = false;
 #pragma unroll 1
-    for (uint32_t c = 0; c < ncol; ++c) {  // (c is wave-uniform: the table comes through the scalar cache)
-        const DcsParams& s = tab[c].s;
-        bool accept = false;
-        float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-        if (live && dcs_in_cells(key, g, s, p)) {
-            if (!have_v) { v = vel[i]; have_v = true; }
-            const float px = p.x + v.x * s.dt, py = p.y + v.y * s.dt, pz = p.z + v.z * s.dt;  // :206-207
-            if (!(px < s.lo[0] || px > s.hi[0] || py < s.lo[1] || py > s.hi[1] || pz < s.lo[2] || pz > s.hi[2])) {
-                bool inside;
-                if (s.kind == SALVA_HIP_SHAPE_MESH) dcs_project_mesh_world(tab[c].mesh, s, px, py, pz, wx, wy, wz, inside);
-                else dcs_project_world(s, px, py, pz, wx, wy, wz, inside);
-                accept = dcs_finish_reg(p, v, px, py, pz, wx, wy, wz, inside, s, moved, slowed);
-            }
-        }
-        const uint32_t k = dcsb_append(accept, counts + ncol, counts + c);
-        if (k < cap) {
-            rec_key[k] = ((unsigned long long)c << shift) | (unsigned long long)i;
-            rec_idx[k] = k;
-            rec[k] = make_float4(wx, wy, wz, __uint_as_float(perm[i]));
-        }
-    }
+    for (uint32_t c = 0; c < ncol; ++c)  // (c is wave-uniform: the table comes through the scalar cache)
+        dcsb_collider<false>(c, i, live, key, p, v, have_v, moved, slowed, vel, perm, g, tab, ncol, cap, shift, counts, rec_key, rec_idx, rec);
     // (a pushed particle has an accepted record: pushes <= records, so the push list fits whenever the records do)
     const uint32_t k = dcsb_append(moved, counts + ncol + 1, nullptr);
     if (k < cap) { push_idx[k] = i; push_pos[k] = p; push_vel[k] = v; }
+}
+// A run that holds compounds: the colliders [c0, c1) of the table — all compounds (COMPOUND) or none — in a launch of their own.  The
+// particle a thread holds travels from one launch to the next through `st_pos` / `st_vel` / `st_moved` (the pass still writes no
+// particle of the working set), so the launches of a run, in slot order, compute what k_dcsb_project would: the same device function
+// per collider on the same values.  The first launch (c0 == 0) reads the working set, the last (c1 == ncol) appends the pushes.
+template <bool COMPOUND>
+__global__ __launch_bounds__(BLOCK) void k_dcsb_segment(uint32_t n, const float4* __restrict__ posm, const float4* __restrict__ vel,
+                                                        const uint32_t* __restrict__ keys, const uint32_t* __restrict__ perm, TileGrid g,
+                                                        const DcsbEntry* __restrict__ tab, uint32_t ncol, uint32_t c0, uint32_t c1, uint32_t cap,
+                                                        uint32_t shift, unsigned long long* __restrict__ counts,
+                                                        unsigned long long* __restrict__ rec_key, uint32_t* __restrict__ rec_idx,
+                                                        float4* __restrict__ rec, uint32_t* __restrict__ push_idx, float4* __restrict__ push_pos,
+                                                        float4* __restrict__ push_vel, float4* __restrict__ st_pos, float4* __restrict__ st_vel,
+                                                        uint8_t* __restrict__ st_moved) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool live = i < n;
+    float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v = p;
+    uint32_t key = 0u;
+    bool have_v = false, moved = false, slowed = false;
+    if (live) {
+        key = keys[i];
+        if (c0 == 0u) p = posm[i];
+        else { p = st_pos[i]; v = st_vel[i]; have_v = true; moved = st_moved[i] != 0; }
+    }
+#pragma unroll 1
+    for (uint32_t c = c0; c < c1; ++c)
+        dcsb_collider<COMPOUND>(c, i, live, key, p, v, have_v, moved, slowed, vel, perm, g, tab, ncol, cap, shift, counts, rec_key, rec_idx, rec);
+    if (c1 == ncol) {
+        const uint32_t k = dcsb_append(moved, counts + ncol + 1, nullptr);
+        if (k < cap) { push_idx[k] = i; push_pos[k] = p; push_vel[k] = v; }
+    } else if (live) {
+        if (!have_v) v = vel[i];
+        st_pos[i] = p; st_vel[i] = v; st_moved[i] = moved ? 1 : 0;
+    }
 }
 // the pushes of a pass whose records fitted (a velocity that no collider changed is written back as it was read)
 __global__ __launch_bounds__(BLOCK) void k_dcsb_push(uint32_t cnt, const uint32_t* __restrict__ push_idx, const float4* __restrict__ push_pos,
@@ -459,8 +436,7 @@ DcsParams dcs_params_host(const float mins[3], const float maxs[3], float h, flo
 
 // the mesh arm: parry's Aabb::transform_by — the local box's centre posed by the collider's pose, -+ |R| half_extents (the matrix
 // form of shape_world_extent)
-DcsParams dcs_params_mesh(const float mins[3], const float maxs[3], const SalvaHipRigidPose& pose, float h, float particle_radius, float dt) {
-    const float* q = pose.rotation;
+void aabb_transform_by(const float mins[3], const float maxs[3], const float t[3], const float q[4], float lo[3], float hi[3]) {
     SalvaHipShape box{};
     box.kind = SALVA_HIP_SHAPE_CUBOID;
     float c[3], ext[3];
@@ -469,14 +445,23 @@ DcsParams dcs_params_mesh(const float mins[3], const float maxs[3], const SalvaH
     // quat_rot on the host
     const float tx = (q[1] * c[2] - q[2] * c[1]) * 2.0f, ty = (q[2] * c[0] - q[0] * c[2]) * 2.0f, tz = (q[0] * c[1] - q[1] * c[0]) * 2.0f;
     const float cx = q[1] * tz - q[2] * ty, cy = q[2] * tx - q[0] * tz, cz = q[0] * ty - q[1] * tx;
-    const float w[3] = {((tx * q[3] + cx) + c[0]) + pose.translation[0], ((ty * q[3] + cy) + c[1]) + pose.translation[1],
-                        ((tz * q[3] + cz) + c[2]) + pose.translation[2]};
-    float lo[3], hi[3];
+    const float w[3] = {((tx * q[3] + cx) + c[0]) + t[0], ((ty * q[3] + cy) + c[1]) + t[1], ((tz * q[3] + cz) + c[2]) + t[2]};
     for (int a = 0; a < 3; ++a) { lo[a] = w[a] - ext[a]; hi[a] = w[a] + ext[a]; }
+}
+DcsParams dcs_params_mesh(const float mins[3], const float maxs[3], const SalvaHipRigidPose& pose, float h, float particle_radius, float dt) {
+    float lo[3], hi[3];
+    aabb_transform_by(mins, maxs, pose.translation, pose.rotation, lo, hi);
     DcsParams s = dcs_params_host(lo, hi, h, particle_radius, dt);
     s.kind = SALVA_HIP_SHAPE_MESH;
     for (int a = 0; a < 3; ++a) s.t[a] = pose.translation[a];
     for (int a = 0; a < 4; ++a) s.q[a] = pose.rotation[a];
+    return s;
+}
+
+// the compound arm: the box of the mesh arm on the compound's local box
+DcsParams dcs_params_compound(const CompoundRes& c, const SalvaHipRigidPose& pose, float h, float particle_radius, float dt) {
+    DcsParams s = dcs_params_mesh(c.mins, c.maxs, pose, h, particle_radius, dt);
+    s.kind = SALVA_HIP_SHAPE_COMPOUND;
     return s;
 }
 
@@ -503,6 +488,12 @@ void launch_dcs_project_mesh(uint32_t cnt, const float4* pred, const MeshDev& me
     k_dcs_project_mesh<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, pred, mesh, s, proj);
     SALVA_HIP_CHECK(hipGetLastError());
 }
+void launch_dcs_compound_project(uint32_t cnt, const float4* pred, const CompoundPartDev* parts, uint32_t nparts, const DcsParams& s,
+                                 float4* proj, hipStream_t st) {
+    if (cnt == 0) return;
+    k_dcs_compound_project<<<div_up(cnt, BLOCK), BLOCK, 0, st>>>(cnt, pred, parts, nparts, s, proj);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
 void launch_dcs_pack(uint32_t cnt, const float4* rows, const uint32_t* gid, const uint32_t* model, float4* out_rows, uint32_t* out_models,
                      hipStream_t st) {
     if (cnt == 0) return;
@@ -523,6 +514,19 @@ void launch_dcsb_project(uint32_t n, const float4* posm, const float4* vel, cons
     if (n == 0) return;
     k_dcsb_project<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, posm, vel, keys, perm, g, tab, ncol, cap, shift, counts, rec_key, rec_idx, rec, push_idx,
                                                        push_pos, push_vel);
+    SALVA_HIP_CHECK(hipGetLastError());
+}
+void launch_dcsb_segment(bool compound, uint32_t n, const float4* posm, const float4* vel, const uint32_t* keys, const uint32_t* perm, TileGrid g,
+                         const DcsbEntry* tab, uint32_t ncol, uint32_t c0, uint32_t c1, uint32_t cap, uint32_t shift, unsigned long long* counts,
+                         unsigned long long* rec_key, uint32_t* rec_idx, float4* rec, uint32_t* push_idx, float4* push_pos, float4* push_vel,
+                         float4* st_pos, float4* st_vel, uint8_t* st_moved, hipStream_t st) {
+    if (n == 0) return;
+    if (compound)
+        k_dcsb_segment<true><<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, posm, vel, keys, perm, g, tab, ncol, c0, c1, cap, shift, counts, rec_key, rec_idx,
+                                                                 rec, push_idx, push_pos, push_vel, st_pos, st_vel, st_moved);
+    else
+        k_dcsb_segment<false><<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, posm, vel, keys, perm, g, tab, ncol, c0, c1, cap, shift, counts, rec_key, rec_idx,
+                                                                  rec, push_idx, push_pos, push_vel, st_pos, st_vel, st_moved);
     SALVA_HIP_CHECK(hipGetLastError());
 }
 void launch_dcsb_push(uint32_t cnt, const uint32_t* push_idx, const float4* push_pos, const float4* push_vel, float4* posm, float4* vel,

@@ -16,6 +16,7 @@
 #include "elastic.h"
 #include "switches.h"
 #include "mesh.h"
+#include "compound.h"
 
 namespace salva {
 
@@ -50,6 +51,7 @@ struct BoundarySlot {
     SalvaHipHostShape dyn_host{};  // dyn_kind == SALVA_HIP_SHAPE_HOST: the host's compute_aabb / project_point callbacks
     SalvaHipRigidPose dyn_pose{};
     std::shared_ptr<MeshRes> dyn_mesh;  // dyn_kind == SALVA_HIP_SHAPE_MESH: the collider's mesh (kept alive: salva_hip_destroy_mesh refuses)
+    std::shared_ptr<CompoundRes> dyn_compound;  // dyn_kind == SALVA_HIP_SHAPE_COMPOUND (kept alive: salva_hip_destroy_compound refuses)
     std::shared_ptr<DevBuf<uint32_t>> dyn_src, dyn_src_model;
 };
 
@@ -116,6 +118,14 @@ class World {
     int64_t add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel);
     int64_t set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
+    // ---- compound colliders (compound.hip): the world's table, DynamicContactSampling on one, the shape query
+    uint32_t create_compound(const SalvaHipCompoundPart* parts, uint32_t nparts);
+    void destroy_compound(uint32_t compound);
+    void set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
+    uint64_t particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                                   uint32_t* indices);
+    uint64_t particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                               uint32_t* indices);
     void update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose);
     void update_boundary_poses(uint32_t count, const uint32_t* slots, const SalvaHipRigidPose* poses);
     void set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
@@ -208,6 +218,8 @@ class World {
     int64_t boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint32_t memberships, uint32_t filter);
     std::vector<std::shared_ptr<MeshRes>> meshes;  // by handle; a destroyed mesh leaves a free entry
     const std::shared_ptr<MeshRes>& mesh_at(uint32_t mesh) const;
+    std::vector<std::shared_ptr<CompoundRes>> compounds;  // by handle, like `meshes`
+    const std::shared_ptr<CompoundRes>& compound_at(uint32_t compound) const;
     void stamp_fluid_models();
     void stamp_boundary_models();
     bool has_dynamic_sampling() const;
@@ -220,6 +232,8 @@ class World {
     DevBuf<unsigned long long> dcsb_counts, dcsb_key[2];
     DevBuf<uint32_t> dcsb_idx[2], dcsb_push_idx;
     DevBuf<float4> dcsb_rec, dcsb_push_pos, dcsb_push_vel;
+    DevBuf<float4> dcsb_st_pos, dcsb_st_vel;  // a run with compounds: the particles between its launches (dcs.hip k_dcsb_segment)
+    DevBuf<uint8_t> dcsb_st_moved;
     uint32_t dcsb_cap = 0;  // records the buffers above are cut for (0: not yet)
     PinnedStage dcsb_stage, pose_stage, wrench_stage;
     DevBuf<char> pose_tab, wrench_tab;  // salva_hip_update_boundary_poses / _get_boundary_wrenches: their entry tables

@@ -622,6 +622,7 @@ void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, cons
     b.n = nn; b.memberships = memberships; b.filter = filter; b.wants_forces = wants_forces;
     b.dyn_kind = 0;  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
     b.dyn_mesh.reset();
+    b.dyn_compound.reset();
     b.vel_zero = true;
     if (nn) {
         scratch_f.ensure(3 * nn, stream, false, 1.1f);
@@ -1066,6 +1067,24 @@ struct ShapeQuery {
     int clo[3], chi[3];     // cell range of the world AABB
     float h, r;             // cell width, particle radius
 };
+// `shape.distance_to_point(identity, l, solid = true)` of a built-in shape for a point in the shape's frame: the one copy, for
+// k_shape_query and for the parts of a compound (k_compound_query)
+__device__ __forceinline__ float shape_solid_distance(int kind, const float p[3], float lx, float ly, float lz) {
+    float d;
+    if (kind == SALVA_HIP_SHAPE_BALL) {
+        d = fmaxf(sqrtf(lx * lx + ly * ly + lz * lz) - p[0], 0.0f);
+    } else if (kind == SALVA_HIP_SHAPE_CAPSULE) {  // distance to the segment (0, -hh..hh, 0), minus the radius
+        const float ey = ly - fminf(fmaxf(ly, -p[0]), p[0]);
+        d = fmaxf(sqrtf(lx * lx + ey * ey + lz * lz) - p[1], 0.0f);
+    } else if (kind == SALVA_HIP_SHAPE_CYLINDER) {  // beyond the caps and beyond the side
+        const float ey = fmaxf(fabsf(ly) - p[0], 0.0f), er = fmaxf(sqrtf(lx * lx + lz * lz) - p[1], 0.0f);
+        d = sqrtf(ey * ey + er * er);
+    } else {
+        const float dx = fmaxf(fabsf(lx) - p[0], 0.0f), dy = fmaxf(fabsf(ly) - p[1], 0.0f), dz = fmaxf(fabsf(lz) - p[2], 0.0f);
+        d = sqrtf(dx * dx + dy * dy + dz * dz);
+    }
+    return d;
+}
 __global__ __launch_bounds__(BLOCK) void k_shape_query(QuerySrc q, ShapeQuery s, uint32_t kind,
                                                        unsigned int* __restrict__ counter, uint32_t cap, uint32_t* __restrict__ out_kind,
                                                        uint32_t* __restrict__ out_index) {
@@ -1080,19 +1099,7 @@ __global__ __launch_bounds__(BLOCK) void k_shape_query(QuerySrc q, ShapeQuery s,
     const float qx = -s.q[0], qy = -s.q[1], qz = -s.q[2], qw = s.q[3];
     const float tx = (qy * vz - qz * vy) * 2.0f, ty = (qz * vx - qx * vz) * 2.0f, tz = (qx * vy - qy * vx) * 2.0f;
     const float lx = vx + qw * tx + (qy * tz - qz * ty), ly = vy + qw * ty + (qz * tx - qx * tz), lz = vz + qw * tz + (qx * ty - qy * tx);
-    float d;
-    if (s.kind == SALVA_HIP_SHAPE_BALL) {
-        d = fmaxf(sqrtf(lx * lx + ly * ly + lz * lz) - s.p[0], 0.0f);
-    } else if (s.kind == SALVA_HIP_SHAPE_CAPSULE) {  // distance to the segment (0, -hh..hh, 0), minus the radius
-        const float ey = ly - fminf(fmaxf(ly, -s.p[0]), s.p[0]);
-        d = fmaxf(sqrtf(lx * lx + ey * ey + lz * lz) - s.p[1], 0.0f);
-    } else if (s.kind == SALVA_HIP_SHAPE_CYLINDER) {  // beyond the caps and beyond the side
-        const float ey = fmaxf(fabsf(ly) - s.p[0], 0.0f), er = fmaxf(sqrtf(lx * lx + lz * lz) - s.p[1], 0.0f);
-        d = sqrtf(ey * ey + er * er);
-    } else {
-        const float dx = fmaxf(fabsf(lx) - s.p[0], 0.0f), dy = fmaxf(fabsf(ly) - s.p[1], 0.0f), dz = fmaxf(fabsf(lz) - s.p[2], 0.0f);
-        d = sqrtf(dx * dx + dy * dy + dz * dz);
-    }
+    const float d = shape_solid_distance(s.kind, s.p, lx, ly, lz);
     if (!(d <= s.r)) return;
     query_emit(q, i, kind, counter, cap, out_kind, out_index);
 }
@@ -1134,6 +1141,116 @@ uint64_t World::particles_in_shape(const float t[3], const float q[4], const Sal
     SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
     if (qf.n) k_shape_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, 0u, cnt.p, cap, dk.p, di.p);
     if (nb) k_shape_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, 1u, cnt.p, cap, dk.p, di.p);
+    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
+}
+
+// The same query for a posed compound and for a posed oriented mesh.  A compound's solid distance is the smallest of
+// its parts', each taken in the part's frame (pose_k^-1 * l, quat_rot with the conjugate); an oriented mesh's is 0 inside and the
+// distance to the closest point outside.  The cell range comes from the posed local box (parry's Aabb::transform_by, dcs.hip).
+struct PosedQuery {
+    float t[3], q[4];       // isometry
+    int clo[3], chi[3];     // cell range of the world AABB
+    float h, r;             // cell width, particle radius
+};
+__device__ __forceinline__ bool posed_query_local(const QuerySrc& q, const PosedQuery& s, uint32_t i, float& lx, float& ly, float& lz) {
+    if (i >= q.n || query_skip(q, i)) return false;
+    const float4 pt = q.pos[i];
+    bool bad = false;
+    const int cx = cell_coord(pt.x, s.h, bad), cy = cell_coord(pt.y, s.h, bad), cz = cell_coord(pt.z, s.h, bad);
+    if (bad || cx < s.clo[0] || cx > s.chi[0] || cy < s.clo[1] || cy > s.chi[1] || cz < s.clo[2] || cz > s.chi[2]) return false;
+    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], pt.x - s.t[0], pt.y - s.t[1], pt.z - s.t[2], lx, ly, lz);
+    return true;
+}
+__device__ __forceinline__ float mesh_solid_distance(const MeshDev& m, float lx, float ly, float lz) {
+    float jx, jy, jz;
+    bool inside;
+    mesh_project_point(m, lx, ly, lz, jx, jy, jz, inside);
+    const float dx = lx - jx, dy = ly - jy, dz = lz - jz;
+    return inside ? 0.0f : sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+__global__ __launch_bounds__(BLOCK) void k_compound_query(QuerySrc q, PosedQuery s, const CompoundPartDev* __restrict__ parts, uint32_t nparts,
+                                                          uint32_t kind, unsigned int* __restrict__ counter, uint32_t cap,
+                                                          uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    float lx, ly, lz;
+    if (!posed_query_local(q, s, i, lx, ly, lz)) return;
+    float d = __builtin_inff();
+#pragma unroll 1
+    for (uint32_t k = 0; k < nparts; ++k) {  // (k is wave-uniform: the table comes through the scalar cache)
+        const CompoundPartDev& P = parts[k];
+        float kx, ky, kz;
+        quat_rot(-P.q[0], -P.q[1], -P.q[2], P.q[3], lx - P.t[0], ly - P.t[1], lz - P.t[2], kx, ky, kz);
+        d = fminf(d, P.kind == SALVA_HIP_SHAPE_MESH ? mesh_solid_distance(P.mesh, kx, ky, kz) : shape_solid_distance(P.kind, P.p, kx, ky, kz));
+    }
+    if (!(d <= s.r)) return;
+    query_emit(q, i, kind, counter, cap, out_kind, out_index);
+}
+__global__ __launch_bounds__(BLOCK) void k_mesh_query(QuerySrc q, PosedQuery s, MeshDev mesh, uint32_t kind, unsigned int* __restrict__ counter,
+                                                      uint32_t cap, uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    float lx, ly, lz;
+    if (!posed_query_local(q, s, i, lx, ly, lz)) return;
+    if (!(mesh_solid_distance(mesh, lx, ly, lz) <= s.r)) return;
+    query_emit(q, i, kind, counter, cap, out_kind, out_index);
+}
+// the checks of particles_in_shape on the pose, and the cell range of the posed box
+static PosedQuery posed_query(const float t[3], const float q[4], const float mins[3], const float maxs[3], float h, float r) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite translation");
+    float qn = 0.0f;
+    for (int a = 0; a < 4; ++a) {
+        if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite rotation");
+        qn += q[a] * q[a];
+    }
+    if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, "shape query: the rotation must be a unit quaternion (x, y, z, w)");
+    PosedQuery s{};
+    for (int a = 0; a < 3; ++a) s.t[a] = t[a];
+    for (int a = 0; a < 4; ++a) s.q[a] = q[a];
+    s.h = h; s.r = r;
+    float lo[3], hi[3];
+    aabb_transform_by(mins, maxs, t, q, lo, hi);
+    for (int a = 0; a < 3; ++a) {  // (clamped like the cell coordinates of the particles: tile.h cell_coord)
+        s.clo[a] = (int)std::min(std::max(floorf(lo[a] / h), -1073741824.0f), 1073741824.0f);
+        s.chi[a] = (int)std::min(std::max(floorf(hi[a] / h), -1073741824.0f), 1073741824.0f);
+    }
+    return s;
+}
+uint64_t World::particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                                      uint32_t* indices) {
+    use_device();
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "compound colliders are not available in a running decomposed world");
+    const std::shared_ptr<CompoundRes> c = compound_at(compound);
+    if (!c->solid)
+        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh part of the compound lacks SALVA_HIP_MESH_ORIENTED and has no solid distance (use salva_hip_particles_intersecting_host_shape)");
+    const PosedQuery s = posed_query(t, q, c->mins, c->maxs, sc.h, prm.particle_radius);
+    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
+    DevBuf<unsigned int> cnt;
+    DevBuf<uint32_t> dk, di;
+    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
+    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
+    if (qf.n) k_compound_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, c->parts.p, c->nparts, 0u, cnt.p, cap, dk.p, di.p);
+    if (nb) k_compound_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, c->parts.p, c->nparts, 1u, cnt.p, cap, dk.p, di.p);
+    SALVA_HIP_CHECK(hipGetLastError());
+    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
+}
+uint64_t World::particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                                  uint32_t* indices) {
+    use_device();
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
+    const std::shared_ptr<MeshRes> m = mesh_at(mesh);
+    if (!(m->flags & SALVA_HIP_MESH_ORIENTED))
+        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh without SALVA_HIP_MESH_ORIENTED has no solid distance (use salva_hip_particles_intersecting_host_shape)");
+    const PosedQuery s = posed_query(t, q, m->mins, m->maxs, sc.h, prm.particle_radius);
+    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
+    DevBuf<unsigned int> cnt;
+    DevBuf<uint32_t> dk, di;
+    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
+    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
+    if (qf.n) k_mesh_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, m->dev(), 0u, cnt.p, cap, dk.p, di.p);
+    if (nb) k_mesh_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, m->dev(), 1u, cnt.p, cap, dk.p, di.p);
+    SALVA_HIP_CHECK(hipGetLastError());
     return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
 }
 
@@ -1743,6 +1860,7 @@ void World::clear_boundary_sampling(uint32_t slot) {
     b.dyn_shape = SalvaHipShape{};
     b.dyn_host = SalvaHipHostShape{};
     b.dyn_mesh.reset();
+    b.dyn_compound.reset();
     b.dyn_src.reset(); b.dyn_src_model.reset();
     // the particles keep the velocities k_boundary_pose / k_dcs_emit wrote for the moving collider (the reference keeps them after
     // unregister_coupling too): from now on make_ctx must not take the upload's "at rest" for them
@@ -1829,9 +1947,9 @@ void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
         HipError local_error(SALVA_HIP_E_INVALID, "");
         bool local_failed = false;
         try {
-        if (n && (b.dyn_kind == SALVA_HIP_SHAPE_HOST || b.dyn_kind == SALVA_HIP_SHAPE_MESH)) {
+        if (n && (b.dyn_kind == SALVA_HIP_SHAPE_HOST || b.dyn_kind == SALVA_HIP_SHAPE_MESH || b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND)) {
             // the host's shape: box tests on the device, the projections on the host, the rest of the loop body on the device;
-            // a mesh: the same pass with the projections on the device as well (k_dcs_project_mesh)
+            // a mesh or a compound: the same pass with the projections on the device as well (k_dcs_project_mesh, k_dcs_compound_project)
             const bool on_host = b.dyn_kind == SALVA_HIP_SHAPE_HOST;
             DcsParams prm_d;
             if (on_host) {
@@ -1840,6 +1958,8 @@ void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
                 for (int a = 0; a < 3; ++a)
                     if (!(mins[a] <= maxs[a])) throw HipError(SALVA_HIP_E_INVALID, "host shape: the aabb callback returned an empty or NaN box");
                 prm_d = dcs_params_host(mins, maxs, sc.h, prm.particle_radius, dt_prev);
+            } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
+                prm_d = dcs_params_compound(*b.dyn_compound, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
             } else {
                 prm_d = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
             }
@@ -1864,6 +1984,8 @@ void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
                     for (uint32_t k = 0; k < ng; ++k)
                         dcs_h_f4[k] = make_float4(dcs_h_proj[3 * k], dcs_h_proj[3 * k + 1], dcs_h_proj[3 * k + 2], dcs_h_inside[k] ? 1.0f : 0.0f);
                     SALVA_HIP_CHECK(hipMemcpyAsync(dcs_proj.p, dcs_h_f4.data(), (size_t)ng * sizeof(float4), hipMemcpyHostToDevice, stream));
+                } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
+                    launch_dcs_compound_project(ng, dcs_out.p, b.dyn_compound->parts.p, b.dyn_compound->nparts, prm_d, dcs_proj.p, stream);
                 } else {
                     launch_dcs_project_mesh(ng, dcs_out.p, b.dyn_mesh->dev(), prm_d, dcs_proj.p, stream);
                 }
@@ -1934,18 +2056,24 @@ void World::run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const T
     char* stage = dcsb_stage.acquire(tab_bytes + cnt_bytes);
     DcsbEntry* tab_h = reinterpret_cast<DcsbEntry*>(stage);
     const unsigned long long* cnt_h = reinterpret_cast<const unsigned long long*>(stage + tab_bytes);
+    bool has_compound = false;
     for (uint32_t c = 0; c < ncol; ++c) {
         const BoundarySlot& b = bounds[run[c]];
         DcsbEntry e{};
         if (b.dyn_kind == SALVA_HIP_SHAPE_MESH) {
             e.s = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
             e.mesh = b.dyn_mesh->dev();
+        } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
+            e.s = dcs_params_compound(*b.dyn_compound, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
+            e.parts = b.dyn_compound->parts.p;
+            e.nparts = b.dyn_compound->nparts;
         } else {
             e.s = dcs_params(b.dyn_shape, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
         }
         e.pose = b.dyn_pose;
         e.slot = run[c];
         tab_h[c] = e;
+        if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) has_compound = true;
     }
     dcsb_tab.ensure(ncol, stream, false, 1.5f);
     dcsb_counts.ensure((size_t)ncol + 2, stream, false, 1.5f);
@@ -1963,8 +2091,22 @@ void World::run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const T
         for (int k = 0; k < 2; ++k) { dcsb_key[k].ensure(dcsb_cap, stream); dcsb_idx[k].ensure(dcsb_cap, stream); }
         dcsb_rec.ensure(dcsb_cap, stream); dcsb_push_idx.ensure(dcsb_cap, stream); dcsb_push_pos.ensure(dcsb_cap, stream); dcsb_push_vel.ensure(dcsb_cap, stream);
         SALVA_HIP_CHECK(hipMemsetAsync(dcsb_counts.p, 0, cnt_bytes, stream));
-        launch_dcsb_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, dcsb_cap, shift, dcsb_counts.p,
-                            dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, stream);
+        if (!has_compound) {
+            launch_dcsb_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, dcsb_cap, shift, dcsb_counts.p,
+                                dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, stream);
+        } else {
+            // compounds project in launches of their own (dcs.hip k_dcsb_segment): one launch per stretch of colliders of one class
+            dcsb_st_pos.ensure(n, stream, false, 1.1f); dcsb_st_vel.ensure(n, stream, false, 1.1f); dcsb_st_moved.ensure(n, stream, false, 1.1f);
+            for (uint32_t c0 = 0; c0 < ncol;) {
+                const bool compound = tab_h[c0].s.kind == SALVA_HIP_SHAPE_COMPOUND;
+                uint32_t c1 = c0 + 1;
+                while (c1 < ncol && (tab_h[c1].s.kind == SALVA_HIP_SHAPE_COMPOUND) == compound) ++c1;
+                launch_dcsb_segment(compound, n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, c0, c1, dcsb_cap, shift,
+                                    dcsb_counts.p, dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p,
+                                    dcsb_st_pos.p, dcsb_st_vel.p, dcsb_st_moved.p, stream);
+                c0 = c1;
+            }
+        }
         SALVA_HIP_CHECK(hipMemcpyAsync(stage + tab_bytes, dcsb_counts.p, cnt_bytes, hipMemcpyDeviceToHost, stream));
         wait_stream();
         ++dcs_stats[0]; ++dcs_stats[1];

@@ -100,6 +100,49 @@ class Mesh:
             del table[id(self)]
 
 
+class Compound:
+    """parry's `Compound` on the device (salva_hip_create_compound): `parts` is a list of (shape, translation,
+    rotation) with `shape` anything coupling.make_shape accepts or a Mesh, and (translation, unit quaternion (i, j, k, w)) the
+    part's pose in the compound's frame.  Accepted by DynamicContactSampling and LiquidWorld.particles_intersecting_shape; ray
+    sampling of a compound stays with HostRayShape.  The device copy belongs to a world and is made on first use there."""
+
+    def __init__(self, parts):
+        from .coupling import make_shape
+
+        self.parts = []
+        for shape, translation, rotation in parts:
+            s = shape if isinstance(shape, (L.Shape, Mesh)) else make_shape(shape)
+            self.parts.append((s, np.ascontiguousarray(translation, F32).reshape(3), np.ascontiguousarray(rotation, F32).reshape(4)))
+
+    def handle(self, world) -> int:
+        """The compound's handle in `world`, created on first use (its meshes' handles with it)."""
+        table = world.__dict__.setdefault("_compound_handles", {})
+        hit = table.get(id(self))
+        if hit is not None:
+            return hit[1]
+        arr = (L.CompoundPart * max(len(self.parts), 1))()
+        for k, (s, t, q) in enumerate(self.parts):
+            if isinstance(s, Mesh):
+                arr[k].kind, arr[k].mesh = L.SHAPE_MESH, s.handle(world)
+            else:
+                arr[k].kind = s.kind
+                arr[k].params[:] = list(s.params)
+            arr[k].translation[:] = [float(x) for x in t]
+            arr[k].rotation_ijkw[:] = [float(x) for x in q]
+        h = C.c_uint32()
+        L.check(world._L.salva_hip_create_compound(world._h, arr, len(self.parts), C.byref(h)))
+        table[id(self)] = (self, h.value)  # (keeps the compound alive, so that its id stays its own)
+        return h.value
+
+    def destroy(self, world):
+        """salva_hip_destroy_compound: refused while a dynamically sampled boundary of `world` still uses the compound."""
+        table = world.__dict__.get("_compound_handles", {})
+        hit = table.get(id(self))
+        if hit is not None:
+            L.check(world._L.salva_hip_destroy_compound(world._h, hit[1]))
+            del table[id(self)]
+
+
 def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
     from .coupling import make_shape
     from .world import DFSPHSolver, LiquidWorld

@@ -1510,19 +1510,28 @@ class LiquidWorld:
     def particles_intersecting_shape(self, translation, rotation, shape):
         """liquid_world.rs:245-280 for `shape` = ("ball", radius), ("cuboid", (hx, hy, hz)), ("capsule", half_height, radius) or
         ("cylinder", half_height, radius) (the last two along their local y axis) posed by the isometry
-        (translation, unit quaternion (i, j, k, w)): particles within the particle radius of the solid shape."""
+        (translation, unit quaternion (i, j, k, w)): particles within the particle radius of the solid shape.  `shape` may also be
+        a sampling.Compound or an oriented sampling.Mesh (salva_hip_particles_intersecting_compound / _mesh)."""
         self.sync_to_device(apply_removal=False)
         from .coupling import make_shape
+        from .sampling import Compound, Mesh
 
-        sh = make_shape(shape)
+        if isinstance(shape, Compound):
+            handle = shape.handle(self)
+            call = lambda *a: self._L.salva_hip_particles_intersecting_compound(self._h, t, q, handle, *a)  # noqa: E731
+        elif isinstance(shape, Mesh):
+            handle = shape.handle(self)
+            call = lambda *a: self._L.salva_hip_particles_intersecting_mesh(self._h, t, q, handle, *a)  # noqa: E731
+        else:
+            sh = make_shape(shape)
+            call = lambda *a: self._L.salva_hip_particles_intersecting_shape(self._h, t, q, C.byref(sh), *a)  # noqa: E731
         t = (C.c_float * 3)(*[float(x) for x in translation])
         q = (C.c_float * 4)(*[float(x) for x in rotation])
         u32p = C.POINTER(C.c_uint32)
         cap = 1024
         while True:
             k, s, i = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
-            total = int(self._L.salva_hip_particles_intersecting_shape(self._h, t, q, C.byref(sh), cap, k.ctypes.data_as(u32p),
-                                                                        s.ctypes.data_as(u32p), i.ctypes.data_as(u32p)))
+            total = int(call(cap, k.ctypes.data_as(u32p), s.ctypes.data_as(u32p), i.ctypes.data_as(u32p)))
             if total < 0:
                 L.check(total)
             if total <= cap:
