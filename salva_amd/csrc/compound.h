@@ -2,7 +2,7 @@
 // cuboid, a capsule, a cylinder or a mesh of the same world, which is what parry's `Compound` is for the bodies rapier users build
 // out of several shapes (a hull of cuboids, a ring of slabs, a convex decomposition handed over as oriented meshes).  The device
 // functions below are the one walk over the parts that DynamicContactSampling (dcs.hip: k_dcs_compound_project, k_dcsb_project) and the
-// shape query (world.hip: k_compound_query) share.
+// shape query (world_query.hip: k_compound_query) share.
 //
 // The projection is this project's reading of parry 0.18's Compound::project_local_point_and_get_feature (a best-first visit of
 // the parts, solid = false): every part projects the point on its own boundary, the part whose projection is nearest wins, ties go

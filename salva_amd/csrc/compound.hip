@@ -19,12 +19,13 @@ void compound_build_table(const SalvaHipCompoundPart* parts, uint32_t nparts, co
         const SalvaHipCompoundPart& in = parts[k];
         CompoundPartDev& d = table[k];
         const bool is_mesh = in.kind == SALVA_HIP_SHAPE_MESH;
+        SalvaHipShape sh{};
+        sh.kind = in.kind;
+        for (int a = 0; a < 3; ++a) sh.params[a] = in.params[a];
         if (!is_mesh) {
-            int np = 0;
-            try { np = shape_param_count(in.kind); }
+            try { shape_param_count(in.kind); }
             catch (const HipError&) { throw HipError(SALVA_HIP_E_INVALID, "compound: a part is a ball, a cuboid, a capsule, a cylinder or a mesh (no nesting, no host parts)"); }
-            for (int a = 0; a < np; ++a)
-                if (!(in.params[a] > 0.0f) || !std::isfinite(in.params[a])) throw HipError(SALVA_HIP_E_INVALID, "compound: shape parameters must be positive and finite");
+            check_shape_params(sh, "compound: shape parameters must be positive and finite");
         } else if (part_meshes[k] == nullptr) {
             throw HipError(SALVA_HIP_E_INVALID, "no such mesh");
         }
@@ -45,9 +46,6 @@ void compound_build_table(const SalvaHipCompoundPart* parts, uint32_t nparts, co
             aabb_transform_by(part_meshes[k]->mins, part_meshes[k]->maxs, d.t, d.q, d.lo, d.hi);
             d.mesh = part_meshes[k]->dev();
         } else {
-            SalvaHipShape sh{};
-            sh.kind = in.kind;
-            for (int a = 0; a < 3; ++a) sh.params[a] = in.params[a];
             float ext[3];
             shape_world_extent(sh, d.q, ext);
             for (int a = 0; a < 3; ++a) { d.lo[a] = d.t[a] - ext[a]; d.hi[a] = d.t[a] + ext[a]; }
@@ -100,23 +98,6 @@ void World::destroy_compound(uint32_t compound) {
         throw HipError(SALVA_HIP_E_INVALID, "the compound is the collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it)");
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     compounds[compound].reset();
-}
-
-// The mesh arm's registration for a compound of this world: gather, projection and apply stay on the device, and the pose handed to
-// salva_hip_update_boundary_pose places the compound.
-void World::set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter) {
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "compound colliders are not available in a running decomposed world");
-    const std::shared_ptr<CompoundRes> c = compound_at(compound);
-    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary(slot, 0, nullptr, nullptr, memberships, filter, keep_forces);
-    BoundarySlot& b = bounds[slot];
-    b.sampling.reset();
-    b.dyn_kind = SALVA_HIP_SHAPE_COMPOUND;
-    b.dyn_shape = SalvaHipShape{};
-    b.dyn_compound = c;
-    b.dyn_pose = SalvaHipRigidPose{};
-    b.dyn_pose.rotation[3] = 1.0f;
-    b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
 }
 
 }  // namespace salva

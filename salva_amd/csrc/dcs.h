@@ -1,4 +1,4 @@
-// dcs.h — DynamicContactSampling (dcs.hip): launcher interface used by world.hip.
+// dcs.h — DynamicContactSampling (dcs.hip): launcher interface used by world_coupling.hip (the shape helpers also by world_query.hip, sample.hip and compound.hip).
 #pragma once
 #include <cmath>
 
@@ -125,6 +125,10 @@ __host__ __device__ __forceinline__ void dcs_project_local(const S& s, float lx,
 
 // number of parameters of a built-in collider shape (include/salva_hip.h); throws SALVA_HIP_E_INVALID for any other kind
 int shape_param_count(int kind);
+// ... and its parameters are positive and finite: throws SALVA_HIP_E_INVALID with `message` (world_coupling.hip)
+void check_shape_params(const SalvaHipShape& shape, const char* message);
+// HGrid::key(lo) .. key(hi) per axis (hgrid.rs:128-129): floor(x / h), clamped like the particles' cell coordinates (tile.h cell_coord)
+void cell_range(const float lo[3], const float hi[3], float h, int clo[3], int chi[3]);
 void shape_world_extent(const SalvaHipShape& shape, const float rotation_ijkw[4], float ext[3]);
 DcsParams dcs_params(const SalvaHipShape& shape, const SalvaHipRigidPose& pose, float h, float particle_radius, float dt);
 // one candidate (projection xyz, host particle index bits) and one flag per fluid particle; pushes particles inside the
@@ -152,7 +156,7 @@ void launch_dcs_emit(uint32_t cnt, const float4* cand, const SalvaHipRigidPose& 
 
 // ---- batched runs (dcs.hip "batched runs").  One entry per collider of a run, in slot order; the pass reads `s` and
 // `mesh`, the emit `pose`, `slot` and what the host fills in once it has the counts: the collider's first boundary row, its first
-// sorted record, and where its rows' source particles go (BoundarySlot::dyn_src).
+// sorted record, and where its rows' source particles go (DynSampling::src, world.h).
 struct CompoundPartDev;  // compound.h
 struct DcsbEntry {
     DcsParams s;

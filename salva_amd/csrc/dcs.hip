@@ -388,6 +388,13 @@ void shape_world_extent(const SalvaHipShape& shape, const float q[4], float ext[
     }
 }
 
+void cell_range(const float lo[3], const float hi[3], float h, int clo[3], int chi[3]) {
+    for (int a = 0; a < 3; ++a) {
+        clo[a] = (int)std::fmin(std::fmax(std::floor(lo[a] / h), -1073741824.0f), 1073741824.0f);
+        chi[a] = (int)std::fmin(std::fmax(std::floor(hi[a] / h), -1073741824.0f), 1073741824.0f);
+    }
+}
+
 // Ball::compute_aabb / Cuboid::compute_aabb of the posed shape, loosened by h + prediction (:196-199), and the cell range
 // HGrid::cells_intersecting_aabb walks (hgrid.rs:128-131).
 DcsParams dcs_params(const SalvaHipShape& shape, const SalvaHipRigidPose& pose, float h, float particle_radius, float dt) {
@@ -406,10 +413,8 @@ DcsParams dcs_params(const SalvaHipShape& shape, const SalvaHipRigidPose& pose, 
     for (int a = 0; a < 3; ++a) {
         s.lo[a] = (pose.translation[a] - ext[a]) - s.reach;
         s.hi[a] = (pose.translation[a] + ext[a]) + s.reach;
-        const float fl = std::floor(s.lo[a] / h), fh = std::floor(s.hi[a] / h);
-        s.clo[a] = (int)std::fmin(std::fmax(fl, -1073741824.0f), 1073741824.0f);
-        s.chi[a] = (int)std::fmin(std::fmax(fh, -1073741824.0f), 1073741824.0f);
     }
+    cell_range(s.lo, s.hi, h, s.clo, s.chi);
     return s;
 }
 
@@ -427,10 +432,8 @@ DcsParams dcs_params_host(const float mins[3], const float maxs[3], float h, flo
     for (int a = 0; a < 3; ++a) {
         s.lo[a] = mins[a] - s.reach;
         s.hi[a] = maxs[a] + s.reach;
-        const float fl = std::floor(s.lo[a] / h), fh = std::floor(s.hi[a] / h);
-        s.clo[a] = (int)std::fmin(std::fmax(fl, -1073741824.0f), 1073741824.0f);
-        s.chi[a] = (int)std::fmin(std::fmax(fh, -1073741824.0f), 1073741824.0f);
     }
+    cell_range(s.lo, s.hi, h, s.clo, s.chi);
     return s;
 }
 

@@ -1,4 +1,4 @@
-// pose.h — the one place a collider-local point is carried into world space on the device (k_boundary_pose in world.hip,
+// pose.h — the one place a collider-local point is carried into world space on the device (k_boundary_pose in world_coupling.hip,
 // k_sample_emit in sample.hip): two paths that pose the same point must produce the same bits.
 #pragma once
 #include "common.h"

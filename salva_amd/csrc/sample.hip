@@ -259,9 +259,7 @@ void check_sample_args(float particle_rad, int mode) {
 
 // half extents of the shape's local AABB (`shape.compute_aabb(&Isometry::identity())`)
 void shape_half_extents(const SalvaHipShape& shape, float ext[3]) {
-    const int np = shape_param_count(shape.kind);
-    for (int a = 0; a < np; ++a)
-        if (!(shape.params[a] > 0.0f) || !std::isfinite(shape.params[a])) throw HipError(SALVA_HIP_E_INVALID, "shape parameters must be positive");
+    check_shape_params(shape, "shape parameters must be positive");
     switch (shape.kind) {
         case SALVA_HIP_SHAPE_BALL: ext[0] = ext[1] = ext[2] = shape.params[0]; break;
         case SALVA_HIP_SHAPE_CUBOID: ext[0] = shape.params[0]; ext[1] = shape.params[1]; ext[2] = shape.params[2]; break;

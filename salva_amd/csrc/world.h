@@ -20,7 +20,30 @@
 
 namespace salva {
 
-struct DcsbEntry;  // dcs.h
+struct DcsParams;  // dcs.h
+struct DcsbEntry;
+
+// ColliderSampling::DynamicContactSampling (integrations/rapier/fluids_pipeline.rs:42-43): the one description of a dynamically
+// sampled collider.  The boundary's particles are re-emitted by every step (World::run_dynamic_sampling, world_coupling.hip); a
+// BoundarySlot that drops the description drops everything of the sampling method with it — the mesh or compound it kept alive
+// (salva_hip_destroy_mesh / _compound refuse while one is held), the host's callbacks and user pointer, the source arrays.
+struct DynSampling {
+    int kind = 0;                           // SALVA_HIP_SHAPE_*
+    SalvaHipShape shape{};                  // a built-in shape (ball, cuboid, capsule, cylinder)
+    SalvaHipHostShape host{};               // SALVA_HIP_SHAPE_HOST: the host's compute_aabb / project_point callbacks
+    std::shared_ptr<MeshRes> mesh;          // SALVA_HIP_SHAPE_MESH
+    std::shared_ptr<CompoundRes> compound;  // SALVA_HIP_SHAPE_COMPOUND
+    SalvaHipRigidPose pose{};               // the collider's last pose (identity until salva_hip_update_boundary_pose)
+    // host index of the fluid particle behind each emitted row (decomposed run: its global id, and `src_model` its fluid — the
+    // particle may live on another rank)
+    DevBuf<uint32_t> src, src_model;
+    DynSampling() { pose.rotation[3] = 1.0f; }
+    bool built_in() const { return kind >= SALVA_HIP_SHAPE_BALL && kind <= SALVA_HIP_SHAPE_CYLINDER; }  // projects inside the pass over the fluid
+    // the only two places that know what each kind needs: the pass's parameters for (h, particle radius, dt) — a host shape's box
+    // comes from its aabb callback — and the collider's half of a batched run's table entry
+    DcsParams params(float h, float particle_radius, float dt) const;
+    void fill_entry(DcsbEntry& e) const;
+};
 
 struct FluidSlot {
     uint64_t n = 0;
@@ -43,16 +66,8 @@ struct BoundarySlot {
     bool vel_zero = true;  // every velocity of the last upload was exactly zero (a sampled boundary's are written on the device: treated as moving)
     // ColliderSampling::StaticSampling(points): collider-local sample points (integrations/rapier/fluids_pipeline.rs:36-41)
     std::shared_ptr<DevBuf<float4>> sampling;
-    // ColliderSampling::DynamicContactSampling (:42-43): the collider's shape and its last pose; the boundary's particles are
-    // re-emitted by every step (World::run_dynamic_sampling), `dyn_src` = host index of the fluid particle behind each
-    // (decomposed run: its global id, and `dyn_src_model` its fluid — the particle may live on another rank)
-    int dyn_kind = 0;
-    SalvaHipShape dyn_shape{};
-    SalvaHipHostShape dyn_host{};  // dyn_kind == SALVA_HIP_SHAPE_HOST: the host's compute_aabb / project_point callbacks
-    SalvaHipRigidPose dyn_pose{};
-    std::shared_ptr<MeshRes> dyn_mesh;  // dyn_kind == SALVA_HIP_SHAPE_MESH: the collider's mesh (kept alive: salva_hip_destroy_mesh refuses)
-    std::shared_ptr<CompoundRes> dyn_compound;  // dyn_kind == SALVA_HIP_SHAPE_COMPOUND (kept alive: salva_hip_destroy_compound refuses)
-    std::shared_ptr<DevBuf<uint32_t>> dyn_src, dyn_src_model;
+    // ColliderSampling::DynamicContactSampling: null for a plain or statically sampled boundary (shared: remove_boundary copies slots)
+    std::shared_ptr<DynSampling> dyn;
 };
 
 struct GridDims {          // tile-aligned dense grid (tile.h)
@@ -65,8 +80,9 @@ struct GridDims {          // tile-aligned dense grid (tile.h)
     size_t ncells() const { return ntiles() * TCELLS; }
 };
 
-// helpers world.hip and world_step.hip share (bits_for and dims_from_bbox are defined in world.hip)
+// helpers the world*.hip files share (bits_for, dims_from_bbox and launch_unpack_xyz are defined in world.hip)
 inline unsigned nblk(uint64_t n) { return div_up(n ? n : 1, BLOCK); }
+void launch_unpack_xyz(uint32_t n, const float4* src, float* dst, hipStream_t s);  // float4 rows -> packed xyz
 int bits_for(uint64_t ncells);  // key bits of a radix sort over `ncells` cells
 struct FoldRule { double budget, target; uint32_t min_period[3]; bool axis[3]; };  // fold when the box exceeds `budget` cells, then down to `target`; axis[a]: may fold
 void dims_from_bbox(const int32_t* bb, GridDims& g, const FoldRule* fold = nullptr);
@@ -118,7 +134,8 @@ class World {
     int64_t add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel);
     int64_t set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
-    // ---- compound colliders (compound.hip): the world's table, DynamicContactSampling on one, the shape query
+    // ---- compound colliders (compound.hip): the world's table; DynamicContactSampling on one (world_coupling.hip) and
+    // the shape query (world_query.hip)
     uint32_t create_compound(const SalvaHipCompoundPart* parts, uint32_t nparts);
     void destroy_compound(uint32_t compound);
     void set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
@@ -190,7 +207,9 @@ class World {
 
   private:
     void use_device() const;
+    // ---- particle queries (world_query.hip)
     struct QuerySrc query_fluid_source();
+    template <typename Launch> uint64_t run_query(uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices, Launch&& launch);
     uint64_t collect_query(unsigned int* d_count, uint32_t* d_kind, uint32_t* d_index, uint32_t cap, uint32_t* kinds, uint32_t* slots,
                            uint32_t* indices);
     uint64_t fluid_offset(uint32_t slot) const;
@@ -198,7 +217,6 @@ class World {
     void ensure_staging_current();
     void upload_tables();
     void build_boundary_grid();
-    void resize_boundary_slot(uint32_t slot, uint64_t nn);
     uint64_t append_particles(uint32_t slot, uint64_t n_add);
     void set_boundary_from(uint32_t slot, uint64_t n, const float* pos, const float* vel, uint32_t memberships, uint32_t filter,
                            bool wants_forces, const std::function<void(float4*)>* fill_dev);
@@ -222,34 +240,44 @@ class World {
     const std::shared_ptr<CompoundRes>& compound_at(uint32_t compound) const;
     void stamp_fluid_models();
     void stamp_boundary_models();
+    // ---- rigid-body coupling (world_coupling.hip)
     bool has_dynamic_sampling() const;
+    void register_dynamic_sampling(uint32_t slot, std::shared_ptr<DynSampling> d, uint32_t memberships, uint32_t filter);
+    void check_pose_target(uint32_t slot, const SalvaHipRigidPose& pose) const;
+    bool accept_pose(BoundarySlot& b, const SalvaHipRigidPose& pose);
     // ... in one pass over the fluid for a run of device-shape colliders (dcs.hip "batched runs")
     static constexpr size_t DCS_BATCH_MIN_RUN = 2;
+    void run_dynamic_sampling();   // between the cell keys and the sort (fluids_pipeline.rs:193-259 inside liquid_world.rs:94-103)
     void run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv);
     void run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const TileGrid& gv);
-    void relayout_boundaries(const std::vector<uint32_t>& run, const uint64_t* counts);
-    DevBuf<DcsbEntry> dcsb_tab;
-    DevBuf<unsigned long long> dcsb_counts, dcsb_key[2];
-    DevBuf<uint32_t> dcsb_idx[2], dcsb_push_idx;
-    DevBuf<float4> dcsb_rec, dcsb_push_pos, dcsb_push_vel;
-    DevBuf<float4> dcsb_st_pos, dcsb_st_vel;  // a run with compounds: the particles between its launches (dcs.hip k_dcsb_segment)
-    DevBuf<uint8_t> dcsb_st_moved;
-    uint32_t dcsb_cap = 0;  // records the buffers above are cut for (0: not yet)
-    PinnedStage dcsb_stage, pose_stage, wrench_stage;
-    DevBuf<char> pose_tab, wrench_tab;  // salva_hip_update_boundary_poses / _get_boundary_wrenches: their entry tables
-    DevBuf<double> wrenches_partial;
+    uint32_t compact_and_count(size_t tb, const float4* in, float4* out, uint32_t count);
+    void relayout_boundaries(const uint32_t* run, size_t nrun, const uint64_t* counts);
     uint64_t dcs_stats[4] = {0, 0, 0, 0};
-    void run_dynamic_sampling();   // between the cell keys and the sort (fluids_pipeline.rs:193-259 inside liquid_world.rs:94-103)
-    DevBuf<float4> dcs_cand, dcs_out, dcs_proj, dcs_cand2;  // (_proj, _cand2: the host-shape arm)
-    std::vector<float> dcs_h_pts, dcs_h_proj;
-    std::vector<float4> dcs_h_f4;
-    std::vector<uint8_t> dcs_h_inside;
-    DevBuf<uint8_t> dcs_flag;
-    // the particles as they were before the push-outs of a pass that may still end in a FoldRetry (World::run_pass / substep)
-    DevBuf<float4> dcs_undo_pos, dcs_undo_vel;
-    DevBuf<uint32_t> dcs_num;
-    // decomposed run: every rank's emitted points, in rank order (dist_gather_emitted): rows, then one uint32 fluid per row
-    DevBuf<unsigned long long> dcs_all;
+    // the scratch of all of the above, grown on demand and kept between calls
+    struct CouplingScratch {
+        // one collider at a time: candidates, compacted rows, (the host-shape / mesh / compound arm:) projections and applied candidates
+        DevBuf<float4> dcs_cand, dcs_out, dcs_proj, dcs_cand2;
+        DevBuf<uint8_t> dcs_flag;
+        DevBuf<uint32_t> dcs_num;
+        std::vector<float> dcs_h_pts, dcs_h_proj;  // the host-shape arm's side of the callback
+        std::vector<float4> dcs_h_f4;
+        std::vector<uint8_t> dcs_h_inside;
+        // the particles as they were before the push-outs of a pass that may still end in a FoldRetry (World::run_pass / substep)
+        DevBuf<float4> dcs_undo_pos, dcs_undo_vel;
+        // decomposed run: every rank's emitted points, in rank order (dist_gather_emitted): rows, then one uint32 fluid per row
+        DevBuf<unsigned long long> dcs_all;
+        // a batched run: the table, the counts, records and their sort keys, the push list
+        DevBuf<DcsbEntry> dcsb_tab;
+        DevBuf<unsigned long long> dcsb_counts, dcsb_key[2];
+        DevBuf<uint32_t> dcsb_idx[2], dcsb_push_idx;
+        DevBuf<float4> dcsb_rec, dcsb_push_pos, dcsb_push_vel;
+        DevBuf<float4> dcsb_st_pos, dcsb_st_vel;  // a run with compounds: the particles between its launches (dcs.hip k_dcsb_segment)
+        DevBuf<uint8_t> dcsb_st_moved;
+        uint32_t dcsb_cap = 0;  // records the buffers above are cut for (0: not yet)
+        PinnedStage dcsb_stage, pose_stage, wrench_stage;
+        DevBuf<char> pose_tab, wrench_tab;  // salva_hip_update_boundary_poses / _get_boundary_wrenches: their entry tables
+        DevBuf<double> wrench_partial, wrenches_partial;  // per-block partial sums of salva_hip_get_boundary_wrench / _wrenches
+    } cpl;
     uint32_t dist_gather_emitted(const float4* rows, uint32_t cnt, const float4** all_rows, const uint32_t** all_models,
                                  const HipError* local_error = nullptr);
     void ensure_cub_temp(size_t bytes);
@@ -435,7 +463,6 @@ class World {
     DevBuf<float4> acc, w, normal, dii, dijpj, iisph_q, iisph_pr, posmr;
     DevBuf<float> visc_beta, visc_target;  // DFSPHViscosity scratch: betas [36][n], strain-rate targets [6][n]
     DevBuf<float4> visc_u0, visc_u1, visc_va;
-    DevBuf<double> wrench_partial;       // per-block partial sums of salva_hip_get_boundary_wrench
     DevBuf<float> he_colors, he_gradcs;  // He2014SurfaceTension state (he2014_surface_tension.rs:15-16)
     DevBuf<float> rho, alpha, kappa, kappa2, rho_star, aii;
     DevBuf<uint32_t> nff, nfb;

@@ -1,10 +1,9 @@
-// world.hip — host side of libsalva_hip: device memory, object edits, the per-model tables, queries, up/download, timing probes.
-// The per-step launch sequence (World::step, World::substep and what they call) is world_step.hip.
+// world.hip — host side of libsalva_hip: device memory, object edits, the per-model tables, up/download, timing probes.
+// The per-step launch sequence (World::step, World::substep and what they call) is world_step.hip, rigid-body coupling and
+// DynamicContactSampling are world_coupling.hip, the particle queries world_query.hip.
 // Host <-> device traffic happens only in set_* / get_*.
 #include "world.h"
-#include "dcs.h"
 #include "bbox.h"
-#include "pose.h"
 
 #include <algorithm>
 #include <cmath>
@@ -62,6 +61,7 @@ __global__ void k_unpack_xyz(uint32_t n, const float4* __restrict__ src, float* 
     const float4 s = src[i];
     dst[3 * i] = s.x; dst[3 * i + 1] = s.y; dst[3 * i + 2] = s.z;
 }
+void launch_unpack_xyz(uint32_t n, const float4* src, float* dst, hipStream_t s) { k_unpack_xyz<<<nblk(n), BLOCK, 0, s>>>(n, src, dst); }
 __global__ void k_unpack_w(uint32_t n, const float4* __restrict__ src, float* __restrict__ dst) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < n) dst[i] = src[i].w;
@@ -620,9 +620,7 @@ void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, cons
     }
     BoundarySlot& b = bounds[slot];
     b.n = nn; b.memberships = memberships; b.filter = filter; b.wants_forces = wants_forces;
-    b.dyn_kind = 0;  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
-    b.dyn_mesh.reset();
-    b.dyn_compound.reset();
+    b.dyn.reset();  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
     b.vel_zero = true;
     if (nn) {
         scratch_f.ensure(3 * nn, stream, false, 1.1f);
@@ -772,7 +770,7 @@ StepCtx World::make_ctx() {
     c.nffb = pass.two_mass ? nffb.p : nullptr;
     c.nffc = (pass.two_mass && pass.nmass > 2u) ? nffc.p : nullptr;
     c.bvel_zero = 1u;  // no boundary particle moves: the passes that subtract a boundary velocity need not stage it
-    for (const BoundarySlot& b : bounds) if (b.n && (!b.vel_zero || b.sampling || b.dyn_kind)) c.bvel_zero = 0u;
+    for (const BoundarySlot& b : bounds) if (b.n && (!b.vel_zero || b.sampling || b.dyn)) c.bvel_zero = 0u;
     c.rho0_tab = rho0_tab.p; c.rho0_single = fluids.empty() ? 1000.0f : fluids[0].density0; c.ff_ok = ff_ok.p; c.fb_ok = fb_ok.p; c.bb_ok = bb_ok.p;
     c.partials = partials.p;
     c.spec_k = -1; c.spec_ring = spec_ring.p; c.spec_pub = nullptr; c.model_counts = model_counts.p; c.w2 = w2.p;
@@ -965,366 +963,6 @@ void World::set_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, con
     // the rest lists from positions0 now (the same lists the state had: rows are sorted); volumes0 stays as given
     elastic_build_rest(e, make_sph_consts(prm.particle_radius * prm.smoothing_factor * 2.0f), elastic_params(fluids[slot].forces[force].p),
                        true, stream);
-}
-
-// LiquidWorld::particles_intersecting_aabb (liquid_world.rs:210-243): particles whose distance to the box is below the
-// particle radius.  The reference walks the cells of its (last step's) grid; here every particle's current position is
-// tested, which finds the same particles plus those that entered the box's cells since the grid was built.
-// Where a query finds its fluid particles.  Single domain: the staging arrays (host order; index = position in the concatenation of
-// the fluids).  Decomposed run: the rank's working set after its last step — ghosts are skipped (their owner reports them), the
-// index is the particle's GLOBAL id and the fluid slot rides in bits 8.. of the kind word.
-struct QuerySrc {
-    const float4* pos; uint32_t n;
-    const uint32_t* gtag;   // nullptr: no ghosts in `pos`
-    const uint32_t* gid;    // nullptr: index = i
-    const uint32_t* model;  // nullptr: the slot follows from the index (collect_query)
-};
-__device__ __forceinline__ bool query_skip(const QuerySrc& q, uint32_t i) { return q.gtag && (q.gtag[i] & 0x80000000u); }
-__device__ __forceinline__ void query_emit(const QuerySrc& q, uint32_t i, uint32_t kind, unsigned int* counter, uint32_t cap, uint32_t* out_kind,
-                                           uint32_t* out_index) {
-    const uint32_t k = atomicAdd(counter, 1u);
-    if (k < cap) { out_kind[k] = kind | (q.model ? q.model[i] << 8 : 0u); out_index[k] = q.gid ? q.gid[i] : i; }
-}
-__global__ __launch_bounds__(BLOCK) void k_aabb_query(QuerySrc q, float3 lo, float3 hi, float r2,
-                                                      uint32_t kind, unsigned int* __restrict__ counter, uint32_t cap,
-                                                      uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= q.n || query_skip(q, i)) return;
-    const float4 p = q.pos[i];
-    const float dx = fmaxf(fmaxf(lo.x - p.x, p.x - hi.x), 0.0f), dy = fmaxf(fmaxf(lo.y - p.y, p.y - hi.y), 0.0f),
-                dz = fmaxf(fmaxf(lo.z - p.z, p.z - hi.z), 0.0f);
-    if (!(dx * dx + dy * dy + dz * dz < r2)) return;
-    query_emit(q, i, kind, counter, cap, out_kind, out_index);
-}
-// Single domain: the staging arrays, refreshed from the working set.  Decomposed run (after its first step): the owned particles of
-// the working set with their global ids — a query is a per-rank operation there, each rank reports what it owns; the union over
-// the ranks is the undivided world's answer (boundary particles near a slab face are held, and reported, by both neighbours).
-QuerySrc World::query_fluid_source() {
-    if (comm && dist_started && sorted_valid) return QuerySrc{posm[cur].p, n, gtag[cur].p, perm[cur].p, model[cur].p};
-    if (comm) throw HipError(SALVA_HIP_E_INVALID, "a query in a decomposed run needs a completed step (global ids exist from then on)");
-    ensure_staging_current();
-    return QuerySrc{st_pos.p, n, nullptr, nullptr, nullptr};
-}
-
-// (kind, global index) pairs collected on the device -> sorted (kind, slot, index-in-slot) triples on the host
-uint64_t World::collect_query(unsigned int* d_count, uint32_t* d_kind, uint32_t* d_index, uint32_t cap, uint32_t* kinds, uint32_t* slots,
-                              uint32_t* indices) {
-    unsigned int total = 0;
-    SALVA_HIP_CHECK(hipMemcpyAsync(&total, d_count, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    const uint32_t m = std::min<uint32_t>(total, cap);
-    if (m == 0 || !kinds || !slots || !indices) return total;
-    std::vector<uint32_t> hk(m), hi_(m);
-    SALVA_HIP_CHECK(hipMemcpy(hk.data(), d_kind, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SALVA_HIP_CHECK(hipMemcpy(hi_.data(), d_index, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    std::vector<uint64_t> keys(m);
-    for (uint32_t k = 0; k < m; ++k) keys[k] = ((uint64_t)hk[k] << 32) | hi_[k];
-    map_query_hits(keys, kinds, slots, indices);
-    return total;
-}
-// (kind word << 32 | global index) keys -> sorted (kind, slot, index-in-slot) triples
-void World::map_query_hits(std::vector<uint64_t>& keys, uint32_t* kinds, uint32_t* slots, uint32_t* indices) {
-    const uint32_t m = (uint32_t)keys.size();
-    std::sort(keys.begin(), keys.end());
-    for (uint32_t k = 0; k < m; ++k) {
-        uint32_t kind = (uint32_t)(keys[k] >> 32);
-        uint64_t g = keys[k] & 0xffffffffull;
-        uint32_t s = 0;
-        if (comm && (kind & 0xffu) == 0) {  // decomposed run: the slot came with the kind word, the index is a global id
-            kinds[k] = 0u; slots[k] = kind >> 8; indices[k] = (uint32_t)g;
-            continue;
-        }
-        kind &= 0xffu;
-        if (kind == 0) { while (s + 1 < fluids.size() && g >= fluids[s].n) { g -= fluids[s].n; ++s; } }
-        else { while (s + 1 < bounds.size() && g >= bounds[s].n) { g -= bounds[s].n; ++s; } }
-        kinds[k] = kind; slots[k] = s; indices[k] = (uint32_t)g;
-    }
-}
-
-uint64_t World::particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                  uint32_t* indices) {
-    use_device();
-    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
-    DevBuf<unsigned int> cnt;
-    DevBuf<uint32_t> dk, di;
-    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
-    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
-    const float r = prm.particle_radius;
-    const float3 lo = make_float3(mins[0], mins[1], mins[2]), hi = make_float3(maxs[0], maxs[1], maxs[2]);
-    if (qf.n) k_aabb_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, lo, hi, r * r, 0u, cnt.p, cap, dk.p, di.p);
-    if (nb) k_aabb_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, lo, hi, r * r, 1u, cnt.p, cap, dk.p, di.p);
-    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
-}
-
-// LiquidWorld::particles_intersecting_shape (liquid_world.rs:245-280) for a ball / cuboid posed by (t, q): the particle must lie
-// in a grid cell the shape's world AABB touches (hgrid.cells_intersecting_aabb: cell range floor(mins / h) .. floor(maxs / h),
-// hgrid.rs:122-133) and `shape.distance_to_point(pos, pt, solid = true) <= particle_radius`.  The point goes into the shape's
-// frame with the inverse isometry (conjugate quaternion); ball: max(|p| - radius, 0); cuboid: |max(|p| - half_extents, 0)|.
-struct ShapeQuery {
-    float t[3], q[4];       // isometry
-    int kind; float p[3];   // shape
-    int clo[3], chi[3];     // cell range of the world AABB
-    float h, r;             // cell width, particle radius
-};
-// `shape.distance_to_point(identity, l, solid = true)` of a built-in shape for a point in the shape's frame: the one copy, for
-// k_shape_query and for the parts of a compound (k_compound_query)
-__device__ __forceinline__ float shape_solid_distance(int kind, const float p[3], float lx, float ly, float lz) {
-    float d;
-    if (kind == SALVA_HIP_SHAPE_BALL) {
-        d = fmaxf(sqrtf(lx * lx + ly * ly + lz * lz) - p[0], 0.0f);
-    } else if (kind == SALVA_HIP_SHAPE_CAPSULE) {  // distance to the segment (0, -hh..hh, 0), minus the radius
-        const float ey = ly - fminf(fmaxf(ly, -p[0]), p[0]);
-        d = fmaxf(sqrtf(lx * lx + ey * ey + lz * lz) - p[1], 0.0f);
-    } else if (kind == SALVA_HIP_SHAPE_CYLINDER) {  // beyond the caps and beyond the side
-        const float ey = fmaxf(fabsf(ly) - p[0], 0.0f), er = fmaxf(sqrtf(lx * lx + lz * lz) - p[1], 0.0f);
-        d = sqrtf(ey * ey + er * er);
-    } else {
-        const float dx = fmaxf(fabsf(lx) - p[0], 0.0f), dy = fmaxf(fabsf(ly) - p[1], 0.0f), dz = fmaxf(fabsf(lz) - p[2], 0.0f);
-        d = sqrtf(dx * dx + dy * dy + dz * dz);
-    }
-    return d;
-}
-__global__ __launch_bounds__(BLOCK) void k_shape_query(QuerySrc q, ShapeQuery s, uint32_t kind,
-                                                       unsigned int* __restrict__ counter, uint32_t cap, uint32_t* __restrict__ out_kind,
-                                                       uint32_t* __restrict__ out_index) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= q.n || query_skip(q, i)) return;
-    const float4 pt = q.pos[i];
-    bool bad = false;
-    const int cx = cell_coord(pt.x, s.h, bad), cy = cell_coord(pt.y, s.h, bad), cz = cell_coord(pt.z, s.h, bad);
-    if (bad || cx < s.clo[0] || cx > s.chi[0] || cy < s.clo[1] || cy > s.chi[1] || cz < s.clo[2] || cz > s.chi[2]) return;
-    // inverse isometry: q^-1 * (pt - t)
-    const float vx = pt.x - s.t[0], vy = pt.y - s.t[1], vz = pt.z - s.t[2];
-    const float qx = -s.q[0], qy = -s.q[1], qz = -s.q[2], qw = s.q[3];
-    const float tx = (qy * vz - qz * vy) * 2.0f, ty = (qz * vx - qx * vz) * 2.0f, tz = (qx * vy - qy * vx) * 2.0f;
-    const float lx = vx + qw * tx + (qy * tz - qz * ty), ly = vy + qw * ty + (qz * tx - qx * tz), lz = vz + qw * tz + (qx * ty - qy * tx);
-    const float d = shape_solid_distance(s.kind, s.p, lx, ly, lz);
-    if (!(d <= s.r)) return;
-    query_emit(q, i, kind, counter, cap, out_kind, out_index);
-}
-uint64_t World::particles_in_shape(const float t[3], const float q[4], const SalvaHipShape& shape, uint64_t capacity, uint32_t* kinds,
-                                   uint32_t* slots, uint32_t* indices) {
-    use_device();
-    const int nparams = shape_param_count(shape.kind);
-    // the pose must be a rigid motion and the shape non-degenerate (the reference takes an Isometry and a parry shape, which
-    // cannot be anything else): NaN / huge values would otherwise reach an undefined float -> int conversion below
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite translation");
-    {
-        float qn = 0.0f;
-        for (int a = 0; a < 4; ++a) {
-            if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite rotation");
-            qn += q[a] * q[a];
-        }
-        if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, "shape query: the rotation must be a unit quaternion (x, y, z, w)");
-    }
-    for (int a = 0; a < nparams; ++a)
-        if (!(shape.params[a] > 0.0f) || !std::isfinite(shape.params[a]))
-            throw HipError(SALVA_HIP_E_INVALID, "shape query: radius / half extents must be positive and finite");
-    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
-    ShapeQuery s{};
-    for (int a = 0; a < 3; ++a) { s.t[a] = t[a]; s.p[a] = shape.params[a]; }
-    for (int a = 0; a < 4; ++a) s.q[a] = q[a];
-    s.kind = shape.kind; s.h = sc.h; s.r = prm.particle_radius;
-    // world AABB (parry compute_aabb; dcs.hip)
-    float ext[3];
-    shape_world_extent(shape, q, ext);
-    for (int a = 0; a < 3; ++a) {  // (clamped like the cell coordinates of the particles: tile.h cell_coord)
-        s.clo[a] = (int)std::min(std::max(floorf((t[a] - ext[a]) / sc.h), -1073741824.0f), 1073741824.0f);
-        s.chi[a] = (int)std::min(std::max(floorf((t[a] + ext[a]) / sc.h), -1073741824.0f), 1073741824.0f);
-    }
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
-    DevBuf<unsigned int> cnt;
-    DevBuf<uint32_t> dk, di;
-    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
-    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
-    if (qf.n) k_shape_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, 0u, cnt.p, cap, dk.p, di.p);
-    if (nb) k_shape_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, 1u, cnt.p, cap, dk.p, di.p);
-    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
-}
-
-// The same query for a posed compound and for a posed oriented mesh.  A compound's solid distance is the smallest of
-// its parts', each taken in the part's frame (pose_k^-1 * l, quat_rot with the conjugate); an oriented mesh's is 0 inside and the
-// distance to the closest point outside.  The cell range comes from the posed local box (parry's Aabb::transform_by, dcs.hip).
-struct PosedQuery {
-    float t[3], q[4];       // isometry
-    int clo[3], chi[3];     // cell range of the world AABB
-    float h, r;             // cell width, particle radius
-};
-__device__ __forceinline__ bool posed_query_local(const QuerySrc& q, const PosedQuery& s, uint32_t i, float& lx, float& ly, float& lz) {
-    if (i >= q.n || query_skip(q, i)) return false;
-    const float4 pt = q.pos[i];
-    bool bad = false;
-    const int cx = cell_coord(pt.x, s.h, bad), cy = cell_coord(pt.y, s.h, bad), cz = cell_coord(pt.z, s.h, bad);
-    if (bad || cx < s.clo[0] || cx > s.chi[0] || cy < s.clo[1] || cy > s.chi[1] || cz < s.clo[2] || cz > s.chi[2]) return false;
-    quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], pt.x - s.t[0], pt.y - s.t[1], pt.z - s.t[2], lx, ly, lz);
-    return true;
-}
-__device__ __forceinline__ float mesh_solid_distance(const MeshDev& m, float lx, float ly, float lz) {
-    float jx, jy, jz;
-    bool inside;
-    mesh_project_point(m, lx, ly, lz, jx, jy, jz, inside);
-    const float dx = lx - jx, dy = ly - jy, dz = lz - jz;
-    return inside ? 0.0f : sqrtf((dx * dx + dy * dy) + dz * dz);
-}
-__global__ __launch_bounds__(BLOCK) void k_compound_query(QuerySrc q, PosedQuery s, const CompoundPartDev* __restrict__ parts, uint32_t nparts,
-                                                          uint32_t kind, unsigned int* __restrict__ counter, uint32_t cap,
-                                                          uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    float lx, ly, lz;
-    if (!posed_query_local(q, s, i, lx, ly, lz)) return;
-    float d = __builtin_inff();
-#pragma unroll 1
-    for (uint32_t k = 0; k < nparts; ++k) {  // (k is wave-uniform: the table comes through the scalar cache)
-        const CompoundPartDev& P = parts[k];
-        float kx, ky, kz;
-        quat_rot(-P.q[0], -P.q[1], -P.q[2], P.q[3], lx - P.t[0], ly - P.t[1], lz - P.t[2], kx, ky, kz);
-        d = fminf(d, P.kind == SALVA_HIP_SHAPE_MESH ? mesh_solid_distance(P.mesh, kx, ky, kz) : shape_solid_distance(P.kind, P.p, kx, ky, kz));
-    }
-    if (!(d <= s.r)) return;
-    query_emit(q, i, kind, counter, cap, out_kind, out_index);
-}
-__global__ __launch_bounds__(BLOCK) void k_mesh_query(QuerySrc q, PosedQuery s, MeshDev mesh, uint32_t kind, unsigned int* __restrict__ counter,
-                                                      uint32_t cap, uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    float lx, ly, lz;
-    if (!posed_query_local(q, s, i, lx, ly, lz)) return;
-    if (!(mesh_solid_distance(mesh, lx, ly, lz) <= s.r)) return;
-    query_emit(q, i, kind, counter, cap, out_kind, out_index);
-}
-// the checks of particles_in_shape on the pose, and the cell range of the posed box
-static PosedQuery posed_query(const float t[3], const float q[4], const float mins[3], const float maxs[3], float h, float r) {
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite translation");
-    float qn = 0.0f;
-    for (int a = 0; a < 4; ++a) {
-        if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite rotation");
-        qn += q[a] * q[a];
-    }
-    if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, "shape query: the rotation must be a unit quaternion (x, y, z, w)");
-    PosedQuery s{};
-    for (int a = 0; a < 3; ++a) s.t[a] = t[a];
-    for (int a = 0; a < 4; ++a) s.q[a] = q[a];
-    s.h = h; s.r = r;
-    float lo[3], hi[3];
-    aabb_transform_by(mins, maxs, t, q, lo, hi);
-    for (int a = 0; a < 3; ++a) {  // (clamped like the cell coordinates of the particles: tile.h cell_coord)
-        s.clo[a] = (int)std::min(std::max(floorf(lo[a] / h), -1073741824.0f), 1073741824.0f);
-        s.chi[a] = (int)std::min(std::max(floorf(hi[a] / h), -1073741824.0f), 1073741824.0f);
-    }
-    return s;
-}
-uint64_t World::particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                      uint32_t* indices) {
-    use_device();
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "compound colliders are not available in a running decomposed world");
-    const std::shared_ptr<CompoundRes> c = compound_at(compound);
-    if (!c->solid)
-        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh part of the compound lacks SALVA_HIP_MESH_ORIENTED and has no solid distance (use salva_hip_particles_intersecting_host_shape)");
-    const PosedQuery s = posed_query(t, q, c->mins, c->maxs, sc.h, prm.particle_radius);
-    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
-    DevBuf<unsigned int> cnt;
-    DevBuf<uint32_t> dk, di;
-    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
-    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
-    if (qf.n) k_compound_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, c->parts.p, c->nparts, 0u, cnt.p, cap, dk.p, di.p);
-    if (nb) k_compound_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, c->parts.p, c->nparts, 1u, cnt.p, cap, dk.p, di.p);
-    SALVA_HIP_CHECK(hipGetLastError());
-    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
-}
-uint64_t World::particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                  uint32_t* indices) {
-    use_device();
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
-    const std::shared_ptr<MeshRes> m = mesh_at(mesh);
-    if (!(m->flags & SALVA_HIP_MESH_ORIENTED))
-        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh without SALVA_HIP_MESH_ORIENTED has no solid distance (use salva_hip_particles_intersecting_host_shape)");
-    const PosedQuery s = posed_query(t, q, m->mins, m->maxs, sc.h, prm.particle_radius);
-    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, 0xfffffff0ull);
-    DevBuf<unsigned int> cnt;
-    DevBuf<uint32_t> dk, di;
-    cnt.ensure(1); dk.ensure(std::max(cap, 1u)); di.ensure(std::max(cap, 1u));
-    SALVA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(unsigned int), stream));
-    if (qf.n) k_mesh_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, s, m->dev(), 0u, cnt.p, cap, dk.p, di.p);
-    if (nb) k_mesh_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, s, m->dev(), 1u, cnt.p, cap, dk.p, di.p);
-    SALVA_HIP_CHECK(hipGetLastError());
-    return collect_query(cnt.p, dk.p, di.p, cap, kinds, slots, indices);
-}
-
-// LiquidWorld::particles_intersecting_shape for a shape whose geometry stays with the host (any parry `Shape`: the reference's
-// query is generic, liquid_world.rs:247-280): the two parry calls — `shape.compute_aabb(pos)` and `shape.distance_to_point(pos,
-// &pt, true)` — are callbacks; the device keeps the cell filter (hgrid.cells_intersecting_aabb, hgrid.rs:122-133) and hands the
-// particles of those cells to the host in one copy.
-__global__ __launch_bounds__(BLOCK) void k_cell_range_query(QuerySrc q, int clo0, int clo1, int clo2, int chi0, int chi1, int chi2, float h,
-                                                            uint32_t kind, unsigned int* __restrict__ counter, uint32_t cap,
-                                                            uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index,
-                                                            float4* __restrict__ out_pos) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= q.n || query_skip(q, i)) return;
-    const float4 pt = q.pos[i];
-    bool bad = false;
-    const int cx = cell_coord(pt.x, h, bad), cy = cell_coord(pt.y, h, bad), cz = cell_coord(pt.z, h, bad);
-    if (bad || cx < clo0 || cx > chi0 || cy < clo1 || cy > chi1 || cz < clo2 || cz > chi2) return;
-    const uint32_t k = atomicAdd(counter, 1u);
-    if (k < cap) { out_kind[k] = kind | (q.model ? q.model[i] << 8 : 0u); out_index[k] = q.gid ? q.gid[i] : i; out_pos[k] = pt; }
-}
-uint64_t World::particles_in_host_shape(const SalvaHipHostQueryShape& shape, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                        uint32_t* indices) {
-    use_device();
-    if (!shape.aabb || !shape.distance) throw HipError(SALVA_HIP_E_INVALID, "a host query shape needs both callbacks");
-    float mins[3], maxs[3];
-    shape.aabb(shape.user, mins, maxs);
-    int clo[3], chi[3];
-    for (int a = 0; a < 3; ++a) {
-        if (!(mins[a] <= maxs[a]) || !std::isfinite(mins[a]) || !std::isfinite(maxs[a]))
-            throw HipError(SALVA_HIP_E_INVALID, "host query shape: the aabb callback returned an empty, infinite or NaN box");
-        clo[a] = (int)std::min(std::max(floorf(mins[a] / sc.h), -1073741824.0f), 1073741824.0f);
-        chi[a] = (int)std::min(std::max(floorf(maxs[a] / sc.h), -1073741824.0f), 1073741824.0f);
-    }
-    const QuerySrc qf = query_fluid_source(), qb{bst_pos.p, nb, nullptr, nullptr, nullptr};
-    // Candidates go into scratch buffers the world keeps (three fresh (n + nb)-sized buffers per call were 190 MB at
-    // 8 x 10^6 particles, allocated and freed synchronously): sized for what queries have needed so far; the kernel counts every
-    // candidate and stores those that fit, so a box that holds more than the buffers do costs one repetition with room.
-    const uint32_t all = qf.n + nb;
-    unsigned int m = 0;
-    for (int attempt = 0;; ++attempt) {
-        const uint32_t ccap = std::min<uint32_t>(std::max<uint32_t>(hq_need, 65536u), std::max(all, 1u));
-        hq_cnt.ensure(1); hq_kind.ensure(ccap, stream, false, 1.25f); hq_index.ensure(ccap, stream, false, 1.25f); hq_pos.ensure(ccap, stream, false, 1.25f);
-        SALVA_HIP_CHECK(hipMemsetAsync(hq_cnt.p, 0, sizeof(unsigned int), stream));
-        if (qf.n) k_cell_range_query<<<nblk(qf.n), BLOCK, 0, stream>>>(qf, clo[0], clo[1], clo[2], chi[0], chi[1], chi[2], sc.h, 0u, hq_cnt.p, ccap, hq_kind.p, hq_index.p, hq_pos.p);
-        if (nb) k_cell_range_query<<<nblk(nb), BLOCK, 0, stream>>>(qb, clo[0], clo[1], clo[2], chi[0], chi[1], chi[2], sc.h, 1u, hq_cnt.p, ccap, hq_kind.p, hq_index.p, hq_pos.p);
-        SALVA_HIP_CHECK(hipGetLastError());
-        SALVA_HIP_CHECK(hipMemcpyAsync(&m, hq_cnt.p, sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        if (m <= ccap) break;
-        if (attempt >= 1) throw HipError(SALVA_HIP_E_HIP, "internal error: the candidate count of a host shape query grew between two passes");
-        hq_need = m + m / 4u;
-    }
-    DevBuf<uint32_t>& dk = hq_kind; DevBuf<uint32_t>& di = hq_index; DevBuf<float4>& dp = hq_pos;
-    if (m == 0) return 0;
-    std::vector<uint32_t> hk(m), hi_(m);
-    std::vector<float4> hp(m);
-    SALVA_HIP_CHECK(hipMemcpy(hk.data(), dk.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SALVA_HIP_CHECK(hipMemcpy(hi_.data(), di.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    SALVA_HIP_CHECK(hipMemcpy(hp.data(), dp.p, m * sizeof(float4), hipMemcpyDeviceToHost));
-    std::vector<float> pts(3 * (size_t)m), dist((size_t)m, std::numeric_limits<float>::infinity());
-    for (unsigned int k = 0; k < m; ++k) { pts[3 * k] = hp[k].x; pts[3 * k + 1] = hp[k].y; pts[3 * k + 2] = hp[k].z; }
-    shape.distance(shape.user, m, pts.data(), dist.data());
-    std::vector<uint64_t> keys;
-    keys.reserve(m);
-    for (unsigned int k = 0; k < m; ++k)
-        if (dist[k] <= prm.particle_radius) keys.push_back(((uint64_t)hk[k] << 32) | hi_[k]);  // liquid_world.rs:263, :272 (NaN: not a hit)
-    const uint64_t total = keys.size();
-    if (total == 0 || !kinds || !slots || !indices) return total;
-    if (keys.size() > capacity) {  // the first `capacity` in the sorted order, like the device arms
-        std::sort(keys.begin(), keys.end());
-        keys.resize((size_t)capacity);
-    }
-    map_query_hits(keys, kinds, slots, indices);
-    return total;
 }
 
 // The contact lists of the last step (they describe the positions the step started from, as the reference's
@@ -1633,579 +1271,6 @@ void World::get_boundary(uint32_t slot, float* volumes, float* forces) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ rigid-body coupling
-// integrations/rapier/fluids_pipeline.rs, StaticSampling arm.  q * v of nalgebra's UnitQuaternion (geometry/
-// quaternion_ops.rs): t = 2 q.vec x v; v' = v + w t + q.vec x t.
-__device__ __forceinline__ void boundary_pose_row(const float4 pt, const SalvaHipRigidPose& p, float4& pos_io, float4& vel_io) {
-    float4 o = pos_io;  // .w (volume slot) untouched
-    pose_point(p.rotation[0], p.rotation[1], p.rotation[2], p.rotation[3], p.translation[0], p.translation[1], p.translation[2], pt.x, pt.y,
-               pt.z, o.x, o.y, o.z);  // (pose.h: shared with the shape sampler's emit kernel)
-    pos_io = o;
-    float4 v = vel_io;  // .w carries the boundary's model id
-    if (p.has_body) {
-        // body.velocity_at_point(pt) with the local point, as the reference writes it (:183)
-        const float dx = pt.x - p.world_com[0], dy = pt.y - p.world_com[1], dz = pt.z - p.world_com[2];
-        v.x = p.linvel[0] + (opaque(p.angvel[1] * dz) - opaque(p.angvel[2] * dy));
-        v.y = p.linvel[1] + (opaque(p.angvel[2] * dx) - opaque(p.angvel[0] * dz));
-        v.z = p.linvel[2] + (opaque(p.angvel[0] * dy) - opaque(p.angvel[1] * dx));
-    } else {
-        v.x = v.y = v.z = 0.0f;
-    }
-    vel_io = v;
-}
-__global__ void k_boundary_pose(uint32_t n, const float4* __restrict__ local, SalvaHipRigidPose p, float4* __restrict__ pos,
-                                float4* __restrict__ vel) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    boundary_pose_row(local[i], p, pos[i], vel[i]);
-}
-// salva_hip_update_boundary_poses: the statically sampled boundaries of one call as one launch over their concatenated rows
-// (`first`: the entry's first row in that concatenation, ascending); the force rows are cleared on the way (clear_forces(true) :262)
-struct PoseEntry { SalvaHipRigidPose pose; const float4* local; uint32_t first, n, off, pad; };
-__global__ void k_boundary_poses(uint32_t total, uint32_t nent, const PoseEntry* __restrict__ ent, float4* __restrict__ pos,
-                                 float4* __restrict__ vel, float4* __restrict__ force) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    uint32_t lo = 0, hi = nent;  // the last entry with first <= i
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) / 2u; if (ent[mid].first <= i) lo = mid; else hi = mid; }
-    const PoseEntry& e = ent[lo];
-    const uint32_t j = i - e.first, row = e.off + j;
-    boundary_pose_row(e.local[j], e.pose, pos[row], vel[row]);
-    force[row] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// per-block partial sums of f and (x - c) x f in f64 (6 doubles per block)
-// block `lb` of `nblocks` over one boundary's rows (grid stride): the one copy of k_boundary_wrench / k_boundary_wrenches
-__device__ __forceinline__ void boundary_wrench_block(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ force, float cx,
-                                                      float cy, float cz, uint32_t lb, uint32_t nblocks, double* __restrict__ partial) {
-    double a[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t i = lb * blockDim.x + threadIdx.x; i < n; i += nblocks * blockDim.x) {
-        const float4 p = pos[i], f = force[i];
-        const float rx = p.x - cx, ry = p.y - cy, rz = p.z - cz;
-        a[0] += f.x; a[1] += f.y; a[2] += f.z;
-        a[3] += (double)(ry * f.z - rz * f.y); a[4] += (double)(rz * f.x - rx * f.z); a[5] += (double)(rx * f.y - ry * f.x);
-    }
-    __shared__ double sh[BLOCK / WAVE][6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double v = a[k];
-        for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x / WAVE][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double v = 0;
-        for (uint32_t w = 0; w < blockDim.x / WAVE; ++w) v += sh[w][threadIdx.x];
-        partial[threadIdx.x] = v;
-    }
-}
-__global__ void k_boundary_wrench(uint32_t n, const float4* __restrict__ pos, const float4* __restrict__ force, float cx, float cy,
-                                  float cz, double* __restrict__ partial) {
-    boundary_wrench_block(n, pos, force, cx, cy, cz, blockIdx.x, gridDim.x, partial + (size_t)blockIdx.x * 6);
-}
-// salva_hip_get_boundary_wrenches: every listed boundary keeps the partition of k_boundary_wrench — its own min(nblk(n), 256) blocks,
-// `block0` the first of them in this launch (ascending) — so that its partial sums are the single call's, bit for bit
-struct WrenchEntry { uint32_t off, n, block0, nblocks; float c[3]; uint32_t pad; };
-__global__ void k_boundary_wrenches(uint32_t nent, const WrenchEntry* __restrict__ ent, const float4* __restrict__ pos,
-                                    const float4* __restrict__ force, double* __restrict__ partial) {
-    uint32_t lo = 0, hi = nent;  // the last entry with block0 <= blockIdx.x
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) / 2u; if (ent[mid].block0 <= blockIdx.x) lo = mid; else hi = mid; }
-    const WrenchEntry e = ent[lo];
-    boundary_wrench_block(e.n, pos + e.off, force + e.off, e.c[0], e.c[1], e.c[2], blockIdx.x - e.block0, e.nblocks, partial + (size_t)blockIdx.x * 6);
-}
-
-void World::set_boundary_sampling(uint32_t slot, uint64_t nn, const float* local_points, uint32_t memberships, uint32_t filter,
-                                  const std::function<void(float4*)>* fill_dev) {
-    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary_from(slot, nn, local_points, nullptr, memberships, filter, keep_forces, fill_dev);
-    auto buf = std::make_shared<DevBuf<float4>>();
-    buf->ensure(nn ? nn : 1);
-    if (nn) {
-        SALVA_HIP_CHECK(hipMemcpyAsync(buf->p, bst_pos.p + boundary_offset(slot), nn * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    bounds[slot].sampling = buf;
-}
-
-void World::update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    BoundarySlot& b = bounds[slot];
-    if (!b.sampling && !b.dyn_kind)
-        throw HipError(SALVA_HIP_E_INVALID, "boundary has no sampling method (salva_hip_set_boundary_sampling / _dynamic_sampling)");
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(pose.rotation[k])) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
-    if (b.dyn_kind) {  // the projection itself runs inside the step, where the reference runs it
-        if (pose.has_body) {
-            const bool wants = pose.is_dynamic != 0;
-            if (wants != b.wants_forces) { b.wants_forces = wants; tables_dirty = true; }
-        }
-        b.dyn_pose = pose;
-        return;
-    }
-    const uint64_t off = boundary_offset(slot);
-    if (pose.has_body) {
-        const bool wants = pose.is_dynamic != 0;
-        if (wants != b.wants_forces) { b.wants_forces = wants; tables_dirty = true; }
-    }
-    if (b.n) {
-        k_boundary_pose<<<nblk(b.n), BLOCK, 0, stream>>>((uint32_t)b.n, b.sampling->p, pose, bst_pos.p + off, bst_vel.p + off);
-        SALVA_HIP_CHECK(hipGetLastError());
-        SALVA_HIP_CHECK(hipMemsetAsync(bforce.p + off, 0, b.n * sizeof(float4), stream));  // boundary.clear_forces(true) :262
-    }
-    b_dirty = true; have_last_ctx = false;
-}
-
-// `count` calls of update_boundary_pose in order, validated as a whole before anything changes: the dynamically sampled slots store
-// their pose, the statically sampled ones share one launch (a slot listed twice: its last pose is the one that stays, as in order)
-void World::update_boundary_poses(uint32_t count, const uint32_t* slots, const SalvaHipRigidPose* poses) {
-    use_device();
-    for (uint32_t k = 0; k < count; ++k) {
-        if (slots[k] >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-        const BoundarySlot& b = bounds[slots[k]];
-        if (!b.sampling && !b.dyn_kind)
-            throw HipError(SALVA_HIP_E_INVALID, "boundary has no sampling method (salva_hip_set_boundary_sampling / _dynamic_sampling)");
-        for (int a = 0; a < 4; ++a)
-            if (!std::isfinite(poses[k].rotation[a])) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
-    }
-    std::vector<uint32_t> launch;  // the entries that write rows
-    for (uint32_t k = 0; k < count; ++k) {
-        BoundarySlot& b = bounds[slots[k]];
-        const SalvaHipRigidPose& pose = poses[k];
-        if (pose.has_body) {
-            const bool wants = pose.is_dynamic != 0;
-            if (wants != b.wants_forces) { b.wants_forces = wants; tables_dirty = true; }
-        }
-        if (b.dyn_kind) { b.dyn_pose = pose; continue; }  // the projection itself runs inside the step, where the reference runs it
-        b_dirty = true; have_last_ctx = false;
-        if (!b.n) continue;
-        bool last = true;
-        for (uint32_t j = k + 1; j < count; ++j) if (slots[j] == slots[k]) last = false;
-        if (last) launch.push_back(k);
-    }
-    if (launch.empty()) return;
-    PoseEntry* ent_h = reinterpret_cast<PoseEntry*>(pose_stage.acquire(launch.size() * sizeof(PoseEntry)));
-    uint64_t total = 0;
-    for (size_t e = 0; e < launch.size(); ++e) {
-        const uint32_t k = launch[e];
-        const BoundarySlot& b = bounds[slots[k]];
-        ent_h[e] = PoseEntry{poses[k], b.sampling->p, (uint32_t)total, (uint32_t)b.n, (uint32_t)boundary_offset(slots[k]), 0u};
-        total += b.n;
-    }
-    if (total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-    pose_tab.ensure(launch.size() * sizeof(PoseEntry), stream, false, 1.5f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(pose_tab.p, ent_h, launch.size() * sizeof(PoseEntry), hipMemcpyHostToDevice, stream));
-    k_boundary_poses<<<nblk(total), BLOCK, 0, stream>>>((uint32_t)total, (uint32_t)launch.size(), reinterpret_cast<const PoseEntry*>(pose_tab.p),
-                                                        bst_pos.p, bst_vel.p, bforce.p);
-    SALVA_HIP_CHECK(hipGetLastError());
-    pose_stage.release(stream);
-}
-
-// ------------------------------------------------------------------------------------------------ DynamicContactSampling
-// ColliderCouplingSet::register_coupling(boundary, collider, ColliderSampling::DynamicContactSampling) (fluids_pipeline.rs:42-43,
-// 96-114): the boundary starts empty; every step re-emits its particles from the fluid near the collider.
-void World::set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter) {
-    const int np = shape_param_count(shape.kind);
-    for (int a = 0; a < np; ++a)
-        if (!(shape.params[a] > 0.0f) || !std::isfinite(shape.params[a])) throw HipError(SALVA_HIP_E_INVALID, "shape parameters must be positive");
-    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary(slot, 0, nullptr, nullptr, memberships, filter, keep_forces);
-    BoundarySlot& b = bounds[slot];
-    b.sampling.reset();
-    b.dyn_kind = shape.kind;
-    b.dyn_shape = shape;
-    b.dyn_pose = SalvaHipRigidPose{};
-    b.dyn_pose.rotation[3] = 1.0f;
-    b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
-}
-
-void World::set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter) {
-    if (!shape.aabb || !shape.project) throw HipError(SALVA_HIP_E_INVALID, "a host shape needs both callbacks");
-    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary(slot, 0, nullptr, nullptr, memberships, filter, keep_forces);
-    BoundarySlot& b = bounds[slot];
-    b.sampling.reset();
-    b.dyn_kind = SALVA_HIP_SHAPE_HOST;
-    b.dyn_shape = SalvaHipShape{};
-    b.dyn_host = shape;
-    b.dyn_pose = SalvaHipRigidPose{};
-    b.dyn_pose.rotation[3] = 1.0f;
-    b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
-}
-
-// The same arm for a collider that is a triangle mesh or a height field of this world (mesh.hip): gather, projection and apply all
-// stay on the device, and the pose handed to salva_hip_update_boundary_pose places the mesh.
-void World::set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter) {
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
-    const std::shared_ptr<MeshRes> m = mesh_at(mesh);
-    const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
-    set_boundary(slot, 0, nullptr, nullptr, memberships, filter, keep_forces);
-    BoundarySlot& b = bounds[slot];
-    b.sampling.reset();
-    b.dyn_kind = SALVA_HIP_SHAPE_MESH;
-    b.dyn_shape = SalvaHipShape{};
-    b.dyn_mesh = m;
-    b.dyn_pose = SalvaHipRigidPose{};
-    b.dyn_pose.rotation[3] = 1.0f;
-    b.dyn_src = std::make_shared<DevBuf<uint32_t>>();
-}
-
-// unregister_coupling (fluids_pipeline.rs:116-125): the boundary stays, with the particles it holds now, as a plain boundary;
-// nothing of the sampling method — in particular no host callback or user pointer — is kept
-void World::clear_boundary_sampling(uint32_t slot) {
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    BoundarySlot& b = bounds[slot];
-    b.sampling.reset();
-    b.dyn_kind = 0;
-    b.dyn_shape = SalvaHipShape{};
-    b.dyn_host = SalvaHipHostShape{};
-    b.dyn_mesh.reset();
-    b.dyn_compound.reset();
-    b.dyn_src.reset(); b.dyn_src_model.reset();
-    // the particles keep the velocities k_boundary_pose / k_dcs_emit wrote for the moving collider (the reference keeps them after
-    // unregister_coupling too): from now on make_ctx must not take the upload's "at rest" for them
-    if (b.n) b.vel_zero = false;
-}
-
-// parameters of a built-in collider shape (include/salva_hip.h); throws for any other kind
-int shape_param_count(int kind) {
-    switch (kind) {
-        case SALVA_HIP_SHAPE_BALL: return 1;
-        case SALVA_HIP_SHAPE_CUBOID: return 3;
-        case SALVA_HIP_SHAPE_CAPSULE: case SALVA_HIP_SHAPE_CYLINDER: return 2;
-        default: throw HipError(SALVA_HIP_E_INVALID, "unknown shape kind (ball, cuboid, capsule (y) and cylinder (y) are built in; other parry shapes belong to the host)");
-    }
-}
-
-bool World::has_dynamic_sampling() const {
-    for (const BoundarySlot& b : bounds) if (b.dyn_kind) return true;
-    return false;
-}
-
-uint64_t World::boundary_len(uint32_t slot) const {
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    return bounds[slot].n;
-}
-
-// Change the particle count of one boundary in place: the rows of the boundaries behind it move, its own rows are left for
-// the caller to fill (forces zeroed).  No allocation once the buffers have grown.
-void World::resize_boundary_slot(uint32_t slot, uint64_t nn) {
-    BoundarySlot& b = bounds[slot];
-    const uint64_t old_n = b.n;
-    if (old_n == nn) return;
-    const uint64_t off = boundary_offset(slot), old_total = nb, new_total = old_total - old_n + nn;
-    if (new_total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-    const uint64_t tail_src = off + old_n, tail_len = old_total - tail_src;
-    DevBuf<float4>* bufs[3] = {&bst_pos, &bst_vel, &bforce};
-    for (DevBuf<float4>* buf : bufs) {
-        buf->ensure(std::max<uint64_t>(new_total, 1), stream, true, 1.5f);
-        if (tail_len) {
-            scratch_f4.ensure(tail_len, stream, false, 1.5f);
-            SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f4.p, buf->p + tail_src, tail_len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-            SALVA_HIP_CHECK(hipMemcpyAsync(buf->p + off + nn, scratch_f4.p, tail_len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-        }
-    }
-    b.n = nn;
-    nb = (uint32_t)new_total;
-    b_dirty = true; have_last_ctx = false;
-}
-
-// The DynamicContactSampling arm of ColliderCouplingManager::update_boundaries (fluids_pipeline.rs:193-259, :262) for every
-// boundary registered with it, in slot order, at the reference's point of the substep: the fluid cell keys exist (grid
-// insertion, liquid_world.rs:90-91), the boundaries are not in the grid yet (:106).  Works on the sorted working set of the
-// previous step (posm[cur] / vel[cur], G().keys[0] = this step's keys in that order).
-void World::run_dynamic_sampling() {
-    const TileGrid gv = gf.device(nullptr);
-    // Maximal runs of consecutive dynamically sampled slots whose shape is on the device go through ONE pass over the fluid
-    // (run_dynamic_sampling_batch).  Slots that are not dynamically sampled do not break a run; a host shape does, and
-    // runs at its place in slot order, so that the pushes keep their order.  A run of one, an empty fluid and every decomposed world
-    // (whose emitted rows go through a collective per collider) take the per-collider path.
-    std::vector<uint32_t> run;
-    for (uint32_t slot = 0; slot < bounds.size();) {
-        if (!bounds[slot].dyn_kind) { ++slot; continue; }
-        run.clear();
-        if (!comm && !sw.dcs_batch_off && n)
-            for (uint32_t s = slot; s < bounds.size() && bounds[s].dyn_kind != SALVA_HIP_SHAPE_HOST; ++s)
-                if (bounds[s].dyn_kind) run.push_back(s);
-        if (run.size() >= DCS_BATCH_MIN_RUN) {
-            run_dynamic_sampling_batch(run, gv);
-            slot = run.back() + 1;
-        } else {
-            run_dynamic_sampling_slot(slot, gv);
-            ++slot;
-        }
-    }
-}
-
-void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
-    {
-        BoundarySlot& b = bounds[slot];
-        uint32_t cnt = 0;
-        const float4* emit_src = nullptr;  // the compacted (projection, source particle) rows
-        // (decomposed run: a failure of the rank-local part must not leave the other ranks waiting in the collective below —
-        // it is parked and travels with the counts, dist_gather_emitted)
-        HipError local_error(SALVA_HIP_E_INVALID, "");
-        bool local_failed = false;
-        try {
-        if (n && (b.dyn_kind == SALVA_HIP_SHAPE_HOST || b.dyn_kind == SALVA_HIP_SHAPE_MESH || b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND)) {
-            // the host's shape: box tests on the device, the projections on the host, the rest of the loop body on the device;
-            // a mesh or a compound: the same pass with the projections on the device as well (k_dcs_project_mesh, k_dcs_compound_project)
-            const bool on_host = b.dyn_kind == SALVA_HIP_SHAPE_HOST;
-            DcsParams prm_d;
-            if (on_host) {
-                float mins[3], maxs[3];
-                b.dyn_host.aabb(b.dyn_host.user, mins, maxs);
-                for (int a = 0; a < 3; ++a)
-                    if (!(mins[a] <= maxs[a])) throw HipError(SALVA_HIP_E_INVALID, "host shape: the aabb callback returned an empty or NaN box");
-                prm_d = dcs_params_host(mins, maxs, sc.h, prm.particle_radius, dt_prev);
-            } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
-                prm_d = dcs_params_compound(*b.dyn_compound, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-            } else {
-                prm_d = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-            }
-            dcs_cand.ensure(n, stream, false, 1.1f); dcs_out.ensure(n, stream, false, 1.1f); dcs_flag.ensure(n, stream, false, 1.1f);
-            dcs_num.ensure(1);
-            launch_dcs_gather(n, posm[cur].p, vel[cur].p, G().keys[0].p, gv, prm_d, dcs_cand.p, dcs_flag.p, stream);
-            ++dcs_stats[0];
-            const size_t tb = select_flagged_temp_bytes(n);
-            ensure_cub_temp(tb);
-            select_flagged_f4(cub_temp.p, tb, dcs_cand.p, dcs_flag.p, dcs_out.p, dcs_num.p, n, stream);
-            SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            wait_stream(); ++dcs_stats[1];
-            const uint32_t ng = h_rb->dcs_count;
-            if (ng) {
-                dcs_proj.ensure(ng, stream, false, 1.5f); dcs_cand2.ensure(ng, stream, false, 1.5f);
-                if (on_host) {
-                    dcs_h_f4.resize(ng); dcs_h_pts.resize(3 * (size_t)ng); dcs_h_proj.assign(3 * (size_t)ng, 0.0f); dcs_h_inside.assign(ng, 0);
-                    SALVA_HIP_CHECK(hipMemcpyAsync(dcs_h_f4.data(), dcs_out.p, (size_t)ng * sizeof(float4), hipMemcpyDeviceToHost, stream));
-                    wait_stream(); ++dcs_stats[1];
-                    for (uint32_t k = 0; k < ng; ++k) { dcs_h_pts[3 * k] = dcs_h_f4[k].x; dcs_h_pts[3 * k + 1] = dcs_h_f4[k].y; dcs_h_pts[3 * k + 2] = dcs_h_f4[k].z; }
-                    b.dyn_host.project(b.dyn_host.user, ng, dcs_h_pts.data(), dcs_h_proj.data(), dcs_h_inside.data());
-                    for (uint32_t k = 0; k < ng; ++k)
-                        dcs_h_f4[k] = make_float4(dcs_h_proj[3 * k], dcs_h_proj[3 * k + 1], dcs_h_proj[3 * k + 2], dcs_h_inside[k] ? 1.0f : 0.0f);
-                    SALVA_HIP_CHECK(hipMemcpyAsync(dcs_proj.p, dcs_h_f4.data(), (size_t)ng * sizeof(float4), hipMemcpyHostToDevice, stream));
-                } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
-                    launch_dcs_compound_project(ng, dcs_out.p, b.dyn_compound->parts.p, b.dyn_compound->nparts, prm_d, dcs_proj.p, stream);
-                } else {
-                    launch_dcs_project_mesh(ng, dcs_out.p, b.dyn_mesh->dev(), prm_d, dcs_proj.p, stream);
-                }
-                // (dcs_out holds the gathered candidates; its compaction goes back into dcs_cand, which is free again)
-                launch_dcs_apply(ng, dcs_out.p, dcs_proj.p, posm[cur].p, vel[cur].p, perm[cur].p, comm ? gtag[cur].p : nullptr, prm_d,
-                                 dcs_cand2.p, dcs_flag.p, stream);
-                select_flagged_f4(cub_temp.p, tb, dcs_cand2.p, dcs_flag.p, dcs_cand.p, dcs_num.p, ng, stream);
-                SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-                wait_stream(); ++dcs_stats[1];  // (also: dcs_h_f4 has been read)
-                cnt = h_rb->dcs_count;
-                emit_src = dcs_cand.p;
-            }
-        } else if (n) {
-            const DcsParams prm_d = dcs_params(b.dyn_shape, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-            dcs_cand.ensure(n, stream, false, 1.1f); dcs_out.ensure(n, stream, false, 1.1f); dcs_flag.ensure(n, stream, false, 1.1f);
-            dcs_num.ensure(1);
-            launch_dcs_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, comm ? gtag[cur].p : nullptr, gv, prm_d, dcs_cand.p,
-                               dcs_flag.p, stream);
-            ++dcs_stats[0];
-            const size_t tb = select_flagged_temp_bytes(n);
-            ensure_cub_temp(tb);
-            select_flagged_f4(cub_temp.p, tb, dcs_cand.p, dcs_flag.p, dcs_out.p, dcs_num.p, n, stream);
-            SALVA_HIP_CHECK(hipMemcpyAsync(&h_rb->dcs_count, dcs_num.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            wait_stream(); ++dcs_stats[1];
-            cnt = h_rb->dcs_count;
-            emit_src = dcs_out.p;
-        }
-        } catch (const HipError& e) {
-            if (!comm) throw;
-            local_failed = true; local_error = e; cnt = 0; emit_src = nullptr;
-        } catch (const std::exception& e) {
-            if (!comm) throw;
-            local_failed = true; local_error = HipError(SALVA_HIP_E_INVALID, e.what()); cnt = 0; emit_src = nullptr;
-        }
-        // Decomposed run: each rank has emitted for the particles it OWNS; every rank then holds every rank's points (a collider's
-        // contact layer: thousands of rows), so a boundary particle near a slab face has its whole boundary neighbourhood — its
-        // volume — and acts on the fluid of both slabs, wherever its source particle lives.  (Mirroring more ghost planes instead
-        // has no bound that holds: the point is the projection of the PREDICTED position, |v| dt + 1.5 h + the penetration depth
-        // from its source.)  Each rank's force accumulator receives what its own fluid exerts: the rows are the same on every
-        // rank, the per-rank forces add up.
-        const uint32_t* emit_models = nullptr;
-        if (comm) cnt = dist_gather_emitted(emit_src, cnt, &emit_src, &emit_models, local_failed ? &local_error : nullptr);
-        resize_boundary_slot(slot, cnt);
-        b_dirty = true;  // same count, new positions
-        dcs_stats[3] += cnt;
-        if (cnt) {
-            const uint64_t off = boundary_offset(slot);
-            b.dyn_src->ensure(cnt, stream, false, 1.5f);
-            launch_dcs_emit(cnt, emit_src, b.dyn_pose, slot, bst_pos.p + off, bst_vel.p + off, b.dyn_src->p, stream);
-            if (emit_models) {
-                if (!b.dyn_src_model) b.dyn_src_model = std::make_shared<DevBuf<uint32_t>>();
-                b.dyn_src_model->ensure(cnt, stream, false, 1.5f);
-                SALVA_HIP_CHECK(hipMemcpyAsync(b.dyn_src_model->p, emit_models, (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-            }
-            SALVA_HIP_CHECK(hipMemsetAsync(bforce.p + off, 0, (size_t)cnt * sizeof(float4), stream));  // clear_forces(true) :262
-        }
-    }
-}
-
-// One run of device-shape colliders (`run`: their slots, ascending, at least two) in one pass over the fluid; dcs.hip "batched runs".
-//   table up -> k_dcsb_project (writes records, the push list and the counts; no particle) -> counts down, ONE wait
-//   -> too small: grow, repeat from the unmodified state -> k_dcsb_push -> sort the record keys -> lay the boundary arrays out once
-//   -> table up again (first row / first record / source array per collider) -> k_dcsb_emit
-void World::run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const TileGrid& gv) {
-    const uint32_t ncol = (uint32_t)run.size();
-    const size_t tab_bytes = (size_t)ncol * sizeof(DcsbEntry), cnt_bytes = ((size_t)ncol + 2) * sizeof(unsigned long long);
-    // (pinned: neither copy makes the host wait; the previous batch's second upload is long done — acquire() checks)
-    char* stage = dcsb_stage.acquire(tab_bytes + cnt_bytes);
-    DcsbEntry* tab_h = reinterpret_cast<DcsbEntry*>(stage);
-    const unsigned long long* cnt_h = reinterpret_cast<const unsigned long long*>(stage + tab_bytes);
-    bool has_compound = false;
-    for (uint32_t c = 0; c < ncol; ++c) {
-        const BoundarySlot& b = bounds[run[c]];
-        DcsbEntry e{};
-        if (b.dyn_kind == SALVA_HIP_SHAPE_MESH) {
-            e.s = dcs_params_mesh(b.dyn_mesh->mins, b.dyn_mesh->maxs, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-            e.mesh = b.dyn_mesh->dev();
-        } else if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) {
-            e.s = dcs_params_compound(*b.dyn_compound, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-            e.parts = b.dyn_compound->parts.p;
-            e.nparts = b.dyn_compound->nparts;
-        } else {
-            e.s = dcs_params(b.dyn_shape, b.dyn_pose, sc.h, prm.particle_radius, dt_prev);
-        }
-        e.pose = b.dyn_pose;
-        e.slot = run[c];
-        tab_h[c] = e;
-        if (b.dyn_kind == SALVA_HIP_SHAPE_COMPOUND) has_compound = true;
-    }
-    dcsb_tab.ensure(ncol, stream, false, 1.5f);
-    dcsb_counts.ensure((size_t)ncol + 2, stream, false, 1.5f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(dcsb_tab.p, tab_h, tab_bytes, hipMemcpyHostToDevice, stream));
-    int nbits = 1;
-    while (nbits < 32 && ((uint64_t)1 << nbits) < (uint64_t)n) ++nbits;
-    int cbits = 1;
-    while (((uint64_t)1 << cbits) < (uint64_t)ncol) ++cbits;
-    const uint32_t shift = (uint32_t)nbits;
-    // the first capacity is a guess (an eighth of the fluid, or SALVA_HIP_DCSB_CAP0 for the tests); afterwards what the fullest pass
-    // so far needed, with half as much again
-    if (dcsb_cap == 0) dcsb_cap = sw.dcsb_cap0 ? sw.dcsb_cap0 : std::max<uint32_t>(n / 8u, 4096u);
-    uint64_t total = 0, npush = 0;
-    for (;;) {
-        for (int k = 0; k < 2; ++k) { dcsb_key[k].ensure(dcsb_cap, stream); dcsb_idx[k].ensure(dcsb_cap, stream); }
-        dcsb_rec.ensure(dcsb_cap, stream); dcsb_push_idx.ensure(dcsb_cap, stream); dcsb_push_pos.ensure(dcsb_cap, stream); dcsb_push_vel.ensure(dcsb_cap, stream);
-        SALVA_HIP_CHECK(hipMemsetAsync(dcsb_counts.p, 0, cnt_bytes, stream));
-        if (!has_compound) {
-            launch_dcsb_project(n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, dcsb_cap, shift, dcsb_counts.p,
-                                dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, stream);
-        } else {
-            // compounds project in launches of their own (dcs.hip k_dcsb_segment): one launch per stretch of colliders of one class
-            dcsb_st_pos.ensure(n, stream, false, 1.1f); dcsb_st_vel.ensure(n, stream, false, 1.1f); dcsb_st_moved.ensure(n, stream, false, 1.1f);
-            for (uint32_t c0 = 0; c0 < ncol;) {
-                const bool compound = tab_h[c0].s.kind == SALVA_HIP_SHAPE_COMPOUND;
-                uint32_t c1 = c0 + 1;
-                while (c1 < ncol && (tab_h[c1].s.kind == SALVA_HIP_SHAPE_COMPOUND) == compound) ++c1;
-                launch_dcsb_segment(compound, n, posm[cur].p, vel[cur].p, G().keys[0].p, perm[cur].p, gv, dcsb_tab.p, ncol, c0, c1, dcsb_cap, shift,
-                                    dcsb_counts.p, dcsb_key[0].p, dcsb_idx[0].p, dcsb_rec.p, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p,
-                                    dcsb_st_pos.p, dcsb_st_vel.p, dcsb_st_moved.p, stream);
-                c0 = c1;
-            }
-        }
-        SALVA_HIP_CHECK(hipMemcpyAsync(stage + tab_bytes, dcsb_counts.p, cnt_bytes, hipMemcpyDeviceToHost, stream));
-        wait_stream();
-        ++dcs_stats[0]; ++dcs_stats[1];
-        total = cnt_h[ncol]; npush = cnt_h[ncol + 1];
-        if (total <= dcsb_cap) break;
-        // nothing has been written but the scratch of this pass: a larger buffer, the same pass again
-        if (total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-        dcsb_cap = (uint32_t)std::min<uint64_t>(total + total / 2, 0xfffffff0ull);
-    }
-    launch_dcsb_push((uint32_t)npush, dcsb_push_idx.p, dcsb_push_pos.p, dcsb_push_vel.p, posm[cur].p, vel[cur].p, stream);
-    std::vector<uint64_t> counts(ncol);
-    for (uint32_t c = 0; c < ncol; ++c) counts[c] = cnt_h[c];
-    relayout_boundaries(run, counts.data());
-    b_dirty = true;  // same counts, new positions
-    dcs_stats[2] += ncol; dcs_stats[3] += total;
-    if (total) {
-        const size_t tb = sort_pairs_u64_temp_bytes((uint32_t)total, nbits + cbits);
-        ensure_cub_temp(tb);
-        sort_pairs_u64(cub_temp.p, tb, dcsb_key[0].p, dcsb_key[1].p, dcsb_idx[0].p, dcsb_idx[1].p, (uint32_t)total, nbits + cbits, stream);
-        uint64_t rec0 = 0;
-        for (uint32_t c = 0; c < ncol; ++c) {
-            BoundarySlot& b = bounds[run[c]];
-            if (counts[c]) b.dyn_src->ensure(counts[c], stream, false, 1.5f);
-            tab_h[c].row0 = (uint32_t)boundary_offset(run[c]);
-            tab_h[c].rec0 = (uint32_t)rec0;
-            tab_h[c].src = b.dyn_src->p;
-            rec0 += counts[c];
-        }
-        SALVA_HIP_CHECK(hipMemcpyAsync(dcsb_tab.p, tab_h, tab_bytes, hipMemcpyHostToDevice, stream));
-        launch_dcsb_emit((uint32_t)total, dcsb_key[1].p, dcsb_idx[1].p, dcsb_rec.p, dcsb_tab.p, shift, bst_pos.p, bst_vel.p, bforce.p, stream);
-    }
-    dcsb_stage.release(stream);
-}
-
-// New particle counts for the slots of `run` (ascending) in one go: every other boundary's rows move at most once, through scratch;
-// the run's own rows are left for the caller to fill.  (resize_boundary_slot, once per collider, moves the tail once per collider.)
-void World::relayout_boundaries(const std::vector<uint32_t>& run, const uint64_t* counts) {
-    const size_t ns = bounds.size();
-    std::vector<uint64_t> old_off(ns + 1, 0), new_off(ns + 1, 0);
-    std::vector<uint8_t> in_run(ns, 0);
-    for (size_t c = 0; c < run.size(); ++c) in_run[run[c]] = 1;
-    bool changed = false;
-    for (size_t s = 0, c = 0; s < ns; ++s) {
-        const uint64_t nn = in_run[s] ? counts[c++] : bounds[s].n;
-        if (nn != bounds[s].n) changed = true;
-        old_off[s + 1] = old_off[s] + bounds[s].n;
-        new_off[s + 1] = new_off[s] + nn;
-    }
-    if (!changed) return;
-    const uint64_t old_total = old_off[ns], new_total = new_off[ns];
-    if (new_total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-    // segments of consecutive slots outside the run that move (they stay contiguous): (source, destination, length)
-    struct Seg { uint64_t src, dst, len; };
-    std::vector<Seg> segs;
-    for (size_t s = run[0]; s < ns; ++s) {
-        if (in_run[s] || !bounds[s].n || old_off[s] == new_off[s]) continue;
-        if (!segs.empty() && segs.back().src + segs.back().len == old_off[s] && segs.back().dst + segs.back().len == new_off[s]) segs.back().len += bounds[s].n;
-        else segs.push_back(Seg{old_off[s], new_off[s], bounds[s].n});
-    }
-    const uint64_t tail_src = old_off[run[0]], tail_len = old_total - tail_src;
-    DevBuf<float4>* bufs[3] = {&bst_pos, &bst_vel, &bforce};
-    for (DevBuf<float4>* buf : bufs) {
-        buf->ensure(std::max<uint64_t>(new_total, 1), stream, true, 1.5f);
-        if (segs.empty()) continue;
-        scratch_f4.ensure(tail_len, stream, false, 1.5f);
-        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f4.p, buf->p + tail_src, tail_len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-        for (const Seg& g : segs)
-            SALVA_HIP_CHECK(hipMemcpyAsync(buf->p + g.dst, scratch_f4.p + (g.src - tail_src), g.len * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-    }
-    for (size_t c = 0; c < run.size(); ++c) bounds[run[c]].n = counts[c];
-    nb = (uint32_t)new_total;
-    b_dirty = true; have_last_ctx = false;
-}
-
-// (fluid slot, index) of the fluid particle each point of a dynamically sampled boundary was projected from
-void World::get_boundary_sources(uint32_t slot, uint32_t* fluid_slots, uint32_t* indices) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const BoundarySlot& b = bounds[slot];
-    if (!b.dyn_kind) throw HipError(SALVA_HIP_E_INVALID, "boundary is not dynamically sampled");
-    if (!b.n) return;
-    std::vector<uint32_t> src(b.n);
-    SALVA_HIP_CHECK(hipMemcpyAsync(src.data(), b.dyn_src->p, b.n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (comm) {  // decomposed run: the global id of the source particle (salva_hip_get_local's `ids`) and its fluid
-        if (indices) SALVA_HIP_CHECK(hipMemcpyAsync(indices, b.dyn_src->p, b.n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        if (fluid_slots) SALVA_HIP_CHECK(hipMemcpyAsync(fluid_slots, b.dyn_src_model->p, b.n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    for (uint64_t k = 0; k < b.n; ++k) {
-        uint32_t f = 0;
-        uint64_t o = 0;
-        while (f + 1 < fluids.size() && src[k] >= o + fluids[f].n) { o += fluids[f].n; ++f; }
-        if (fluid_slots) fluid_slots[k] = f;
-        if (indices) indices[k] = (uint32_t)(src[k] - o);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host force callbacks
 __global__ void k_add_acc_from_host(uint32_t n, const uint32_t* __restrict__ perm, uint32_t off, uint32_t nn,
                                     const float* __restrict__ in, float4* __restrict__ acc) {
@@ -2274,94 +1339,6 @@ void World::set_fluid_field(uint32_t slot, int field, const float* data) {
     SALVA_HIP_CHECK(hipGetLastError());
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     sorted_valid = false; bbox_known = false; have_last_ctx = false;
-}
-
-void World::get_boundary_particles(uint32_t slot, float* positions, float* velocities) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const uint64_t nn = bounds[slot].n, off = boundary_offset(slot);
-    if (nn == 0) return;
-    scratch_f.ensure(3 * nn, stream, false, 1.1f);
-    for (int k = 0; k < 2; ++k) {
-        float* out = k == 0 ? positions : velocities;
-        if (!out) continue;
-        k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, (k == 0 ? bst_pos.p : bst_vel.p) + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(out, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
-void World::get_boundary_wrench(uint32_t slot, const float point[3], float force[3], float torque[3]) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const BoundarySlot& b = bounds[slot];
-    for (int k = 0; k < 3; ++k) force[k] = torque[k] = 0.0f;
-    if (!b.n || !b.wants_forces) return;
-    const uint64_t off = boundary_offset(slot);
-    const uint32_t nblocks = (uint32_t)std::min<uint64_t>(nblk(b.n), 256);
-    wrench_partial.ensure((size_t)256 * 6);  // per-step call in a coupled run: no allocation on the way
-    k_boundary_wrench<<<nblocks, BLOCK, 0, stream>>>((uint32_t)b.n, bst_pos.p + off, bforce.p + off, point[0], point[1], point[2], wrench_partial.p);
-    SALVA_HIP_CHECK(hipGetLastError());
-    std::vector<double> h((size_t)nblocks * 6);
-    SALVA_HIP_CHECK(hipMemcpyAsync(h.data(), wrench_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    for (uint32_t k = 0; k < nblocks; ++k)
-        for (int j = 0; j < 6; ++j) acc[j] += h[(size_t)k * 6 + j];
-    for (int k = 0; k < 3; ++k) { force[k] = (float)acc[k]; torque[k] = (float)acc[3 + k]; }
-}
-
-// `count` calls of get_boundary_wrench with one launch, one copy and one wait (points / forces / torques: 3 floats per entry)
-void World::get_boundary_wrenches(uint32_t count, const uint32_t* slots, const float* points, float* forces, float* torques) {
-    use_device();
-    for (uint32_t k = 0; k < count; ++k)
-        if (slots[k] >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    std::vector<uint32_t> live;  // the entries with something to sum
-    uint64_t nblocks = 0;
-    for (uint32_t k = 0; k < count; ++k) {
-        const BoundarySlot& b = bounds[slots[k]];
-        for (int a = 0; a < 3; ++a) forces[3 * (size_t)k + a] = torques[3 * (size_t)k + a] = 0.0f;
-        if (!b.n || !b.wants_forces) continue;
-        live.push_back(k);
-        nblocks += std::min<uint64_t>(nblk(b.n), 256);
-    }
-    if (live.empty()) return;
-    const size_t ent_bytes = live.size() * sizeof(WrenchEntry), part_bytes = (size_t)nblocks * 6 * sizeof(double);
-    char* stage = wrench_stage.acquire(ent_bytes + part_bytes);
-    WrenchEntry* ent_h = reinterpret_cast<WrenchEntry*>(stage);
-    uint32_t block0 = 0;
-    for (size_t e = 0; e < live.size(); ++e) {
-        const uint32_t k = live[e];
-        const BoundarySlot& b = bounds[slots[k]];
-        const uint32_t nbk = (uint32_t)std::min<uint64_t>(nblk(b.n), 256);
-        ent_h[e] = WrenchEntry{(uint32_t)boundary_offset(slots[k]), (uint32_t)b.n, block0, nbk, {points[3 * (size_t)k], points[3 * (size_t)k + 1], points[3 * (size_t)k + 2]}, 0u};
-        block0 += nbk;
-    }
-    wrench_tab.ensure(ent_bytes, stream, false, 1.5f);
-    wrenches_partial.ensure((size_t)nblocks * 6, stream, false, 1.5f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(wrench_tab.p, ent_h, ent_bytes, hipMemcpyHostToDevice, stream));
-    k_boundary_wrenches<<<(uint32_t)nblocks, BLOCK, 0, stream>>>((uint32_t)live.size(), reinterpret_cast<const WrenchEntry*>(wrench_tab.p), bst_pos.p,
-                                                                 bforce.p, wrenches_partial.p);
-    SALVA_HIP_CHECK(hipGetLastError());
-    SALVA_HIP_CHECK(hipMemcpyAsync(stage + ent_bytes, wrenches_partial.p, part_bytes, hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    const double* h = reinterpret_cast<const double*>(stage + ent_bytes);
-    for (size_t e = 0; e < live.size(); ++e) {
-        double acc[6] = {0, 0, 0, 0, 0, 0};
-        for (uint32_t k = 0; k < ent_h[e].nblocks; ++k)
-            for (int j = 0; j < 6; ++j) acc[j] += h[(size_t)(ent_h[e].block0 + k) * 6 + j];
-        for (int a = 0; a < 3; ++a) { forces[3 * (size_t)live[e] + a] = (float)acc[a]; torques[3 * (size_t)live[e] + a] = (float)acc[3 + a]; }
-    }
-}
-
-void World::clear_boundary_forces(uint32_t slot) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const uint64_t nn = bounds[slot].n, off = boundary_offset(slot);
-    if (nn) {
-        SALVA_HIP_CHECK(hipMemsetAsync(bforce.p + off, 0, nn * sizeof(float4), stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
 }
 
 uint64_t World::device_bytes() const {

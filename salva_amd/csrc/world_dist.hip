@@ -296,14 +296,14 @@ uint32_t World::dist_gather_emitted(const float4* rows, uint32_t cnt, const floa
     // peer transport a 256-value pass per 256 table words, whatever the number of ranks.)
     const size_t blk = (2 * (size_t)maxc + ((size_t)maxc + 1) / 2 + 1) & ~(size_t)1;  // (even: float4 rows start every section)
     const size_t words_al = (words + 1) & ~(size_t)1;
-    dcs_all.ensure(words_al + blk * ((size_t)size + 1), stream, false, 1.5f);
-    float4* out_rows = reinterpret_cast<float4*>(dcs_all.p);
-    uint32_t* out_models = reinterpret_cast<uint32_t*>(dcs_all.p + 2 * (size_t)total);
+    cpl.dcs_all.ensure(words_al + blk * ((size_t)size + 1), stream, false, 1.5f);
+    float4* out_rows = reinterpret_cast<float4*>(cpl.dcs_all.p);
+    uint32_t* out_models = reinterpret_cast<uint32_t*>(cpl.dcs_all.p + 2 * (size_t)total);
     if (size == 1) {
         launch_dcs_pack(cnt, rows, perm[cur].p, model[cur].p, out_rows, out_models, stream);
     } else {
         if (blk >= ((size_t)1 << 30)) throw HipError(SALVA_HIP_E_CAPACITY, "too many dynamically sampled boundary particles");
-        unsigned long long* mine = dcs_all.p + words_al;
+        unsigned long long* mine = cpl.dcs_all.p + words_al;
         unsigned long long* all = mine + blk;
         SALVA_HIP_CHECK(hipMemsetAsync(mine, 0, blk * sizeof(unsigned long long), stream));
         launch_dcs_pack(cnt, rows, perm[cur].p, model[cur].p, reinterpret_cast<float4*>(mine), reinterpret_cast<uint32_t*>(mine + 2 * (size_t)maxc), stream);

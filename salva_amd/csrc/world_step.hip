@@ -1,5 +1,6 @@
 // world_step.hip — the step path of libsalva_hip's host side: World::step and the phases of World::substep, the solves they run and the
-// host <-> device publications they wait for.  (world.hip: construction, object edits, tables, queries, downloads.)
+// host <-> device publications they wait for.  (world.hip: construction, object edits, tables, downloads; world_coupling.hip:
+// coupling and DynamicContactSampling; world_query.hip: queries.)
 //
 // Restates the control flow of /root/reference/src/liquid_world.rs:67-158 (step_with_coupling with the no-op
 // `()` coupling manager), src/solver/pressure/dfsph_solver.rs:667-708 (DFSPH step, iteration protocol :432-503)
@@ -729,7 +730,7 @@ int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
         upload_tables();  // (any_wants_forces)
         if (any_wants_forces && !coupling_cb)
             for (const BoundarySlot& b : bounds)
-                if (b.wants_forces && (b.sampling || b.dyn_kind))
+                if (b.wants_forces && (b.sampling || b.dyn))
                     // the reference clears a coupled boundary's forces and transmits their impulse in EVERY substep with that substep's
                     // dt (fluids_pipeline.rs:262, :266-287): one wrench per step() cannot carry that.  The caller's own loop can.
                     throw HipError(SALVA_HIP_E_INVALID, "CFL sub-stepping with a coupled boundary that wants forces needs salva_hip_set_coupling_callback "
@@ -1328,9 +1329,9 @@ bool World::run_pass(const PassSnapshot& snap, float& dt, const float g[3], Salv
             // its cell is no longer the one it was inserted under), so the particles are kept as they were until that is decided.
             p.dcs_undo = n != 0 && gf.folded() && !fold_locked;
             if (p.dcs_undo) {
-                dcs_undo_pos.ensure(n, stream, false, 1.1f); dcs_undo_vel.ensure(n, stream, false, 1.1f);
-                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_pos.p, posm[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-                SALVA_HIP_CHECK(hipMemcpyAsync(dcs_undo_vel.p, vel[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+                cpl.dcs_undo_pos.ensure(n, stream, false, 1.1f); cpl.dcs_undo_vel.ensure(n, stream, false, 1.1f);
+                SALVA_HIP_CHECK(hipMemcpyAsync(cpl.dcs_undo_pos.p, posm[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+                SALVA_HIP_CHECK(hipMemcpyAsync(cpl.dcs_undo_vel.p, vel[cur].p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
             }
             run_dynamic_sampling();
             p.dcs_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
@@ -1516,8 +1517,8 @@ int World::substep(float& dt, const float g[3], SalvaHipStepStats& st) {
             // (size_pass throws behind reorder_working_set, which has flipped `cur` to the sorted copy of the PUSHED particles: the
             // snapshot's `cur` is the buffer the kept copies belong to, in their order)
             snap.restore(*this);
-            SALVA_HIP_CHECK(hipMemcpyAsync(posm[cur].p, dcs_undo_pos.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-            SALVA_HIP_CHECK(hipMemcpyAsync(vel[cur].p, dcs_undo_vel.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            SALVA_HIP_CHECK(hipMemcpyAsync(posm[cur].p, cpl.dcs_undo_pos.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            SALVA_HIP_CHECK(hipMemcpyAsync(vel[cur].p, cpl.dcs_undo_vel.p, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         }
         throw;
     }

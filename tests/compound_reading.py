@@ -119,7 +119,7 @@ def callbacks(parts, body, log=None):
 
 
 def shape_distance(shape, l):
-    """distance_to_point(identity, l, solid = true) of a built-in shape, as world.hip's shape_solid_distance computes it."""
+    """distance_to_point(identity, l, solid = true) of a built-in shape, as world_query.hip's shape_solid_distance computes it."""
     x, y, z = l[:, 0], l[:, 1], l[:, 2]
     if shape[0] == "ball":
         return np.maximum(np.sqrt((x * x + y * y) + z * z) - F(shape[1]), F(0)).astype(F)
