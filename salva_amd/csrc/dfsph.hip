@@ -1123,7 +1123,7 @@ __global__ __launch_bounds__(FINALIZE_THREADS) void k_finalize_error(const float
     // chained step, the chain broke upstream (device_types.h StepCtx::gate): this test does not exist
     if (gate && gate_words_closed(gate[0], gate[1], close_stage)) return;
     const u32x4 c0 = reinterpret_cast<const u32x4*>(ctl)[0], c1 = reinterpret_cast<const u32x4*>(ctl)[1];
-    // (skipped: the tests of earlier iterations that were not launched because they could not end the solve — i < min_iter, World::run_solve
+    // (skipped: the tests of earlier iterations that were not launched because they could not end the solve — i < min_iter, World::SolveTest
     // — count as failed ones: one apply / iteration and one tick each)
     const uint32_t done = c0.x, iters = c0.y + skipped, seq = c0.w + 1u + skipped, min_iter = c1.y, mode = c1.z;
     const float tol = __uint_as_float(c1.x);
@@ -1187,7 +1187,7 @@ __global__ void k_decide(const float* __restrict__ sums, uint32_t nmodels, const
     ctl->seq = s;
     publish_ctl(ctl, pub, s);
 }
-// the same decision for a speculative decomposed solve (World::run_solve, spec_dist): iteration k reads ring[k & 1] and the record of
+// the same decision for a speculative decomposed solve (World::solve_batches, spec_dist): iteration k reads ring[k & 1] and the record of
 // iteration k + 1 goes to ring[(k + 1) & 1] — the apply pass of iteration k runs beside this kernel and still reads the old one
 __global__ void k_decide_ring(const float* __restrict__ sums, uint32_t nmodels, const uint32_t* __restrict__ model_counts, SolveCtl* ring, int k,
                               SolveCtl* pub) {

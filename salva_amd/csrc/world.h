@@ -283,9 +283,25 @@ class World {
     void ensure_cub_temp(size_t bytes);
     StepCtx make_ctx();
     struct SolveResult { uint32_t iters; float err; };
-    template <typename Eval, typename Apply>
-    SolveResult run_solve(StepCtx c, int which, float tol, int min_iter, int max_iter, uint32_t mode, Eval&& eval, Apply&& apply,
-                          bool spec_apply = false, int chain_stage = 0, int from = 0, bool chain_open = false);
+    // The iterative solves (world_step.hip): a solve is described once ...
+    struct SolveSpec {
+        int which; float tol; int min_iter, max_iter; uint32_t mode;  // which: its control block (0 divergence, 1 pressure, 2 viscosity)
+        const DevBuf<float4>* ghosts;   // decomposed runs: the field whose ghosts are refreshed behind every apply (null: none)
+        bool spec_apply;                // the convergence test rides in the apply pass (dfsph.hip spec_decide): waited solves only
+        SolveCtl init() const { return SolveCtl{0u, 0u, 0.0f, 0u, tol, (uint32_t)std::max(min_iter, 0), mode, 0u}; }
+    };
+    // ... and enqueued by one of three protocols: eval(ctx, iteration), apply(ctx, iteration, the stream it launches on)
+    enum class ChainLink { Opens, Follows };  // the first chained solve of a step opens the device-side gate, the second finds it open
+    template <typename Eval, typename Apply>  // waited: growing batches from iteration 0, one host wait per batch
+    SolveResult solve_waited(const StepCtx& c, const SolveSpec& s, Eval&& eval, Apply&& apply) { begin_solve(s, false); return solve_batches(c, s, 0, eval, apply); }
+    template <typename Eval, typename Apply>  // chained: one batch and no wait; its outcome comes with the end-of-step publication
+    void solve_chained(StepCtx c, const SolveSpec& s, ChainLink link, Eval&& eval, Apply&& apply);
+    template <typename Eval, typename Apply>  // the continuation of a chained batch that fell short: waited batches from where it ended
+    SolveResult solve_continued(const StepCtx& c, const SolveSpec& s, Eval&& eval, Apply&& apply) { return solve_batches(c, s, pass.solve[s.which].enqueued, eval, apply); }
+    void begin_solve(const SolveSpec& s, bool opens_chain);  // (what the three share: world_step.hip)
+    struct SolveTest;
+    template <typename Apply> void apply_and_refresh(const StepCtx& c, const SolveSpec& s, int it, Apply& apply);
+    template <typename Eval, typename Apply> SolveResult solve_batches(StepCtx c, const SolveSpec& s, int from, Eval& eval, Apply& apply);
     // Chained steps (device_types.h StepCtx::gate, World::dfsph_solve): both solves of a DFSPH step and everything between and behind
     // them are enqueued without a wait; the end-of-step publication carries their outcome.
     bool chain_allowed() const;
@@ -312,6 +328,7 @@ class World {
     // launch shapes `lds` / `halo_stride`, which every size_pass rewrites whole and the constructor seeds with Switches::ds_level.)
     // (World::choose_grid: the size of the (folded) cell table, of the dense tile table, and the bound of the compact per-slot tables)
     struct GridShape { size_t ncf = 0; uint32_t ntiles = 0, nslots_bound = 0; };
+    static constexpr int NUM_SOLVES = 3;  // divergence, pressure, viscosity
     // What each pass (World::run_pass) decides for the phases behind it.
     struct Attempt {
         bool spec = false;          // launch shapes from the previous step's totals (World::substep: "One pass over the step")
@@ -337,12 +354,11 @@ class World {
         bool fold_stats = false; uint32_t fold_bbox_blocks = 0; const uint32_t* fold_bbox_gate = nullptr;
         bool fused_first_divergence = false;  // this pass's density pass also ran the divergence solve's first evaluate (dfsph.hip)
         bool iisph_dii_fused = false;  // this pass's density pass wrote d_ii (k_density_alpha<true>): iisph_solve skips k_iisph_dii
-        SolveCtl pre_init1{}; bool pre_init1_valid = false;  // the pressure solve's initial control block, written by the divergence solve's k_init_ctl launch
-        bool solve_owes_apply[3] = {false, false, false};  // the apply behind a batch's last test, left to whoever continues the solve
-        hipStream_t spec_dist_stream = nullptr;  // non-null while run_solve launches a decomposed speculative apply: where its kernel goes
+        // What the protocols of a solve hand each other: the apply behind a batch's last test is left to whoever continues the solve; iterations its chained
+        // batch enqueued (where a continuation starts); the pressure solve's initial control block, for the divergence solve's k_init_ctl launch to write too
+        struct SolveState { bool owes_apply = false; int enqueued = 0; bool pre_init_valid = false; SolveCtl pre_init{}; } solve[NUM_SOLVES];
         // this pass was enqueued chained and its outcome has not been read yet / the divergence solve included (not while its count is rising)
         bool chain_pending = false, chain_div_pending = false;
-        int chain_batch[2] = {0, 0};    // iterations enqueued for the divergence / the pressure solve (where a continuation starts)
         float chain_dt_prev = 0.0f, chain_inv_dt_prev = 0.0f;  // TimestepManager::{dt, inv_dt} as the chained attempt found them
         uint32_t dforce_tables = 0;  // SALVA_HIP_DEVICE_NEEDS_* the contact tables hold for this pass's lists (0: not built)
     };
@@ -398,12 +414,16 @@ class World {
     DistArrays dist_arrays(int which);
     void dist_prepare();        // migration + ghost planes, before the grid is built
     void dist_build_lists();    // after the cell sort
+    template <typename T, typename Gather, typename Scatter> void refresh_ghosts(T* field, Gather gather, Scatter scatter);
     void refresh_f32(float* field);
     void refresh_f4(float4* field);
     void ensure_particle_capacity(size_t cap);
-    void finalize_solve(SolveCtl* ctl, SolveCtl* pub, uint32_t skipped = 0);
+    void allreduce_host_u64(std::vector<unsigned long long>& v);  // in place, waited for; collective
+    uint32_t num_models() const { return (uint32_t)std::max<size_t>(fluids.size(), 1); }  // fluid models, at least 1 (what per-model tables are cut for)
+    template <typename Decide> void allreduced_test(const SolveCtl* record, Decide&& decide);
+    void finalize_solve(SolveCtl* ctl, SolveCtl* pub, uint32_t skipped);
+    void finalize_solve_ring(int it, SolveCtl* pub);  // ... of a decomposed solve with speculative applies (dfsph.hip k_decide_ring)
 
-    static constexpr int NUM_SOLVES = 3;  // divergence, pressure, viscosity
     const Switches sw = Switches::from_env();  // ---- 1. what the environment asked for when the world was made (switches.h)
     // ---- 3. What one step deliberately hands to the next (with `pre` and `lds` / `halo_stride` further down); PassSnapshot puts
     // back what a discarded pass has overwritten of it.  Host edits invalidate it where they happen (world.hip).
@@ -445,7 +465,7 @@ class World {
     size_t h_dl_cap[2] = {0, 0};
     struct PendingDownload { bool active = false; float* dst[2] = {nullptr, nullptr}; bool staged[2] = {false, false}; size_t bytes = 0; } dl;
     hipEvent_t ev_pre_refresh = nullptr, ev_interior = nullptr;
-    // decomposed solves with speculative applies (World::run_solve): evaluate done -> the apply may start on stream2; apply done ->
+    // decomposed solves with speculative applies (World::solve_batches): evaluate done -> the apply may start on stream2; apply done ->
     // the main stream may refresh what it wrote
     hipEvent_t ev_spec_eval = nullptr, ev_spec_apply = nullptr;
     template <typename Launch> void evaluate_split(const StepCtx& c, int iteration, Launch&& launch);

@@ -680,7 +680,7 @@ static inline bool groups_test(uint32_t m1, uint32_t f1, uint32_t m2, uint32_t f
 void World::upload_tables() {
     if (!tables_dirty) return;
     lists_checked = sw.trust_cap0;  // the objects changed: the next step checks the list capacity before it solves (World::step)
-    const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1), nbm = (uint32_t)std::max<size_t>(bounds.size(), 1);
+    const uint32_t nm = num_models(), nbm = (uint32_t)std::max<size_t>(bounds.size(), 1);
     std::vector<float> r0(nm, 1000.0f);
     std::vector<uint32_t> counts(nm, 0);
     std::vector<uint8_t> ff(nm * nm, 1), fb(nm * nbm, 1), bb(nbm * nbm, 1), bw(nbm, 0);
@@ -758,7 +758,7 @@ StepCtx World::make_ctx() {
     c.bforce_scale = bforce_scale();
     c.bwants = bwants.p;
     c.gb = gb.device(cell_start_b.p);
-    c.nmodels = (uint32_t)std::max<size_t>(fluids.size(), 1);
+    c.nmodels = num_models();
     c.nbmodels = (uint32_t)std::max<size_t>(bounds.size(), 1);
     c.mass_uniform = mass_uniform;
     c.two_mass = pass.two_mass ? 1u : 0u;
@@ -986,7 +986,7 @@ uint64_t World::get_fluid_contacts(uint32_t slot, int boundary, uint64_t* offset
     const uint64_t total = offs[nn];
     if (offsets) memcpy(offsets, offs.data(), (nn + 1) * sizeof(uint64_t));
     if (!j_model || !j || capacity < total || total == 0) return total;
-    std::vector<uint32_t> moff(std::max<size_t>(fluids.size(), 1), 0), boff(std::max<size_t>(bounds.size(), 1), 0);
+    std::vector<uint32_t> moff(num_models(), 0), boff(std::max<size_t>(bounds.size(), 1), 0);
     for (uint32_t s = 0; s < fluids.size(); ++s) moff[s] = (uint32_t)fluid_offset(s);
     for (uint32_t s = 0; s < bounds.size(); ++s) boff[s] = (uint32_t)boundary_offset(s);
     DevBuf<uint64_t> d_offs;

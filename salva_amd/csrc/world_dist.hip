@@ -43,6 +43,15 @@ void World::set_domain(Transport* transport, int lo, int hi, uint32_t gid_off) {
     sorted_valid = false; bbox_known = false; dist_started = false; tables_dirty = true; nbr_bounds_valid = false;
 }
 
+// All-reduce (sum) a short host vector in place through the one staging buffer, and wait for it.  Collective.
+void World::allreduce_host_u64(std::vector<unsigned long long>& v) {
+    plane_hist.ensure(v.size());
+    SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, v.data(), v.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    comm->allreduce_sum_u64(plane_hist.p, (int)v.size(), stream);
+    SALVA_HIP_CHECK(hipMemcpyAsync(v.data(), plane_hist.p, v.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
 // Load balancing ("re-cut every M steps").  All ranks call it between two steps.  Every rank contributes the
 // histogram of its owned particles over the cell planes; the sums are all-reduced, and every rank computes the same new
 // cuts: the plane where the running count passes k N / size, kept between the old cuts on either side (so that a particle
@@ -59,11 +68,7 @@ void World::rebalance(int32_t* new_lo, int32_t* new_hi) {
     std::vector<unsigned long long> rng(2 * (size_t)size, 0ull);
     rng[2 * rank] = (unsigned long long)((long long)my_lo + (long long)OFF);
     rng[2 * rank + 1] = (unsigned long long)((long long)my_hi + (long long)OFF);
-    plane_hist.ensure(std::max<size_t>(2 * (size_t)size, 64));
-    SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, rng.data(), rng.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    comm->allreduce_sum_u64(plane_hist.p, 2 * size, stream);
-    SALVA_HIP_CHECK(hipMemcpyAsync(rng.data(), plane_hist.p, rng.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    allreduce_host_u64(rng);
     std::vector<long long> lo(size), hi(size);
     for (int r = 0; r < size; ++r) { lo[r] = (long long)rng[2 * r] - (long long)OFF; hi[r] = (long long)rng[2 * r + 1] - (long long)OFF; }
     const long long base = lo[0], len = hi[size - 1] - lo[0] + 1;
@@ -131,36 +136,21 @@ void World::ensure_particle_capacity(size_t cap) {
 void World::dist_prepare() {
     // the per-fluid particle counts of the error averages are global and constant (no creation / deletion here)
     if (!dist_started) {
-        const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
+        const uint32_t nm = num_models();
         std::vector<unsigned long long> cnt(nm, 0);
         for (uint32_t f = 0; f < fluids.size(); ++f) cnt[f] = fluids[f].n;
-        d_counters.ensure(std::max<size_t>(4, nm));
-        SALVA_HIP_CHECK(hipMemcpyAsync(d_counters.p, cnt.data(), nm * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-        comm->allreduce_sum_u64(d_counters.p, (int)nm, stream);
-        SALVA_HIP_CHECK(hipMemcpyAsync(cnt.data(), d_counters.p, nm * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        std::vector<uint32_t> c32(nm);
-        for (uint32_t f = 0; f < nm; ++f) {
+        allreduce_host_u64(cnt);
+        for (uint32_t f = 0; f < nm; ++f)
             if (cnt[f] >= 0xffffffffull) throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 particles in one fluid");
-            c32[f] = (uint32_t)cnt[f];
-        }
-        global_counts = c32;
-        SALVA_HIP_CHECK(hipMemcpyAsync(model_counts.p, c32.data(), nm * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        global_counts.assign(cnt.begin(), cnt.end());
+        SALVA_HIP_CHECK(hipMemcpyAsync(model_counts.p, global_counts.data(), nm * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         SALVA_HIP_CHECK(hipStreamSynchronize(stream));
         d_sums.ensure(nm);
         // the first global id no particle has: where dist_add_particles continues numbering
-        {
-            const int size = comm->size(), rank = comm->rank();
-            std::vector<unsigned long long> top((size_t)size, 0ull);
-            top[rank] = (unsigned long long)gid_offset + n;
-            plane_hist.ensure(std::max<size_t>((size_t)size, 64));
-            SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, top.data(), top.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-            comm->allreduce_sum_u64(plane_hist.p, size, stream);
-            SALVA_HIP_CHECK(hipMemcpyAsync(top.data(), plane_hist.p, top.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-            gid_next = 0;
-            for (auto t : top) gid_next = std::max<uint64_t>(gid_next, t);
-        }
+        std::vector<unsigned long long> top((size_t)comm->size(), 0ull);
+        top[comm->rank()] = (unsigned long long)gid_offset + n;
+        allreduce_host_u64(top);
+        gid_next = *std::max_element(top.begin(), top.end());
         dist_started = true;
     }
     const bool has_lo = comm->has_lo(), has_hi = comm->has_hi();
@@ -272,25 +262,17 @@ uint32_t World::dist_gather_emitted(const float4* rows, uint32_t cnt, const floa
     std::vector<unsigned long long> counts((size_t)size + 1, 0ull);
     counts[rank] = local_error ? 0ull : cnt;
     counts[size] = local_error ? 1ull : 0ull;
-    if (size > 1) {
-        plane_hist.ensure(std::max<size_t>((size_t)size + 1, 64));
-        SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, counts.data(), counts.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-        comm->allreduce_sum_u64(plane_hist.p, size + 1, stream);
-        SALVA_HIP_CHECK(hipMemcpyAsync(counts.data(), plane_hist.p, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
+    if (size > 1) allreduce_host_u64(counts);
     if (local_error) throw *local_error;
     if (counts[size])
         throw HipError(SALVA_HIP_E_INVALID, "dynamic contact sampling failed on another rank of the decomposed world (its own error says why); "
                                             "every rank leaves the step");
-    unsigned long long total = 0, before = 0;
-    for (int r = 0; r < size; ++r) { if (r < rank) before += counts[r]; total += counts[r]; }
+    unsigned long long total = 0, maxc = 0;
+    for (int r = 0; r < size; ++r) { total += counts[r]; maxc = std::max(maxc, counts[r]); }
     if (total >= 0x3fffffffull) throw HipError(SALVA_HIP_E_CAPACITY, "too many dynamically sampled boundary particles");
     *all_rows = nullptr; *all_models = nullptr;
     if (total == 0) return 0;
     const size_t words = 2 * (size_t)total + ((size_t)total + 1) / 2;  // float4 rows, then uint32 fluids
-    unsigned long long maxc = 0;
-    for (int r = 0; r < size; ++r) maxc = std::max(maxc, counts[r]);
     // every rank's section — rows, then fluids — in a block of one stride, gathered (Transport::allgather_u64), then copied side by
     // side into the table every rank builds its boundary from.  (Round 5 summed a zeroed table through the sum all-reduce: over the
     // peer transport a 256-value pass per 256 table words, whatever the number of ranks.)
@@ -318,7 +300,6 @@ uint32_t World::dist_gather_emitted(const float4* rows, uint32_t cnt, const floa
             at += counts[r];
         }
     }
-    (void)before;
     *all_rows = out_rows; *all_models = out_models;
     return (uint32_t)total;
 }
@@ -327,8 +308,6 @@ void World::dist_build_lists() {
     launch_dist_lists(n, gtag[cur].p, send_lo_idx.p, send_hi_idx.p, ghost_lo_idx.p, ghost_hi_idx.p, stream);
 }
 
-// Refresh one per-particle field of the ghosts from its owners: gather the mirrored edge-plane particles into a dense
-// buffer, one sendrecv with both neighbours, scatter into the ghost slots.  All on the world's stream.
 // ---- event pairs around the exchanges of a step (world.h dist_times); only while the stage timers are on
 size_t World::dist_time_begin(int kind) {
     if (!prm.enable_timers) return (size_t)-1;
@@ -358,50 +337,50 @@ void World::dist_time_fold() {
     pass.dist_ev_used = 0;
 }
 
-void World::refresh_f32(float* field) {
+// Refresh one per-particle field of the ghosts from its owners: gather the mirrored edge-plane particles into a dense
+// buffer, one sendrecv with both neighbours, scatter into the ghost slots.  All on the world's stream.
+template <typename T, typename Gather, typename Scatter>
+void World::refresh_ghosts(T* field, Gather gather, Scatter scatter) {
     if (!comm->has_lo() && !comm->has_hi()) return;
     SALVA_HIP_CHECK(hipEventRecord(ev_pre_refresh, stream));  // (what evaluate_split lets the interior tiles start after)
     const size_t tm = dist_time_begin(0);
-    float* sb = reinterpret_cast<float*>(fbuf_send.p);
-    float* rb = reinterpret_cast<float*>(fbuf_recv.p);
-    launch_gather_f32(nborder_lo, send_lo_idx.p, field, sb, stream);
-    launch_gather_f32(nborder_hi, send_hi_idx.p, field, sb + nborder_lo, stream);
-    comm->sendrecv(sb, nborder_lo * sizeof(float), sb + nborder_lo, nborder_hi * sizeof(float), rb, nghost_lo * sizeof(float),
-                   rb + nghost_lo, nghost_hi * sizeof(float), stream);
-    launch_scatter_f32(nghost_lo, ghost_lo_idx.p, rb, field, stream);
-    launch_scatter_f32(nghost_hi, ghost_hi_idx.p, rb + nghost_lo, field, stream);
+    T* sb = reinterpret_cast<T*>(fbuf_send.p);
+    T* rb = reinterpret_cast<T*>(fbuf_recv.p);
+    gather(nborder_lo, send_lo_idx.p, field, sb, stream);
+    gather(nborder_hi, send_hi_idx.p, field, sb + nborder_lo, stream);
+    comm->sendrecv(sb, nborder_lo * sizeof(T), sb + nborder_lo, nborder_hi * sizeof(T), rb, nghost_lo * sizeof(T),
+                   rb + nghost_lo, nghost_hi * sizeof(T), stream);
+    scatter(nghost_lo, ghost_lo_idx.p, rb, field, stream);
+    scatter(nghost_hi, ghost_hi_idx.p, rb + nghost_lo, field, stream);
     dist_time_end(tm);
 }
-void World::refresh_f4(float4* field) {
-    if (!comm->has_lo() && !comm->has_hi()) return;
-    SALVA_HIP_CHECK(hipEventRecord(ev_pre_refresh, stream));
-    const size_t tm = dist_time_begin(0);
-    float4* sb = fbuf_send.p;
-    float4* rb = fbuf_recv.p;
-    launch_gather_idx_f4(nborder_lo, send_lo_idx.p, field, sb, stream);
-    launch_gather_idx_f4(nborder_hi, send_hi_idx.p, field, sb + nborder_lo, stream);
-    comm->sendrecv(sb, nborder_lo * sizeof(float4), sb + nborder_lo, nborder_hi * sizeof(float4), rb, nghost_lo * sizeof(float4),
-                   rb + nghost_lo, nghost_hi * sizeof(float4), stream);
-    launch_scatter_idx_f4(nghost_lo, ghost_lo_idx.p, rb, field, stream);
-    launch_scatter_idx_f4(nghost_hi, ghost_hi_idx.p, rb + nghost_lo, field, stream);
-    dist_time_end(tm);
-}
+void World::refresh_f32(float* field) { refresh_ghosts(field, launch_gather_f32, launch_scatter_f32); }
+void World::refresh_f4(float4* field) { refresh_ghosts(field, launch_gather_idx_f4, launch_scatter_idx_f4); }
 
+// The all-reduced convergence test: per-fluid sums of the error partials (one per launched, non-empty tile; `record` says whether
+// the solve is still running) -> all-reduce -> `decide`.
+template <typename Decide>
+void World::allreduced_test(const SolveCtl* record, Decide&& decide) {
+    const uint32_t nm = num_models();
+    const size_t tm = dist_time_begin(1);
+    launch_sum_partials(partials.p, pass.nlaunch, nm, record, d_sums.p, stream);
+    comm->allreduce_sum_f32(d_sums.p, (int)nm, stream);
+    decide(nm);
+    dist_time_end(tm);
+}
 // Error reduction + break test of an iterative solve; with a transport the per-fluid sums are all-reduced first.
 void World::finalize_solve(SolveCtl* ctl, SolveCtl* pub, uint32_t skipped) {
-    const unsigned ntiles = pass.nlaunch;  // one partial per launched (non-empty) tile
-    const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
     if (!comm || comm->size() == 1) {
         // (folding this into the evaluate kernels through a last-workgroup reduction was measured 7x slower: the
         // device-scope release every workgroup needs writes the XCD's whole L2 back)
-        launch_finalize_error(partials.p, ntiles, nm, model_counts.p, ctl, pub, stream, nullptr, nullptr, 0u, skipped);
+        launch_finalize_error(partials.p, pass.nlaunch, num_models(), model_counts.p, ctl, pub, stream, nullptr, nullptr, 0u, skipped);
         return;
     }
-    const size_t tm = dist_time_begin(1);
-    launch_sum_partials(partials.p, ntiles, nm, ctl, d_sums.p, stream);
-    comm->allreduce_sum_f32(d_sums.p, (int)nm, stream);
-    launch_decide(d_sums.p, nm, model_counts.p, ctl, pub, stream, skipped);
-    dist_time_end(tm);
+    allreduced_test(ctl, [&](uint32_t nm) { launch_decide(d_sums.p, nm, model_counts.p, ctl, pub, stream, skipped); });
+}
+// ... of iteration `it` of a decomposed solve with speculative applies: reads the ring's record of `it`, writes that of it + 1
+void World::finalize_solve_ring(int it, SolveCtl* pub) {
+    allreduced_test(spec_ring.p + (it & 1), [&](uint32_t nm) { launch_decide_ring(d_sums.p, nm, model_counts.p, spec_ring.p, it, pub, stream); });
 }
 
 // ---- particle creation and removal in a running decomposed world.  Both are COLLECTIVE: every rank calls them between the
@@ -423,17 +402,13 @@ __global__ __launch_bounds__(BLOCK) void k_dist_append(uint32_t n_add, uint32_t 
 
 // per-fluid count changes of this rank -> the global counts, on every rank
 void World::dist_update_counts(const std::vector<long long>& delta) {
-    const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
+    const uint32_t nm = num_models();
     std::vector<unsigned long long> buf(2 * (size_t)nm, 0ull);  // [added | removed]
     for (uint32_t f = 0; f < nm && f < delta.size(); ++f) {
         if (delta[f] >= 0) buf[f] = (unsigned long long)delta[f];
         else buf[nm + f] = (unsigned long long)(-delta[f]);
     }
-    plane_hist.ensure(std::max<size_t>(2 * (size_t)nm, 64));
-    SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, buf.data(), buf.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    comm->allreduce_sum_u64(plane_hist.p, (int)buf.size(), stream);
-    SALVA_HIP_CHECK(hipMemcpyAsync(buf.data(), plane_hist.p, buf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    allreduce_host_u64(buf);
     if (global_counts.size() != nm) global_counts.assign(nm, 0u);
     for (uint32_t f = 0; f < nm; ++f) {
         const unsigned long long c = (unsigned long long)global_counts[f] + buf[f] - std::min<unsigned long long>(buf[nm + f], (unsigned long long)global_counts[f] + buf[f]);
@@ -465,11 +440,7 @@ void World::dist_add_particles(uint32_t slot, uint64_t n_add, const float* pos, 
     std::vector<unsigned long long> adds((size_t)size + 1, 0ull);
     adds[rank] = local_error.empty() ? n_add : 0ull;
     adds[size] = local_error.empty() ? 0ull : 1ull;  // ranks that cannot take their particles
-    plane_hist.ensure(std::max<size_t>((size_t)size + 1, 64));
-    SALVA_HIP_CHECK(hipMemcpyAsync(plane_hist.p, adds.data(), adds.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    comm->allreduce_sum_u64(plane_hist.p, size + 1, stream);
-    SALVA_HIP_CHECK(hipMemcpyAsync(adds.data(), plane_hist.p, adds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    allreduce_host_u64(adds);
     if (adds[size] != 0)  // every rank leaves here, together, with nothing changed
         throw HipError(local_error.empty() ? SALVA_HIP_E_CAPACITY : SALVA_HIP_E_INVALID,
                        local_error.empty() ? "add_particles failed on another rank of the run: nothing was added anywhere" : local_error);
@@ -478,7 +449,7 @@ void World::dist_add_particles(uint32_t slot, uint64_t n_add, const float* pos, 
     if (gid_next + total >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "global particle ids exhausted");
     const uint64_t gid0 = gid_next + before;
     gid_next += total;
-    std::vector<long long> delta(std::max<size_t>(fluids.size(), 1), 0);
+    std::vector<long long> delta(num_models(), 0);
     delta[slot] = (long long)n_add;
     dist_update_counts(delta);
     if (n_add == 0) return;
@@ -514,7 +485,7 @@ uint64_t World::delete_owned(uint32_t n_ids, const uint32_t* gids) {
     if (!comm) throw HipError(SALVA_HIP_E_INVALID, "delete_owned is for multi-GPU worlds (a single domain deletes by host index: salva_hip_delete_particles)");
     if (!dist_started || !sorted_valid) throw HipError(SALVA_HIP_E_INVALID, "no step has run yet");
     if (n_ids && !gids) throw HipError(SALVA_HIP_E_INVALID, "null id list");
-    const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
+    const uint32_t nm = num_models();
     std::vector<long long> delta(nm, 0);
     if (n_ids && n) {
         std::vector<uint32_t> ids(gids, gids + n_ids);

@@ -210,122 +210,140 @@ __global__ void k_init_ctl(SolveCtl* ctl, SolveCtl* ring, SolveCtl init, uint32_
     if (chain_open) { chain_open[0] = 1u; chain_open[1] = 0u; }  // (Readback::chain_ok / chain_stage: the first solve of a chained step)
     if (ring) { ring[0] = init; ring[1] = init; }  // (dfsph.hip spec_decide: the test rides in the apply pass; iteration k reads spec_ring[k & 1])
 }
-template <typename Eval, typename Apply>
-World::SolveResult World::run_solve(StepCtx c, int which, float tol, int min_iter, int max_iter, uint32_t mode, Eval&& eval,
-                                    Apply&& apply, bool spec_apply, int chain_stage, int from, bool chain_open) {
-    // Every convergence test publishes its outcome to host-mapped memory (k_finalize_error; in a decomposed run k_decide,
-    // behind the all-reduce), and the host waits for the test count it enqueued — it then decides (and enqueues what
-    // follows) while the batch's last apply pass is still running.
-    SolveCtl* const pub = sw.no_publish ? nullptr : h_pub + which;
-    c.ctl = d_ctl.p + which;
-    if (from == 0) {
-        SolveCtl& init = h_ctl[NUM_SOLVES + which];
-        init = SolveCtl{0u, 0u, 0.0f, 0u, tol, (uint32_t)std::max(min_iter, 0), mode, 0u};
-        h_ctl[which] = init;
-        // (one tiny kernel with the record as its argument instead of up to three copies from pageable host memory, each of which
-        // stalls the host until its staging copy is done; the first solve of a chained step also opens the chain)
-        const bool have = which == 1 && pass.pre_init1_valid && memcmp(&pass.pre_init1, &init, sizeof(SolveCtl)) == 0 && !chain_open;
-        if (!have) {
-            const bool both = which == 0 && pass.pre_init1_valid;  // (World::dfsph_solve has said what the pressure solve will start from)
-            k_init_ctl<<<1, 1, 0, stream>>>(d_ctl.p + which, spec_apply ? spec_ring.p : nullptr, init, chain_open ? &d_rb.p->chain_ok : nullptr,
-                                            both ? d_ctl.p + 1 : nullptr, both ? pass.pre_init1 : init);
-            SALVA_HIP_CHECK(hipGetLastError());
-        }
-        if (which == 1) pass.pre_init1_valid = false;
-        if (pub) { pub->done = 0u; pub->iters = 0u; pub->err = 0.0f; __atomic_store_n(&pub->seq, 0u, __ATOMIC_RELEASE); }
+// The control block of a solve that starts at iteration 0: the one place that initialises it, whatever the protocol.
+void World::begin_solve(const SolveSpec& s, bool opens_chain) {
+    const int which = s.which;
+    const SolveCtl init = h_ctl[which] = h_ctl[NUM_SOLVES + which] = s.init();
+    // (one tiny kernel with the record as its argument instead of up to three copies from pageable host memory, each of which
+    // stalls the host until its staging copy is done; the first solve of a chained step also opens the chain)
+    Attempt::SolveState& next = pass.solve[1];  // (World::dfsph_solve has said what the pressure solve will start from)
+    const bool have = which == 1 && next.pre_init_valid && memcmp(&next.pre_init, &init, sizeof(SolveCtl)) == 0 && !opens_chain;
+    if (!have) {
+        const bool both = which == 0 && next.pre_init_valid;
+        k_init_ctl<<<1, 1, 0, stream>>>(d_ctl.p + which, s.spec_apply ? spec_ring.p : nullptr, init, opens_chain ? &d_rb.p->chain_ok : nullptr,
+                                        both ? d_ctl.p + 1 : nullptr, both ? next.pre_init : init);
+        SALVA_HIP_CHECK(hipGetLastError());
     }
-    // First batch: what the previous step's solve needed (iters applies + the converged evaluate) — consecutive steps
-    // need about the same, so the usual cost is one read-back per solve; a batch that overshoots only enqueues kernels
-    // that return at once, one that falls short continues in doubling batches.
-    int i = from, batch = std::max(2, std::min<int>((int)last_iters[which] + 1, max_iter));
-    const bool multi = comm && comm->size() > 1;
-    // Two launches a solve does not need (round 6; a kernel that returns at once still costs a launch of 2 200 workgroups, ~5 us, and
-    // a one-block test ~4.6 us plus its gaps — 23 us of a 0.61 ms free-fall step):
-    //  * the tests of iterations i < min_iter cannot end the solve (`err <= tol && i >= min`): they are not launched — the next test
-    //    that is counts them (`skipped`: iters and seq advance as if they had failed).  In a decomposed run that is an all-reduce less.
-    //  * the apply behind the LAST test of a batch runs only if that test fails, which the batch is sized not to expect: it is
-    //    enqueued by whoever continues the solve (`owed`), and never when the solve has converged.  Not in decomposed runs (a ghost
-    //    refresh rides behind every apply) and not where the test rides in the apply pass itself (spec_apply).
-    const bool lazy_apply = !multi && !spec_apply;
-    uint32_t skipped = 0u;
-    auto test = [&](int it, bool last_of_batch, const uint32_t* gate, uint32_t* close, uint32_t stage) {
-        if (it < min_iter && it + 1 < max_iter && !last_of_batch) { ++skipped; return; }
-        if (!multi) launch_finalize_error(partials.p, pass.nlaunch, (uint32_t)std::max<size_t>(fluids.size(), 1), model_counts.p, d_ctl.p + which, pub, stream, gate, close, stage, skipped);
-        else finalize_solve(d_ctl.p + which, pub, skipped);
+    if (which == 1) next.pre_init_valid = false;
+    if (SolveCtl* const pub = sw.no_publish ? nullptr : h_pub + which) { pub->done = 0u; pub->iters = 0u; pub->err = 0.0f; __atomic_store_n(&pub->seq, 0u, __ATOMIC_RELEASE); }
+}
+// Every convergence test publishes its outcome to host-mapped memory (k_finalize_error; in a decomposed run k_decide,
+// behind the all-reduce), and the host waits for the test count it enqueued — it then decides (and enqueues what
+// follows) while the batch's last apply pass is still running.
+// Two launches a solve does not need (round 6; a kernel that returns at once still costs a launch of 2 200 workgroups, ~5 us, and
+// a one-block test ~4.6 us plus its gaps — 23 us of a 0.61 ms free-fall step):
+//  * the tests of iterations i < min_iter cannot end the solve (`err <= tol && i >= min`): they are not launched — the next test
+//    that is counts them (`skipped`: iters and seq advance as if they had failed).  In a decomposed run that is an all-reduce less.
+//  * the apply behind the LAST test of a batch runs only if that test fails, which the batch is sized not to expect: it is
+//    enqueued by whoever continues the solve (`owes_apply`), and never when the solve has converged.  Not in decomposed runs (a
+//    ghost refresh rides behind every apply) and not where the test rides in the apply pass itself (spec_apply): `lazy_apply`.
+struct World::SolveTest {
+    World& w; const SolveSpec& s; uint32_t skipped = 0u;
+    SolveCtl* const pub = w.sw.no_publish ? nullptr : w.h_pub + s.which;
+    const bool multi = w.comm && w.comm->size() > 1, lazy_apply = !multi && !s.spec_apply;
+    void operator()(int it, bool last_of_batch, const uint32_t* gate, uint32_t* close, uint32_t close_stage) {
+        if (it < s.min_iter && it + 1 < s.max_iter && !last_of_batch) { ++skipped; return; }
+        SolveCtl* const ctl = w.d_ctl.p + s.which;
+        if (!multi) launch_finalize_error(w.partials.p, w.pass.nlaunch, w.num_models(), w.model_counts.p, ctl, pub, w.stream, gate, close, close_stage, skipped);
+        else w.finalize_solve(ctl, pub, skipped);
         skipped = 0u;
+    }
+};
+// The apply pass of iteration `it` on the main stream and, in a decomposed run, the ghost refresh of what it wrote.
+template <typename Apply>
+void World::apply_and_refresh(const StepCtx& c, const SolveSpec& s, int it, Apply& apply) {
+    apply(c, it, stream);
+    if (comm && s.ghosts) refresh_f4(s.ghosts->p);
+}
+// First batch: what the previous step's solve needed (iters applies + the converged evaluate) — consecutive steps
+// need about the same, so the usual cost is one read-back per solve; a batch that overshoots only enqueues kernels
+// that return at once, one that falls short continues in doubling batches.
+static int first_batch(uint32_t last_iters, int max_iter) { return std::max(2, std::min<int>((int)last_iters + 1, max_iter)); }
+// Chained (device_types.h StepCtx::gate): ONE batch and no wait.  The batch is what the previous step needed plus, while the
+// count is rising (the impact: 2, 4, 14, 18, 30 ... iterations in consecutive steps), what it rose by last time — a surplus
+// iteration costs three kernels that return at once, a batch that falls short costs the chain (every kernel behind this
+// solve returns at once and the host comes back through solve_continued).  Its LAST test closes the chain when it
+// fails, unless the batch runs to max_iter: then the solve is over whatever that test says.
+// The outcome is pending: World::adopt_chain_outcome reads it from the end-of-step publication.
+template <typename Eval, typename Apply>
+void World::solve_chained(StepCtx c, const SolveSpec& s, ChainLink link, Eval&& eval, Apply&& apply) {
+    const int which = s.which;
+    begin_solve(s, link == ChainLink::Opens);
+    c.ctl = d_ctl.p + which;
+    SolveTest test{*this, s};
+    const int rise = (int)last_iters[which] > (int)prev_iters[which] ? std::min((int)last_iters[which] - (int)prev_iters[which], 8) : 0;
+    const int nbatch = std::min(first_batch(last_iters[which], s.max_iter) + rise, s.max_iter);
+    // (Readback::chain_stage: 1 = the divergence, 2 = the pressure solve; its own last test may shut the gate: the apply behind that test still runs)
+    const uint32_t stage = c.gate_stage = (uint32_t)which + 1u;
+    for (int k = 0; k < nbatch; ++k) {
+        eval(c, k);
+        const bool closes = k == nbatch - 1 && nbatch < s.max_iter;
+        test(k, k == nbatch - 1, c.gate, closes ? &d_rb.p->chain_ok : nullptr, stage);
+        if (closes && test.lazy_apply) pass.solve[which].owes_apply = true;  // (only a continuation needs it)
+        else apply_and_refresh(c, s, k, apply);
+    }
+    pass.solve[which].enqueued = nbatch;
+}
+// Growing batches from iteration `from` on, one host wait per batch: a waited solve (from 0, behind begin_solve) or the continuation
+// of a chained batch that fell short (from where it ended, behind the apply it owed).  One of three per-iteration bodies, chosen once:
+template <typename Eval, typename Apply>
+World::SolveResult World::solve_batches(StepCtx c, const SolveSpec& s, int from, Eval& eval, Apply& apply) {
+    const int which = s.which, max_iter = s.max_iter;
+    c.ctl = d_ctl.p + which;
+    SolveTest test{*this, s};
+    SolveCtl* const pub = test.pub;
+    if (from > 0 && pass.solve[which].owes_apply) { apply_and_refresh(c, s, from - 1, apply); pass.solve[which].owes_apply = false; }
+    // plain: evaluate, test, apply — returns whether the apply was left to the continuation (the batch's last one: lazy applies)
+    auto plain = [&](int it, bool last_of_batch) {
+        eval(c, it); test(it, last_of_batch, nullptr, nullptr, 0u);
+        const bool owes = test.lazy_apply && last_of_batch && it + 1 < max_iter;
+        if (!owes) apply_and_refresh(c, s, it, apply);
+        return owes;
     };
-    if (from > 0 && pass.solve_owes_apply[which]) { apply(c, from - 1); pass.solve_owes_apply[which] = false; }  // (the apply the batch before left to its successor)
-    if (chain_stage) {
-        // Chained (device_types.h StepCtx::gate): ONE batch and no wait.  The batch is what the previous step needed plus, while the
-        // count is rising (the impact: 2, 4, 14, 18, 30 ... iterations in consecutive steps), what it rose by last time — a surplus
-        // iteration costs three kernels that return at once, a batch that falls short costs the chain (every kernel behind this
-        // solve returns at once and the host comes back here with `from` = this batch).  Its LAST test closes the chain when it
-        // fails, unless the batch runs to max_iter: then the solve is over whatever that test says.
-        const int rise = (int)last_iters[which] > (int)prev_iters[which] ? std::min((int)last_iters[which] - (int)prev_iters[which], 8) : 0;
-        const int nbatch = std::min(batch + rise, max_iter);
-        c.gate_stage = (uint32_t)chain_stage;  // (its own last test may shut the gate: the apply behind that test still runs)
-        for (int k = 0; k < nbatch; ++k) {
-            eval(c, k);
-            const bool closes = k == nbatch - 1 && nbatch < max_iter;
-            test(k, k == nbatch - 1, c.gate, closes ? &d_rb.p->chain_ok : nullptr, (uint32_t)chain_stage);
-            if (closes && lazy_apply) pass.solve_owes_apply[which] = true;  // (only a continuation needs it)
-            else apply(c, k);
-        }
-        pass.chain_batch[which] = nbatch;
-        return SolveResult{0u, 0.0f};  // (pending: World::adopt_chain_outcome reads it from the end-of-step publication)
-    }
-    if (from > 0) batch = (from <= 2) ? 4 : 8;
-    while (i < max_iter) {
-        const int nbatch = std::min(batch, max_iter - i);
-        bool owes = false;
-        for (int k = 0; k < nbatch; ++k) {
-            if (spec_apply && multi) {
-                // A decomposed solve with speculative applies (round 6): the all-reduced test and the apply pass do not wait for
-                // each other.  Main stream: error sums -> all-reduce -> k_decide_ring (the record of iteration it + 1).  Second
-                // stream: the apply pass, into the other w buffer, reading the record of iteration `it` only.  Then the ghost
-                // refresh of what the apply wrote, behind both — one communicator, one operation at a time.  A converged test leaves
-                // the apply and its refresh unused (w stays where it was), exactly as in the single domain (dfsph.hip spec_decide).
-                const int it = i + k;
-                c.spec_k = it; c.spec_external = 1u; c.spec_pub = nullptr;
-                eval(c, it);
-                SALVA_HIP_CHECK(hipEventRecord(ev_spec_eval, stream));
-                SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_spec_eval, 0));
-                pass.spec_dist_stream = stream2;
-                apply(c, it);  // (the kernel only: World::dfsph_solve's lambda leaves the refresh to the lines below)
-                pass.spec_dist_stream = nullptr;
-                SALVA_HIP_CHECK(hipEventRecord(ev_spec_apply, stream2));
-                const uint32_t nm = (uint32_t)std::max<size_t>(fluids.size(), 1);
-                const size_t tm = dist_time_begin(1);
-                launch_sum_partials(partials.p, pass.nlaunch, nm, spec_ring.p + (it & 1), d_sums.p, stream);
-                comm->allreduce_sum_f32(d_sums.p, (int)nm, stream);
-                launch_decide_ring(d_sums.p, nm, model_counts.p, spec_ring.p, it, pub, stream);
-                dist_time_end(tm);
-                SALVA_HIP_CHECK(hipStreamWaitEvent(stream, ev_spec_apply, 0));
-                refresh_f4((it & 1) ? w.p : w2.p);  // what the apply of iteration `it` wrote: the buffer of parity it + 1
-                continue;
+    // speculative applies in a single domain: the test rides in the apply pass (dfsph.hip spec_decide)
+    auto spec = [&](int it, bool) { c.spec_k = it; c.spec_pub = pub; eval(c, it); apply_and_refresh(c, s, it, apply); return false; };
+    // A decomposed solve with speculative applies (round 6): the all-reduced test and the apply pass do not wait for
+    // each other.  Main stream: error sums -> all-reduce -> k_decide_ring (the record of iteration it + 1).  Second
+    // stream: the apply pass, into the other w buffer, reading the record of iteration `it` only.  Then the ghost
+    // refresh of what the apply wrote, behind both — one communicator, one operation at a time.  A converged test leaves
+    // the apply and its refresh unused (w stays where it was), exactly as in the single domain (dfsph.hip spec_decide).
+    auto spec_dist = [&](int it, bool) {
+        c.spec_k = it; c.spec_external = 1u; c.spec_pub = nullptr; eval(c, it);
+        SALVA_HIP_CHECK(hipEventRecord(ev_spec_eval, stream));
+        SALVA_HIP_CHECK(hipStreamWaitEvent(stream2, ev_spec_eval, 0));
+        apply(c, it, stream2);
+        SALVA_HIP_CHECK(hipEventRecord(ev_spec_apply, stream2));
+        finalize_solve_ring(it, pub);
+        SALVA_HIP_CHECK(hipStreamWaitEvent(stream, ev_spec_apply, 0));
+        refresh_f4((it & 1) ? s.ghosts->p : w2.p);  // what the apply of iteration `it` wrote: the buffer of parity it + 1
+        return false;
+    };
+    auto batches = [&](auto&& iterate) {
+        int i = from, batch = from > 0 ? (from <= 2 ? 4 : 8) : first_batch(last_iters[which], max_iter);
+        while (i < max_iter) {
+            const int nbatch = std::min(batch, max_iter - i);
+            bool owes = false;
+            for (int k = 0; k < nbatch; ++k) owes = iterate(i + k, k == nbatch - 1);
+            if (pub) {
+                const uint32_t expect = (uint32_t)(i + nbatch);
+                spin_until([&] { return __atomic_load_n(&pub->seq, __ATOMIC_ACQUIRE) >= expect; },
+                           "internal error: a solver batch finished without publishing its control block");
+                h_ctl[which].done = pub->done; h_ctl[which].iters = pub->iters; h_ctl[which].err = pub->err;
+            } else {
+                // (no publication: read the newest record back — after i + nbatch iterations that is spec_ring[(i + nbatch) & 1])
+                const SolveCtl* src = s.spec_apply ? spec_ring.p + ((i + nbatch) & 1) : d_ctl.p + which;
+                SALVA_HIP_CHECK(hipMemcpyAsync(&h_ctl[which], src, sizeof(SolveCtl), hipMemcpyDeviceToHost, stream));
+                wait_stream();
             }
-            if (spec_apply) { c.spec_k = i + k; c.spec_pub = pub; }
-            eval(c, i + k);
-            if (!spec_apply) test(i + k, k == nbatch - 1, nullptr, nullptr, 0u);
-            if (lazy_apply && k == nbatch - 1 && i + nbatch < max_iter) owes = true;
-            else apply(c, i + k);
+            i += nbatch;
+            if (h_ctl[which].done) break;
+            if (owes) apply_and_refresh(c, s, i - 1, apply);  // the batch's last test failed: the apply it counted
+            batch = (i <= 2) ? 4 : 8;
         }
-        if (pub) {
-            const uint32_t expect = (uint32_t)(i + nbatch);
-            spin_until([&] { return __atomic_load_n(&pub->seq, __ATOMIC_ACQUIRE) >= expect; },
-                       "internal error: a solver batch finished without publishing its control block");
-            h_ctl[which].done = pub->done; h_ctl[which].iters = pub->iters; h_ctl[which].err = pub->err;
-        } else {
-            // (no publication: read the newest record back — after i + nbatch iterations that is spec_ring[(i + nbatch) & 1])
-            const SolveCtl* src = spec_apply ? spec_ring.p + ((i + nbatch) & 1) : d_ctl.p + which;
-            SALVA_HIP_CHECK(hipMemcpyAsync(&h_ctl[which], src, sizeof(SolveCtl), hipMemcpyDeviceToHost, stream));
-            wait_stream();
-        }
-        i += nbatch;
-        if (h_ctl[which].done) break;
-        if (owes) apply(c, i - 1);  // the batch's last test failed: the apply it counted
-        batch = (i <= 2) ? 4 : 8;
-    }
+    };
+    if (!s.spec_apply) batches(plain);
+    else if (test.multi) batches(spec_dist);
+    else batches(spec);
     prev_iters[which] = last_iters[which];
     last_iters[which] = h_ctl[which].iters;
     return SolveResult{h_ctl[which].iters, h_ctl[which].err};
@@ -349,16 +367,11 @@ void World::run_forces(const StepCtx& c) {
                     launch_visc_va(c, dt_prev, visc_va.p, stream);
                     if (comm) refresh_f4(visc_va.p);
                     launch_visc_strain(c, lds, f, 0, coef, visc_va.p, visc_beta.p, visc_target.p, visc_u0.p, visc_u1.p, stream);
-                    const SolveResult rv = run_solve(
-                        c, 2, max_err, min_it, max_it, 0u,
-                        [&](const StepCtx& cc, int) {
-                            launch_visc_strain(cc, lds, f, 1, coef, visc_va.p, visc_beta.p, visc_target.p, visc_u0.p, visc_u1.p, stream);
-                        },
-                        [&](const StepCtx& cc, int) {
-                            // (u of the inner ghost plane was computed here from refreshed v + a dt: no exchange needed)
-                            launch_visc_accel(cc, lds, f, inv_dt_prev, dt_prev, visc_u0.p, visc_u1.p, visc_va.p, stream);
-                            if (comm) refresh_f4(visc_va.p);
-                        });
+                    // (u of the inner ghost plane was computed here from refreshed v + a dt: only visc_va travels, behind every apply)
+                    const SolveSpec visc{2, max_err, min_it, max_it, 0u, &visc_va, false};
+                    const SolveResult rv = solve_waited(c, visc,
+                        [&](const StepCtx& cc, int) { launch_visc_strain(cc, lds, f, 1, coef, visc_va.p, visc_beta.p, visc_target.p, visc_u0.p, visc_u1.p, stream); },
+                        [&](const StepCtx& cc, int, hipStream_t s) { launch_visc_accel(cc, lds, f, inv_dt_prev, dt_prev, visc_u0.p, visc_u1.p, visc_va.p, s); });
                     fluids[f].force_iters.resize(fluids[f].forces.size(), 0u);
                     fluids[f].force_errs.resize(fluids[f].forces.size(), 0.0f);
                     fluids[f].force_iters[&d - fluids[f].forces.data()] = rv.iters;
@@ -585,7 +598,7 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     // then computed in vain (~30 us once per solve), so: only when the previous step's solve ran 16 iterations or more; not with boundary reaction forces (an
     // apply that is thrown away must not have added to them) and not in decomposed runs (the test sits behind an all-reduce).
     // Decomposed runs (round 6): the same double buffer lets the apply run BESIDE the all-reduced test instead of behind it
-    // (World::run_solve); there the wasted apply is cheaper than the all-reduces it hides from four iterations on.
+    // (World::solve_batches); there the wasted apply is cheaper than the all-reduces it hides from four iterations on.
     const bool multi_rank = comm && comm->size() > 1;
     const bool spec_apply = !resume && !sw.spec_apply_off && !any_wants_forces &&
                             (multi_rank ? (!sw.spec_dist_off && last_iters[0] >= 4u) : (!comm && last_iters[0] >= 16u));
@@ -603,25 +616,20 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
         if (it == 0 && pass.fused_first_divergence) return;  // (k_density_alpha_div_p3 wrote kappa and the error partials already)
         evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_divergence(cs, lds, s); });
     };
-    auto div_apply = [&](const StepCtx& cc, int) {
-        // decomposed runs: kappa of the inner ghost plane was computed here from refreshed w — the applies of the
-        // owned particles read nothing else, so only w travels, once per iteration
-        launch_divergence_apply(cc, lds, inv_dt_lag, pass.spec_dist_stream ? pass.spec_dist_stream : stream);
-        if (comm && !pass.spec_dist_stream) refresh_f4(w.p);  // (a speculative decomposed apply: run_solve refreshes the buffer it wrote)
-    };
+    // decomposed runs: kappa of the inner ghost plane was computed here from refreshed w — the applies of the
+    // owned particles read nothing else, so only w travels, once per iteration (SolveSpec::ghosts)
+    auto div_apply = [&](const StepCtx& cc, int, hipStream_t s) { launch_divergence_apply(cc, lds, inv_dt_lag, s); };
     const float div_tol = prm.max_divergence_error * inv_dt_prev * 0.01f;
-    SolveResult rd{0u, 0.0f};
+    const SolveSpec div{0, div_tol, prm.min_divergence_iter, prm.max_divergence_iter, 0u, &w, spec_apply};
+    const SolveSpec press{1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 0u, &w, false};
+    SolveResult rd{0u, 0.0f}, rp{0u, 0.0f};  // (what a chained solve reports until World::adopt_chain_outcome has read its outcome)
     // (the pressure solve's control block is initialised by the divergence solve's launch — unless that solve has to open the chain)
-    if (resume == 0 && (!chain || chain_div)) {
-        pass.pre_init1 = SolveCtl{0u, 0u, 0.0f, 0u, prm.max_density_error, (uint32_t)std::max(prm.min_pressure_iter, 0), 0u, 0u};
-        pass.pre_init1_valid = true;
-    }
+    if (resume == 0 && (!chain || chain_div)) { pass.solve[1].pre_init = press.init(); pass.solve[1].pre_init_valid = true; }
     if (resume <= 1) {
-        rd = run_solve(c, 0, div_tol, prm.min_divergence_iter, prm.max_divergence_iter, 0u, div_eval, div_apply, spec_apply, chain_div ? 1 : 0,
-                       resume == 1 ? pass.chain_batch[0] : 0, chain_div);
-        if (spec_apply && multi_rank) {
-            if (sw.dist_trace) fprintf(stderr, "salva_hip dist[%d]: divergence solve with applies beside the all-reduce, %u iterations\n", comm->rank(), rd.iters);
-        }
+        if (chain_div) solve_chained(c, div, ChainLink::Opens, div_eval, div_apply);
+        else if (resume == 1) rd = solve_continued(c, div, div_eval, div_apply);
+        else rd = solve_waited(c, div, div_eval, div_apply);
+        if (spec_apply && multi_rank && sw.dist_trace) fprintf(stderr, "salva_hip dist[%d]: divergence solve with applies beside the all-reduce, %u iterations\n", comm->rank(), rd.iters);
         if (spec_apply && (rd.iters & 1u)) {  // an odd number of committed applies: w lives in the second buffer
             std::swap(w.p, w2.p); std::swap(w.cap, w2.cap);
             c.w = w.p; c.w2 = w2.p; cg.w = w.p; cg.w2 = w2.p;
@@ -640,13 +648,11 @@ void World::dfsph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
         if (comm) refresh_f4(w.p);
     }
     // pressure_solve (:432-464)
-    const SolveResult rp = run_solve(
-        cg, 1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 0u,
-        [&](const StepCtx& cc, int it) { evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_pred_density(cs, lds, dt, s); }); },
-        [&](const StepCtx& cc, int) {
-            launch_pressure_apply(cc, lds, inv_dt, stream);
-            if (comm) refresh_f4(w.p);
-        }, false, chain ? 2 : 0, resume == 2 ? pass.chain_batch[1] : 0, chain && !chain_div);
+    auto press_eval = [&](const StepCtx& cc, int it) { evaluate_split(cc, it, [&](const StepCtx& cs, hipStream_t s) { launch_pred_density(cs, lds, dt, s); }); };
+    auto press_apply = [&](const StepCtx& cc, int, hipStream_t s) { launch_pressure_apply(cc, lds, inv_dt, s); };
+    if (chain) solve_chained(cg, press, chain_div ? ChainLink::Follows : ChainLink::Opens, press_eval, press_apply);
+    else if (resume == 2) rp = solve_continued(cg, press, press_eval, press_apply);
+    else rp = solve_waited(cg, press, press_eval, press_apply);
     st.n_pressure_iters = (int32_t)rp.iters;
     st.density_error = rp.err;
     launch_update_positions(cg, dt, bbox_partials.p, nullptr, stream);  // (the per-block boxes are folded by the end-of-step publication)
@@ -675,8 +681,8 @@ void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
     float* const pb = kappa2.p;
     const float omega = 0.5f;  // :53
     // pressure_solve (:422-456): iteration j reads p_j and writes p_{j+1}; the two buffers alternate (the reference swaps)
-    const SolveResult rp = run_solve(
-        c, 1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 1u,
+    const SolveSpec press{1, prm.max_density_error, prm.min_pressure_iter, prm.max_pressure_iter, 1u, nullptr, false};
+    const SolveResult rp = solve_waited(c, press,
         [&](const StepCtx& cc, int j) {
             const float* pr = (j & 1) ? pb : pa;
             float* pw = (j & 1) ? pa : pb;
@@ -684,7 +690,7 @@ void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
             launch_iisph_next_pressure(cc, lds, dt, omega, pr, pw, stream);
             if (comm) refresh_f32(pw);
         },
-        [&](const StepCtx&, int) {});
+        [&](const StepCtx&, int, hipStream_t) {});  // (the evaluate wrote p_{j+1} and refreshed it: nothing to apply)
     st.n_pressure_iters = (int32_t)rp.iters;
     st.density_error = rp.err;
     const float* p = (rp.iters & 1u) ? pb : pa;
@@ -1004,7 +1010,7 @@ void World::ensure_slot_tables(uint32_t nslots_bound) {
     const uint32_t nslots = std::max<uint32_t>(nslots_bound, 1u);
     slot_info.ensure(nslots, stream, false, 1.5f);
     d_maxhalo.ensure(4);
-    partials.ensure((size_t)nslots * std::max<size_t>(fluids.size(), 1), stream, false, 1.5f);
+    partials.ensure((size_t)nslots * num_models(), stream, false, 1.5f);
     tile_list_stats.ensure(tile_list_stats_bytes(nslots), stream, false, 1.5f);
     if (pass.two_mass) {  // (per slot; Tile::setup reads them in every tile kernel, k_nbr_tile writes them)
         tile_mass_bits.ensure(nslots, stream, false, 1.5f);
