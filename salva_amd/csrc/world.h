@@ -80,12 +80,12 @@ struct GridDims {          // tile-aligned dense grid (tile.h)
     size_t ncells() const { return ntiles() * TCELLS; }
 };
 
-// helpers the world*.hip files share (bits_for, dims_from_bbox and launch_unpack_xyz are defined in world.hip)
+// helpers the world*.hip files share (bits_for and dims_from_bbox are defined in world.hip)
 inline unsigned nblk(uint64_t n) { return div_up(n ? n : 1, BLOCK); }
-void launch_unpack_xyz(uint32_t n, const float4* src, float* dst, hipStream_t s);  // float4 rows -> packed xyz
 int bits_for(uint64_t ncells);  // key bits of a radix sort over `ncells` cells
 struct FoldRule { double budget, target; uint32_t min_period[3]; bool axis[3]; };  // fold when the box exceeds `budget` cells, then down to `target`; axis[a]: may fold
 void dims_from_bbox(const int32_t* bb, GridDims& g, const FoldRule* fold = nullptr);
+struct Piece { uint64_t src_off, len; bool from_old; };  // a run of rows of a spliced host-order array (World::splice_fluid_rows)
 
 class World {
   public:
@@ -188,8 +188,8 @@ class World {
     uint64_t get_owned(uint32_t cap, uint32_t* gids, float* pos, float* vel, uint32_t* models);
     uint64_t delete_owned(uint32_t n_ids, const uint32_t* gids);
     uint32_t owned_count() const { return comm ? n_owned : n; }
-    float time_pred_density(int reps);
     float time_kernel(int kernel, int reps);
+    float time_pred_density(int reps) { return time_kernel(0, reps); }
     void tile_tables(uint32_t slot, uint32_t* info16, uint32_t* halo_row, uint32_t cap_row, uint32_t* counts, uint32_t cap_counts, uint32_t* entries,
                      uint32_t cap_entries);  // salva_hip_get_tile_tables
 #ifdef SALVA_HIP_DIAG
@@ -214,7 +214,28 @@ class World {
                            uint32_t* indices);
     uint64_t fluid_offset(uint32_t slot) const;
     uint64_t boundary_offset(uint32_t slot) const;
+    struct SlotSpan { uint64_t n, off; };         // a slot's particles: how many, and the first one's row in the host-order arrays
+    SlotSpan fluid_span(uint32_t slot) const;     // ... of a slot that exists: "fluid slot out of range" otherwise
+    SlotSpan boundary_span(uint32_t slot) const;
+    // ---- the host-order arrays have one editor (world_objects.hip) ...
     void ensure_staging_current();
+    float default_particle_volume() const;
+    void splice_fluid_rows(const std::vector<Piece>& pieces, uint64_t new_total, const std::vector<Piece>* dv_pieces = nullptr);
+    void splice_boundary_rows(const std::vector<Piece>& pieces, uint64_t new_total);
+    void fill_fluid_defaults(uint64_t at, uint64_t count);
+    void order_invalidated(bool tables);  // what an edit of the fluids' rows ends (tables: the per-model tables too)
+    void boundaries_invalidated();
+    // ... and one pair of transfer helpers through scratch_f: host -> device (world_objects.hip), device -> host (world_io.hip).
+    // Each waits for the stream, except stage_floats, the half that the accumulating uploads share.
+    float* stage_floats(const float* host, size_t count);
+    void upload_xyz(const float* host, float4* dst, uint64_t count, bool keep_w);
+    void upload_w(const float* host, float4* dst, uint64_t count);
+    void download_xyz(const float4* src, uint64_t count, float* out);
+    void download_w(const float4* src, uint64_t count, float* out);
+    void download_f32(const float* src, uint64_t count, float* out);
+    template <typename Launch>  // what salva_hip_get_fluid_contacts and _get_local_contacts share (world_io.hip)
+    uint64_t export_contacts(uint64_t rows, const uint32_t* d_counts, bool with_moff, uint64_t* offsets, uint32_t* j_model, uint32_t* j,
+                             uint64_t capacity, Launch&& launch);
     void upload_tables();
     void build_boundary_grid();
     uint64_t append_particles(uint32_t slot, uint64_t n_add);
@@ -426,7 +447,7 @@ class World {
 
     const Switches sw = Switches::from_env();  // ---- 1. what the environment asked for when the world was made (switches.h)
     // ---- 3. What one step deliberately hands to the next (with `pre` and `lds` / `halo_stride` further down); PassSnapshot puts
-    // back what a discarded pass has overwritten of it.  Host edits invalidate it where they happen (world.hip).
+    // back what a discarded pass has overwritten of it.  Host edits invalidate it where they happen (world_objects.hip).
     uint32_t last_iters[NUM_SOLVES] = {1u, 1u, 1u};  // iterations of the previous step's divergence / pressure solve (batch sizing)
     uint32_t prev_iters[NUM_SOLVES] = {1u, 1u, 1u};  // ... and of the step before it (a rising count widens a chained batch)
     float mass_uniform = 0.0f;  // StepCtx::mass_uniform as the last exact pass found it (0: masses differ, or not known)

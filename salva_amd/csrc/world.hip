@@ -1,7 +1,8 @@
-// world.hip — host side of libsalva_hip: device memory, object edits, the per-model tables, up/download, timing probes.
-// The per-step launch sequence (World::step, World::substep and what they call) is world_step.hip, rigid-body coupling and
-// DynamicContactSampling are world_coupling.hip, the particle queries world_query.hip.
-// Host <-> device traffic happens only in set_* / get_*.
+// world.hip — host side of libsalva_hip: the LDS limit, the environment switches, construction, slot offsets, the per-model tables,
+// the step context, grid dimensions, the boundary grid, device_bytes, the tile-table export and the timing probes.
+// The per-step launch sequence (World::step, World::substep and what they call) is world_step.hip, the edits of the fluid and boundary
+// sets and of their host-order arrays world_objects.hip, the read-backs world_io.hip, rigid-body coupling and DynamicContactSampling
+// world_coupling.hip, the particle queries world_query.hip.
 #include "world.h"
 #include "bbox.h"
 
@@ -28,86 +29,10 @@ void raise_tile_lds_limit(const void* kernel, uint32_t bytes) {
     g = want;
 }
 
-// ------------------------------------------------------------------------------------------------ small helpers
-__global__ void k_pack_xyz(uint32_t n, const float* __restrict__ src, float4* __restrict__ dst, int keep_w, float wval) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    float4 d = dst[i];
-    d.x = src[3 * i]; d.y = src[3 * i + 1]; d.z = src[3 * i + 2];
-    if (!keep_w) d.w = wval;
-    dst[i] = d;
-}
-__global__ void k_pack_w(uint32_t n, const float* __restrict__ src, float4* __restrict__ dst) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) reinterpret_cast<float*>(&dst[i])[3] = src[i];
-}
-__global__ void k_fill_f4(uint32_t n, float4* __restrict__ dst, float4 v, int keep_w) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (keep_w) v.w = dst[i].w;
-    dst[i] = v;
-}
-__global__ void k_fill_w(uint32_t n, float4* __restrict__ dst, float v) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) reinterpret_cast<float*>(&dst[i])[3] = v;
-}
-__global__ void k_fill_u32(uint32_t n, uint32_t* __restrict__ dst, uint32_t v) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) dst[i] = v;
-}
-__global__ void k_unpack_xyz(uint32_t n, const float4* __restrict__ src, float* __restrict__ dst) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float4 s = src[i];
-    dst[3 * i] = s.x; dst[3 * i + 1] = s.y; dst[3 * i + 2] = s.z;
-}
-void launch_unpack_xyz(uint32_t n, const float4* src, float* dst, hipStream_t s) { k_unpack_xyz<<<nblk(n), BLOCK, 0, s>>>(n, src, dst); }
-__global__ void k_unpack_w(uint32_t n, const float4* __restrict__ src, float* __restrict__ dst) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) dst[i] = src[i].w;
-}
-__global__ void k_set_bmodel(uint32_t n, float4* __restrict__ bvel, uint32_t m) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) reinterpret_cast<float*>(&bvel[i])[3] = __uint_as_float(m);
-}
-
-struct Piece { uint64_t src_off, len; bool from_old; };
-
-template <typename T>
-static void rebuild(DevBuf<T>& buf, const std::vector<Piece>& pieces, uint64_t new_total, hipStream_t s) {
-    DevBuf<T> nb;
-    nb.ensure(new_total ? new_total : 1);
-    uint64_t off = 0;
-    for (const Piece& p : pieces) {
-        if (p.from_old && p.len)
-            SALVA_HIP_CHECK(hipMemcpyAsync(nb.p + off, buf.p + p.src_off, p.len * sizeof(T), hipMemcpyDeviceToDevice, s));
-        off += p.len;
-    }
-    SALVA_HIP_CHECK(hipStreamSynchronize(s));
-    std::swap(buf.p, nb.p);
-    std::swap(buf.cap, nb.cap);
-}
-
 int bits_for(uint64_t ncells) {
     int b = 1;
     while (b < 32 && ((uint64_t)1 << b) < ncells) ++b;
     return b;
-}
-
-// the model id of every staged particle: a slot's particles move when a slot before it changes its length
-void World::stamp_fluid_models() {
-    uint64_t o = 0;
-    for (uint32_t s = 0; s < fluids.size(); ++s) {
-        if (fluids[s].n) k_fill_u32<<<nblk(fluids[s].n), BLOCK, 0, stream>>>((uint32_t)fluids[s].n, st_model.p + o, s);
-        o += fluids[s].n;
-    }
-}
-void World::stamp_boundary_models() {  // (boundary model ids ride in bst_vel.w)
-    uint64_t o = 0;
-    for (uint32_t s = 0; s < bounds.size(); ++s) {
-        if (bounds[s].n) k_set_bmodel<<<nblk(bounds[s].n), BLOCK, 0, stream>>>((uint32_t)bounds[s].n, bst_vel.p + o, s);
-        o += bounds[s].n;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ switches
@@ -246,6 +171,15 @@ uint64_t World::boundary_offset(uint32_t slot) const {
     for (uint32_t s = 0; s < slot; ++s) o += bounds[s].n;
     return o;
 }
+// a slot that exists: its particle count and its first row in the host-order arrays
+World::SlotSpan World::fluid_span(uint32_t slot) const {
+    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
+    return {fluids[slot].n, fluid_offset(slot)};
+}
+World::SlotSpan World::boundary_span(uint32_t slot) const {
+    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
+    return {bounds[slot].n, boundary_offset(slot)};
+}
 
 FluidArrays World::arrays(int which) {
     FluidArrays a;
@@ -255,421 +189,6 @@ FluidArrays World::arrays(int which) {
 }
 
 void World::ensure_cub_temp(size_t bytes) { cub_temp.ensure(bytes ? bytes : 1, stream, false, 1.25f); }
-
-// Bring the canonical (host-order) staging arrays up to date with the sorted working set.
-void World::ensure_staging_current() {
-    if (staging_current) return;
-    if (comm && dist_started)
-        throw HipError(SALVA_HIP_E_INVALID, "host-order fluid arrays are not maintained in a multi-GPU run: use salva_hip_get_owned");
-    if (sorted_valid && n) {
-        launch_sorted_to_stage(n, arrays(cur), st_pos.p, st_vel.p, st_dv.p, stream);
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    staging_current = true;
-}
-
-// ------------------------------------------------------------------------------------------------ fluids
-void World::set_fluid(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, const float* vol,
-                      const float* acc_h, const float* dvs, float density0, uint32_t memberships, uint32_t filter,
-                      uint32_t dirty) {
-    use_device();
-    if (slot > fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range (slots are dense)");
-    if (slot >= (uint32_t)MAX_MODELS) throw HipError(SALVA_HIP_E_CAPACITY, "at most 32 fluids per world");
-    const bool is_new = slot == fluids.size();
-    if ((uint64_t)n - (is_new ? 0 : fluids[slot].n) + nn >= 0xfffffff0ull)
-        throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 fluid particles on one device");
-    ensure_staging_current();
-    const uint64_t old_n = is_new ? 0 : fluids[slot].n;
-    const bool resized = is_new || old_n != nn;
-    if (resized) {
-        if (nn && !pos) throw HipError(SALVA_HIP_E_INVALID, "positions are required when a fluid is created or resized");
-        dirty = SALVA_HIP_DIRTY_ALL;
-    }
-    if (is_new) fluids.emplace_back();
-    const uint64_t off = fluid_offset(slot);
-    const uint64_t old_total = n;
-    const uint64_t new_total = old_total - old_n + nn;
-    if (resized) {
-        std::vector<Piece> pieces = {{0, off, true}, {0, nn, false}, {off + old_n, old_total - off - old_n, true}};
-        rebuild(st_pos, pieces, new_total, stream);
-        rebuild(st_vel, pieces, new_total, stream);
-        rebuild(st_dv, pieces, new_total, stream);
-        rebuild(st_acc, pieces, new_total, stream);
-        rebuild(st_model, pieces, new_total, stream);
-        n = (uint32_t)new_total;
-        if (nn) {
-            // defaults: zero velocity / velocity change / acceleration, Fluid::particle_volume (fluid.rs:110-120)
-            const float r = prm.particle_radius;
-            const float default_vol = r * r * r * 6.4f;  // 8 * 0.8
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_pos.p + off, make_float4(0, 0, 0, default_vol), 0);
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_vel.p + off, make_float4(0, 0, 0, 0), 0);
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_dv.p + off, make_float4(0, 0, 0, 0), 0);
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_acc.p + off, make_float4(0, 0, 0, 0), 0);
-        }
-        if (is_new && !dvs) {
-            auto it = sticky.find(slot);
-            if (it != sticky.end()) {  // buffer[slot] of a fluid removed since the last step: inherited (world.h `sticky`)
-                const uint64_t inherit = std::min<uint64_t>(it->second.len, nn);
-                if (inherit) SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + off, it->second.data->p, inherit * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-                if (it->second.len <= nn) sticky.erase(it);
-            }
-        }
-        // model ids of every slot at/after this one may have moved
-        fluids[slot].n = nn;
-        stamp_fluid_models();
-    }
-    FluidSlot& f = fluids[slot];
-    f.density0 = density0; f.memberships = memberships; f.filter = filter;
-    {   // the fluid's one volume, if it has one (FluidSlot::vol_uniform): a resize filled the default in, an upload may change it
-        const float r = prm.particle_radius;
-        if (resized) f.vol_uniform = r * r * r * 6.4f;
-        if (nn && (dirty & SALVA_HIP_DIRTY_VOLUMES) && vol) {
-            bool same = true;
-            for (uint64_t k = 1; k < nn && same; ++k) same = vol[k] == vol[0];
-            f.vol_uniform = same ? vol[0] : std::numeric_limits<float>::quiet_NaN();
-        }
-    }
-    auto upload3 = [&](const float* src, float4* dst, int keep_w) {
-        scratch_f.ensure(3 * nn, stream, false, 1.1f);
-        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, src, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-        k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, dst, keep_w, 0.0f);
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    };
-    if (nn) {
-        if ((dirty & SALVA_HIP_DIRTY_POSITIONS) && pos) upload3(pos, st_pos.p + off, 1);
-        if ((dirty & SALVA_HIP_DIRTY_VELOCITIES) && vel_h) upload3(vel_h, st_vel.p + off, 1);
-        if ((dirty & SALVA_HIP_DIRTY_VOLUMES) && vol) {
-            scratch_f.ensure(nn, stream, false, 1.1f);
-            SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, vol, nn * sizeof(float), hipMemcpyHostToDevice, stream));
-            k_pack_w<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, st_pos.p + off);
-            SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        }
-        if ((dirty & SALVA_HIP_DIRTY_ACCELERATIONS) && acc_h) {
-            // accelerations are zero between steps; the first user upload must not resurrect stale staging values
-            if (!acc_user) SALVA_HIP_CHECK(hipMemsetAsync(st_acc.p, 0, (size_t)n * sizeof(float4), stream));
-            upload3(acc_h, st_acc.p + off, 1);
-            acc_user = true;
-        }
-        if (dvs) upload3(dvs, st_dv.p + off, 1);
-    }
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    sorted_valid = false;
-    bbox_known = false;
-    tables_dirty = true;
-    have_last_ctx = false;
-}
-
-// Fluid::add_particles (fluid.rs:126-150): append to the fluid's arrays — default volume, zero acceleration, zero
-// velocity change (the solver's buffers grow with zeros, dfsph_solver.rs:526-549) — without re-uploading the rest.
-void World::add_particles(uint32_t slot, uint64_t n_add, const float* pos, const float* vel_h) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (comm && dist_started) { dist_add_particles(slot, n_add, pos, vel_h); return; }  // (collective, world_dist.hip)
-    if (n_add == 0) return;
-    if (!pos) throw HipError(SALVA_HIP_E_INVALID, "positions are required");
-    const uint64_t at = append_particles(slot, n_add);
-    scratch_f.ensure(3 * n_add, stream, false, 1.1f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
-    k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_pos.p + at, 1, 0.0f);
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    if (vel_h) {
-        SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, vel_h, 3 * n_add * sizeof(float), hipMemcpyHostToDevice, stream));
-        k_pack_xyz<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, scratch_f.p, st_vel.p + at, 1, 0.0f);
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
-// The growing half of add_particles: room for n_add particles behind the fluid's last one, filled with the defaults (zero position,
-// velocity and acceleration, default volume, the inherited velocity-change tail).  Returns the staging index of the first new
-// particle; the caller writes positions (and velocities) there — from the host (add_particles) or on the device
-// (add_particles_sampled, sample.hip).
-uint64_t World::append_particles(uint32_t slot, uint64_t n_add) {
-    if ((uint64_t)n + n_add >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 fluid particles on one device");
-    ensure_staging_current();
-    const uint64_t old_n = fluids[slot].n, off = fluid_offset(slot), at = off + old_n, old_total = n, new_total = old_total + n_add;
-    std::vector<Piece> pieces = {{0, at, true}, {0, n_add, false}, {at, old_total - at, true}};
-    rebuild(st_pos, pieces, new_total, stream);
-    rebuild(st_vel, pieces, new_total, stream);
-    rebuild(st_dv, pieces, new_total, stream);
-    rebuild(st_acc, pieces, new_total, stream);
-    rebuild(st_model, pieces, new_total, stream);
-    n = (uint32_t)new_total;
-    fluids[slot].n = old_n + n_add;
-    {   // (the new particles have the default volume: the fluid keeps ONE volume only if that is the one it had)
-        const float r = prm.particle_radius, default_vol = r * r * r * 6.4f;
-        FluidSlot& f = fluids[slot];
-        if (old_n == 0) f.vol_uniform = default_vol;
-        else if (!(f.vol_uniform == default_vol)) f.vol_uniform = std::numeric_limits<float>::quiet_NaN();
-    }
-    const float r = prm.particle_radius;
-    k_fill_f4<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, st_pos.p + at, make_float4(0, 0, 0, r * r * r * 6.4f), 0);
-    k_fill_f4<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, st_vel.p + at, make_float4(0, 0, 0, 0), 0);
-    k_fill_f4<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, st_dv.p + at, make_float4(0, 0, 0, 0), 0);
-    k_fill_f4<<<nblk(n_add), BLOCK, 0, stream>>>((uint32_t)n_add, st_acc.p + at, make_float4(0, 0, 0, 0), 0);
-    {
-        auto it = sticky.find(slot);
-        if (it != sticky.end() && it->second.len > old_n) {  // `velocity_changes[slot].resize(n)` exposes the inherited tail
-            const uint64_t take = std::min<uint64_t>(it->second.len - old_n, n_add);
-            SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + at, it->second.data->p + old_n, take * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-        }
-    }
-    stamp_fluid_models();
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    sorted_valid = false; bbox_known = false; tables_dirty = true; have_last_ctx = false;
-    return at;
-}
-
-// Fluid::apply_particles_removal (fluid.rs:88-98) together with the compaction of the solver's velocity_changes
-// (dfsph_solver.rs:550-560 / iisph_solver.rs:505-537): a stable compaction (`filter_from_mask`, helper.rs:4-12) of every
-// per-particle array of the fluid, on the device.  `mask[i] != 0` deletes particle i.  Returns the remaining count.
-uint64_t World::delete_particles(uint32_t slot, const uint8_t* mask) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "host indices do not exist in a running multi-GPU world: delete by global id (salva_hip_delete_owned)");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0 || !mask) return nn;
-    ensure_staging_current();
-    // keep flags over the whole staging range (other fluids are kept)
-    std::vector<uint8_t> keep((size_t)n, 1);
-    uint64_t kept = 0;
-    for (uint64_t k = 0; k < nn; ++k) { keep[off + k] = mask[k] ? 0 : 1; kept += keep[off + k]; }
-    if (kept == nn) return nn;
-    DevBuf<uint8_t> d_keep;
-    DevBuf<uint32_t> d_num;
-    d_keep.ensure(n); d_num.ensure(1);
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_keep.p, keep.data(), (size_t)n, hipMemcpyHostToDevice, stream));
-    const uint64_t new_total = (uint64_t)n - (nn - kept);
-    auto compact = [&](DevBuf<float4>& buf) {
-        DevBuf<float4> out;
-        out.ensure(std::max<uint64_t>(new_total, 1));
-        const size_t tb = select_flagged_temp_bytes(n);
-        ensure_cub_temp(tb);
-        select_flagged_f4(cub_temp.p, tb, buf.p, d_keep.p, out.p, d_num.p, n, stream);
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        std::swap(buf.p, out.p);
-        std::swap(buf.cap, out.cap);
-    };
-    compact(st_pos); compact(st_vel); compact(st_dv); compact(st_acc);
-    {
-        // an inherited solver buffer (world.h `sticky`) is filtered with the same mask by the reference — after its resize, so
-        // the entries beyond the fluid's particles (handed to particles added before the next step) just move down
-        auto it = sticky.find(slot);
-        if (it != sticky.end() && it->second.len) {
-            const uint64_t L = it->second.len, head = std::min<uint64_t>(L, nn);
-            std::vector<uint8_t> k2((size_t)L, 1);
-            uint64_t kept2 = 0;
-            for (uint64_t k = 0; k < L; ++k) { if (k < head) k2[k] = mask[k] ? 0 : 1; kept2 += k2[k]; }
-            DevBuf<uint8_t> d_k2;
-            d_k2.ensure(L);
-            SALVA_HIP_CHECK(hipMemcpyAsync(d_k2.p, k2.data(), (size_t)L, hipMemcpyHostToDevice, stream));
-            auto out = std::make_shared<DevBuf<float4>>();
-            out->ensure(std::max<uint64_t>(kept2, 1));
-            const size_t tb = select_flagged_temp_bytes((uint32_t)L);
-            ensure_cub_temp(tb);
-            select_flagged_f4(cub_temp.p, tb, it->second.data->p, d_k2.p, out->p, d_num.p, (uint32_t)L, stream);
-            SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-            it->second.data = out;
-            it->second.len = kept2;
-        }
-    }
-    n = (uint32_t)new_total;
-    fluids[slot].n = kept;
-    stamp_fluid_models();
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    sorted_valid = false; bbox_known = false; tables_dirty = true; have_last_ctx = false;
-    return kept;
-}
-
-void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_DEVICE)
-            throw HipError(SALVA_HIP_E_INVALID, "unknown non-pressure force kind (only built-ins run on the device)");
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind == SALVA_HIP_FORCE_DEVICE) {
-            if (comm)  // ghost rows and the local view's ownership rules are not part of SalvaHipDeviceView
-                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE is not available in a decomposed world (salva_hip_set_domain)");
-            if (!(f[k].p[0] >= 0.0f && f[k].p[0] <= 7.0f && f[k].p[0] == (float)(uint32_t)f[k].p[0]))
-                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE: p[0] must be a sum of SALVA_HIP_DEVICE_NEEDS_* bits (0 ... 7)");
-        }
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009) {
-            if (comm)  // the rest lists cross slabs and have no ghost protocol
-                throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity is not available in a decomposed world (salva_hip_set_domain)");
-            for (int q = 3; q < 5; ++q)
-                if (!(f[k].p[q] == 0.0f || f[k].p[q] == 1.0f || f[k].p[q] == 2.0f || f[k].p[q] == 3.0f))
-                    throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity: p[3] / p[4] must be a SALVA_HIP_KERNEL_* kind");
-        }
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind == SALVA_HIP_FORCE_DFSPH_VISCOSITY && !(f[k].p[0] >= 0.0f && f[k].p[0] <= 1.0f))
-            throw HipError(SALVA_HIP_E_INVALID, "The viscosity coefficient must be between 0.0 and 1.0.");  // dfsph_viscosity.rs:104-108
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind == SALVA_HIP_FORCE_WCSPH_TENSION && f[k].p[1] != 0.0f)
-            // wcsph_surface_tension.rs:66-83 walks the fluid-fluid contacts while indexing the boundaries: it panics
-            throw HipError(SALVA_HIP_E_INVALID, "WCSPHSurfaceTension: a non-zero boundary coefficient panics in the reference (index out of bounds)");
-    // an elastic entry keeps its state when entry k is what it was (same kind, bit-identical p[]): the Python mirror re-uploads the
-    // whole list when any coefficient changes, and a block must not lose its rest shape because another force was appended
-    FluidSlot& fs = fluids[slot];
-    std::vector<std::shared_ptr<ElasticState>> el(nf);
-    for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009 && k < fs.forces.size() && k < fs.elastic.size() && fs.elastic[k] &&
-            fs.forces[k].kind == f[k].kind && memcmp(fs.forces[k].p, f[k].p, sizeof(f[k].p)) == 0)
-            el[k] = fs.elastic[k];
-    fs.forces.assign(f, f + nf);
-    fs.elastic = std::move(el);
-}
-
-void World::remove_fluid(uint32_t slot) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    ensure_staging_current();
-    // ContiguousArena::remove is a swap-remove (contiguous_arena.rs): the last fluid takes the freed slot.
-    const uint32_t last = (uint32_t)fluids.size() - 1;
-    const uint64_t off = fluid_offset(slot), len = fluids[slot].n;
-    const uint64_t loff = fluid_offset(last), llen = fluids[last].n;
-    std::vector<Piece> pieces;
-    pieces.push_back({0, off, true});
-    if (slot != last) {
-        pieces.push_back({loff, llen, true});
-        pieces.push_back({off + len, loff - off - len, true});
-    }
-    const uint64_t new_total = n - len;
-    rebuild(st_pos, pieces, new_total, stream);
-    rebuild(st_vel, pieces, new_total, stream);
-    {
-        // The solver's per-fluid buffers are positional in the reference and are NOT swapped with the object
-        // (liquid_world.rs:171-173 removes from the arena only; init_with_fluids then resizes `velocity_changes[slot]` /
-        // `pressures[slot]` to the new occupant's particle count, dfsph_solver.rs:526-549 / iisph_solver.rs:479-501): the
-        // fluid that moves into the freed slot inherits the removed fluid's velocity changes and pressures, truncated
-        // or zero-extended, and the buffer of the last slot lives on until the next step (a fluid added before then
-        // inherits it).  Reproduced: results must match the reference's, quirks included.  See `sticky` in world.h.
-        auto content_of = [&](uint32_t sl, uint64_t o, uint64_t l) {
-            auto it = sticky.find(sl);
-            if (it != sticky.end()) return it->second;
-            StickyBuf b;
-            b.data = std::make_shared<DevBuf<float4>>();
-            b.len = l;
-            b.data->ensure(std::max<uint64_t>(l, 1));
-            if (l) SALVA_HIP_CHECK(hipMemcpyAsync(b.data->p, st_dv.p + o, l * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-            return b;
-        };
-        const StickyBuf A = content_of(slot, off, len);
-        const StickyBuf B = slot != last ? content_of(last, loff, llen) : StickyBuf{};
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        std::vector<Piece> dvp;
-        dvp.push_back({0, off, true});
-        if (slot != last) {
-            dvp.push_back({0, llen, false});
-            dvp.push_back({off + len, loff - off - len, true});
-        }
-        rebuild(st_dv, dvp, new_total, stream);
-        sticky.erase(slot);
-        sticky.erase(last);
-        if (slot != last) {
-            const uint64_t inherit = std::min(A.len, llen);
-            if (inherit) SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + off, A.data->p, inherit * sizeof(float4), hipMemcpyDeviceToDevice, stream));
-            if (llen > inherit) SALVA_HIP_CHECK(hipMemsetAsync(st_dv.p + off + inherit, 0, (llen - inherit) * sizeof(float4), stream));
-            if (A.len > llen) sticky[slot] = A;  // its tail goes to particles added before the next step
-            sticky[last] = B;
-        } else {
-            sticky[last] = A;
-        }
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    rebuild(st_acc, pieces, new_total, stream);
-    rebuild(st_model, pieces, new_total, stream);
-    if (slot != last) fluids[slot] = fluids[last];
-    fluids.pop_back();
-    n = (uint32_t)new_total;
-    stamp_fluid_models();
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    sorted_valid = false; bbox_known = false; tables_dirty = true; have_last_ctx = false;
-}
-
-// ------------------------------------------------------------------------------------------------ boundaries
-void World::set_boundary(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships,
-                         uint32_t filter, bool wants_forces) {
-    set_boundary_from(slot, nn, pos, vel_h, memberships, filter, wants_forces, nullptr);
-}
-
-// fill_dev != nullptr: the positions are written on the device — (*fill_dev)(first float4 of the slot), enqueued on the world's
-// stream — instead of uploaded from `pos` (set_boundary_sampling_from_shape, sample.hip)
-void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships, uint32_t filter,
-                              bool wants_forces, const std::function<void(float4*)>* fill_dev) {
-    use_device();
-    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
-    const bool is_new = slot == bounds.size();
-    const uint64_t old_n = is_new ? 0 : bounds[slot].n;
-    if ((uint64_t)nb - old_n + nn >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
-    if (nn && !pos && !fill_dev) throw HipError(SALVA_HIP_E_INVALID, "boundary positions are required");
-    if (is_new) bounds.emplace_back();
-    const uint64_t off = boundary_offset(slot);
-    const uint64_t old_total = nb, new_total = old_total - old_n + nn;
-    const bool resized = is_new || old_n != nn;
-    if (resized) {
-        std::vector<Piece> pieces = {{0, off, true}, {0, nn, false}, {off + old_n, old_total - off - old_n, true}};
-        rebuild(bst_pos, pieces, new_total, stream);
-        rebuild(bst_vel, pieces, new_total, stream);
-        rebuild(bforce, pieces, new_total, stream);
-        nb = (uint32_t)new_total;
-        if (nn) {
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_pos.p + off, make_float4(0, 0, 0, 0), 0);
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_vel.p + off, make_float4(0, 0, 0, 0), 0);
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bforce.p + off, make_float4(0, 0, 0, 0), 0);
-        }
-    }
-    BoundarySlot& b = bounds[slot];
-    b.n = nn; b.memberships = memberships; b.filter = filter; b.wants_forces = wants_forces;
-    b.dyn.reset();  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
-    b.vel_zero = true;
-    if (nn) {
-        scratch_f.ensure(3 * nn, stream, false, 1.1f);
-        if (fill_dev) {
-            (*fill_dev)(bst_pos.p + off);
-        } else {
-            SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, pos, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-            k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, bst_pos.p + off, 0, 0.0f);
-        }
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        b.vel_zero = true;
-        if (vel_h)
-            for (uint64_t k = 0; k < 3 * nn && b.vel_zero; ++k) b.vel_zero = vel_h[k] == 0.0f;
-        if (vel_h) {
-            SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, vel_h, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-            k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, bst_vel.p + off, 0, 0.0f);
-        } else {
-            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_vel.p + off, make_float4(0, 0, 0, 0), 0);
-        }
-    }
-    // boundary model ids ride in bst_vel.w
-    stamp_boundary_models();
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    b_dirty = true; tables_dirty = true; have_last_ctx = false;
-}
-
-void World::remove_boundary(uint32_t slot) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const uint32_t last = (uint32_t)bounds.size() - 1;
-    const uint64_t off = boundary_offset(slot), len = bounds[slot].n;
-    const uint64_t loff = boundary_offset(last), llen = bounds[last].n;
-    std::vector<Piece> pieces;
-    pieces.push_back({0, off, true});
-    if (slot != last) {
-        pieces.push_back({loff, llen, true});
-        pieces.push_back({off + len, loff - off - len, true});
-    }
-    const uint64_t new_total = nb - len;
-    rebuild(bst_pos, pieces, new_total, stream);
-    rebuild(bst_vel, pieces, new_total, stream);
-    rebuild(bforce, pieces, new_total, stream);
-    if (slot != last) bounds[slot] = bounds[last];
-    bounds.pop_back();
-    nb = (uint32_t)new_total;
-    stamp_boundary_models();
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    b_dirty = true; tables_dirty = true; have_last_ctx = false;
-}
 
 // ------------------------------------------------------------------------------------------------ tables
 // InteractionGroups::test (interaction_groups.rs:64-69)
@@ -875,7 +394,7 @@ void World::build_boundary_grid() {
 
 // ------------------------------------------------------------------------------------------------ Becker2009Elasticity (elastic.hip)
 ElasticState& World::elastic_state(uint32_t slot, uint32_t force) {
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
+    fluid_span(slot);  // (the range check)
     FluidSlot& fs = fluids[slot];
     if (force >= fs.forces.size() || fs.forces[force].kind != SALVA_HIP_FORCE_BECKER2009)
         throw HipError(SALVA_HIP_E_INVALID, "that force entry is not a Becker2009Elasticity");
@@ -894,451 +413,6 @@ bool World::elastic_stale() const {
                 if (!e || e->n0 != f.n || !e->list_valid) return true;
             }
     return false;
-}
-
-// The state is read and written at its own particle count n0: the fluid's count, except between a change of that count and the
-// next step, when the state still has the old length (the next step re-initialises it from there: quirk 1 needs the old volumes0).
-uint64_t World::get_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, float* positions0, float* volumes0, float* rotations,
-                                     float* stress, float* grad_tr) {
-    use_device();
-    ElasticState& e = elastic_state(slot, force);
-    if (e.n0 == 0) return 0;
-    if (nn == 0) return e.nnz;  // (sizing call)
-    if (nn != e.n0) throw HipError(SALVA_HIP_E_INVALID, "n is not the elastic state's particle count (salva_hip_get_elasticity_contacts)");
-    if (positions0) {
-        std::vector<float4> t(nn);
-        SALVA_HIP_CHECK(hipMemcpyAsync(t.data(), e.p0.p, nn * sizeof(float4), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        for (uint64_t i = 0; i < nn; ++i) { positions0[3 * i] = t[i].x; positions0[3 * i + 1] = t[i].y; positions0[3 * i + 2] = t[i].z; }
-    }
-    auto down = [&](float* dst, const float* src, size_t cnt) {
-        if (dst) SALVA_HIP_CHECK(hipMemcpyAsync(dst, src, cnt * sizeof(float), hipMemcpyDeviceToHost, stream));
-    };
-    down(volumes0, e.vol0.p, nn);
-    down(rotations, e.rot.p, 9 * nn);
-    down(stress, e.sig.p, 6 * nn);
-    down(grad_tr, e.F.p, 9 * nn);
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    return e.nnz;
-}
-
-uint64_t World::get_elasticity_contacts(uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets, uint32_t* j, uint64_t capacity) {
-    use_device();
-    ElasticState& e = elastic_state(slot, force);
-    if (n0) *n0 = e.n0;
-    if (e.n0 == 0 || capacity < e.nnz) return e.n0 ? e.nnz : 0;
-    if (offsets) SALVA_HIP_CHECK(hipMemcpyAsync(offsets, e.off.p, (e.n0 + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (j) SALVA_HIP_CHECK(hipMemcpyAsync(j, e.nbr.p, e.nnz * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    return e.nnz;
-}
-
-void World::set_elasticity_state(uint32_t slot, uint32_t force, uint64_t nn, const float* positions0, const float* volumes0,
-                                 const float* rotations) {
-    use_device();
-    ElasticState& e = elastic_state(slot, force);
-    if (nn == 0) throw HipError(SALVA_HIP_E_INVALID, "an elastic state needs at least one particle");
-    const bool fresh = e.n0 != nn;
-    if (fresh && !positions0) throw HipError(SALVA_HIP_E_INVALID, "positions0 is required when the state is new or changes length");
-    e.p0.ensure(nn, stream, !fresh, 1.1f); e.hp.ensure(nn, stream, false, 1.1f);
-    e.vol0.ensure(nn, stream, !fresh, 1.1f); e.rot.ensure(9 * nn, stream, !fresh, 1.1f);
-    e.rot_new.ensure(9 * nn, stream, false, 1.1f); e.sig.ensure(6 * nn, stream, false, 1.1f); e.F.ensure(9 * nn, stream, false, 1.1f);
-    if (fresh) {
-        SALVA_HIP_CHECK(hipMemsetAsync(e.vol0.p, 0, nn * sizeof(float), stream));
-        SALVA_HIP_CHECK(hipMemsetAsync(e.sig.p, 0, 6 * nn * sizeof(float), stream));
-        SALVA_HIP_CHECK(hipMemsetAsync(e.F.p, 0, 9 * nn * sizeof(float), stream));
-        launch_elastic_identity(e, 0, nn, stream);
-    }
-    if (positions0) {
-        std::vector<float4> t(nn);
-        for (uint64_t i = 0; i < nn; ++i) t[i] = make_float4(positions0[3 * i], positions0[3 * i + 1], positions0[3 * i + 2], 0.0f);
-        SALVA_HIP_CHECK(hipMemcpyAsync(e.p0.p, t.data(), nn * sizeof(float4), hipMemcpyHostToDevice, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    if (volumes0) SALVA_HIP_CHECK(hipMemcpyAsync(e.vol0.p, volumes0, nn * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (rotations) SALVA_HIP_CHECK(hipMemcpyAsync(e.rot.p, rotations, 9 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    e.n0 = nn;
-    e.ran = false;
-    // the rest lists from positions0 now (the same lists the state had: rows are sorted); volumes0 stays as given
-    elastic_build_rest(e, make_sph_consts(prm.particle_radius * prm.smoothing_factor * 2.0f), elastic_params(fluids[slot].forces[force].p),
-                       true, stream);
-}
-
-// The contact lists of the last step (they describe the positions the step started from, as the reference's
-// ContactManager does after `step`).  offsets: n+1 entries; entries are written only if `capacity` holds them all.
-uint64_t World::get_fluid_contacts(uint32_t slot, int boundary, uint64_t* offsets, uint32_t* j_model, uint32_t* j, uint64_t capacity) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (comm) throw HipError(SALVA_HIP_E_INVALID, "host-order contact export does not exist in a multi-GPU run: use salva_hip_get_local_contacts");
-    if (!have_last_ctx || !sorted_valid) throw HipError(SALVA_HIP_E_INVALID, "no completed step: there are no contact lists yet");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    std::vector<uint32_t> cnt(nn, 0);
-    DevBuf<uint32_t> d_cnt;
-    d_cnt.ensure(std::max<size_t>(n, 1));
-    if (!(boundary && nb == 0) && nn) {
-        launch_unsort_u32(n, perm[cur].p, boundary ? nfb.p : nff.p, d_cnt.p, stream);
-        SALVA_HIP_CHECK(hipMemcpyAsync(cnt.data(), d_cnt.p + off, nn * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    std::vector<uint64_t> offs(nn + 1, 0);
-    for (uint64_t k = 0; k < nn; ++k) offs[k + 1] = offs[k] + cnt[k];
-    const uint64_t total = offs[nn];
-    if (offsets) memcpy(offsets, offs.data(), (nn + 1) * sizeof(uint64_t));
-    if (!j_model || !j || capacity < total || total == 0) return total;
-    std::vector<uint32_t> moff(num_models(), 0), boff(std::max<size_t>(bounds.size(), 1), 0);
-    for (uint32_t s = 0; s < fluids.size(); ++s) moff[s] = (uint32_t)fluid_offset(s);
-    for (uint32_t s = 0; s < bounds.size(); ++s) boff[s] = (uint32_t)boundary_offset(s);
-    DevBuf<uint64_t> d_offs;
-    DevBuf<uint32_t> d_moff, d_boff, d_jm, d_j;
-    d_offs.ensure(nn + 1); d_moff.ensure(moff.size()); d_boff.ensure(boff.size()); d_jm.ensure(total); d_j.ensure(total);
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_offs.p, offs.data(), (nn + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_moff.p, moff.data(), moff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_boff.p, boff.data(), boff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    flags_clean = false;
-    launch_export_contacts(last_ctx, G().keys[1].p, slot, boundary, d_offs.p, d_moff.p, d_boff.p, d_jm.p, d_j.p, stream);
-    SALVA_HIP_CHECK(hipMemcpyAsync(j_model, d_jm.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipMemcpyAsync(j, d_j.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    return total;
-}
-
-// ---- the working set as it is (include/salva_hip.h "local view"): sorted order, global ids; per rank in a decomposed run
-__global__ void k_local_ghost_flags(uint32_t n, const uint32_t* __restrict__ gtag, uint8_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (gtag && (gtag[i] & 0x80000000u)) ? 1 : 0;
-}
-void World::get_local(uint32_t* ids, uint32_t* fluid_slots, uint8_t* is_ghost, float* positions, float* velocities, float* densities, float* volumes) {
-    use_device();
-    if (!sorted_valid || (!have_last_ctx && !in_force_cb)) throw HipError(SALVA_HIP_E_INVALID, "no completed step: the working set has no order yet");
-    if (n == 0) return;
-    if (ids) SALVA_HIP_CHECK(hipMemcpyAsync(ids, perm[cur].p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (fluid_slots) SALVA_HIP_CHECK(hipMemcpyAsync(fluid_slots, model[cur].p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (is_ghost) {
-        DevBuf<uint8_t> flags;
-        flags.ensure(n);
-        k_local_ghost_flags<<<nblk(n), BLOCK, 0, stream>>>(n, comm ? gtag[cur].p : nullptr, flags.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(is_ghost, flags.p, (size_t)n, hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    scratch_f.ensure(3 * (size_t)n, stream, false, 1.1f);
-    for (int k = 0; k < 2; ++k) {
-        float* out = k == 0 ? positions : velocities;
-        if (!out) continue;
-        // inside a force callback fluid.velocities equal w = v + dv (dfsph_solver.rs:688-693), as in force_get_state
-        const float4* src = k == 0 ? posm[cur].p : (in_force_cb ? last_ctx.w : vel[cur].p);
-        k_unpack_xyz<<<nblk(n), BLOCK, 0, stream>>>(n, src, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(out, scratch_f.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    if (densities) SALVA_HIP_CHECK(hipMemcpyAsync(densities, rho.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (volumes) {  // (they ride in vel.w, device_types.h)
-        k_unpack_w<<<nblk(n), BLOCK, 0, stream>>>(n, vel[cur].p, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(volumes, scratch_f.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    }
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-}
-uint64_t World::get_local_contacts(int boundary, uint64_t* offsets, uint32_t* j_model, uint32_t* j, uint64_t capacity) {
-    use_device();
-    if (!have_last_ctx || !sorted_valid) throw HipError(SALVA_HIP_E_INVALID, "no completed step: there are no contact lists yet");
-    std::vector<uint32_t> cnt(n, 0);
-    if (!(boundary && nb == 0) && n) {
-        SALVA_HIP_CHECK(hipMemcpyAsync(cnt.data(), boundary ? nfb.p : nff.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    std::vector<uint64_t> offs((size_t)n + 1, 0);
-    for (uint64_t k = 0; k < n; ++k) offs[k + 1] = offs[k] + cnt[k];
-    const uint64_t total = offs[n];
-    if (offsets) memcpy(offsets, offs.data(), ((size_t)n + 1) * sizeof(uint64_t));
-    if (!j_model || !j || capacity < total || total == 0) return total;
-    std::vector<uint32_t> boff(std::max<size_t>(bounds.size(), 1), 0);
-    for (uint32_t s = 0; s < bounds.size(); ++s) boff[s] = (uint32_t)boundary_offset(s);
-    DevBuf<uint64_t> d_offs;
-    DevBuf<uint32_t> d_boff, d_jm, d_j;
-    d_offs.ensure((size_t)n + 1); d_boff.ensure(boff.size()); d_jm.ensure(total); d_j.ensure(total);
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_offs.p, offs.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    SALVA_HIP_CHECK(hipMemcpyAsync(d_boff.p, boff.data(), boff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    flags_clean = false;
-    launch_export_contacts_local(last_ctx, G().keys[1].p, boundary, d_offs.p, d_boff.p, d_jm.p, d_j.p, stream);
-    SALVA_HIP_CHECK(hipMemcpyAsync(j_model, d_jm.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipMemcpyAsync(j, d_j.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    return total;
-}
-__global__ void k_add_acc_local(uint32_t n, const float* __restrict__ in, float4* __restrict__ acc) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    float4 a = acc[s];
-    a.x += in[3 * (size_t)s]; a.y += in[3 * (size_t)s + 1]; a.z += in[3 * (size_t)s + 2];
-    acc[s] = a;
-}
-void World::force_add_local_accelerations(const float* acc_h) {
-    use_device();
-    if (!in_force_cb) throw HipError(SALVA_HIP_E_INVALID, "only available inside a force callback");
-    if (!acc_h) throw HipError(SALVA_HIP_E_INVALID, "null accelerations");
-    if (n == 0) return;
-    scratch_f.ensure(3 * (size_t)n, stream, false, 1.1f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, acc_h, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, stream));
-    // (what lands on a ghost is overwritten by the refresh of w that follows the forces, world_dist)
-    k_add_acc_local<<<nblk(n), BLOCK, 0, stream>>>(n, scratch_f.p, last_ctx.acc);
-    SALVA_HIP_CHECK(hipGetLastError());
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-}
-
-void World::get_force_stats(uint32_t slot, uint32_t force, int32_t* iters, float* err) {
-    if (slot >= fluids.size() || force >= fluids[slot].forces.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot / force index out of range");
-    const FluidSlot& f = fluids[slot];
-    if (iters) *iters = force < f.force_iters.size() ? (int32_t)f.force_iters[force] : 0;
-    if (err) *err = force < f.force_errs.size() ? f.force_errs[force] : 0.0f;
-}
-
-// ------------------------------------------------------------------------------------------------ downloads
-void World::get_fluid(uint32_t slot, float* pos, float* vel_out) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0) return;
-    ensure_staging_current();
-    scratch_f.ensure(3 * nn, stream, false, 1.1f);
-    if (pos) {
-        k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_pos.p + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(pos, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    if (vel_out) {
-        k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_vel.p + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(vel_out, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
-// ---- asynchronous read-back.  The reference's users read fluid.positions / velocities after every step
-// (integrations/rapier/testbed_plugin.rs:361-367); the synchronous salva_hip_get_fluid costs 0.6 ms per step at 10^6 particles
-// (un-sort into the staging arrays, unpack, copy, stream synchronisation, per array, serial with the step: 1.91 against 1.31 ms per
-// step over the bench protocol, tools/pcie_probe.py — round 3's "5.57 ms" compared different steps of the scene).  Here: two scatter kernels on the main stream write (x, y, z) in host order straight from the sorted
-// working set (~10 us), the copy stream takes them out behind an event while the main stream already runs the next step, and
-// the host collects them with salva_hip_wait_download.  A destination in pinned memory (salva_hip_host_alloc / _register) is
-// written by the DMA engine directly; a pageable one goes through the library's pinned buffers and one memcpy in the wait.
-__global__ void k_scatter_xyz(uint32_t n, const uint32_t* __restrict__ perm, uint32_t off, uint32_t nn, const float4* __restrict__ src,
-                              float* __restrict__ dst) {
-    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-    if (s >= n) return;
-    const uint32_t h = perm[s] - off;
-    if (h >= nn) return;  // (another fluid's particle)
-    const float4 v = src[s];
-    dst[3 * (size_t)h] = v.x; dst[3 * (size_t)h + 1] = v.y; dst[3 * (size_t)h + 2] = v.z;
-}
-static bool host_pointer_is_pinned(const void* p) {
-    hipPointerAttribute_t a{};
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }  // (plain malloc'ed memory is unknown to the runtime)
-    return a.type == hipMemoryTypeHost;
-}
-void World::get_fluid_async(uint32_t slot, float* pos, float* vel_out) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "host-order fluid arrays are not maintained in a multi-GPU run: use salva_hip_get_owned");
-    wait_download();  // one download in flight
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0 || (!pos && !vel_out)) return;
-    if (!dl_stream) {
-        SALVA_HIP_CHECK(hipStreamCreateWithFlags(&dl_stream, hipStreamNonBlocking));
-        SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev_dl_ready, hipEventDisableTiming));
-        SALVA_HIP_CHECK(hipEventCreateWithFlags(&ev_dl_done, hipEventDisableTiming));
-    }
-    const size_t bytes = 3 * nn * sizeof(float);
-    float* dsts[2] = {pos, vel_out};
-    const float4* sorted_src[2] = {posm[cur].p, vel[cur].p};
-    const float4* staged_src[2] = {st_pos.p + off, st_vel.p + off};
-    const bool from_sorted = sorted_valid && !staging_current;
-    for (int a = 0; a < 2; ++a) {
-        if (!dsts[a]) continue;
-        dl_dev[a].ensure(3 * nn, stream, false, 1.1f);
-        if (from_sorted) k_scatter_xyz<<<nblk(n), BLOCK, 0, stream>>>(n, perm[cur].p, (uint32_t)off, (uint32_t)nn, sorted_src[a], dl_dev[a].p);
-        else k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, staged_src[a], dl_dev[a].p);
-    }
-    SALVA_HIP_CHECK(hipGetLastError());
-    SALVA_HIP_CHECK(hipEventRecord(ev_dl_ready, stream));
-    SALVA_HIP_CHECK(hipStreamWaitEvent(dl_stream, ev_dl_ready, 0));
-    dl = PendingDownload{};
-    dl.bytes = bytes;
-    for (int a = 0; a < 2; ++a) {
-        if (!dsts[a]) continue;
-        dl.dst[a] = dsts[a];
-        dl.staged[a] = !host_pointer_is_pinned(dsts[a]);
-        float* target = dsts[a];
-        if (dl.staged[a]) {
-            if (h_dl_cap[a] < bytes) {
-                if (h_dl[a]) SALVA_HIP_CHECK(hipHostFree(h_dl[a]));
-                h_dl[a] = nullptr; h_dl_cap[a] = 0;
-                const size_t cap = bytes + bytes / 8;
-                SALVA_HIP_CHECK(hipHostMalloc((void**)&h_dl[a], cap, hipHostMallocDefault));
-                h_dl_cap[a] = cap;
-            }
-            target = h_dl[a];
-        }
-        SALVA_HIP_CHECK(hipMemcpyAsync(target, dl_dev[a].p, bytes, hipMemcpyDeviceToHost, dl_stream));
-    }
-    SALVA_HIP_CHECK(hipEventRecord(ev_dl_done, dl_stream));
-    dl.active = true;
-}
-void World::wait_download() {
-    if (!dl.active) return;
-    use_device();
-    dl.active = false;
-    SALVA_HIP_CHECK(hipEventSynchronize(ev_dl_done));
-    for (int a = 0; a < 2; ++a)
-        if (dl.dst[a] && dl.staged[a]) memcpy(dl.dst[a], h_dl[a], dl.bytes);
-}
-
-void World::get_fluid_field(uint32_t slot, int field, float* out) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (!out) throw HipError(SALVA_HIP_E_INVALID, "null output");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "per-fluid host-order access is not available in a multi-GPU run: use salva_hip_get_owned");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0) return;
-    const bool vec = field == SALVA_HIP_FIELD_VELOCITY_CHANGE || field == SALVA_HIP_FIELD_ACCELERATION;
-    const size_t width = vec ? 3 : 1;
-    scratch_f.ensure(std::max<size_t>(3 * nn, n), stream, false, 1.1f);
-    auto finish = [&](const float* src) {
-        SALVA_HIP_CHECK(hipMemcpyAsync(out, src, width * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    };
-    switch (field) {
-        case SALVA_HIP_FIELD_VELOCITY_CHANGE:
-            ensure_staging_current();
-            k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_dv.p + off, scratch_f.p);
-            finish(scratch_f.p);
-            return;
-        case SALVA_HIP_FIELD_PRESSURE:
-            ensure_staging_current();
-            k_unpack_w<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_dv.p + off, scratch_f.p);
-            finish(scratch_f.p);
-            return;
-        case SALVA_HIP_FIELD_VOLUME:
-            ensure_staging_current();
-            k_unpack_w<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_pos.p + off, scratch_f.p);
-            finish(scratch_f.p);
-            return;
-        case SALVA_HIP_FIELD_ACCELERATION:
-            // accelerations are zero after every step (integrate_and_clear_accelerations) unless the host set them
-            if (acc_user) {
-                k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, st_acc.p + off, scratch_f.p);
-                finish(scratch_f.p);
-            } else {
-                memset(out, 0, 3 * nn * sizeof(float));
-            }
-            return;
-        default: break;
-    }
-    // per-step solver scratch lives in sorted order: valid only right after a step
-    if (!sorted_valid || !have_last_ctx)
-        throw HipError(SALVA_HIP_E_INVALID, "solver scratch fields are only available right after a step");
-    switch (field) {
-        case SALVA_HIP_FIELD_DENSITY: launch_unsort_f32(n, perm[cur].p, rho.p, scratch_f.p, stream); break;
-        case SALVA_HIP_FIELD_ALPHA: launch_unsort_f32(n, perm[cur].p, alpha.p, scratch_f.p, stream); break;
-        case SALVA_HIP_FIELD_NUM_FLUID_CONTACTS: launch_unsort_u32_as_f32(n, perm[cur].p, nff.p, scratch_f.p, stream); break;
-        case SALVA_HIP_FIELD_NUM_BOUNDARY_CONTACTS:
-            if (nb == 0) { memset(out, 0, nn * sizeof(float)); return; }
-            launch_unsort_u32_as_f32(n, perm[cur].p, nfb.p, scratch_f.p, stream);
-            break;
-        default: throw HipError(SALVA_HIP_E_INVALID, "unknown field");
-    }
-    finish(scratch_f.p + off);
-}
-
-void World::get_boundary(uint32_t slot, float* volumes, float* forces) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const uint64_t nn = bounds[slot].n, off = boundary_offset(slot);
-    if (nn == 0) return;
-    if (volumes) {
-        upload_tables();
-        build_boundary_grid();
-        scratch_f4.ensure(nb);
-        scratch_f.ensure(nb, stream, false, 1.1f);
-        launch_unsort_f4(nb, bperm.p, bposv.p, scratch_f4.p, stream);
-        k_unpack_w<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f4.p + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(volumes, scratch_f.p, nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    if (forces) {
-        scratch_f.ensure(3 * nn, stream, false, 1.1f);
-        k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bforce.p + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(forces, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ host force callbacks
-__global__ void k_add_acc_from_host(uint32_t n, const uint32_t* __restrict__ perm, uint32_t off, uint32_t nn,
-                                    const float* __restrict__ in, float4* __restrict__ acc) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    const uint32_t g = perm[s] - off;  // host index within the fluid (wraps for other fluids)
-    if (g >= nn) return;
-    float4 a = acc[s];
-    a.x += in[3 * g]; a.y += in[3 * g + 1]; a.z += in[3 * g + 2];
-    acc[s] = a;
-}
-
-void World::force_get_state(uint32_t slot, float* positions, float* velocities, float* densities) {
-    use_device();
-    if (!in_force_cb) throw HipError(SALVA_HIP_E_INVALID, "only available inside a force callback");
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0) return;
-    scratch_f4.ensure(n);
-    scratch_f.ensure(std::max<size_t>(3 * nn, n), stream, false, 1.1f);
-    for (int k = 0; k < 2; ++k) {
-        float* out = k == 0 ? positions : velocities;
-        if (!out) continue;
-        // fluid.velocities equal w = v + dv while the forces run (dfsph_solver.rs:688-693)
-        launch_unsort_f4(n, perm[cur].p, k == 0 ? last_ctx.posm : last_ctx.w, scratch_f4.p, stream);
-        k_unpack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f4.p + off, scratch_f.p);
-        SALVA_HIP_CHECK(hipMemcpyAsync(out, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    if (densities) {
-        launch_unsort_f32(n, perm[cur].p, last_ctx.rho, scratch_f.p, stream);
-        SALVA_HIP_CHECK(hipMemcpyAsync(densities, scratch_f.p + off, nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
-void World::force_add_accelerations(uint32_t slot, const float* acc_h) {
-    use_device();
-    if (!in_force_cb) throw HipError(SALVA_HIP_E_INVALID, "only available inside a force callback");
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (!acc_h) throw HipError(SALVA_HIP_E_INVALID, "null accelerations");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0) return;
-    scratch_f.ensure(3 * nn, stream, false, 1.1f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, acc_h, 3 * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-    k_add_acc_from_host<<<nblk(n), BLOCK, 0, stream>>>(n, perm[cur].p, (uint32_t)off, (uint32_t)nn, scratch_f.p, last_ctx.acc);
-    SALVA_HIP_CHECK(hipGetLastError());
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-}
-
-// checkpoint restore: the two pieces of solver state that live next to the fluid arrays (velocity_changes, IISPH pressures)
-void World::set_fluid_field(uint32_t slot, int field, const float* data) {
-    use_device();
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (!data) throw HipError(SALVA_HIP_E_INVALID, "null data");
-    if (field != SALVA_HIP_FIELD_VELOCITY_CHANGE && field != SALVA_HIP_FIELD_PRESSURE)
-        throw HipError(SALVA_HIP_E_INVALID, "only velocity_changes and pressures can be set");
-    const uint64_t nn = fluids[slot].n, off = fluid_offset(slot);
-    if (nn == 0) return;
-    ensure_staging_current();
-    const size_t width = field == SALVA_HIP_FIELD_VELOCITY_CHANGE ? 3 : 1;
-    scratch_f.ensure(width * nn, stream, false, 1.1f);
-    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, data, width * nn * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (field == SALVA_HIP_FIELD_VELOCITY_CHANGE) k_pack_xyz<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, st_dv.p + off, 1, 0.0f);
-    else k_pack_w<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, scratch_f.p, st_dv.p + off);
-    SALVA_HIP_CHECK(hipGetLastError());
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    sorted_valid = false; bbox_known = false; have_last_ctx = false;
 }
 
 uint64_t World::device_bytes() const {
@@ -1360,29 +434,19 @@ uint64_t World::device_bytes() const {
     return b;
 }
 
-// Average duration (microseconds) of one k_pred_density launch on the last step's lists, by HIP events on the
-// world's own stream.  The kernel only rewrites scratch (kappa, partials), so the world's state is unaffected.
-float World::time_pred_density(int reps) {
-    use_device();
-    if (!have_last_ctx || !sorted_valid || n == 0) throw HipError(SALVA_HIP_E_INVALID, "no completed step to time");
-    if (reps < 1) reps = 1;
-#ifdef SALVA_HIP_DIAG
-    if (sw.tile_timing) tile_timing_report();
-#endif
-    flags_clean = false;  // (a between-step launch may raise an error flag: the next step clears them itself — ADVICE r04)
-    launch_pred_density(last_ctx, lds, last_dt, stream);  // warm-up
-    SALVA_HIP_CHECK(hipEventRecord(ev[0], stream));
-    for (int r = 0; r < reps; ++r) launch_pred_density(last_ctx, lds, last_dt, stream);
-    SALVA_HIP_CHECK(hipEventRecord(ev[1], stream));
+// warm-up, `reps` launches between two HIP events on the world's stream: microseconds per launch
+template <typename Launch>
+static float time_launches(hipStream_t stream, hipEvent_t begin, hipEvent_t end, int reps, Launch&& launch) {
+    launch();  // warm-up
+    SALVA_HIP_CHECK(hipEventRecord(begin, stream));
+    for (int r = 0; r < reps; ++r) launch();
+    SALVA_HIP_CHECK(hipEventRecord(end, stream));
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    SALVA_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    SALVA_HIP_CHECK(hipEventElapsedTime(&ms, begin, end));
     return ms * 1000.0f / (float)reps;
 }
 
-
-// Average duration (microseconds) of one launch of a neighbour-sum kernel on the last step's lists (HIP events on the world's
-// stream): 0 k_pred_density, 1 k_divergence, 2 k_iisph_next_pressure, 3 k_iisph_dij_pj.  Scratch outputs only.
 void World::tile_tables(uint32_t slot, uint32_t* info, uint32_t* halo_row, uint32_t cap_row, uint32_t* counts, uint32_t cap_counts, uint32_t* entries,
                         uint32_t cap_entries) {
     use_device();
@@ -1421,18 +485,23 @@ void World::tile_tables(uint32_t slot, uint32_t* info, uint32_t* halo_row, uint3
     info[12] = o;
 }
 
+// Average duration (microseconds) of one launch of a neighbour-sum kernel on the last step's lists (HIP events on the world's
+// stream): 0 k_pred_density, 1 k_divergence, 2 k_iisph_next_pressure, 3 k_iisph_dij_pj.  Scratch outputs only (k_pred_density
+// rewrites kappa and partials), so the world's state is unaffected.
 float World::time_kernel(int kernel, int reps) {
     use_device();
     if (!have_last_ctx || !sorted_valid || n == 0) throw HipError(SALVA_HIP_E_INVALID, "no completed step to time");
-    if (kernel == 0) return time_pred_density(reps);
     if (reps < 1) reps = 1;
+#ifdef SALVA_HIP_DIAG
+    if (kernel == 0 && sw.tile_timing) tile_timing_report();
+#endif
     const bool iisph = prm.solver == SALVA_HIP_SOLVER_IISPH;
     if (kernel == 4 && comm) throw HipError(SALVA_HIP_E_INVALID, "not available in a multi-GPU run");
     if ((kernel == 2 || kernel == 3) && !iisph) throw HipError(SALVA_HIP_E_INVALID, "an IISPH kernel needs an IISPH world");
     if (kernel == 1 && iisph) throw HipError(SALVA_HIP_E_INVALID, "k_divergence needs a DFSPH world");
     StepCtx cd = last_ctx;
     cd.ctl = nullptr;
-    flags_clean = false;  // (see time_pred_density)
+    flags_clean = false;  // (a between-step launch may raise an error flag: the next step clears them itself — ADVICE r04)
     if (kernel == 6) {  // the apply pass updates w in place: let it run on a copy (w2 is free outside a speculative solve)
         if (iisph) throw HipError(SALVA_HIP_E_INVALID, "k_divergence_apply needs a DFSPH world");
         w2.ensure(n, stream, false, 1.1f);
@@ -1473,6 +542,7 @@ float World::time_kernel(int kernel, int reps) {
     const uint32_t el_off = el ? (uint32_t)fluid_offset(el_slot) : 0u;
     auto launch = [&]() {
         switch (kernel) {
+            case 0: launch_pred_density(last_ctx, lds, last_dt, stream); break;  // (the step's own context, control block included)
             case 7: launch_elastic_rot_stress(cd, *el, el_p, stream); break;  // (reads rot; writes rot_new and the copies of sigma, F)
             case 8: launch_elastic_forces(cd, el_off, *el, el_p, acc_copy.p, stream); break;
             case 1: launch_divergence(cd, lds, stream); break;
@@ -1504,14 +574,7 @@ float World::time_kernel(int kernel, int reps) {
             default: throw HipError(SALVA_HIP_E_INVALID, "unknown kernel id");
         }
     };
-    launch();  // warm-up
-    SALVA_HIP_CHECK(hipEventRecord(ev[0], stream));
-    for (int r = 0; r < reps; ++r) launch();
-    SALVA_HIP_CHECK(hipEventRecord(ev[1], stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    float ms = 0.0f;
-    SALVA_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return ms * 1000.0f / (float)reps;
+    return time_launches(stream, ev[0], ev[1], reps, launch);
 }
 
 }  // namespace salva

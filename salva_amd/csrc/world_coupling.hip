@@ -551,21 +551,6 @@ void World::get_boundary_sources(uint32_t slot, uint32_t* fluid_slots, uint32_t*
     }
 }
 
-void World::get_boundary_particles(uint32_t slot, float* positions, float* velocities) {
-    use_device();
-    if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");
-    const uint64_t nn = bounds[slot].n, off = boundary_offset(slot);
-    if (nn == 0) return;
-    scratch_f.ensure(3 * nn, stream, false, 1.1f);
-    for (int k = 0; k < 2; ++k) {
-        float* out = k == 0 ? positions : velocities;
-        if (!out) continue;
-        launch_unpack_xyz((uint32_t)nn, (k == 0 ? bst_pos.p : bst_vel.p) + off, scratch_f.p, stream);
-        SALVA_HIP_CHECK(hipMemcpyAsync(out, scratch_f.p, 3 * nn * sizeof(float), hipMemcpyDeviceToHost, stream));
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    }
-}
-
 void World::get_boundary_wrench(uint32_t slot, const float point[3], float force[3], float torque[3]) {
     use_device();
     if (slot >= bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range");

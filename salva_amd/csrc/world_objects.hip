@@ -1,0 +1,473 @@
+// world_objects.hip — edits of the fluid and boundary sets: the ONE editor of the host-order ("staging") arrays st_pos / st_vel /
+// st_dv / st_acc / st_model and bst_pos / bst_vel / bforce (splice, default fill, model stamps, invalidation), and the host -> device
+// half of the transfer helpers.  The read-backs are world_io.hip.
+#include "world.h"
+
+#include <algorithm>
+#include <cstring>
+#include <limits>
+
+namespace salva {
+
+__global__ void k_pack_xyz(uint32_t n, const float* __restrict__ src, float4* __restrict__ dst, int keep_w, float wval) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    float4 d = dst[i];
+    d.x = src[3 * i]; d.y = src[3 * i + 1]; d.z = src[3 * i + 2];
+    if (!keep_w) d.w = wval;
+    dst[i] = d;
+}
+__global__ void k_pack_w(uint32_t n, const float* __restrict__ src, float4* __restrict__ dst) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) reinterpret_cast<float*>(&dst[i])[3] = src[i];
+}
+__global__ void k_fill_f4(uint32_t n, float4* __restrict__ dst, float4 v) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) dst[i] = v;
+}
+__global__ void k_fill_u32(uint32_t n, uint32_t* __restrict__ dst, uint32_t v) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) dst[i] = v;
+}
+__global__ void k_set_bmodel(uint32_t n, float4* __restrict__ bvel, uint32_t m) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) reinterpret_cast<float*>(&bvel[i])[3] = __uint_as_float(m);
+}
+
+// ------------------------------------------------------------------------------------------------ host -> device
+// Every helper sizes scratch_f, enqueues on the world's stream and waits: scratch_f is free again when it returns.
+float* World::stage_floats(const float* host, size_t count) {  // (the half the accumulating uploads of world_io.hip share: no wait)
+    scratch_f.ensure(count, stream, false, 1.1f);
+    SALVA_HIP_CHECK(hipMemcpyAsync(scratch_f.p, host, count * sizeof(float), hipMemcpyHostToDevice, stream));
+    return scratch_f.p;
+}
+void World::upload_xyz(const float* host, float4* dst, uint64_t count, bool keep_w) {  // packed xyz -> float4 rows; w kept or zeroed
+    k_pack_xyz<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, stage_floats(host, 3 * count), dst, keep_w ? 1 : 0, 0.0f);
+    SALVA_HIP_CHECK(hipGetLastError());
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+}
+void World::upload_w(const float* host, float4* dst, uint64_t count) {
+    k_pack_w<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, stage_floats(host, count), dst);
+    SALVA_HIP_CHECK(hipGetLastError());
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// ------------------------------------------------------------------------------------------------ the editor
+template <typename T>
+static void rebuild(DevBuf<T>& buf, const std::vector<Piece>& pieces, uint64_t new_total, hipStream_t s) {
+    DevBuf<T> nb;
+    nb.ensure(new_total ? new_total : 1);
+    uint64_t off = 0;
+    for (const Piece& p : pieces) {
+        if (p.from_old && p.len)
+            SALVA_HIP_CHECK(hipMemcpyAsync(nb.p + off, buf.p + p.src_off, p.len * sizeof(T), hipMemcpyDeviceToDevice, s));
+        off += p.len;
+    }
+    SALVA_HIP_CHECK(hipStreamSynchronize(s));
+    std::swap(buf.p, nb.p);
+    std::swap(buf.cap, nb.cap);
+}
+
+// The new arrays are the pieces in order: rows of the old array (from_old) or room that the caller fills.  dv_pieces: another cut
+// for st_dv (remove_fluid: the solver's buffers do not move with the fluid).
+void World::splice_fluid_rows(const std::vector<Piece>& pieces, uint64_t new_total, const std::vector<Piece>* dv_pieces) {
+    rebuild(st_pos, pieces, new_total, stream);
+    rebuild(st_vel, pieces, new_total, stream);
+    rebuild(st_dv, dv_pieces ? *dv_pieces : pieces, new_total, stream);
+    rebuild(st_acc, pieces, new_total, stream);
+    rebuild(st_model, pieces, new_total, stream);
+    n = (uint32_t)new_total;
+}
+void World::splice_boundary_rows(const std::vector<Piece>& pieces, uint64_t new_total) {
+    rebuild(bst_pos, pieces, new_total, stream);
+    rebuild(bst_vel, pieces, new_total, stream);
+    rebuild(bforce, pieces, new_total, stream);
+    nb = (uint32_t)new_total;
+}
+
+float World::default_particle_volume() const {  // Fluid::particle_volume (fluid.rs:110-120)
+    const float r = prm.particle_radius;
+    return r * r * r * 6.4f;  // 8 * 0.8
+}
+
+// defaults: zero position / velocity / velocity change / acceleration, the default volume
+void World::fill_fluid_defaults(uint64_t at, uint64_t count) {
+    if (!count) return;
+    const float4 zero = make_float4(0, 0, 0, 0);
+    k_fill_f4<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, st_pos.p + at, make_float4(0, 0, 0, default_particle_volume()));
+    k_fill_f4<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, st_vel.p + at, zero);
+    k_fill_f4<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, st_dv.p + at, zero);
+    k_fill_f4<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, st_acc.p + at, zero);
+}
+
+// the model id of every staged particle: a slot's particles move when a slot before it changes its length
+void World::stamp_fluid_models() {
+    uint64_t o = 0;
+    for (uint32_t s = 0; s < fluids.size(); ++s) {
+        if (fluids[s].n) k_fill_u32<<<nblk(fluids[s].n), BLOCK, 0, stream>>>((uint32_t)fluids[s].n, st_model.p + o, s);
+        o += fluids[s].n;
+    }
+}
+void World::stamp_boundary_models() {  // (boundary model ids ride in bst_vel.w)
+    uint64_t o = 0;
+    for (uint32_t s = 0; s < bounds.size(); ++s) {
+        if (bounds[s].n) k_set_bmodel<<<nblk(bounds[s].n), BLOCK, 0, stream>>>((uint32_t)bounds[s].n, bst_vel.p + o, s);
+        o += bounds[s].n;
+    }
+}
+
+// What an edit of the host-order arrays ends: the sorted working set, the cell box and the last step's lists (and, when the
+// fluids themselves changed, the per-model tables) / the boundary grid, the tables, the last step's lists.
+void World::order_invalidated(bool tables) {
+    sorted_valid = false; bbox_known = false; have_last_ctx = false;
+    if (tables) tables_dirty = true;
+}
+void World::boundaries_invalidated() { b_dirty = true; tables_dirty = true; have_last_ctx = false; }
+
+// Bring the canonical (host-order) staging arrays up to date with the sorted working set.
+void World::ensure_staging_current() {
+    if (staging_current) return;
+    if (comm && dist_started)
+        throw HipError(SALVA_HIP_E_INVALID, "host-order fluid arrays are not maintained in a multi-GPU run: use salva_hip_get_owned");
+    if (sorted_valid && n) {
+        launch_sorted_to_stage(n, arrays(cur), st_pos.p, st_vel.p, st_dv.p, stream);
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    staging_current = true;
+}
+
+// ------------------------------------------------------------------------------------------------ fluids
+void World::set_fluid(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, const float* vol,
+                      const float* acc_h, const float* dvs, float density0, uint32_t memberships, uint32_t filter,
+                      uint32_t dirty) {
+    use_device();
+    if (slot > fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range (slots are dense)");
+    if (slot >= (uint32_t)MAX_MODELS) throw HipError(SALVA_HIP_E_CAPACITY, "at most 32 fluids per world");
+    const bool is_new = slot == fluids.size();
+    if ((uint64_t)n - (is_new ? 0 : fluids[slot].n) + nn >= 0xfffffff0ull)
+        throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 fluid particles on one device");
+    ensure_staging_current();
+    const uint64_t old_n = is_new ? 0 : fluids[slot].n;
+    const bool resized = is_new || old_n != nn;
+    if (resized) {
+        if (nn && !pos) throw HipError(SALVA_HIP_E_INVALID, "positions are required when a fluid is created or resized");
+        dirty = SALVA_HIP_DIRTY_ALL;
+    }
+    if (is_new) fluids.emplace_back();
+    const uint64_t off = fluid_offset(slot);
+    const uint64_t old_total = n;
+    const uint64_t new_total = old_total - old_n + nn;
+    if (resized) {
+        splice_fluid_rows({{0, off, true}, {0, nn, false}, {off + old_n, old_total - off - old_n, true}}, new_total);
+        fill_fluid_defaults(off, nn);
+        if (is_new && !dvs) {
+            auto it = sticky.find(slot);
+            if (it != sticky.end()) {  // buffer[slot] of a fluid removed since the last step: inherited (world.h `sticky`)
+                const uint64_t inherit = std::min<uint64_t>(it->second.len, nn);
+                if (inherit) SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + off, it->second.data->p, inherit * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+                if (it->second.len <= nn) sticky.erase(it);
+            }
+        }
+        // model ids of every slot at/after this one may have moved
+        fluids[slot].n = nn;
+        stamp_fluid_models();
+    }
+    FluidSlot& f = fluids[slot];
+    f.density0 = density0; f.memberships = memberships; f.filter = filter;
+    {   // the fluid's one volume, if it has one (FluidSlot::vol_uniform): a resize filled the default in, an upload may change it
+        if (resized) f.vol_uniform = default_particle_volume();
+        if (nn && (dirty & SALVA_HIP_DIRTY_VOLUMES) && vol) {
+            bool same = true;
+            for (uint64_t k = 1; k < nn && same; ++k) same = vol[k] == vol[0];
+            f.vol_uniform = same ? vol[0] : std::numeric_limits<float>::quiet_NaN();
+        }
+    }
+    if (nn) {
+        if ((dirty & SALVA_HIP_DIRTY_POSITIONS) && pos) upload_xyz(pos, st_pos.p + off, nn, true);
+        if ((dirty & SALVA_HIP_DIRTY_VELOCITIES) && vel_h) upload_xyz(vel_h, st_vel.p + off, nn, true);
+        if ((dirty & SALVA_HIP_DIRTY_VOLUMES) && vol) upload_w(vol, st_pos.p + off, nn);
+        if ((dirty & SALVA_HIP_DIRTY_ACCELERATIONS) && acc_h) {
+            // accelerations are zero between steps; the first user upload must not resurrect stale staging values
+            if (!acc_user) SALVA_HIP_CHECK(hipMemsetAsync(st_acc.p, 0, (size_t)n * sizeof(float4), stream));
+            upload_xyz(acc_h, st_acc.p + off, nn, true);
+            acc_user = true;
+        }
+        if (dvs) upload_xyz(dvs, st_dv.p + off, nn, true);
+    }
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    order_invalidated(true);
+}
+
+// Fluid::add_particles (fluid.rs:126-150): append to the fluid's arrays — default volume, zero acceleration, zero
+// velocity change (the solver's buffers grow with zeros, dfsph_solver.rs:526-549) — without re-uploading the rest.
+void World::add_particles(uint32_t slot, uint64_t n_add, const float* pos, const float* vel_h) {
+    use_device();
+    fluid_span(slot);
+    if (comm && dist_started) { dist_add_particles(slot, n_add, pos, vel_h); return; }  // (collective, world_dist.hip)
+    if (n_add == 0) return;
+    if (!pos) throw HipError(SALVA_HIP_E_INVALID, "positions are required");
+    const uint64_t at = append_particles(slot, n_add);
+    upload_xyz(pos, st_pos.p + at, n_add, true);
+    if (vel_h) upload_xyz(vel_h, st_vel.p + at, n_add, true);
+}
+
+// The growing half of add_particles: room for n_add particles behind the fluid's last one, filled with the defaults (zero position,
+// velocity and acceleration, default volume, the inherited velocity-change tail).  Returns the staging index of the first new
+// particle; the caller writes positions (and velocities) there — from the host (add_particles) or on the device
+// (add_particles_sampled, sample.hip).
+uint64_t World::append_particles(uint32_t slot, uint64_t n_add) {
+    if ((uint64_t)n + n_add >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "more than 2^32 fluid particles on one device");
+    ensure_staging_current();
+    const uint64_t old_n = fluids[slot].n, off = fluid_offset(slot), at = off + old_n, old_total = n, new_total = old_total + n_add;
+    splice_fluid_rows({{0, at, true}, {0, n_add, false}, {at, old_total - at, true}}, new_total);
+    fluids[slot].n = old_n + n_add;
+    {   // (the new particles have the default volume: the fluid keeps ONE volume only if that is the one it had)
+        const float default_vol = default_particle_volume();
+        FluidSlot& f = fluids[slot];
+        if (old_n == 0) f.vol_uniform = default_vol;
+        else if (!(f.vol_uniform == default_vol)) f.vol_uniform = std::numeric_limits<float>::quiet_NaN();
+    }
+    fill_fluid_defaults(at, n_add);
+    {
+        auto it = sticky.find(slot);
+        if (it != sticky.end() && it->second.len > old_n) {  // `velocity_changes[slot].resize(n)` exposes the inherited tail
+            const uint64_t take = std::min<uint64_t>(it->second.len - old_n, n_add);
+            SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + at, it->second.data->p + old_n, take * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        }
+    }
+    stamp_fluid_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    order_invalidated(true);
+    return at;
+}
+
+// Fluid::apply_particles_removal (fluid.rs:88-98) together with the compaction of the solver's velocity_changes
+// (dfsph_solver.rs:550-560 / iisph_solver.rs:505-537): a stable compaction (`filter_from_mask`, helper.rs:4-12) of every
+// per-particle array of the fluid, on the device.  `mask[i] != 0` deletes particle i.  Returns the remaining count.
+uint64_t World::delete_particles(uint32_t slot, const uint8_t* mask) {
+    use_device();
+    const SlotSpan sp = fluid_span(slot);
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "host indices do not exist in a running multi-GPU world: delete by global id (salva_hip_delete_owned)");
+    const uint64_t nn = sp.n, off = sp.off;
+    if (nn == 0 || !mask) return nn;
+    ensure_staging_current();
+    // keep flags over the whole staging range (other fluids are kept)
+    std::vector<uint8_t> keep((size_t)n, 1);
+    uint64_t kept = 0;
+    for (uint64_t k = 0; k < nn; ++k) { keep[off + k] = mask[k] ? 0 : 1; kept += keep[off + k]; }
+    if (kept == nn) return nn;
+    DevBuf<uint8_t> d_keep;
+    DevBuf<uint32_t> d_num;
+    d_keep.ensure(n); d_num.ensure(1);
+    SALVA_HIP_CHECK(hipMemcpyAsync(d_keep.p, keep.data(), (size_t)n, hipMemcpyHostToDevice, stream));
+    const uint64_t new_total = (uint64_t)n - (nn - kept);
+    auto compact = [&](DevBuf<float4>& buf) {
+        DevBuf<float4> out;
+        out.ensure(std::max<uint64_t>(new_total, 1));
+        const size_t tb = select_flagged_temp_bytes(n);
+        ensure_cub_temp(tb);
+        select_flagged_f4(cub_temp.p, tb, buf.p, d_keep.p, out.p, d_num.p, n, stream);
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        std::swap(buf.p, out.p);
+        std::swap(buf.cap, out.cap);
+    };
+    compact(st_pos); compact(st_vel); compact(st_dv); compact(st_acc);
+    {
+        // an inherited solver buffer (world.h `sticky`) is filtered with the same mask by the reference — after its resize, so
+        // the entries beyond the fluid's particles (handed to particles added before the next step) just move down
+        auto it = sticky.find(slot);
+        if (it != sticky.end() && it->second.len) {
+            const uint64_t L = it->second.len, head = std::min<uint64_t>(L, nn);
+            std::vector<uint8_t> k2((size_t)L, 1);
+            uint64_t kept2 = 0;
+            for (uint64_t k = 0; k < L; ++k) { if (k < head) k2[k] = mask[k] ? 0 : 1; kept2 += k2[k]; }
+            DevBuf<uint8_t> d_k2;
+            d_k2.ensure(L);
+            SALVA_HIP_CHECK(hipMemcpyAsync(d_k2.p, k2.data(), (size_t)L, hipMemcpyHostToDevice, stream));
+            auto out = std::make_shared<DevBuf<float4>>();
+            out->ensure(std::max<uint64_t>(kept2, 1));
+            const size_t tb = select_flagged_temp_bytes((uint32_t)L);
+            ensure_cub_temp(tb);
+            select_flagged_f4(cub_temp.p, tb, it->second.data->p, d_k2.p, out->p, d_num.p, (uint32_t)L, stream);
+            SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+            it->second.data = out;
+            it->second.len = kept2;
+        }
+    }
+    n = (uint32_t)new_total;
+    fluids[slot].n = kept;
+    stamp_fluid_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    order_invalidated(true);
+    return kept;
+}
+
+void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
+    fluid_span(slot);
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_DEVICE)
+            throw HipError(SALVA_HIP_E_INVALID, "unknown non-pressure force kind (only built-ins run on the device)");
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_DEVICE) {
+            if (comm)  // ghost rows and the local view's ownership rules are not part of SalvaHipDeviceView
+                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE is not available in a decomposed world (salva_hip_set_domain)");
+            if (!(f[k].p[0] >= 0.0f && f[k].p[0] <= 7.0f && f[k].p[0] == (float)(uint32_t)f[k].p[0]))
+                throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FORCE_DEVICE: p[0] must be a sum of SALVA_HIP_DEVICE_NEEDS_* bits (0 ... 7)");
+        }
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009) {
+            if (comm)  // the rest lists cross slabs and have no ghost protocol
+                throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity is not available in a decomposed world (salva_hip_set_domain)");
+            for (int q = 3; q < 5; ++q)
+                if (!(f[k].p[q] == 0.0f || f[k].p[q] == 1.0f || f[k].p[q] == 2.0f || f[k].p[q] == 3.0f))
+                    throw HipError(SALVA_HIP_E_INVALID, "Becker2009Elasticity: p[3] / p[4] must be a SALVA_HIP_KERNEL_* kind");
+        }
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_DFSPH_VISCOSITY && !(f[k].p[0] >= 0.0f && f[k].p[0] <= 1.0f))
+            throw HipError(SALVA_HIP_E_INVALID, "The viscosity coefficient must be between 0.0 and 1.0.");  // dfsph_viscosity.rs:104-108
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_WCSPH_TENSION && f[k].p[1] != 0.0f)
+            // wcsph_surface_tension.rs:66-83 walks the fluid-fluid contacts while indexing the boundaries: it panics
+            throw HipError(SALVA_HIP_E_INVALID, "WCSPHSurfaceTension: a non-zero boundary coefficient panics in the reference (index out of bounds)");
+    // an elastic entry keeps its state when entry k is what it was (same kind, bit-identical p[]): the Python mirror re-uploads the
+    // whole list when any coefficient changes, and a block must not lose its rest shape because another force was appended
+    FluidSlot& fs = fluids[slot];
+    std::vector<std::shared_ptr<ElasticState>> el(nf);
+    for (uint32_t k = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_BECKER2009 && k < fs.forces.size() && k < fs.elastic.size() && fs.elastic[k] &&
+            fs.forces[k].kind == f[k].kind && memcmp(fs.forces[k].p, f[k].p, sizeof(f[k].p)) == 0)
+            el[k] = fs.elastic[k];
+    fs.forces.assign(f, f + nf);
+    fs.elastic = std::move(el);
+}
+
+// ContiguousArena::remove is a swap-remove (contiguous_arena.rs): the last object takes the freed slot.
+static std::vector<Piece> swap_remove_pieces(bool is_last, uint64_t off, uint64_t len, uint64_t loff, uint64_t llen) {
+    std::vector<Piece> pieces;
+    pieces.push_back({0, off, true});
+    if (!is_last) {
+        pieces.push_back({loff, llen, true});
+        pieces.push_back({off + len, loff - off - len, true});
+    }
+    return pieces;
+}
+
+void World::remove_fluid(uint32_t slot) {
+    use_device();
+    fluid_span(slot);
+    ensure_staging_current();
+    const uint32_t last = (uint32_t)fluids.size() - 1;
+    const uint64_t off = fluid_offset(slot), len = fluids[slot].n;
+    const uint64_t loff = fluid_offset(last), llen = fluids[last].n;
+    const uint64_t new_total = n - len;
+    {
+        // The solver's per-fluid buffers are positional in the reference and are NOT swapped with the object
+        // (liquid_world.rs:171-173 removes from the arena only; init_with_fluids then resizes `velocity_changes[slot]` /
+        // `pressures[slot]` to the new occupant's particle count, dfsph_solver.rs:526-549 / iisph_solver.rs:479-501): the
+        // fluid that moves into the freed slot inherits the removed fluid's velocity changes and pressures, truncated
+        // or zero-extended, and the buffer of the last slot lives on until the next step (a fluid added before then
+        // inherits it).  Reproduced: results must match the reference's, quirks included.  See `sticky` in world.h.
+        auto content_of = [&](uint32_t sl, uint64_t o, uint64_t l) {
+            auto it = sticky.find(sl);
+            if (it != sticky.end()) return it->second;
+            StickyBuf b;
+            b.data = std::make_shared<DevBuf<float4>>();
+            b.len = l;
+            b.data->ensure(std::max<uint64_t>(l, 1));
+            if (l) SALVA_HIP_CHECK(hipMemcpyAsync(b.data->p, st_dv.p + o, l * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            return b;
+        };
+        const StickyBuf A = content_of(slot, off, len);
+        const StickyBuf B = slot != last ? content_of(last, loff, llen) : StickyBuf{};
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        std::vector<Piece> dvp;
+        dvp.push_back({0, off, true});
+        if (slot != last) {
+            dvp.push_back({0, llen, false});
+            dvp.push_back({off + len, loff - off - len, true});
+        }
+        splice_fluid_rows(swap_remove_pieces(slot == last, off, len, loff, llen), new_total, &dvp);
+        sticky.erase(slot);
+        sticky.erase(last);
+        if (slot != last) {
+            const uint64_t inherit = std::min(A.len, llen);
+            if (inherit) SALVA_HIP_CHECK(hipMemcpyAsync(st_dv.p + off, A.data->p, inherit * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+            if (llen > inherit) SALVA_HIP_CHECK(hipMemsetAsync(st_dv.p + off + inherit, 0, (llen - inherit) * sizeof(float4), stream));
+            if (A.len > llen) sticky[slot] = A;  // its tail goes to particles added before the next step
+            sticky[last] = B;
+        } else {
+            sticky[last] = A;
+        }
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    if (slot != last) fluids[slot] = fluids[last];
+    fluids.pop_back();
+    stamp_fluid_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    order_invalidated(true);
+}
+
+// ------------------------------------------------------------------------------------------------ boundaries
+void World::set_boundary(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships,
+                         uint32_t filter, bool wants_forces) {
+    set_boundary_from(slot, nn, pos, vel_h, memberships, filter, wants_forces, nullptr);
+}
+
+// fill_dev != nullptr: the positions are written on the device — (*fill_dev)(first float4 of the slot), enqueued on the world's
+// stream — instead of uploaded from `pos` (set_boundary_sampling_from_shape, sample.hip)
+void World::set_boundary_from(uint32_t slot, uint64_t nn, const float* pos, const float* vel_h, uint32_t memberships, uint32_t filter,
+                              bool wants_forces, const std::function<void(float4*)>* fill_dev) {
+    use_device();
+    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
+    const bool is_new = slot == bounds.size();
+    const uint64_t old_n = is_new ? 0 : bounds[slot].n;
+    if ((uint64_t)nb - old_n + nn >= 0xfffffff0ull) throw HipError(SALVA_HIP_E_CAPACITY, "too many boundary particles");
+    if (nn && !pos && !fill_dev) throw HipError(SALVA_HIP_E_INVALID, "boundary positions are required");
+    if (is_new) bounds.emplace_back();
+    const uint64_t off = boundary_offset(slot);
+    const uint64_t old_total = nb, new_total = old_total - old_n + nn;
+    const float4 zero = make_float4(0, 0, 0, 0);
+    if (is_new || old_n != nn) {
+        splice_boundary_rows({{0, off, true}, {0, nn, false}, {off + old_n, old_total - off - old_n, true}}, new_total);
+        if (nn) {
+            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_pos.p + off, zero);
+            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_vel.p + off, zero);
+            k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bforce.p + off, zero);
+        }
+    }
+    BoundarySlot& b = bounds[slot];
+    b.n = nn; b.memberships = memberships; b.filter = filter; b.wants_forces = wants_forces;
+    b.dyn.reset();  // (re)uploading particles makes it a plain boundary; the sampling setters mark it again
+    b.vel_zero = true;
+    if (nn) {
+        scratch_f.ensure(3 * nn, stream, false, 1.1f);  // (whoever writes the positions: World::device_bytes stays what it was)
+        if (fill_dev) {
+            (*fill_dev)(bst_pos.p + off);
+            SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        } else {
+            upload_xyz(pos, bst_pos.p + off, nn, false);
+        }
+        if (vel_h)
+            for (uint64_t k = 0; k < 3 * nn && b.vel_zero; ++k) b.vel_zero = vel_h[k] == 0.0f;
+        if (vel_h) upload_xyz(vel_h, bst_vel.p + off, nn, false);
+        else k_fill_f4<<<nblk(nn), BLOCK, 0, stream>>>((uint32_t)nn, bst_vel.p + off, zero);
+    }
+    // boundary model ids ride in bst_vel.w
+    stamp_boundary_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    boundaries_invalidated();
+}
+
+void World::remove_boundary(uint32_t slot) {
+    use_device();
+    const SlotSpan sp = boundary_span(slot);
+    const uint32_t last = (uint32_t)bounds.size() - 1;
+    splice_boundary_rows(swap_remove_pieces(slot == last, sp.off, sp.n, boundary_offset(last), bounds[last].n), nb - sp.n);
+    if (slot != last) bounds[slot] = bounds[last];
+    bounds.pop_back();
+    stamp_boundary_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    boundaries_invalidated();
+}
+
+}  // namespace salva
