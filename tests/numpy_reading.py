@@ -275,35 +275,41 @@ class DenseWorld:
 
     # ------------------------------------------------------------------------------------------------------------
     def _forces(self, m, mb):
-        """predict_advection after `acceleration += gravity`: XSPHViscosity::solve (xsph_viscosity.rs:31-95) with the
-        timestep's CURRENT inv_dt — the previous step's, advance() comes afterwards."""
+        """predict_advection after `acceleration += gravity`: every fluid's XSPH entry, then its other forces in list order."""
         full = (self.ff, self.wff, self.gff, self.fb, self.wfb, self.gfb)
         for f in range(self.nfluids):
             if f not in self.xsph and not self.forces.get(f):
                 continue
-            # a fluid's forces see the contacts of ITS particles, and of those only the ones inside the fluid
-            # (`if c.i_model == c.j_model` in every fluid arm) plus all boundary contacts: the same tables with the other rows and
-            # the other fluids' columns blanked
-            rows = self.model == f
-            inside = rows[:, None] & rows[None, :]
-            self._rows, self._rho0f = rows, float(self.rho0[rows][0]) if rows.any() else 0.0
-            self.ff, self.wff, self.gff = full[0] & inside, np.where(inside, full[1], 0.0), np.where(inside[:, :, None], full[2], 0.0)
-            self.fb, self.wfb, self.gfb = full[3] & rows[:, None], np.where(rows[:, None], full[4], 0.0), np.where(rows[:, None, None], full[5], 0.0)
+            self._mask_to_fluid(f, full)
             if f in self.xsph:
-                cf, cb = self.xsph[f]
-                add = np.zeros_like(self.a)
-                if cf != 0.0:
-                    coef = cf * self.wff * (m / self.rho)[None, :]     # c.weight * volumes[j] * density0 / densities[j]
-                    add += (coef[:, :, None] * (self.v[None, :, :] - self.v[:, None, :])).sum(axis=1) * self.inv_dt
-                if cb != 0.0:
-                    coef = cb * self.wfb * mb / self.rho[:, None]
-                    delta = coef[:, :, None] * (self.vb[None, :, :] - self.v[:, None, :])
-                    add += delta.sum(axis=1) * self.inv_dt
-                    self.bforce += (delta * (-m * self.inv_dt)[:, None, None]).sum(axis=0)   # xsph_viscosity.rs:87-88
-                self.a += add
+                self.a += self._force_xsph(m, mb, *self.xsph[f])
             for force in self.forces.get(f, []):
                 self.a += getattr(self, "_force_" + force[0])(m, mb, *force[1:])
         self.ff, self.wff, self.gff, self.fb, self.wfb, self.gfb = full
+
+    def _mask_to_fluid(self, f, full):
+        """A fluid's forces see the contacts of ITS particles, and of those only the ones inside the fluid
+        (`if c.i_model == c.j_model` in every fluid arm) plus all boundary contacts: the tables `full` with the other rows and
+        the other fluids' columns blanked."""
+        rows = self.model == f
+        inside = rows[:, None] & rows[None, :]
+        self._rows, self._rho0f = rows, float(self.rho0[rows][0]) if rows.any() else 0.0
+        self.ff, self.wff, self.gff = full[0] & inside, np.where(inside, full[1], 0.0), np.where(inside[:, :, None], full[2], 0.0)
+        self.fb, self.wfb, self.gfb = full[3] & rows[:, None], np.where(rows[:, None], full[4], 0.0), np.where(rows[:, None, None], full[5], 0.0)
+
+    def _force_xsph(self, m, mb, cf, cb):
+        """XSPHViscosity::solve (xsph_viscosity.rs:31-95) with the timestep's CURRENT inv_dt — the previous step's, advance()
+        comes afterwards."""
+        add = np.zeros_like(self.a)
+        if cf != 0.0:
+            coef = cf * self.wff * (m / self.rho)[None, :]     # c.weight * volumes[j] * density0 / densities[j]
+            add += (coef[:, :, None] * (self.v[None, :, :] - self.v[:, None, :])).sum(axis=1) * self.inv_dt
+        if cb != 0.0:
+            coef = cb * self.wfb * mb / self.rho[:, None]
+            delta = coef[:, :, None] * (self.vb[None, :, :] - self.v[:, None, :])
+            add += delta.sum(axis=1) * self.inv_dt
+            self.bforce += (delta * (-m * self.inv_dt)[:, None, None]).sum(axis=0)   # xsph_viscosity.rs:87-88
+        return add
 
     # ---- the other built-in NonPressureForces, as dense pair expressions.  Self contacts are in the lists (contacts.rs) and
     # contribute nothing: r_ij = 0 makes v.r = 0 (not < 0), the gradient 0 and the unit direction undefined (-> zero vector).
