@@ -129,7 +129,7 @@ pub enum CompoundPartShape<'a> {
 /// parry's `Compound` on the device (`salva_hip_create_compound`): 1 to 64 posed parts.  From a parry compound: one
 /// part per `(part_pos, shape)` of `compound.shapes()`, a convex part handed over as the oriented triangle mesh of its hull.  Belongs
 /// to the world it was created in; `destroy` hands it back (refused while a dynamically sampled boundary still uses it).  Ray
-/// sampling of a compound is not on the device.
+/// sampling of a compound is on the device as well: `surface_ray_sample` / `volume_ray_sample`.
 pub struct Compound {
     id: u32,
 }
@@ -158,6 +158,33 @@ impl Compound {
 
     pub fn destroy(self, world: &mut LiquidWorld) -> Result<(), Error> {
         check(unsafe { ffi::salva_hip_destroy_compound(world.raw(), self.id) })
+    }
+
+    fn ray_sample(&self, world: &mut LiquidWorld, particle_rad: Real, mode: i32) -> Result<Vec<Point<Real>>, Error> {
+        let raw = world.raw();
+        let n = unsafe { ffi::salva_hip_sample_compound(raw, self.id, particle_rad, mode, 0, std::ptr::null_mut()) };
+        if n < 0 {
+            check(n as i32)?;
+        }
+        let mut pts = vec![Point::<Real>::origin(); n as usize];
+        if n > 0 {
+            let m = unsafe { ffi::salva_hip_sample_compound(raw, self.id, particle_rad, mode, n as u64, pts.as_mut_ptr() as *mut f32) };
+            if m < 0 {
+                check(m as i32)?;
+            }
+        }
+        Ok(pts)
+    }
+
+    /// `shape_surface_ray_sample(&compound, particle_rad)` on the device (`salva_hip_sample_compound`): one thread per lattice ray
+    /// casts at every part in the part's own frame, no host casts.
+    pub fn surface_ray_sample(&self, world: &mut LiquidWorld, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+        self.ray_sample(world, particle_rad, ffi::SALVA_HIP_SAMPLE_SURFACE).ok()
+    }
+
+    /// `shape_volume_ray_sample(&compound, particle_rad)` on the device.
+    pub fn volume_ray_sample(&self, world: &mut LiquidWorld, particle_rad: Real) -> Option<Vec<Point<Real>>> {
+        self.ray_sample(world, particle_rad, ffi::SALVA_HIP_SAMPLE_VOLUME).ok()
     }
 }
 

@@ -799,8 +799,7 @@ int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t 
  * parts); non-positive or non-finite params; a non-finite translation or a rotation that is not unit within 1e-3; an unknown mesh
  * handle; destroying a mesh that a compound still names; destroying a compound that is still the collider of a dynamically sampled
  * boundary (salva_hip_clear_boundary_sampling, a re-registration or the boundary's removal release it).
- * Out of scope: ray sampling of a compound (rays are axis-aligned in the compound's frame, not in a rotated part's: it stays with
- * salva_hip_sample_host_shape), decomposed worlds, nested compounds, convex-hull construction (hand the hull over as an oriented mesh). */
+ * Out of scope: decomposed worlds, nested compounds, convex-hull construction (hand the hull over as an oriented mesh). */
 enum { SALVA_HIP_SHAPE_COMPOUND = 6 };            /* never passed in a SalvaHipShape */
 enum { SALVA_HIP_COMPOUND_MAX_PARTS = 64 };
 typedef struct SalvaHipCompoundPart {
@@ -826,6 +825,21 @@ int64_t salva_hip_particles_intersecting_compound(SalvaHipWorld* world, const fl
                                                   uint32_t* indices);
 int64_t salva_hip_particles_intersecting_mesh(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
                                               uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices);
+/* salva_hip_sample_mesh, salva_hip_add_particles_sampled_mesh and salva_hip_set_boundary_sampling_from_mesh with a compound in place
+ * of the mesh; conventions, return values and error codes are theirs.  The lattice is that of the compound's local box, the merge of
+ * its parts' boxes.  One thread per ray casts against every part in the part's own frame - a reading of parry 0.18's
+ * Compound::cast_local_ray with solid = false: the cast at a part is the smallest t >= 0 at which the ray crosses the part's boundary
+ * (the entry from outside, the exit from inside), the compound's is the smallest over its parts, equal t from two parts is one hit -
+ * so the faces of overlapping parts that lie inside the compound are hits, as they are for parry.  A ray with more than 64 accepted
+ * hits ends the call with SALVA_HIP_E_CAPACITY; an unknown handle is SALVA_HIP_E_INVALID.  A boundary sampled this way keeps its
+ * points, not the compound: salva_hip_destroy_compound succeeds afterwards.  The last two are refused in a running decomposed world,
+ * like their shape twins. */
+int64_t salva_hip_sample_compound(SalvaHipWorld* world, uint32_t compound, float particle_rad, int32_t mode, uint64_t capacity,
+                                  float* out_xyz);
+int64_t salva_hip_add_particles_sampled_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, const float translation[3],
+                                                 const float rotation_ijkw[4], int32_t mode, const float velocity[3]);
+int64_t salva_hip_set_boundary_sampling_from_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
+                                                      uint32_t filter);
 
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);

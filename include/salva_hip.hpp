@@ -247,10 +247,11 @@ class Mesh {
 };
 
 // parry's Compound on the device (salva_hip_create_compound): a list of 1 .. 64 posed parts, each a ball, a cuboid, a
-// capsule, a cylinder or a Mesh of the same world; RAII over the handle.  Accepted by Boundary::dynamic_compound and
-// LiquidWorld::particles_intersecting_shape.  Belongs to the world it was created in and must be destroyed before it and before the
-// meshes it names; a compound that is still the collider of a dynamically sampled boundary stays alive in the library until that
-// boundary lets go of it.  Ray sampling of a compound is not on the device (salva_hip_sample_host_shape).
+// capsule, a cylinder or a Mesh of the same world; RAII over the handle.  Accepted by Boundary::dynamic_compound,
+// Boundary::sampled_from_shape, LiquidWorld::add_particles_from_shape, LiquidWorld::particles_intersecting_shape and
+// sampling::shape_surface_ray_sample / shape_volume_ray_sample.  Belongs to the world it was created in and must be destroyed before it
+// and before the meshes it names; a compound that is still the collider of a dynamically sampled boundary stays alive in the library
+// until that boundary lets go of it (a boundary sampled from it keeps its points only).
 class Compound {
   public:
     struct Part {
@@ -340,7 +341,7 @@ class Boundary {  // object/boundary.rs
         return b;
     }
     // ... and for a compound of the world (salva_hip_set_boundary_dynamic_sampling_compound)
-    uint32_t compound_id = 0;  // with dynamic_shape.kind == SALVA_HIP_SHAPE_COMPOUND
+    uint32_t compound_id = 0;  // with dynamic_shape.kind / sampled_shape.kind == SALVA_HIP_SHAPE_COMPOUND
     static Boundary dynamic_compound(const Compound& compound, InteractionGroups groups = {}) {
         Boundary b({}, groups);
         b.dynamic_shape = SalvaHipShape{SALVA_HIP_SHAPE_COMPOUND, {0, 0, 0}};
@@ -359,6 +360,13 @@ class Boundary {  // object/boundary.rs
     static Boundary sampled_from_shape(const SalvaHipShape& shape, InteractionGroups groups = {}) {
         Boundary b({}, groups);
         b.sampled_shape = shape;
+        return b;
+    }
+    // ... of a compound (salva_hip_set_boundary_sampling_from_compound): the boundary keeps its points, not the compound
+    static Boundary sampled_from_shape(const Compound& compound, InteractionGroups groups = {}) {
+        Boundary b({}, groups);
+        b.sampled_shape = SalvaHipShape{SALVA_HIP_SHAPE_COMPOUND, {0, 0, 0}};
+        b.compound_id = compound.id();
         return b;
     }
     size_t num_particles() const {
@@ -814,6 +822,23 @@ class LiquidWorld {  // liquid_world.rs
         if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
         return (size_t)k;
     }
+    size_t add_particles_from_shape(FluidHandle h, const Compound& compound, const Vec3& translation,
+                                    const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1}, int mode = SALVA_HIP_SAMPLE_VOLUME,
+                                    const Vec3* velocity = nullptr) {
+        upload_new_objects();
+        Fluid& f = fluids_[h];
+        upload(f, (uint32_t)h);
+        const int64_t k = salva_hip_add_particles_sampled_compound(w_, (uint32_t)h, compound.id(), translation.data(), rotation_ijkw.data(), mode,
+                                                                   velocity ? velocity->data() : nullptr);
+        if (k < 0) check((int)k);
+        const size_t n = f.positions.size() + (size_t)k;
+        f.positions.resize(n); f.velocities.resize(n);
+        f.accelerations.resize(n, Vec3{0, 0, 0});
+        f.volumes.resize(n, f.default_particle_volume());
+        f.deleted_.resize(n, false);
+        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        return (size_t)k;
+    }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));
     }
@@ -989,6 +1014,9 @@ class LiquidWorld {  // liquid_world.rs
         if (b.sampled_shape.kind) {
             const int64_t k = b.sampled_shape.kind == SALVA_HIP_SHAPE_MESH
                                   ? salva_hip_set_boundary_sampling_from_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter)
+                              : b.sampled_shape.kind == SALVA_HIP_SHAPE_COMPOUND
+                                  ? salva_hip_set_boundary_sampling_from_compound(w_, slot, b.compound_id, b.interaction_groups.memberships,
+                                                                                  b.interaction_groups.filter)
                                   : salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, b.interaction_groups.memberships,
                                                                                b.interaction_groups.filter);
             if (k < 0) check((int)k);
@@ -1110,6 +1138,22 @@ inline std::vector<Vec3> shape_surface_ray_sample(LiquidWorld& world, const Mesh
 }
 inline std::vector<Vec3> shape_volume_ray_sample(LiquidWorld& world, const Mesh& mesh, Real particle_rad) {
     return ray_sample(world, mesh, particle_rad, SALVA_HIP_SAMPLE_VOLUME);
+}
+inline std::vector<Vec3> ray_sample(LiquidWorld& world, const Compound& compound, Real particle_rad, int mode) {
+    const int64_t n = salva_hip_sample_compound(world.handle(), compound.id(), particle_rad, mode, 0, nullptr);
+    if (n < 0) check((int)n);
+    std::vector<Vec3> pts((size_t)n);
+    if (n) {
+        const int64_t m = salva_hip_sample_compound(world.handle(), compound.id(), particle_rad, mode, (uint64_t)n, pts[0].data());
+        if (m < 0) check((int)m);
+    }
+    return pts;
+}
+inline std::vector<Vec3> shape_surface_ray_sample(LiquidWorld& world, const Compound& compound, Real particle_rad) {
+    return ray_sample(world, compound, particle_rad, SALVA_HIP_SAMPLE_SURFACE);
+}
+inline std::vector<Vec3> shape_volume_ray_sample(LiquidWorld& world, const Compound& compound, Real particle_rad) {
+    return ray_sample(world, compound, particle_rad, SALVA_HIP_SAMPLE_VOLUME);
 }
 }  // namespace sampling
 

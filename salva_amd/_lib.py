@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_set_device_force_callback", "salva_hip_device_view_read", "salva_hip_get_device_force_stats",
     "salva_hip_create_compound", "salva_hip_destroy_compound", "salva_hip_set_boundary_dynamic_sampling_compound",
     "salva_hip_particles_intersecting_compound", "salva_hip_particles_intersecting_mesh",
+    "salva_hip_sample_compound", "salva_hip_add_particles_sampled_compound", "salva_hip_set_boundary_sampling_from_compound",
 ]
 
 
@@ -362,6 +363,13 @@ def lib():
         L.salva_hip_particles_intersecting_compound.restype = C.c_int64
         L.salva_hip_particles_intersecting_mesh.argtypes = [vp, fp, fp, u32, u64, up, up, up]
         L.salva_hip_particles_intersecting_mesh.restype = C.c_int64
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_sample_compound"):
+        L.salva_hip_sample_compound.argtypes = [vp, u32, f32, i32, u64, fp]
+        L.salva_hip_sample_compound.restype = C.c_int64
+        L.salva_hip_add_particles_sampled_compound.argtypes = [vp, u32, u32, fp, fp, i32, fp]
+        L.salva_hip_add_particles_sampled_compound.restype = C.c_int64
+        L.salva_hip_set_boundary_sampling_from_compound.argtypes = [vp, u32, u32, u32, u32]
+        L.salva_hip_set_boundary_sampling_from_compound.restype = C.c_int64
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

@@ -101,12 +101,12 @@ class StaticSampling:
     @classmethod
     def from_shape(cls, shape) -> "StaticSampling":
         """`StaticSampling(shape_surface_ray_sample(shape, particle_radius))` with the points produced and kept on the device
-        (salva_hip_set_boundary_sampling_from_shape); `shape` is what make_shape takes, or a
-        sampling.Mesh (salva_hip_set_boundary_sampling_from_mesh)."""
-        from .sampling import Mesh
+        (salva_hip_set_boundary_sampling_from_shape); `shape` is what make_shape takes, a
+        sampling.Mesh (salva_hip_set_boundary_sampling_from_mesh) or a sampling.Compound (salva_hip_set_boundary_sampling_from_compound)."""
+        from .sampling import Compound, Mesh
 
         self = cls(np.zeros((0, 3), F32))
-        self.shape = shape if isinstance(shape, (L.Shape, Mesh)) else make_shape(shape)
+        self.shape = shape if isinstance(shape, (L.Shape, Mesh, Compound)) else make_shape(shape)
         return self
 
 
@@ -274,8 +274,11 @@ class ColliderCouplingSet:
                     k = int(world._L.salva_hip_set_boundary_sampling_from_shape(
                         world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
                 else:
-                    k = int(world._L.salva_hip_set_boundary_sampling_from_mesh(
-                        world._h, b._slot, e.sampling.shape.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
+                    from .sampling import Compound
+
+                    from_handle = (world._L.salva_hip_set_boundary_sampling_from_compound if isinstance(e.sampling.shape, Compound)
+                                   else world._L.salva_hip_set_boundary_sampling_from_mesh)
+                    k = int(from_handle(world._h, b._slot, e.sampling.shape.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
                 if k < 0:
                     L.check(k)
                 b._n_sampled = k

@@ -21,6 +21,7 @@
 #include "dcs.h"
 #include "mesh.h"
 #include "pose.h"
+#include "raycast.h"
 
 // (the Makefile's -ffp-contract=off already says so; the sampler's bit-for-bit specification must not depend on a build flag)
 #pragma clang fp contract(off)
@@ -168,8 +169,11 @@ __device__ __forceinline__ void mark_bit(const SampleGrid& g, int axis, uint32_t
     atomicOr(&bits[word_of(g, qx, qy, qz)], 1u << (qz & 31u));
 }
 
-__global__ __launch_bounds__(BLOCK) void k_sample_mesh_mark(SampleGrid g, MeshDev mesh, int volume, uint32_t* __restrict__ bits,
-                                                            uint32_t* __restrict__ err) {
+// One lattice ray of a shape that is cast at: `cast(axis, cj, ck, o)` is the toi of the ray along +axis through (cj, ck) from the
+// coordinate o, +inf for a miss.
+template <typename Cast>
+__device__ __forceinline__ void mark_ray_hits(const SampleGrid& g, int volume, uint32_t* __restrict__ bits, uint32_t* __restrict__ err,
+                                              const Cast& cast) {
     uint64_t t = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     const uint64_t r0 = (uint64_t)g.ny * g.nz, r1 = (uint64_t)g.nz * g.nx, r2 = (uint64_t)g.nx * g.ny;
     int axis;
@@ -189,10 +193,10 @@ __global__ __launch_bounds__(BLOCK) void k_sample_mesh_mark(SampleGrid g, MeshDe
     float o = oi, prev = 0.0f;
     bool entry = true, has_prev = false;
     for (int hits = 0;; ++hits) {
-        const float h = mesh_next_hit(mesh, axis, cj, ck, o);
-        if (!(h < __builtin_inff())) break;
+        const float toi = cast(axis, cj, ck, o);
+        if (!(toi < __builtin_inff())) break;
         if (hits == MESH_MAX_HITS) { atomicOr(err, 1u); break; }
-        const float toi = h - o, impact = o + toi;
+        const float impact = o + toi;
         if (!volume) {
             const float f = (impact - oi) / g.s;
             const uint32_t q = sat_u32(entry ? ceilf(f) : floorf(f));
@@ -208,6 +212,21 @@ __global__ __launch_bounds__(BLOCK) void k_sample_mesh_mark(SampleGrid g, MeshDe
         }
         o = o + (toi + step);
     }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_sample_mesh_mark(SampleGrid g, MeshDev mesh, int volume, uint32_t* __restrict__ bits,
+                                                            uint32_t* __restrict__ err) {
+    mark_ray_hits(g, volume, bits, err, [&](int axis, float cj, float ck, float o) { return mesh_next_hit(mesh, axis, cj, ck, o) - o; });
+}
+
+// The same for a compound (raycast.h): every accepted hit is one walk over the parts.  The part index is wave-uniform
+// and the table const __restrict__, so the parts' records come through the scalar cache as in k_dcs_compound_project.
+__global__ __launch_bounds__(BLOCK) void k_compound_mark(SampleGrid g, const CompoundPartDev* __restrict__ parts, uint32_t nparts, int volume,
+                                                         uint32_t* __restrict__ bits, uint32_t* __restrict__ err) {
+    mark_ray_hits(g, volume, bits, err, [&](int axis, float cj, float ck, float o) {
+        return compound_cast_ray<true>(parts, nparts, sel3(axis, o, ck, cj), sel3(axis, cj, o, ck), sel3(axis, ck, cj, o), axis == 0 ? 1.0f : 0.0f,
+                                       axis == 1 ? 1.0f : 0.0f, axis == 2 ? 1.0f : 0.0f);
+    });
 }
 
 // cnt[w] = set bits of word w; cnt[nwords] = 0, so that the exclusive scan over nwords + 1 entries ends in the total
@@ -494,20 +513,29 @@ int64_t World::set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipSha
     return boundary_from_sampled(slot, L, memberships, filter);
 }
 
-// ---- the same three for a triangle mesh (mesh.h): a second mark kernel, everything behind it shared
-void World::sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L) {
+// ---- the same three for a triangle mesh (mesh.h): a second mark kernel, everything behind it shared.  `launch` starts
+// the mark kernel of a shape that is cast at hit by hit (a mesh, a compound) over the lattice of [mins, maxs]; its error word is a
+// ray with more than 64 accepted hits.
+void World::sample_mark_cast(const float mins[3], const float maxs[3], float particle_rad, int mode, SampleLattice& L,
+                             const std::function<void(const SampleGrid&, uint64_t, int)>& launch, const char* too_many_hits) {
     check_sample_args(particle_rad, mode);
-    sample_lattice(mesh.mins, mesh.maxs, particle_rad, L);
+    sample_lattice(mins, maxs, particle_rad, L);
     const SampleGrid& g = L.g;
     const uint64_t rays = (uint64_t)g.ny * g.nz + (uint64_t)g.nz * g.nx + (uint64_t)g.nx * g.ny;
     smp_err.ensure(1);
     SALVA_HIP_CHECK(hipMemsetAsync(smp_err.p, 0, sizeof(uint32_t), stream));
-    k_sample_mesh_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, mesh.dev(), mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0, smp_bits.p, smp_err.p);
+    launch(g, rays, mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0);
     SALVA_HIP_CHECK(hipGetLastError());
     uint32_t err = 0;
     SALVA_HIP_CHECK(hipMemcpyAsync(&err, smp_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    if (err) throw HipError(SALVA_HIP_E_CAPACITY, "mesh sampling: a ray crosses the mesh more than 64 times");
+    if (err) throw HipError(SALVA_HIP_E_CAPACITY, too_many_hits);
+}
+
+void World::sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L) {
+    sample_mark_cast(mesh.mins, mesh.maxs, particle_rad, mode, L, [&](const SampleGrid& g, uint64_t rays, int volume) {
+        k_sample_mesh_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, mesh.dev(), volume, smp_bits.p, smp_err.p);
+    }, "mesh sampling: a ray crosses the mesh more than 64 times");
 }
 
 int64_t World::sample_mesh(uint32_t mesh, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
@@ -531,6 +559,38 @@ int64_t World::set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uin
     if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
     SampleLattice L;
     sample_mark_mesh(*mesh_at(mesh), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
+    return boundary_from_sampled(slot, L, memberships, filter);
+}
+
+// ---- and for a compound (raycast.h): a third mark kernel.  The lattice is that of the unloosened merge of the parts'
+// boxes, parry's local AABB of a compound.  Nothing keeps the compound: a boundary sampled from it holds its points only.
+void World::sample_mark_compound(const CompoundRes& c, float particle_rad, int mode, SampleLattice& L) {
+    sample_mark_cast(c.mins, c.maxs, particle_rad, mode, L, [&](const SampleGrid& g, uint64_t rays, int volume) {
+        k_compound_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, c.parts.p, c.nparts, volume, smp_bits.p, smp_err.p);
+    }, "compound sampling: a ray crosses the parts' boundaries more than 64 times");
+}
+
+int64_t World::sample_compound(uint32_t compound, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
+    use_device();
+    SampleLattice L;
+    sample_mark_compound(*compound_at(compound), particle_rad, mode, L);
+    return sample_download(L, capacity, out_xyz);
+}
+
+int64_t World::add_particles_sampled_compound(uint32_t slot, uint32_t compound, const float t[3], const float q[4], int mode, const float* vel_h) {
+    use_device();
+    check_add_sampled(slot, t, q);
+    SampleLattice L;
+    sample_mark_compound(*compound_at(compound), prm.particle_radius, mode, L);
+    return append_sampled(slot, L, t, q, vel_h);
+}
+
+int64_t World::set_boundary_sampling_from_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter) {
+    use_device();
+    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
+    SampleLattice L;
+    sample_mark_compound(*compound_at(compound), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
     return boundary_from_sampled(slot, L, memberships, filter);
 }
 

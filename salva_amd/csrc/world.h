@@ -22,6 +22,7 @@ namespace salva {
 
 struct DcsParams;  // dcs.h
 struct DcsbEntry;
+struct SampleGrid;  // sample.hip
 
 // ColliderSampling::DynamicContactSampling (integrations/rapier/fluids_pipeline.rs:42-43): the one description of a dynamically
 // sampled collider.  The boundary's particles are re-emitted by every step (World::run_dynamic_sampling, world_coupling.hip); a
@@ -139,6 +140,9 @@ class World {
     uint32_t create_compound(const SalvaHipCompoundPart* parts, uint32_t nparts);
     void destroy_compound(uint32_t compound);
     void set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
+    int64_t sample_compound(uint32_t compound, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
+    int64_t add_particles_sampled_compound(uint32_t slot, uint32_t compound, const float t[3], const float q[4], int mode, const float* vel);
+    int64_t set_boundary_sampling_from_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
     uint64_t particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                    uint32_t* indices);
     uint64_t particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
@@ -251,7 +255,10 @@ class World {
     int64_t sample_download(const SampleLattice& L, uint64_t capacity, float* out_xyz);
     void sample_mark(const SalvaHipShape& shape, float particle_rad, int mode, SampleLattice& L);
     void sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L);
-    DevBuf<uint32_t> smp_err;  // k_sample_mesh_mark: a ray with more than 64 accepted hits
+    void sample_mark_compound(const CompoundRes& c, float particle_rad, int mode, SampleLattice& L);
+    void sample_mark_cast(const float mins[3], const float maxs[3], float particle_rad, int mode, SampleLattice& L,
+                          const std::function<void(const SampleGrid&, uint64_t, int)>& launch, const char* too_many_hits);
+    DevBuf<uint32_t> smp_err;  // k_sample_mesh_mark, k_compound_mark: a ray with more than 64 accepted hits
     void check_add_sampled(uint32_t slot, const float t[3], const float q[4]) const;
     int64_t append_sampled(uint32_t slot, const SampleLattice& L, const float t[3], const float q[4], const float* vel);
     int64_t boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint32_t memberships, uint32_t filter);

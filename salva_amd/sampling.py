@@ -1,7 +1,7 @@
 """sampling/ray_sampling.rs: `shape_surface_ray_sample` / `shape_volume_ray_sample` on the device (salva_hip_sample_shape,
 DESIGN.md §13).  A shape is what salva_amd.coupling.make_shape takes — ("ball", r), ("cuboid", (hx, hy, hz)), ("capsule", hh, r),
-("cylinder", hh, r) — a Mesh (triangle mesh or height field, cast at on the device: DESIGN.md §14), or a HostRayShape for anything
-else."""
+("cylinder", hh, r) — a Mesh (triangle mesh or height field, cast at on the device: DESIGN.md §14), a Compound of such parts
+(DESIGN.md §17), or a HostRayShape for anything else."""
 from __future__ import annotations
 
 import ctypes as C
@@ -103,8 +103,10 @@ class Mesh:
 class Compound:
     """parry's `Compound` on the device (salva_hip_create_compound): `parts` is a list of (shape, translation,
     rotation) with `shape` anything coupling.make_shape accepts or a Mesh, and (translation, unit quaternion (i, j, k, w)) the
-    part's pose in the compound's frame.  Accepted by DynamicContactSampling and LiquidWorld.particles_intersecting_shape; ray
-    sampling of a compound stays with HostRayShape.  The device copy belongs to a world and is made on first use there."""
+    part's pose in the compound's frame.  Accepted wherever a shape is: shape_surface_ray_sample / shape_volume_ray_sample (one
+    thread per ray casts at every part in the part's frame: salva_hip_sample_compound), Fluid.add_particles_from_shape,
+    StaticSampling.from_shape, DynamicContactSampling and LiquidWorld.particles_intersecting_shape.  The device copy belongs to a
+    world and is made on first use there."""
 
     def __init__(self, parts):
         from .coupling import make_shape
@@ -159,6 +161,9 @@ def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
     elif isinstance(shape, Mesh):
         def call(cap, out):
             return w._L.salva_hip_sample_mesh(w._h, shape.handle(w), float(particle_rad), mode, cap, out)
+    elif isinstance(shape, Compound):
+        def call(cap, out):
+            return w._L.salva_hip_sample_compound(w._h, shape.handle(w), float(particle_rad), mode, cap, out)
     else:
         s = shape if isinstance(shape, L.Shape) else make_shape(shape)
 

@@ -500,7 +500,7 @@ class Fluid:
 
     def add_particles_from_shape(self, shape, translation=(0.0, 0.0, 0.0), rotation=(0.0, 0.0, 0.0, 1.0), mode: int = 1, velocity=None) -> int:
         """`add_particles(&shape_volume_ray_sample(shape, r).transform_by(pose), &[velocity; n])` on the device
-        (salva_hip_add_particles_sampled): the shape — what coupling.make_shape takes, or a sampling.Mesh — is sampled at the world's particle radius
+        (salva_hip_add_particles_sampled): the shape — what coupling.make_shape takes, a sampling.Mesh or a sampling.Compound — is sampled at the world's particle radius
         (mode 1 = volume, 0 = surface), posed by `translation` and the unit quaternion `rotation` (i, j, k, w) and appended; the
         points never visit the host.  The fluid must live in a world.  Returns the number of particles added."""
         from .coupling import make_shape
@@ -511,13 +511,15 @@ class Fluid:
         w._upload_new_objects()
         if self._resized or self._dirty:
             w._sync_fluid(self, apply_removal=False)
-        from .sampling import Mesh
+        from .sampling import Compound, Mesh
 
         t, q = np.ascontiguousarray(translation, F32).reshape(3), np.ascontiguousarray(rotation, F32).reshape(4)
         v = np.ascontiguousarray(velocity, F32).reshape(3) if velocity is not None else None
         self._pull()  # (the host copies must be current BEFORE the fluid grows: a read-back fills as many rows as the device holds)
         if isinstance(shape, Mesh):  # (salva_hip_add_particles_sampled_mesh)
             k = int(w._L.salva_hip_add_particles_sampled_mesh(w._h, self._slot, shape.handle(w), _fp(t), _fp(q), int(mode), _fp(v)))
+        elif isinstance(shape, Compound):  # (salva_hip_add_particles_sampled_compound)
+            k = int(w._L.salva_hip_add_particles_sampled_compound(w._h, self._slot, shape.handle(w), _fp(t), _fp(q), int(mode), _fp(v)))
         else:
             s = shape if isinstance(shape, L.Shape) else make_shape(shape)
             k = int(w._L.salva_hip_add_particles_sampled(w._h, self._slot, C.byref(s), _fp(t), _fp(q), int(mode), _fp(v)))
