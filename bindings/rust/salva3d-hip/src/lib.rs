@@ -7,6 +7,7 @@
 pub mod ffi;
 pub mod dist;
 mod liquid_world;
+pub mod region;
 #[cfg(feature = "rapier")]
 pub mod coupling;
 #[cfg(feature = "parry")]
@@ -14,3 +15,4 @@ pub mod sampling;
 
 pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};
+pub use region::Region;

@@ -200,6 +200,7 @@ pub struct LiquidWorld {
     last_stats: ffi::SalvaHipStepStats,
     cfl_mode: i32,       // what set_cfl_substepping was last called with (coupling.rs: the manager's calls move into the substep loop)
     device_forces: Box<DeviceForceTable>,  // boxed: the C side holds its address as the device callback's user pointer
+    nsinks: usize,       // registered sinks (add_sink): a step may shorten fluids on the device
 }
 
 // Send: the C side keeps no thread-affine state — every entry point selects the world's device and stream itself, and the
@@ -266,6 +267,7 @@ impl LiquidWorld {
             last_stats: unsafe { std::mem::zeroed() },
             cfl_mode: 0,
             device_forces: Box::new(Vec::new()),
+            nsinks: 0,
         })
     }
 
@@ -490,12 +492,107 @@ impl LiquidWorld {
         Ok(())
     }
 
+    /// Deletes, at once and on the device, the particles of `fluid` (None: of every fluid) that `region` selects at their current
+    /// positions (`salva_hip_delete_particles_in_region`): what examples3d/faucet3.rs:69-104 does with a host scan and
+    /// `delete_particle_at_next_timestep`, without a position crossing PCIe for the test.  The host arrays are compacted with the
+    /// mask the call returns.  Returns the number of particles deleted.
+    pub fn delete_particles_in(&mut self, region: &crate::Region, fluid: Option<FluidHandle>) -> Result<usize, Error> {
+        self.sync()?;
+        self.upload()?;
+        self.unpin_all(); // (the Vecs are about to shrink)
+        let no_fluid = || Error { code: ffi::SALVA_HIP_E_INVALID, message: "no such fluid".into() };
+        let only = match fluid {
+            Some(h) => Some(self.fluids.iter().position(|(k, _)| k == h).ok_or_else(no_fluid)?),
+            None => None,
+        };
+        let total: usize = self.fluids.as_slice().iter().enumerate().filter(|(s, _)| only.map_or(true, |o| o == *s)).map(|(_, f)| f.num_particles()).sum();
+        let mut mask = vec![0u8; total.max(1)];
+        let slot = only.map_or(ffi::SALVA_HIP_ALL_FLUIDS, |s| s as u32);
+        let k = unsafe { ffi::salva_hip_delete_particles_in_region(self.raw, &region.raw, slot, mask.as_mut_ptr()) };
+        if k < 0 {
+            check(k as i32)?;
+        }
+        let mut at = 0;
+        for (s, f) in self.fluids.as_mut_slice().iter_mut().enumerate() {
+            if k == 0 || !only.map_or(true, |o| o == s) {
+                continue;
+            }
+            let n = f.num_particles();
+            for i in 0..n {
+                if mask[at + i] != 0 {
+                    f.delete_particle_at_next_timestep(i);
+                }
+            }
+            f.apply_particles_removal(); // (pub(crate) upstream: README.md)
+            at += n;
+        }
+        Ok(k as usize)
+    }
+    /// Registers `region` as a sink of `fluid` (None: of every fluid): every step starts by deleting what it selects, on the device,
+    /// at the cost of one small host wait (`salva_hip_add_sink`).  Returns the sink's handle.
+    pub fn add_sink(&mut self, region: &crate::Region, fluid: Option<FluidHandle>) -> Result<u32, Error> {
+        self.upload()?;
+        let no_fluid = || Error { code: ffi::SALVA_HIP_E_INVALID, message: "no such fluid".into() };
+        let slot = match fluid {
+            Some(h) => self.fluids.iter().position(|(k, _)| k == h).ok_or_else(no_fluid)? as u32,
+            None => ffi::SALVA_HIP_ALL_FLUIDS,
+        };
+        let mut sink = 0u32;
+        check(unsafe { ffi::salva_hip_add_sink(self.raw, &region.raw, slot, &mut sink) })?;
+        self.nsinks += 1;
+        Ok(sink)
+    }
+    pub fn remove_sink(&mut self, sink: u32) -> Result<(), Error> {
+        check(unsafe { ffi::salva_hip_remove_sink(self.raw, sink) })?;
+        self.nsinks -= 1;
+        Ok(())
+    }
+    pub fn set_sink_pose(&mut self, sink: u32, translation: &Vector3<Real>, rotation: &na::UnitQuaternion<Real>) -> Result<(), Error> {
+        let (t, q) = ([translation.x, translation.y, translation.z], [rotation.i, rotation.j, rotation.k, rotation.w]);
+        check(unsafe { ffi::salva_hip_set_sink_pose(self.raw, sink, t.as_ptr(), q.as_ptr()) })
+    }
+    /// [particles the sink deleted in the last step, in total]
+    pub fn sink_stats(&self, sink: u32) -> Result<[u64; 2], Error> {
+        let mut out = [0u64; 2];
+        check(unsafe { ffi::salva_hip_get_sink_stats(self.raw, sink, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// A step in which a sink fired shortened fluids on the device: the host arrays follow — the tail goes (every array and the
+    /// deletion mask, through the fluid's own removal), the volumes come from the device, positions and velocities with the next `sync`.
+    fn follow_sinks(&mut self) -> Result<(), Error> {
+        let mut shrunk = false;
+        for (slot, f) in self.fluids.as_slice().iter().enumerate() {
+            shrunk |= unsafe { ffi::salva_hip_fluid_len(self.raw, slot as u32) } as usize != f.num_particles();
+        }
+        if !shrunk {
+            return Ok(());
+        }
+        self.unpin_all();
+        for (slot, f) in self.fluids.as_mut_slice().iter_mut().enumerate() {
+            let (n, old) = (unsafe { ffi::salva_hip_fluid_len(self.raw, slot as u32) } as usize, f.num_particles());
+            if n >= old {
+                continue;
+            }
+            for i in n..old {
+                f.delete_particle_at_next_timestep(i);
+            }
+            f.apply_particles_removal();
+            if n != 0 {
+                check(unsafe { ffi::salva_hip_get_fluid_field(self.raw, slot as u32, ffi::SALVA_HIP_FIELD_VOLUME, f.volumes.as_mut_ptr()) })?;
+            }
+        }
+        Ok(())
+    }
+
     /// `LiquidWorld::step(dt, gravity)` (liquid_world.rs:62-158 with the `()` coupling manager).
     pub fn step(&mut self, dt: Real, gravity: &Vector3<Real>) -> Result<(), Error> {
         self.upload()?;
         let g = [gravity.x, gravity.y, gravity.z];
         check(unsafe { ffi::salva_hip_step(self.raw, dt, g.as_ptr(), &mut self.last_stats) })?;
         self.device_newer = true;
+        if self.nsinks != 0 {
+            self.follow_sinks()?;
+        }
         self.refresh_counters()?;
         if self.auto_sync {
             self.sync()?;

@@ -841,6 +841,75 @@ int64_t salva_hip_add_particles_sampled_compound(SalvaHipWorld* world, uint32_t 
 int64_t salva_hip_set_boundary_sampling_from_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
                                                       uint32_t filter);
 
+/* ---- Deleting particles by region, on the device.  The reference's long-running scenes scan `fluid.positions` on
+ * the host every frame and mark what left with `delete_particle_at_next_timestep` (examples3d/faucet3.rs:69-104); the next `step`
+ * removes it (liquid_world.rs:79-81).  Here the test and the removal both stay on the device: no position crosses PCIe.
+ * A particle MATCHES a region when its position is finite and its solid distance d to the region, evaluated in f32 by the device
+ * functions of the particle queries, satisfies d <= margin (margin finite and >= 0; margin 0: the centre is inside or on the surface;
+ * margin = the particle radius: the set of salva_hip_particles_intersecting_shape without that query's cell-range filter):
+ *   HALFSPACE  d = normal . (x - point); `normal` points out of the half-space and must be unit within 1e-3 (squared norm)
+ *   AABB       the distance to the box [mins, maxs], as in salva_hip_particles_intersecting_aabb
+ *   SHAPE      a ball, cuboid, capsule or cylinder posed by translation / rotation_ijkw (unit within 1e-3)
+ *   MESH       the posed mesh `handle`; oriented meshes only (any other has no solid distance: SALVA_HIP_E_INVALID)
+ *   COMPOUND   the posed compound `handle`: the smallest of its parts' distances; refused when a part is a non-oriented mesh
+ * SALVA_HIP_REGION_INVERT in `flags` selects the particles that do NOT match instead — a particle with a non-finite position never
+ * matches, so INVERT selects it: "everything that left the tank".  Fields a kind does not name are ignored. */
+enum {
+    SALVA_HIP_REGION_HALFSPACE = 1,
+    SALVA_HIP_REGION_AABB = 2,
+    SALVA_HIP_REGION_SHAPE = 3,
+    SALVA_HIP_REGION_MESH = 4,
+    SALVA_HIP_REGION_COMPOUND = 5
+};
+enum { SALVA_HIP_REGION_INVERT = 1 };
+#define SALVA_HIP_REGION_VERSION 1
+#define SALVA_HIP_REGION_BYTES 128
+#define SALVA_HIP_ALL_FLUIDS 4294967295u  /* as `fluid_slot`: every fluid of the world */
+typedef struct SalvaHipRegion {
+    uint32_t struct_size;            /* SALVA_HIP_REGION_BYTES */
+    uint32_t version;                /* SALVA_HIP_REGION_VERSION */
+    int32_t kind;                    /* SALVA_HIP_REGION_* */
+    uint32_t flags;                  /* 0 or SALVA_HIP_REGION_INVERT */
+    float margin;
+    uint32_t handle;                 /* MESH: salva_hip_create_mesh's; COMPOUND: salva_hip_create_compound's */
+    SalvaHipShape shape;             /* SHAPE */
+    float point[3], normal[3];       /* HALFSPACE */
+    float mins[3], maxs[3];          /* AABB */
+    float translation[3];            /* SHAPE, MESH, COMPOUND: the pose */
+    float rotation_ijkw[4];
+    uint32_t reserved[3];
+} SalvaHipRegion;
+/* Removes the particles of fluid `fluid_slot` (SALVA_HIP_ALL_FLUIDS: of every fluid) that `region` selects, at once: the CURRENT
+ * positions are tested — what salva_hip_get_fluid would return — and the world afterwards is exactly the world after
+ * salva_hip_delete_particles with the same mask (stable order; velocity changes, pressures, accelerations and inherited solver
+ * buffers compacted alike).  Returns the number of particles deleted, negative on error.  `deleted_mask_or_null` receives one byte
+ * per particle of the fluid as it was before the call (all fluids: concatenated in slot order), non-zero = deleted, so that a mirror
+ * compacts its own copies.  When nothing is selected the world is left untouched: the next step is bit-identical to one without the
+ * call, and the call costs one predicate pass and one small host wait.
+ * SALVA_HIP_E_INVALID: a struct_size / version other than this header's; an unknown kind, flag, slot or handle; a non-finite point,
+ * box or pose, a normal or rotation that is not unit within 1e-3, a negative or non-finite margin, non-positive shape parameters,
+ * mins > maxs; a call inside a force or coupling callback; a running decomposed world (salva_hip_delete_owned remains the way). */
+int64_t salva_hip_delete_particles_in_region(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot,
+                                             uint8_t* deleted_mask_or_null);
+/* Sinks: regions the world applies by itself.  At the start of every salva_hip_step — where the reference removes the particles
+ * marked for deletion, before the first substep and once per step whatever the sub-stepping — each registered sink is applied, in
+ * handle order, to the positions at step entry: salva_hip_delete_particles_in_region made from inside (a particle that two sinks
+ * select counts for the first).  A world with sinks pays one small host wait per step, however many sinks it has (their counts of
+ * selected rows come back together, before anything is moved).
+ *   salva_hip_add_sink        registers `region` for `fluid_slot` (validated as above); `*sink_out` is its handle.  A sink shares
+ *                             ownership of its mesh or compound the way a boundary slot does: salva_hip_destroy_mesh / _compound of a
+ *                             handle that a sink names is SALVA_HIP_E_INVALID.  Refused in a decomposed world (salva_hip_set_domain).
+ *   salva_hip_remove_sink     forgets it; the handle may be given out again.
+ *   salva_hip_set_sink_pose   moves a SHAPE, MESH or COMPOUND sink (any other kind: SALVA_HIP_E_INVALID).
+ *   salva_hip_get_sink_stats  out2 = {particles the sink deleted in the last step, in total}.
+ * A sink belongs to its fluid, not to the slot number: salva_hip_remove_fluid, a swap-remove, takes the sinks of the removed fluid
+ * with it (their handles are free again) and the sinks of the fluid that moves into the freed slot follow it there; sinks of
+ * SALVA_HIP_ALL_FLUIDS stay.  salva_hip_set_fluid of an existing slot leaves its sinks in place. */
+int salva_hip_add_sink(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot, uint32_t* sink_out);
+int salva_hip_remove_sink(SalvaHipWorld* world, uint32_t sink);
+int salva_hip_set_sink_pose(SalvaHipWorld* world, uint32_t sink, const float translation[3], const float rotation_ijkw[4]);
+int salva_hip_get_sink_stats(const SalvaHipWorld* world, uint32_t sink, uint64_t out2[2]);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

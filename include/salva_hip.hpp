@@ -280,6 +280,55 @@ class Compound {
     uint32_t id_ = 0;
 };
 
+// Where particles are deleted on the device (SalvaHipRegion): LiquidWorld::delete_particles_in and ::add_sink.  A
+// particle matches when its solid distance to the region is <= margin; `invert` selects the particles that do not match.
+struct Region : SalvaHipRegion {
+    static Region half_space(const Vec3& point, const Vec3& outward_normal, Real margin = 0, bool invert = false) {
+        Region r = base(SALVA_HIP_REGION_HALFSPACE, margin, invert);
+        for (int a = 0; a < 3; ++a) { r.point[a] = point[a]; r.normal[a] = outward_normal[a]; }
+        return r;
+    }
+    static Region aabb(const Vec3& mins, const Vec3& maxs, Real margin = 0, bool invert = false) {
+        Region r = base(SALVA_HIP_REGION_AABB, margin, invert);
+        for (int a = 0; a < 3; ++a) { r.mins[a] = mins[a]; r.maxs[a] = maxs[a]; }
+        return r;
+    }
+    static Region shape(const SalvaHipShape& shape, const Vec3& translation = {0, 0, 0}, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1},
+                        Real margin = 0, bool invert = false) {
+        Region r = posed(SALVA_HIP_REGION_SHAPE, translation, rotation_ijkw, margin, invert);
+        r.SalvaHipRegion::shape = shape;
+        return r;
+    }
+    static Region mesh(const Mesh& mesh, const Vec3& translation = {0, 0, 0}, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1},
+                       Real margin = 0, bool invert = false) {
+        Region r = posed(SALVA_HIP_REGION_MESH, translation, rotation_ijkw, margin, invert);
+        r.handle = mesh.id();
+        return r;
+    }
+    static Region compound(const Compound& compound, const Vec3& translation = {0, 0, 0}, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1},
+                           Real margin = 0, bool invert = false) {
+        Region r = posed(SALVA_HIP_REGION_COMPOUND, translation, rotation_ijkw, margin, invert);
+        r.handle = compound.id();
+        return r;
+    }
+
+  private:
+    static Region base(int kind, Real margin, bool invert) {
+        Region r{};
+        r.struct_size = SALVA_HIP_REGION_BYTES; r.version = SALVA_HIP_REGION_VERSION;
+        r.kind = kind; r.flags = invert ? (uint32_t)SALVA_HIP_REGION_INVERT : 0u; r.margin = margin;
+        r.rotation_ijkw[3] = 1.0f;
+        return r;
+    }
+    static Region posed(int kind, const Vec3& t, const std::array<Real, 4>& q, Real margin, bool invert) {
+        Region r = base(kind, margin, invert);
+        for (int a = 0; a < 3; ++a) r.translation[a] = t[a];
+        for (int a = 0; a < 4; ++a) r.rotation_ijkw[a] = q[a];
+        return r;
+    }
+};
+using SinkHandle = uint32_t;
+
 class Boundary {  // object/boundary.rs
   public:
     std::vector<Vec3> positions, velocities;
@@ -668,9 +717,10 @@ class LiquidWorld {  // liquid_world.rs
         for (size_t s = 0; s < fluids_.size(); ++s) upload(fluids_[s], (uint32_t)s);
         for (size_t s = 0; s < boundaries_.size(); ++s) upload(boundaries_[s], (uint32_t)s);
         const int rc = salva_hip_step(w_, dt, gravity.data(), &stats_);
+        if (nsinks_ && rc == SALVA_HIP_OK) follow_sinks();
         for (size_t s = 0; s < fluids_.size(); ++s) {  // the reference's host arrays are current after every step
             Fluid& f = fluids_[s];
-            if (f.num_particles())
+            if (f.num_particles() && readback_)
                 check(salva_hip_get_fluid(w_, (uint32_t)s, f.positions[0].data(), f.velocities[0].data()));
             for (auto& a : f.accelerations) a = Vec3{0, 0, 0};
         }
@@ -802,7 +852,7 @@ class LiquidWorld {  // liquid_world.rs
         f.accelerations.resize(n, Vec3{0, 0, 0});
         f.volumes.resize(n, f.default_particle_volume());
         f.deleted_.resize(n, false);
-        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        if (n && readback_) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
         return (size_t)k;
     }
     size_t add_particles_from_shape(FluidHandle h, const Mesh& mesh, const Vec3& translation,
@@ -819,7 +869,7 @@ class LiquidWorld {  // liquid_world.rs
         f.accelerations.resize(n, Vec3{0, 0, 0});
         f.volumes.resize(n, f.default_particle_volume());
         f.deleted_.resize(n, false);
-        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        if (n && readback_) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
         return (size_t)k;
     }
     size_t add_particles_from_shape(FluidHandle h, const Compound& compound, const Vec3& translation,
@@ -836,8 +886,74 @@ class LiquidWorld {  // liquid_world.rs
         f.accelerations.resize(n, Vec3{0, 0, 0});
         f.volumes.resize(n, f.default_particle_volume());
         f.deleted_.resize(n, false);
-        if (n) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+        if (n && readback_) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
         return (size_t)k;
+    }
+    // Deletes, at once and on the device, the particles of fluid `h` that `region` selects at their current positions
+    // (salva_hip_delete_particles_in_region); the host arrays are compacted with the mask the call returns.  Returns how many.
+    size_t delete_particles_in(const Region& region, FluidHandle h) {
+        upload_new_objects();
+        Fluid& f = fluids_[h];
+        upload(f, (uint32_t)h);
+        std::vector<uint8_t> mask(f.num_particles() + 1, 0);
+        const int64_t k = salva_hip_delete_particles_in_region(w_, &region, (uint32_t)h, mask.data());
+        if (k < 0) check((int)k);
+        if (k) compact_host(f, mask.data());
+        return (size_t)k;
+    }
+    // ... of every fluid
+    size_t delete_particles_in(const Region& region) {
+        upload_new_objects();
+        size_t total = 1;
+        for (size_t s = 0; s < fluids_.size(); ++s) { upload(fluids_[s], (uint32_t)s); total += fluids_[s].num_particles(); }
+        std::vector<uint8_t> mask(total, 0);
+        const int64_t k = salva_hip_delete_particles_in_region(w_, &region, SALVA_HIP_ALL_FLUIDS, mask.data());
+        if (k < 0) check((int)k);
+        size_t at = 0;
+        for (size_t s = 0; k && s < fluids_.size(); ++s) {
+            const size_t n = fluids_[s].num_particles();
+            compact_host(fluids_[s], mask.data() + at);
+            at += n;
+        }
+        return (size_t)k;
+    }
+    // Sinks: every step starts by deleting what the region selects, on the device, at the cost of one small host wait per step
+    // (salva_hip_add_sink).  remove_fluid takes the removed fluid's sinks with it.  After a step in which a sink fired the host arrays have the new length.
+    SinkHandle add_sink(const Region& region, FluidHandle h) {
+        upload_new_objects();
+        SinkHandle sink = 0;
+        check(salva_hip_add_sink(w_, &region, (uint32_t)h, &sink));
+        ++nsinks_;
+        return sink;
+    }
+    SinkHandle add_sink(const Region& region) {
+        upload_new_objects();
+        SinkHandle sink = 0;
+        check(salva_hip_add_sink(w_, &region, SALVA_HIP_ALL_FLUIDS, &sink));
+        ++nsinks_;
+        return sink;
+    }
+    void remove_sink(SinkHandle sink) { check(salva_hip_remove_sink(w_, sink)); --nsinks_; }
+    void set_sink_pose(SinkHandle sink, const Vec3& translation, const std::array<Real, 4>& rotation_ijkw = {0, 0, 0, 1}) {
+        check(salva_hip_set_sink_pose(w_, sink, translation.data(), rotation_ijkw.data()));
+    }
+    // {deleted in the last step, deleted in total}
+    std::array<uint64_t, 2> sink_stats(SinkHandle sink) const {
+        std::array<uint64_t, 2> out{0, 0};
+        check(salva_hip_get_sink_stats(w_, sink, out.data()));
+        return out;
+    }
+    // The reference's host arrays are current after every step, which costs a read-back per step.  A loop that does not look at
+    // them (an emitter and sinks that stay on the device) switches it off; refresh() then reads one fluid, or all, back on demand.
+    // While it is off `positions` / `velocities` have the right length and stale content: the rows add_particles_from_shape appends
+    // are zero-filled until the next refresh().
+    void set_readback(bool on) { readback_ = on; }
+    void refresh(FluidHandle h) {
+        Fluid& f = fluids_[h];
+        if (f.num_particles()) check(salva_hip_get_fluid(w_, (uint32_t)h, f.positions[0].data(), f.velocities[0].data()));
+    }
+    void refresh() {
+        for (size_t s = 0; s < fluids_.size(); ++s) refresh((FluidHandle)s);
     }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));
@@ -855,6 +971,32 @@ class LiquidWorld {  // liquid_world.rs
     }
 
   private:
+    static void compact_host(Fluid& f, const uint8_t* deleted) {
+        size_t k = 0;
+        for (size_t i = 0; i < f.positions.size(); ++i) {
+            if (deleted[i]) continue;
+            f.positions[k] = f.positions[i]; f.velocities[k] = f.velocities[i];
+            f.accelerations[k] = f.accelerations[i]; f.volumes[k] = f.volumes[i];
+            f.deleted_[k] = f.deleted_[i];
+            ++k;
+        }
+        f.positions.resize(k); f.velocities.resize(k); f.accelerations.resize(k); f.volumes.resize(k); f.deleted_.resize(k);
+    }
+    // a step in which a sink fired shortened fluids on the device: the host arrays follow (volumes that differ come from the device)
+    void follow_sinks() {
+        for (size_t s = 0; s < fluids_.size(); ++s) {
+            Fluid& f = fluids_[s];
+            const size_t n = (size_t)salva_hip_fluid_len(w_, (uint32_t)s);
+            if (n == f.num_particles()) continue;
+            f.positions.resize(n); f.velocities.resize(n); f.accelerations.assign(n, Vec3{0, 0, 0}); f.deleted_.assign(n, false);
+            bool uniform = true;
+            for (Real v : f.volumes) uniform = uniform && v == f.volumes[0];
+            f.volumes.resize(n);
+            if (n && !uniform) check(salva_hip_get_fluid_field(w_, (uint32_t)s, SALVA_HIP_FIELD_VOLUME, f.volumes.data()));
+        }
+    }
+    uint32_t nsinks_ = 0;
+    bool readback_ = true;
     // Objects added since the last step exist only on the host: a swap-remove must see the same dense sets on both sides.
     // Pending particle deletions stay pending (they are applied at the top of the next step, fluid.rs:88-98).
     void upload_new_objects() {

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_create_compound", "salva_hip_destroy_compound", "salva_hip_set_boundary_dynamic_sampling_compound",
     "salva_hip_particles_intersecting_compound", "salva_hip_particles_intersecting_mesh",
     "salva_hip_sample_compound", "salva_hip_add_particles_sampled_compound", "salva_hip_set_boundary_sampling_from_compound",
+    "salva_hip_delete_particles_in_region", "salva_hip_add_sink", "salva_hip_remove_sink", "salva_hip_set_sink_pose", "salva_hip_get_sink_stats",
 ]
 
 
@@ -158,6 +159,18 @@ class CompoundPart(C.Structure):
     _fields_ = [("kind", C.c_int32), ("params", C.c_float * 3), ("mesh", C.c_uint32), ("translation", C.c_float * 3),
                 ("rotation_ijkw", C.c_float * 4)]
 
+
+class Region(C.Structure):
+    """SalvaHipRegion (include/salva_hip.h): where salva_hip_delete_particles_in_region and the sinks delete."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("kind", C.c_int32), ("flags", C.c_uint32), ("margin", C.c_float),
+                ("handle", C.c_uint32), ("shape", Shape), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("mins", C.c_float * 3),
+                ("maxs", C.c_float * 3), ("translation", C.c_float * 3), ("rotation_ijkw", C.c_float * 4), ("reserved", C.c_uint32 * 3)]
+
+
+REGION_HALFSPACE, REGION_AABB, REGION_SHAPE, REGION_MESH, REGION_COMPOUND = 1, 2, 3, 4, 5
+REGION_INVERT = 1
+REGION_BYTES, REGION_VERSION = 128, 1  # SALVA_HIP_REGION_BYTES / _VERSION
+ALL_FLUIDS = 0xFFFFFFFF
 
 KERNEL_CUBIC_SPLINE, KERNEL_POLY6, KERNEL_SPIKY, KERNEL_VISCOSITY = 0, 1, 2, 3
 SHAPE_BALL, SHAPE_CUBOID, SHAPE_CAPSULE, SHAPE_CYLINDER, SHAPE_MESH, SHAPE_COMPOUND = 1, 2, 3, 4, 5, 6
@@ -370,6 +383,13 @@ def lib():
         L.salva_hip_add_particles_sampled_compound.restype = C.c_int64
         L.salva_hip_set_boundary_sampling_from_compound.argtypes = [vp, u32, u32, u32, u32]
         L.salva_hip_set_boundary_sampling_from_compound.restype = C.c_int64
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_delete_particles_in_region"):
+        L.salva_hip_delete_particles_in_region.argtypes = [vp, C.POINTER(Region), u32, C.POINTER(C.c_uint8)]
+        L.salva_hip_delete_particles_in_region.restype = C.c_int64
+        L.salva_hip_add_sink.argtypes = [vp, C.POINTER(Region), u32, C.POINTER(u32)]
+        L.salva_hip_remove_sink.argtypes = [vp, u32]
+        L.salva_hip_set_sink_pose.argtypes = [vp, u32, fp, fp]
+        L.salva_hip_get_sink_stats.argtypes = [vp, u32, C.POINTER(u64)]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

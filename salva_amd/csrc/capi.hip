@@ -46,6 +46,10 @@ static void not_in_force_callback(const SalvaHipWorld* world) {
     if (world->w->in_force_callback())
         throw salva::HipError(SALVA_HIP_E_INVALID, "this entry point is not available inside a force callback");
 }
+static void not_in_coupling_callback(const SalvaHipWorld* world) {
+    if (world->w->in_coupling_callback())
+        throw salva::HipError(SALVA_HIP_E_INVALID, "this entry point is not available inside a coupling callback");
+}
 
 extern "C" {
 
@@ -989,6 +993,58 @@ int64_t salva_hip_set_boundary_sampling_from_compound(SalvaHipWorld* world, uint
         return SALVA_HIP_OK;
     });
     return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+static_assert(sizeof(SalvaHipRegion) == SALVA_HIP_REGION_BYTES, "SalvaHipRegion: the header's size constant is what the mirrors check");
+int64_t salva_hip_delete_particles_in_region(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot,
+                                             uint8_t* deleted_mask_or_null) { WorldLock _lk(world);
+    int64_t r = 0;
+    const int rc = guarded([&]() -> int {
+        if (!world || !region) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        not_in_coupling_callback(world);
+        r = world->w->delete_particles_in_region(*region, fluid_slot, deleted_mask_or_null);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
+}
+
+int salva_hip_add_sink(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot, uint32_t* sink_out) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !region || !sink_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        not_in_coupling_callback(world);
+        *sink_out = world->w->add_sink(*region, fluid_slot);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_remove_sink(SalvaHipWorld* world, uint32_t sink) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
+        not_in_force_callback(world);
+        not_in_coupling_callback(world);
+        world->w->remove_sink(sink);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_set_sink_pose(SalvaHipWorld* world, uint32_t sink, const float translation[3], const float rotation_ijkw[4]) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        not_in_force_callback(world);
+        not_in_coupling_callback(world);
+        world->w->set_sink_pose(sink, translation, rotation_ijkw);
+        return SALVA_HIP_OK;
+    });
+}
+
+int salva_hip_get_sink_stats(const SalvaHipWorld* world, uint32_t sink, uint64_t out2[2]) { WorldLock _lk(world);
+    return guarded([&]() -> int {
+        if (!world || !out2) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
+        world->w->get_sink_stats(sink, out2);
+        return SALVA_HIP_OK;
+    });
 }
 
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }

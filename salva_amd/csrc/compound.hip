@@ -95,7 +95,7 @@ const std::shared_ptr<CompoundRes>& World::compound_at(uint32_t compound) const 
 void World::destroy_compound(uint32_t compound) {
     use_device();
     if (compound_at(compound).use_count() > 1)
-        throw HipError(SALVA_HIP_E_INVALID, "the compound is the collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it)");
+        throw HipError(SALVA_HIP_E_INVALID, "the compound is the collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it) or the region of a sink (salva_hip_remove_sink releases it)");
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     compounds[compound].reset();
 }

@@ -225,7 +225,7 @@ const std::shared_ptr<MeshRes>& World::mesh_at(uint32_t mesh) const {
 void World::destroy_mesh(uint32_t mesh) {
     use_device();
     if (mesh_at(mesh).use_count() > 1)
-        throw HipError(SALVA_HIP_E_INVALID, "the mesh is the collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it) or a part of a compound (salva_hip_destroy_compound releases it)");
+        throw HipError(SALVA_HIP_E_INVALID, "the mesh is the collider of a dynamically sampled boundary (salva_hip_clear_boundary_sampling releases it) or a part of a compound (salva_hip_destroy_compound releases it), or the region of a sink (salva_hip_remove_sink releases it)");
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     meshes[mesh].reset();
 }

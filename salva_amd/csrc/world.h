@@ -17,6 +17,7 @@
 #include "switches.h"
 #include "mesh.h"
 #include "compound.h"
+#include "sink.h"
 
 namespace salva {
 
@@ -103,6 +104,12 @@ class World {
     int step(float dt, const float g[3], SalvaHipStepStats* stats);
     void add_particles(uint32_t slot, uint64_t n_add, const float* pos, const float* vel);
     uint64_t delete_particles(uint32_t slot, const uint8_t* mask);
+    // ---- deleting by region on the device, and the sinks a step applies by itself (world_sink.hip, sink.hip)
+    int64_t delete_particles_in_region(const SalvaHipRegion& region, uint32_t slot, uint8_t* deleted_mask);
+    uint32_t add_sink(const SalvaHipRegion& region, uint32_t slot);
+    void remove_sink(uint32_t sink);
+    void set_sink_pose(uint32_t sink, const float t[3], const float q[4]);
+    void get_sink_stats(uint32_t sink, uint64_t out[2]) const;
     uint64_t particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                uint32_t* indices);
     uint64_t particles_in_shape(const float t[3], const float q[4], const SalvaHipShape& shape, uint64_t capacity, uint32_t* kinds,
@@ -165,6 +172,7 @@ class World {
     void force_get_state(uint32_t slot, float* positions, float* velocities, float* densities);
     void force_add_accelerations(uint32_t slot, const float* acc);
     bool in_force_callback() const { return in_force_cb; }
+    bool in_coupling_callback() const { return in_coupling_cb; }
     // user-defined forces as kernels (SALVA_HIP_FORCE_DEVICE; userforce.hip)
     void set_device_force_callback(SalvaHipDeviceForceCallback cb, void* user, SalvaHipWorld* owner) { dforce_cb = cb; dforce_user = user; dforce_owner = owner; }
     void device_view_read(const void* device_src, void* host_dst, uint64_t bytes);
@@ -243,6 +251,23 @@ class World {
     void upload_tables();
     void build_boundary_grid();
     uint64_t append_particles(uint32_t slot, uint64_t n_add);
+    // the end of an edit that was decided on the device: one keep flag per row of the host-order arrays, and how many rows of each
+    // fluid they drop (world_objects.hip)
+    void apply_keep_flags(const uint8_t* d_keep, const uint32_t* deleted_per_slot);
+    // a region with what it keeps alive, validated; a registered one, and the scratch of both
+    struct RegionRes { SinkRegionDev dev{}; std::shared_ptr<MeshRes> mesh; std::shared_ptr<CompoundRes> compound; };
+    RegionRes resolve_region(const SalvaHipRegion& region) const;
+    uint64_t delete_in_regions(uint32_t count, const RegionRes* const* rs, const uint32_t* slots, uint64_t* deleted, uint8_t* deleted_mask,
+                               SlotSpan sp);
+    struct Sink { bool live = false; RegionRes res; uint32_t slot = 0; uint64_t last = 0, total = 0; };
+    void sinks_after_remove_fluid(uint32_t slot, uint32_t last);
+    std::vector<Sink> sinks;  // by handle; a removed sink leaves a free entry
+    Sink& sink_at(uint32_t sink);
+    void apply_sinks();
+    DevBuf<uint8_t> sink_keep;
+    DevBuf<float4> st_spare[4];  // where apply_keep_flags compacts to; the arrays it replaces become the next call's room
+    DevBuf<uint32_t> sink_deleted, sink_scan;
+    PinnedStage sink_stage;
     void set_boundary_from(uint32_t slot, uint64_t n, const float* pos, const float* vel, uint32_t memberships, uint32_t filter,
                            bool wants_forces, const std::function<void(float4*)>* fill_dev);
     // the shape sampler's lattice (sample.hip): bit lattice, per-word counts and offsets, the three coordinate arrays, packed output;
@@ -642,6 +667,7 @@ class World {
     void* coupling_user = nullptr;
     SalvaHipWorld* coupling_owner = nullptr;
     void call_coupling(int phase, float dt);
+    bool in_coupling_cb = false;
     float dt_prev = 0.0f, inv_dt_prev = 0.0f;  // TimestepManager::{dt, inv_dt} persist across steps (timestep_manager.rs:23-34)
     StepCtx last_ctx{};
     float last_dt = 0.0f;

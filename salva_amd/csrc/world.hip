@@ -353,8 +353,8 @@ void dims_from_bbox(const int32_t* bb, GridDims& g, const FoldRule* fold) {
         char msg[512];
         snprintf(msg, sizeof msg,
                  "the cell table over the particles' bounding box (%d x %d x %d tiles of %dx%dx%d cells) would take %.1f GiB, over the "
-                 "%.1f GiB budget: particles are too spread out for the dense grid — delete strays (salva_hip_particles_intersecting_aabb "
-                 "+ salva_hip_delete_particles) or raise SALVA_HIP_CELL_TABLE_GIB",
+                 "%.1f GiB budget: particles are too spread out for the dense grid — delete strays (salva_hip_delete_particles_in_region, "
+                 "or a sink around the scene: salva_hip_add_sink) or raise SALVA_HIP_CELL_TABLE_GIB",
                  g.nt[0], g.nt[1], g.nt[2], TX, TY, TZ, gib, budget_gib);
         throw HipError(SALVA_HIP_E_CAPACITY, msg);
     }
@@ -419,6 +419,8 @@ uint64_t World::device_bytes() const {
     uint64_t b = 0;
     auto add = [&](size_t x) { b += x; };
     add(st_pos.bytes()); add(st_vel.bytes()); add(st_dv.bytes()); add(st_acc.bytes()); add(st_model.bytes());
+    for (const DevBuf<float4>& spare : st_spare) add(spare.bytes());  // (region deletes: world_objects.hip apply_keep_flags)
+    add(sink_keep.bytes()); add(sink_deleted.bytes()); add(sink_scan.bytes());
     for (int k = 0; k < 2; ++k) {
         add(posm[k].bytes()); add(vel[k].bytes()); add(dv[k].bytes()); add(model[k].bytes()); add(perm[k].bytes());
         for (const GridTabs& t : gtab) { add(t.keys[k].bytes()); add(t.idx[k].bytes()); }

@@ -302,6 +302,55 @@ uint64_t World::delete_particles(uint32_t slot, const uint8_t* mask) {
     return kept;
 }
 
+// The same edit when the flags were written on the device (delete_particles_in_region, world_sink.hip): d_keep holds one flag per row
+// of the host-order arrays, which are current; deleted_per_slot[s] is how many rows of fluid s it drops (their sum is not zero).
+// The four arrays move together from one scan of the flags (sink.hip) into arrays the world keeps for this, and the host waits once,
+// at the end; an inherited solver buffer is filtered with its fluid's flags as above.
+void World::apply_keep_flags(const uint8_t* d_keep, const uint32_t* deleted_per_slot) {
+    uint64_t gone = 0;
+    for (uint32_t s = 0; s < fluids.size(); ++s) {
+        if (deleted_per_slot[s] > fluids[s].n) throw HipError(SALVA_HIP_E_HIP, "internal error: more rows flagged than the fluid holds");
+        gone += deleted_per_slot[s];
+    }
+    if (gone == 0 || gone > n) throw HipError(SALVA_HIP_E_HIP, "internal error: a device edit that drops nothing, or more than there is");
+    const uint64_t new_total = (uint64_t)n - gone;
+    const uint32_t cap = (uint32_t)std::max<uint64_t>(new_total, 1);
+    DevBuf<float4>(&out)[4] = st_spare;  // (kept between calls: a faucet's sinks fire every few steps, and hipMalloc / hipFree wait for the device)
+    for (DevBuf<float4>& o : out) o.ensure(cap, stream, false, 1.1f);
+    sink_scan.ensure(sink_scan_words(n));
+    {
+        const float4* src[4] = {st_pos.p, st_vel.p, st_dv.p, st_acc.p};
+        float4* dst[4] = {out[0].p, out[1].p, out[2].p, out[3].p};
+        launch_sink_compact(d_keep, n, n, sink_scan.p, src, dst, 4, (uint32_t)new_total, stream);
+    }
+    uint64_t off = 0;
+    for (uint32_t s = 0; s < fluids.size(); off += fluids[s].n, ++s) {
+        auto it = sticky.find(s);
+        if (!deleted_per_slot[s] || it == sticky.end() || !it->second.len) continue;
+        // (the entries beyond the fluid's particles just move down; how many of the first `head` go is the compaction's own count)
+        const uint64_t L = it->second.len, head = std::min<uint64_t>(L, fluids[s].n);
+        auto moved = std::make_shared<DevBuf<float4>>();
+        moved->ensure(std::max<uint64_t>(L, 1));
+        DevBuf<uint32_t> scan2;
+        scan2.ensure(sink_scan_words((uint32_t)L));
+        const float4* src[4] = {it->second.data->p, nullptr, nullptr, nullptr};
+        float4* dst[4] = {moved->p, nullptr, nullptr, nullptr};
+        launch_sink_compact(d_keep + off, (uint32_t)head, (uint32_t)L, scan2.p, src, dst, 1, (uint32_t)L, stream);
+        uint32_t kept2 = 0;
+        SALVA_HIP_CHECK(hipMemcpyAsync(&kept2, scan2.p + sink_scan_words((uint32_t)L) - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        it->second.data = moved;
+        it->second.len = kept2;
+    }
+    DevBuf<float4>* cur4[4] = {&st_pos, &st_vel, &st_dv, &st_acc};
+    for (int a = 0; a < 4; ++a) { std::swap(cur4[a]->p, out[a].p); std::swap(cur4[a]->cap, out[a].cap); }
+    n = (uint32_t)new_total;
+    for (uint32_t s = 0; s < fluids.size(); ++s) fluids[s].n -= deleted_per_slot[s];
+    stamp_fluid_models();
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    order_invalidated(true);
+}
+
 void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
     fluid_span(slot);
     for (uint32_t k = 0; k < nf; ++k)
@@ -402,6 +451,7 @@ void World::remove_fluid(uint32_t slot) {
     }
     if (slot != last) fluids[slot] = fluids[last];
     fluids.pop_back();
+    sinks_after_remove_fluid(slot, last);
     stamp_fluid_models();
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
     order_invalidated(true);

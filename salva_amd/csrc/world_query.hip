@@ -2,6 +2,7 @@
 // particles, the five query kernels, and the host code that runs them and maps their hits to (kind, slot, index) triples.
 #include "world.h"
 #include "dcs.h"
+#include "solid_distance.h"
 
 #include <algorithm>
 #include <cmath>
@@ -119,24 +120,6 @@ struct ShapeQuery {
     int clo[3], chi[3];     // cell range of the world AABB
     float h, r;             // cell width, particle radius
 };
-// `shape.distance_to_point(identity, l, solid = true)` of a built-in shape for a point in the shape's frame: the one copy, for
-// k_shape_query and for the parts of a compound (k_compound_query)
-__device__ __forceinline__ float shape_solid_distance(int kind, const float p[3], float lx, float ly, float lz) {
-    float d;
-    if (kind == SALVA_HIP_SHAPE_BALL) {
-        d = fmaxf(sqrtf(lx * lx + ly * ly + lz * lz) - p[0], 0.0f);
-    } else if (kind == SALVA_HIP_SHAPE_CAPSULE) {  // distance to the segment (0, -hh..hh, 0), minus the radius
-        const float ey = ly - fminf(fmaxf(ly, -p[0]), p[0]);
-        d = fmaxf(sqrtf(lx * lx + ey * ey + lz * lz) - p[1], 0.0f);
-    } else if (kind == SALVA_HIP_SHAPE_CYLINDER) {  // beyond the caps and beyond the side
-        const float ey = fmaxf(fabsf(ly) - p[0], 0.0f), er = fmaxf(sqrtf(lx * lx + lz * lz) - p[1], 0.0f);
-        d = sqrtf(ey * ey + er * er);
-    } else {
-        const float dx = fmaxf(fabsf(lx) - p[0], 0.0f), dy = fmaxf(fabsf(ly) - p[1], 0.0f), dz = fmaxf(fabsf(lz) - p[2], 0.0f);
-        d = sqrtf(dx * dx + dy * dy + dz * dz);
-    }
-    return d;
-}
 __global__ __launch_bounds__(BLOCK) void k_shape_query(QuerySrc q, ShapeQuery s, uint32_t kind,
                                                        unsigned int* __restrict__ counter, uint32_t cap, uint32_t* __restrict__ out_kind,
                                                        uint32_t* __restrict__ out_index) {
@@ -187,9 +170,7 @@ uint64_t World::particles_in_shape(const float t[3], const float q[4], const Sal
     });
 }
 
-// The same query for a posed compound and for a posed oriented mesh.  A compound's solid distance is the smallest of
-// its parts', each taken in the part's frame (pose_k^-1 * l, quat_rot with the conjugate); an oriented mesh's is 0 inside and the
-// distance to the closest point outside.  The cell range comes from the posed local box (parry's Aabb::transform_by, dcs.hip).
+// The same query for a posed compound and for a posed oriented mesh (the distances: solid_distance.h).  The cell range comes from the posed local box (parry's Aabb::transform_by, dcs.hip).
 struct PosedQuery {
     float t[3], q[4];       // isometry
     int clo[3], chi[3];     // cell range of the world AABB
@@ -204,27 +185,13 @@ __device__ __forceinline__ bool posed_query_local(const QuerySrc& q, const Posed
     quat_rot(-s.q[0], -s.q[1], -s.q[2], s.q[3], pt.x - s.t[0], pt.y - s.t[1], pt.z - s.t[2], lx, ly, lz);
     return true;
 }
-__device__ __forceinline__ float mesh_solid_distance(const MeshDev& m, float lx, float ly, float lz) {
-    float jx, jy, jz;
-    bool inside;
-    mesh_project_point(m, lx, ly, lz, jx, jy, jz, inside);
-    const float dx = lx - jx, dy = ly - jy, dz = lz - jz;
-    return inside ? 0.0f : sqrtf((dx * dx + dy * dy) + dz * dz);
-}
 __global__ __launch_bounds__(BLOCK) void k_compound_query(QuerySrc q, PosedQuery s, const CompoundPartDev* __restrict__ parts, uint32_t nparts,
                                                           uint32_t kind, unsigned int* __restrict__ counter, uint32_t cap,
                                                           uint32_t* __restrict__ out_kind, uint32_t* __restrict__ out_index) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     float lx, ly, lz;
     if (!posed_query_local(q, s, i, lx, ly, lz)) return;
-    float d = __builtin_inff();
-#pragma unroll 1
-    for (uint32_t k = 0; k < nparts; ++k) {  // (k is wave-uniform: the table comes through the scalar cache)
-        const CompoundPartDev& P = parts[k];
-        float kx, ky, kz;
-        quat_rot(-P.q[0], -P.q[1], -P.q[2], P.q[3], lx - P.t[0], ly - P.t[1], lz - P.t[2], kx, ky, kz);
-        d = fminf(d, P.kind == SALVA_HIP_SHAPE_MESH ? mesh_solid_distance(P.mesh, kx, ky, kz) : shape_solid_distance(P.kind, P.p, kx, ky, kz));
-    }
+    const float d = compound_solid_distance(parts, nparts, lx, ly, lz);
     if (!(d <= s.r)) return;
     query_emit(q, i, kind, counter, cap, out_kind, out_index);
 }

@@ -704,6 +704,8 @@ void World::iisph_solve(StepCtx& c, float& dt, const float g[3], SalvaHipStepSta
 // ------------------------------------------------------------------------------------------------ step
 int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
     use_device();
+    // (the particles marked for deletion go first, liquid_world.rs:79-81: before init_with_fluids drops the inherited solver buffers)
+    apply_sinks();
     SalvaHipStepStats st{};
     st.nparticles = n;
     for (uint64_t& v : dcs_stats) v = 0;
@@ -769,8 +771,12 @@ int World::step(float dt, const float g[3], SalvaHipStepStats* stats) {
 
 void World::call_coupling(int phase, float dt) {
     if (!coupling_cb) return;
-    if (coupling_cb(coupling_user, coupling_owner, phase, dt) != 0)
-        throw HipError(SALVA_HIP_E_INVALID, "the coupling callback reported an error");
+    in_coupling_cb = true;
+    int rc;
+    try { rc = coupling_cb(coupling_user, coupling_owner, phase, dt); }
+    catch (...) { in_coupling_cb = false; throw; }
+    in_coupling_cb = false;
+    if (rc != 0) throw HipError(SALVA_HIP_E_INVALID, "the coupling callback reported an error");
 }
 
 // ------------------------------------------------------------------------------------------------ substep: what its phases share

@@ -753,6 +753,7 @@ class LiquidWorld:
         self._counters_stale = False
         self.last_stats = L.StepStats()
         self._nsteps = 0
+        self._sinks = {}  # sink handle -> region (salva_hip_add_sink)
         self._pending_download = None
 
     def __del__(self):
@@ -1036,6 +1037,8 @@ class LiquidWorld:
         st = L.StepStats()
         rc = self._L.salva_hip_step(self._h, dt, g, C.byref(st))
         self._nsteps += 1
+        if self._sinks:
+            self._resize_after_sinks()
         for f in self._fluids:
             f._device_newer = True
             if f._acc_touched:
@@ -1590,6 +1593,77 @@ class LiquidWorld:
             owner = self._boundaries._items[int(s[j])] if k[j] else self._fluids._items[int(s[j])]
             out.append(("boundary" if k[j] else "fluid", owner, int(i[j])))
         return out
+
+    # ---- deleting by region on the device (salva_hip_delete_particles_in_region, sinks)
+    @staticmethod
+    def _compact_mirror(f: Fluid, deleted: np.ndarray):
+        """The host copies of `f` after the device dropped the rows of `deleted` (stale rows stay stale: _device_newer is kept)."""
+        keep = ~deleted
+        f._positions = np.ascontiguousarray(f._positions[keep])
+        f._velocities = np.ascontiguousarray(f._velocities[keep])
+        f._accelerations = np.ascontiguousarray(f._accelerations[keep])
+        f._volumes = np.ascontiguousarray(f._volumes[keep])
+        f._deleted = np.ascontiguousarray(f._deleted[keep])
+        f._pins = None
+
+    def delete_particles_in(self, region, fluid: Optional[Fluid] = None) -> int:
+        """Deletes, at once and on the device, the particles of `fluid` (None: of every fluid) that `region` (salva_amd.regions)
+        selects at their current positions; returns how many.  No position visits the host; the host copies are compacted with the
+        mask the call returns.  Particles marked with delete_particle_at_next_timestep stay marked."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        targets = list(self._fluids) if fluid is None else [fluid]
+        slot = L.ALL_FLUIDS if fluid is None else fluid._slot
+        r = region._struct(self)
+        mask = np.zeros(max(sum(f.num_particles() for f in targets), 1), np.uint8)
+        k = int(self._L.salva_hip_delete_particles_in_region(self._h, C.byref(r), slot, mask.ctypes.data_as(C.POINTER(C.c_uint8))))
+        if k < 0:
+            L.check(k)
+        if k:
+            at = 0
+            for f in sorted(targets, key=lambda f: f._slot):
+                n = f.num_particles()
+                self._compact_mirror(f, mask[at:at + n].astype(bool))
+                at += n
+        return k
+
+    def add_sink(self, region, fluid: Optional[Fluid] = None) -> int:
+        """Registers `region` as a sink of `fluid` (None: of every fluid): every `step` starts by deleting what it selects, on the
+        device, at the cost of one small host wait.  Returns the sink's handle."""
+        self.sync_to_device(apply_removal=False)
+        r, h = region._struct(self), C.c_uint32(0)
+        L.check(self._L.salva_hip_add_sink(self._h, C.byref(r), L.ALL_FLUIDS if fluid is None else fluid._slot, C.byref(h)))
+        self._sinks[h.value] = region  # (keeps the region's mesh / compound object alive)
+        return h.value
+
+    def remove_sink(self, sink: int):
+        L.check(self._L.salva_hip_remove_sink(self._h, int(sink)))
+        self._sinks.pop(int(sink), None)
+
+    def set_sink_pose(self, sink: int, translation, rotation=(0.0, 0.0, 0.0, 1.0)):
+        t, q = np.ascontiguousarray(translation, F32).reshape(3), np.ascontiguousarray(rotation, F32).reshape(4)
+        L.check(self._L.salva_hip_set_sink_pose(self._h, int(sink), _fp(t), _fp(q)))
+
+    def sink_stats(self, sink: int):
+        """(particles the sink deleted in the last step, in total)"""
+        out = (C.c_uint64 * 2)()
+        L.check(self._L.salva_hip_get_sink_stats(self._h, int(sink), out))
+        return int(out[0]), int(out[1])
+
+    def _resize_after_sinks(self):
+        """A step in which a sink fired shortened fluids on the device: the host copies follow (positions and velocities are read
+        back on the next access, accelerations are zero after a step, the volumes come from the device unless they are uniform)."""
+        for f in self._fluids:
+            n = int(self._L.salva_hip_fluid_len(self._h, f._slot))
+            if n == f.num_particles():
+                continue
+            uniform = len(f._volumes) > 0 and bool((f._volumes == f._volumes[0]).all())
+            vol = np.full(n, f._volumes[0] if uniform else 0, F32)
+            if n and not uniform:
+                L.check(self._L.salva_hip_get_fluid_field(self._h, f._slot, L.FIELD_VOLUME, _fp(vol)))
+            f._positions, f._velocities, f._accelerations = np.zeros((n, 3), F32), np.zeros((n, 3), F32), np.zeros((n, 3), F32)
+            f._volumes, f._deleted, f._pins = vol, np.zeros(n, bool), None
+            f._device_newer = True
 
     def device_bytes(self) -> int:
         return int(self._L.salva_hip_device_bytes(self._h))
