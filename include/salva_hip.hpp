@@ -1130,37 +1130,20 @@ class LiquidWorld {  // liquid_world.rs
     void upload(Boundary& b, uint32_t slot) {
         if (!b.dirty_) return;
         const size_t n = b.num_particles();
-        if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_HOST) {
-            check(salva_hip_set_boundary_dynamic_sampling_host(w_, slot, &b.dynamic_host, b.interaction_groups.memberships,
-                                                               b.interaction_groups.filter));
+        // the forms a geometry takes: a built-in shape by pointer, a mesh or a compound by its handle
+        const uint32_t m = b.interaction_groups.memberships, f = b.interaction_groups.filter;
+        if (const int kind = b.dynamic_shape.kind) {
+            check(kind == SALVA_HIP_SHAPE_HOST       ? salva_hip_set_boundary_dynamic_sampling_host(w_, slot, &b.dynamic_host, m, f)
+                  : kind == SALVA_HIP_SHAPE_COMPOUND ? salva_hip_set_boundary_dynamic_sampling_compound(w_, slot, b.compound_id, m, f)
+                  : kind == SALVA_HIP_SHAPE_MESH     ? salva_hip_set_boundary_dynamic_sampling_mesh(w_, slot, b.mesh_id, m, f)
+                                                     : salva_hip_set_boundary_dynamic_sampling(w_, slot, &b.dynamic_shape, m, f));
             b.dirty_ = false;
             return;
         }
-        if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_COMPOUND) {
-            check(salva_hip_set_boundary_dynamic_sampling_compound(w_, slot, b.compound_id, b.interaction_groups.memberships,
-                                                                   b.interaction_groups.filter));
-            b.dirty_ = false;
-            return;
-        }
-        if (b.dynamic_shape.kind == SALVA_HIP_SHAPE_MESH) {
-            check(salva_hip_set_boundary_dynamic_sampling_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter));
-            b.dirty_ = false;
-            return;
-        }
-        if (b.dynamic_shape.kind) {
-            check(salva_hip_set_boundary_dynamic_sampling(w_, slot, &b.dynamic_shape, b.interaction_groups.memberships,
-                                                          b.interaction_groups.filter));
-            b.dirty_ = false;
-            return;
-        }
-        if (b.sampled_shape.kind) {
-            const int64_t k = b.sampled_shape.kind == SALVA_HIP_SHAPE_MESH
-                                  ? salva_hip_set_boundary_sampling_from_mesh(w_, slot, b.mesh_id, b.interaction_groups.memberships, b.interaction_groups.filter)
-                              : b.sampled_shape.kind == SALVA_HIP_SHAPE_COMPOUND
-                                  ? salva_hip_set_boundary_sampling_from_compound(w_, slot, b.compound_id, b.interaction_groups.memberships,
-                                                                                  b.interaction_groups.filter)
-                                  : salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, b.interaction_groups.memberships,
-                                                                               b.interaction_groups.filter);
+        if (const int kind = b.sampled_shape.kind) {
+            const int64_t k = kind == SALVA_HIP_SHAPE_MESH       ? salva_hip_set_boundary_sampling_from_mesh(w_, slot, b.mesh_id, m, f)
+                              : kind == SALVA_HIP_SHAPE_COMPOUND ? salva_hip_set_boundary_sampling_from_compound(w_, slot, b.compound_id, m, f)
+                                                                 : salva_hip_set_boundary_sampling_from_shape(w_, slot, &b.sampled_shape, m, f);
             if (k < 0) check((int)k);
             b.sampled_n_ = (size_t)k;
             b.dirty_ = false;

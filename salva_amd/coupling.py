@@ -244,6 +244,8 @@ class ColliderCouplingSet:
 
     # CouplingManager::update_boundaries (:146-264), StaticSampling arm
     def update_boundaries(self, world):
+        from .sampling import geometry_entry
+
         slots, poses = [], []  # all poses go in with one call, in the order of the entries (salva_hip_update_boundary_poses)
         for e in self.entries.values():
             b = e.boundary
@@ -257,28 +259,14 @@ class ColliderCouplingSet:
                 e.uploaded = True
             if not e.uploaded and isinstance(e.sampling, DynamicContactSampling):
                 b._sampled = b._dynamic = True
-                if e.sampling.compound is not None:
-                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling_compound(
-                        world._h, b._slot, e.sampling.compound.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
-                elif e.sampling.mesh is not None:
-                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling_mesh(
-                        world._h, b._slot, e.sampling.mesh.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
-                else:
-                    L.check(world._L.salva_hip_set_boundary_dynamic_sampling(
-                        world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
+                entry, geom = geometry_entry(world, "set_boundary_dynamic_sampling", e.sampling.compound or e.sampling.mesh or e.sampling.shape)
+                L.check(entry(world._h, b._slot, geom, b.interaction_groups.memberships, b.interaction_groups.filter))
                 b._dirty = False
                 e.uploaded = True
             if not e.uploaded and getattr(e.sampling, "shape", None) is not None and isinstance(e.sampling, StaticSampling):
                 b._sampled = True
-                if isinstance(e.sampling.shape, L.Shape):
-                    k = int(world._L.salva_hip_set_boundary_sampling_from_shape(
-                        world._h, b._slot, C.byref(e.sampling.shape), b.interaction_groups.memberships, b.interaction_groups.filter))
-                else:
-                    from .sampling import Compound
-
-                    from_handle = (world._L.salva_hip_set_boundary_sampling_from_compound if isinstance(e.sampling.shape, Compound)
-                                   else world._L.salva_hip_set_boundary_sampling_from_mesh)
-                    k = int(from_handle(world._h, b._slot, e.sampling.shape.handle(world), b.interaction_groups.memberships, b.interaction_groups.filter))
+                entry, geom = geometry_entry(world, "set_boundary_sampling_from", e.sampling.shape)
+                k = int(entry(world._h, b._slot, geom, b.interaction_groups.memberships, b.interaction_groups.filter))
                 if k < 0:
                     L.check(k)
                 b._n_sampled = k

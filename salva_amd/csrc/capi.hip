@@ -1,6 +1,7 @@
 // capi.hip — the extern "C" boundary of libsalva_hip.so (declared in include/salva_hip.h).
 // Exceptions never cross the ABI: every entry point maps them to an error code + thread-local message.
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include <memory>
@@ -51,6 +52,39 @@ static void not_in_coupling_callback(const SalvaHipWorld* world) {
         throw salva::HipError(SALVA_HIP_E_INVALID, "this entry point is not available inside a coupling callback");
 }
 
+// The two shapes most entry points have.  `required`: the pointers that must not be null besides the world — an entry that names none
+// reports "null world", one that names some reports "null argument" for the world as well.  `refused_in`: the callbacks the call is
+// refused inside of; which entries name which is not uniform (DESIGN.md §19 lists the differences within the geometry family).
+// An entry with another null rule, another message or a return value of its own stays written out.
+enum : unsigned { ANYWHERE = 0, NOT_IN_FORCE_CB = 1, NOT_IN_COUPLING_CB = 2 };
+static void check_entry(const SalvaHipWorld* world, std::initializer_list<const void*> required, unsigned refused_in) {
+    bool null = !world;
+    for (const void* p : required) null = null || !p;
+    if (null) throw salva::HipError(SALVA_HIP_E_INVALID, required.size() ? "null argument" : "null world");
+    if (refused_in & NOT_IN_FORCE_CB) not_in_force_callback(world);
+    if (refused_in & NOT_IN_COUPLING_CB) not_in_coupling_callback(world);
+}
+// ... returning a status
+template <typename F>
+static int status_entry(const SalvaHipWorld* world, std::initializer_list<const void*> required, unsigned refused_in, F&& body) {
+    return guarded([&]() -> int {
+        check_entry(world, required, refused_in);
+        body(*world->w);
+        return SALVA_HIP_OK;
+    });
+}
+// ... returning a count, or a negative status
+template <typename F>
+static int64_t count_entry(const SalvaHipWorld* world, std::initializer_list<const void*> required, unsigned refused_in, F&& body) {
+    int64_t count = 0;
+    const int rc = guarded([&]() -> int {
+        check_entry(world, required, refused_in);
+        count = (int64_t)body(*world->w);
+        return SALVA_HIP_OK;
+    });
+    return rc == SALVA_HIP_OK ? count : (int64_t)rc;
+}
+
 extern "C" {
 
 void salva_hip_default_params(SalvaHipParams* p) {
@@ -95,12 +129,9 @@ int salva_hip_set_fluid(SalvaHipWorld* world, uint32_t slot, uint64_t n, const f
                         const float* velocities_xyz, const float* volumes, const float* accelerations_xyz,
                         const float* velocity_changes_xyz, float density0, uint32_t memberships, uint32_t filter,
                         uint32_t dirty_mask) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_fluid(slot, n, positions_xyz, velocities_xyz, volumes, accelerations_xyz, velocity_changes_xyz,
-                            density0, memberships, filter, dirty_mask);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        w.set_fluid(slot, n, positions_xyz, velocities_xyz, volumes, accelerations_xyz, velocity_changes_xyz, density0, memberships, filter,
+                    dirty_mask);
     });
 }
 
@@ -114,31 +145,18 @@ int salva_hip_set_fluid_forces(SalvaHipWorld* world, uint32_t slot, const SalvaH
 }
 
 int salva_hip_remove_fluid(SalvaHipWorld* world, uint32_t slot) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->remove_fluid(slot);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.remove_fluid(slot); });
 }
 
 int salva_hip_set_boundary(SalvaHipWorld* world, uint32_t slot, uint64_t n, const float* positions_xyz,
                            const float* velocities_xyz, uint32_t memberships, uint32_t filter, int32_t wants_forces) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_boundary(slot, n, positions_xyz, velocities_xyz, memberships, filter, wants_forces != 0);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        w.set_boundary(slot, n, positions_xyz, velocities_xyz, memberships, filter, wants_forces != 0);
     });
 }
 
 int salva_hip_remove_boundary(SalvaHipWorld* world, uint32_t slot) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->remove_boundary(slot);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.remove_boundary(slot); });
 }
 
 uint32_t salva_hip_num_fluids(const SalvaHipWorld* world) { WorldLock _lk(world); return world ? (uint32_t)world->w->fluids.size() : 0; }
@@ -159,37 +177,21 @@ int salva_hip_step(SalvaHipWorld* world, float dt, const float gravity[3], Salva
 }
 
 int salva_hip_get_fluid(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->get_fluid(slot, positions_xyz, velocities_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.get_fluid(slot, positions_xyz, velocities_xyz); });
 }
 
 int salva_hip_get_fluid_field(SalvaHipWorld* world, uint32_t slot, int32_t field, float* out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_fluid_field(slot, field, out);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.get_fluid_field(slot, field, out); });
 }
 
 int salva_hip_get_boundary(SalvaHipWorld* world, uint32_t slot, float* volumes, float* forces_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_boundary(slot, volumes, forces_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.get_boundary(slot, volumes, forces_xyz); });
 }
 
 int salva_hip_set_boundary_sampling(SalvaHipWorld* world, uint32_t slot, uint64_t n, const float* local_points_xyz,
                                     uint32_t memberships, uint32_t filter) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_boundary_sampling(slot, n, local_points_xyz, memberships, filter);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        w.set_boundary_sampling(slot, n, local_points_xyz, memberships, filter);
     });
 }
 
@@ -219,7 +221,7 @@ int salva_hip_set_boundary_dynamic_sampling(SalvaHipWorld* world, uint32_t slot,
         if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
         if (!collider_shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null shape");
         not_in_force_callback(world);
-        world->w->set_boundary_dynamic_sampling(slot, *collider_shape, memberships, filter);
+        world->w->set_boundary_dynamic_sampling(slot, *collider_shape, memberships, filter);  // (the shape form of the geometry family)
         return SALVA_HIP_OK;
     });
 }
@@ -236,52 +238,29 @@ int salva_hip_set_boundary_dynamic_sampling_host(SalvaHipWorld* world, uint32_t 
 }
 
 int salva_hip_get_dist_timing(const SalvaHipWorld* world, double out4[4]) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !out4) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        world->w->get_dist_timing(out4);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {out4}, ANYWHERE, [&](World& w) { w.get_dist_timing(out4); });
 }
 uint64_t salva_hip_local_len(const SalvaHipWorld* world) { WorldLock _lk(world); return world ? world->w->local_len() : 0; }
 int salva_hip_get_local(SalvaHipWorld* world, uint32_t* ids, uint32_t* fluid_slots, uint8_t* is_ghost, float* positions_xyz,
                         float* velocities_xyz, float* densities, float* volumes) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_local(ids, fluid_slots, is_ghost, positions_xyz, velocities_xyz, densities, volumes);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, ANYWHERE, [&](World& w) {
+        w.get_local(ids, fluid_slots, is_ghost, positions_xyz, velocities_xyz, densities, volumes);
     });
 }
 int64_t salva_hip_get_local_contacts(SalvaHipWorld* world, int32_t boundary_contacts, uint64_t* offsets, uint32_t* j_model, uint32_t* j,
                                      uint64_t capacity) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        total = (int64_t)world->w->get_local_contacts(boundary_contacts, offsets, j_model, j, capacity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, ANYWHERE, [&](World& w) {
+        return w.get_local_contacts(boundary_contacts, offsets, j_model, j, capacity);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 int salva_hip_force_add_local_accelerations(SalvaHipWorld* world, const float* accelerations_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->force_add_local_accelerations(accelerations_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.force_add_local_accelerations(accelerations_xyz); });
 }
 int salva_hip_get_fluid_async(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->get_fluid_async(slot, positions_xyz, velocities_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.get_fluid_async(slot, positions_xyz, velocities_xyz); });
 }
 int salva_hip_wait_download(SalvaHipWorld* world) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->wait_download();
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.wait_download(); });
 }
 void* salva_hip_host_alloc(SalvaHipWorld* world, uint64_t bytes) { WorldLock _lk(world);
     void* p = nullptr;
@@ -315,86 +294,42 @@ int salva_hip_host_unregister(void* p) {
 }
 
 int salva_hip_clear_boundary_sampling(SalvaHipWorld* world, uint32_t slot) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->clear_boundary_sampling(slot);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.clear_boundary_sampling(slot); });
 }
 
 int salva_hip_get_boundary_sources(SalvaHipWorld* world, uint32_t slot, uint32_t* fluid_slots, uint32_t* indices) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_boundary_sources(slot, fluid_slots, indices);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.get_boundary_sources(slot, fluid_slots, indices); });
 }
 
 int salva_hip_set_force_callback(SalvaHipWorld* world, SalvaHipForceCallback cb, void* user) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->set_force_callback(cb, user, world);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.set_force_callback(cb, user, world); });
 }
 
 int salva_hip_set_device_force_callback(SalvaHipWorld* world, SalvaHipDeviceForceCallback cb, void* user) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_device_force_callback(cb, user, world);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.set_device_force_callback(cb, user, world); });
 }
 static_assert(sizeof(SalvaHipDeviceView) == SALVA_HIP_DEVICE_VIEW_BYTES, "SalvaHipDeviceView: the header's size constant is what the mirrors check");
 int salva_hip_device_view_read(SalvaHipWorld* world, const void* device_src, void* host_dst, uint64_t bytes) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->device_view_read(device_src, host_dst, bytes);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.device_view_read(device_src, host_dst, bytes); });
 }
 int salva_hip_get_device_force_stats(const SalvaHipWorld* world, uint64_t out4[4]) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !out4) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        world->w->get_device_force_stats(out4);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {out4}, ANYWHERE, [&](World& w) { w.get_device_force_stats(out4); });
 }
 
 int salva_hip_set_coupling_callback(SalvaHipWorld* world, SalvaHipCouplingCallback cb, void* user) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_coupling_callback(cb, user, world);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.set_coupling_callback(cb, user, world); });
 }
 
 int salva_hip_force_get_state(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz, float* densities) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->force_get_state(slot, positions_xyz, velocities_xyz, densities);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.force_get_state(slot, positions_xyz, velocities_xyz, densities); });
 }
 
 int salva_hip_force_add_accelerations(SalvaHipWorld* world, uint32_t slot, const float* accelerations_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->force_add_accelerations(slot, accelerations_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.force_add_accelerations(slot, accelerations_xyz); });
 }
 
 int salva_hip_set_fluid_field(SalvaHipWorld* world, uint32_t slot, int32_t field, const float* data) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_fluid_field(slot, field, data);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.set_fluid_field(slot, field, data); });
 }
 
 int salva_hip_get_timestep(const SalvaHipWorld* world, float* dt, float* inv_dt) { WorldLock _lk(world);
@@ -404,20 +339,11 @@ int salva_hip_get_timestep(const SalvaHipWorld* world, float* dt, float* inv_dt)
 }
 
 int salva_hip_set_timestep(SalvaHipWorld* world, float dt, float inv_dt) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_timestep(dt, inv_dt);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.set_timestep(dt, inv_dt); });
 }
 
 int salva_hip_get_boundary_particles(SalvaHipWorld* world, uint32_t slot, float* positions_xyz, float* velocities_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_boundary_particles(slot, positions_xyz, velocities_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.get_boundary_particles(slot, positions_xyz, velocities_xyz); });
 }
 
 int salva_hip_get_boundary_wrench(SalvaHipWorld* world, uint32_t slot, const float point[3], float force[3], float torque[3]) { WorldLock _lk(world);
@@ -440,20 +366,11 @@ int salva_hip_get_boundary_wrenches(SalvaHipWorld* world, uint32_t n, const uint
 }
 
 int salva_hip_get_dcs_stats(const SalvaHipWorld* world, uint64_t out4[4]) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !out4) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        world->w->get_dcs_stats(out4);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {out4}, ANYWHERE, [&](World& w) { w.get_dcs_stats(out4); });
 }
 
 int salva_hip_clear_boundary_forces(SalvaHipWorld* world, uint32_t slot) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->clear_boundary_forces(slot);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.clear_boundary_forces(slot); });
 }
 
 uint64_t salva_hip_device_bytes(const SalvaHipWorld* world) { WorldLock _lk(world); return world ? world->w->device_bytes() : 0; }
@@ -488,18 +405,10 @@ float salva_hip_time_kernel(SalvaHipWorld* world, int32_t kernel, int32_t reps) 
 }
 
 int salva_hip_enable_counters(SalvaHipWorld* world, int32_t enabled) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->set_timers(enabled != 0);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.set_timers(enabled != 0); });
 }
 int salva_hip_set_cfl(SalvaHipWorld* world, int32_t mode, float cfl_coeff, int32_t min_num_substeps, int32_t max_num_substeps) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->set_cfl(mode, cfl_coeff, min_num_substeps, max_num_substeps);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.set_cfl(mode, cfl_coeff, min_num_substeps, max_num_substeps); });
 }
 int64_t salva_hip_get_substeps(const SalvaHipWorld* world, float* out, uint64_t capacity) { WorldLock _lk(world);
     int64_t n = 0;
@@ -513,11 +422,7 @@ int64_t salva_hip_get_substeps(const SalvaHipWorld* world, float* out, uint64_t 
     return rc == SALVA_HIP_OK ? n : (int64_t)rc;
 }
 int salva_hip_get_counters(const SalvaHipWorld* world, SalvaHipCounters* out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        *out = world->w->counters;
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {out}, ANYWHERE, [&](World& w) { *out = w.counters; });
 }
 
 #ifdef SALVA_HIP_DIAG
@@ -646,405 +551,231 @@ int salva_hip_comm_time(SalvaHipComm* comm, uint64_t bytes, int32_t iters, float
     });
 }
 int salva_hip_set_domain(SalvaHipWorld* world, SalvaHipComm* comm, int32_t cell_lo, int32_t cell_hi, uint32_t gid_offset) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !comm) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        world->w->set_domain(comm->t, cell_lo, cell_hi, gid_offset);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {comm}, NOT_IN_FORCE_CB, [&](World& w) { w.set_domain(comm->t, cell_lo, cell_hi, gid_offset); });
 }
 int salva_hip_rebalance(SalvaHipWorld* world, int32_t* cell_lo, int32_t* cell_hi) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->rebalance(cell_lo, cell_hi);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.rebalance(cell_lo, cell_hi); });
 }
 int64_t salva_hip_get_owned(SalvaHipWorld* world, uint32_t capacity, uint32_t* gids, float* positions_xyz, float* velocities_xyz,
                             uint32_t* fluid_slots) { WorldLock _lk(world);
-    int64_t count = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        count = (int64_t)world->w->get_owned(capacity, gids, positions_xyz, velocities_xyz, fluid_slots);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, ANYWHERE, [&](World& w) {
+        return w.get_owned(capacity, gids, positions_xyz, velocities_xyz, fluid_slots);
     });
-    return rc == SALVA_HIP_OK ? count : (int64_t)rc;
 }
 
 int64_t salva_hip_delete_owned(SalvaHipWorld* world, uint32_t n, const uint32_t* gids) { WorldLock _lk(world);
-    int64_t count = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        count = (int64_t)world->w->delete_owned(n, gids);
-        return SALVA_HIP_OK;
-    });
-    return rc == SALVA_HIP_OK ? count : (int64_t)rc;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { return w.delete_owned(n, gids); });
 }
 
 int64_t salva_hip_particles_intersecting_aabb(SalvaHipWorld* world, const float mins[3], const float maxs[3], uint64_t capacity,
                                              uint32_t* kinds, uint32_t* slots, uint32_t* indices) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !mins || !maxs) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        total = (int64_t)world->w->particles_in_aabb(mins, maxs, capacity, kinds, slots, indices);
-        return SALVA_HIP_OK;
+    return count_entry(world, {mins, maxs}, ANYWHERE, [&](World& w) {
+        return w.particles_in_aabb(mins, maxs, capacity, kinds, slots, indices);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 int64_t salva_hip_particles_intersecting_shape(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
                                               const SalvaHipShape* shape, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                               uint32_t* indices) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        total = (int64_t)world->w->particles_in_shape(translation, rotation_ijkw, *shape, capacity, kinds, slots, indices);
-        return SALVA_HIP_OK;
+    return count_entry(world, {translation, rotation_ijkw, shape}, ANYWHERE, [&](World& w) {
+        return w.particles_in(*shape, translation, rotation_ijkw, capacity, kinds, slots, indices);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 int64_t salva_hip_particles_intersecting_host_shape(SalvaHipWorld* world, const SalvaHipHostQueryShape* shape, uint64_t capacity,
                                                     uint32_t* kinds, uint32_t* slots, uint32_t* indices) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        total = (int64_t)world->w->particles_in_host_shape(*shape, capacity, kinds, slots, indices);
-        return SALVA_HIP_OK;
+    return count_entry(world, {shape}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.particles_in_host_shape(*shape, capacity, kinds, slots, indices);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 int salva_hip_add_particles(SalvaHipWorld* world, uint32_t slot, uint64_t n_add, const float* positions_xyz, const float* velocities_xyz) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->add_particles(slot, n_add, positions_xyz, velocities_xyz);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.add_particles(slot, n_add, positions_xyz, velocities_xyz); });
 }
 int64_t salva_hip_delete_particles(SalvaHipWorld* world, uint32_t slot, const uint8_t* deleted_mask) { WorldLock _lk(world);
-    int64_t kept = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        kept = (int64_t)world->w->delete_particles(slot, deleted_mask);
-        return SALVA_HIP_OK;
-    });
-    return rc == SALVA_HIP_OK ? kept : (int64_t)rc;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { return w.delete_particles(slot, deleted_mask); });
 }
 
 int64_t salva_hip_get_fluid_contacts(SalvaHipWorld* world, uint32_t slot, int32_t boundary_contacts, uint64_t* offsets,
                                      uint32_t* j_model, uint32_t* j, uint64_t capacity) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        total = (int64_t)world->w->get_fluid_contacts(slot, boundary_contacts, offsets, j_model, j, capacity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, ANYWHERE, [&](World& w) {
+        return w.get_fluid_contacts(slot, boundary_contacts, offsets, j_model, j, capacity);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 
 int salva_hip_get_force_stats(SalvaHipWorld* world, uint32_t slot, uint32_t force, int32_t* iters, float* error) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->get_force_stats(slot, force, iters, error);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, ANYWHERE, [&](World& w) { w.get_force_stats(slot, force, iters, error); });
 }
 
 int64_t salva_hip_get_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, float* positions0_xyz,
                                        float* volumes0, float* rotations9, float* stress6, float* grad_tr9) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        r = (int64_t)world->w->get_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9, stress6, grad_tr9);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, ANYWHERE, [&](World& w) {
+        return w.get_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9, stress6, grad_tr9);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int salva_hip_set_elasticity_state(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t n, const float* positions0_xyz,
                                    const float* volumes0, const float* rotations9) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        world->w->set_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, ANYWHERE, [&](World& w) {
+        w.set_elasticity_state(slot, force, n, positions0_xyz, volumes0, rotations9);
     });
 }
 
 int64_t salva_hip_get_elasticity_contacts(SalvaHipWorld* world, uint32_t slot, uint32_t force, uint64_t* n0, uint32_t* offsets,
                                           uint32_t* j, uint64_t capacity) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        r = (int64_t)world->w->get_elasticity_contacts(slot, force, n0, offsets, j, capacity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, ANYWHERE, [&](World& w) {
+        return w.get_elasticity_contacts(slot, force, n0, offsets, j, capacity);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_sample_shape(SalvaHipWorld* world, const SalvaHipShape* shape, float particle_rad, int32_t mode, uint64_t capacity,
                                float* out_xyz) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->sample_shape(*shape, particle_rad, mode, capacity, out_xyz);
-        return SALVA_HIP_OK;
+    return count_entry(world, {shape}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.sample(*shape, particle_rad, mode, capacity, out_xyz);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_sample_host_shape(SalvaHipWorld* world, const SalvaHipHostRayShape* shape, float particle_rad, int32_t mode,
                                     uint64_t capacity, float* out_xyz) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->sample_host_shape(*shape, particle_rad, mode, capacity, out_xyz);
-        return SALVA_HIP_OK;
+    return count_entry(world, {shape}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.sample_host_shape(*shape, particle_rad, mode, capacity, out_xyz);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_add_particles_sampled(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, const float translation[3],
                                         const float rotation_ijkw[4], int32_t mode, const float velocity[3]) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !shape || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->add_particles_sampled(slot, *shape, translation, rotation_ijkw, mode, velocity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {shape, translation, rotation_ijkw}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.add_particles_sampled(slot, *shape, translation, rotation_ijkw, mode, velocity);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_set_boundary_sampling_from_shape(SalvaHipWorld* world, uint32_t slot, const SalvaHipShape* shape, uint32_t memberships,
                                                    uint32_t filter) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !shape) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->set_boundary_sampling_from_shape(slot, *shape, memberships, filter);
-        return SALVA_HIP_OK;
+    return count_entry(world, {shape}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.set_boundary_sampling_from(slot, *shape, memberships, filter);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int salva_hip_create_mesh(SalvaHipWorld* world, const float* vertices_xyz, uint32_t nv, const uint32_t* indices, uint32_t nt,
                           uint32_t flags, uint32_t* mesh_out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !mesh_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        *mesh_out = world->w->create_mesh(vertices_xyz, nv, indices, nt, flags);
-        return SALVA_HIP_OK;
+    return status_entry(world, {mesh_out}, NOT_IN_FORCE_CB, [&](World& w) {
+        *mesh_out = w.create_mesh(vertices_xyz, nv, indices, nt, flags);
     });
 }
 
 int salva_hip_create_heightfield(SalvaHipWorld* world, const float* heights, uint32_t nrows, uint32_t ncols, const float scale[3],
                                  uint32_t* mesh_out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !mesh_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        *mesh_out = world->w->create_heightfield(heights, nrows, ncols, scale);
-        return SALVA_HIP_OK;
+    return status_entry(world, {mesh_out}, NOT_IN_FORCE_CB, [&](World& w) {
+        *mesh_out = w.create_heightfield(heights, nrows, ncols, scale);
     });
 }
 
 int salva_hip_destroy_mesh(SalvaHipWorld* world, uint32_t mesh) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->destroy_mesh(mesh);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.destroy_mesh(mesh); });
 }
 
 int64_t salva_hip_sample_mesh(SalvaHipWorld* world, uint32_t mesh, float particle_rad, int32_t mode, uint64_t capacity,
                               float* out_xyz) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        r = world->w->sample_mesh(mesh, particle_rad, mode, capacity, out_xyz);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.sample({SALVA_HIP_SHAPE_MESH, mesh}, particle_rad, mode, capacity, out_xyz);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_add_particles_sampled_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, const float translation[3],
                                              const float rotation_ijkw[4], int32_t mode, const float velocity[3]) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->add_particles_sampled_mesh(slot, mesh, translation, rotation_ijkw, mode, velocity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {translation, rotation_ijkw}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.add_particles_sampled(slot, {SALVA_HIP_SHAPE_MESH, mesh}, translation, rotation_ijkw, mode, velocity);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_set_boundary_sampling_from_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
                                                   uint32_t filter) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        r = world->w->set_boundary_sampling_from_mesh(slot, mesh, memberships, filter);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.set_boundary_sampling_from(slot, {SALVA_HIP_SHAPE_MESH, mesh}, memberships, filter);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int salva_hip_set_boundary_dynamic_sampling_mesh(SalvaHipWorld* world, uint32_t slot, uint32_t mesh, uint32_t memberships,
                                                  uint32_t filter) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_boundary_dynamic_sampling_mesh(slot, mesh, memberships, filter);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        w.set_boundary_dynamic_sampling(slot, {SALVA_HIP_SHAPE_MESH, mesh}, memberships, filter);
     });
 }
 
 int salva_hip_create_compound(SalvaHipWorld* world, const SalvaHipCompoundPart* parts, uint32_t nparts, uint32_t* compound_out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !compound_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        *compound_out = world->w->create_compound(parts, nparts);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {compound_out}, NOT_IN_FORCE_CB, [&](World& w) { *compound_out = w.create_compound(parts, nparts); });
 }
 
 int salva_hip_destroy_compound(SalvaHipWorld* world, uint32_t compound) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->destroy_compound(compound);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) { w.destroy_compound(compound); });
 }
 
 int salva_hip_set_boundary_dynamic_sampling_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
                                                      uint32_t filter) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        world->w->set_boundary_dynamic_sampling_compound(slot, compound, memberships, filter);
-        return SALVA_HIP_OK;
+    return status_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        w.set_boundary_dynamic_sampling(slot, {SALVA_HIP_SHAPE_COMPOUND, compound}, memberships, filter);
     });
 }
 
 int64_t salva_hip_particles_intersecting_compound(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
                                                   uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                                   uint32_t* indices) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        total = (int64_t)world->w->particles_in_compound(translation, rotation_ijkw, compound, capacity, kinds, slots, indices);
-        return SALVA_HIP_OK;
+    return count_entry(world, {translation, rotation_ijkw}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.particles_in({SALVA_HIP_SHAPE_COMPOUND, compound}, translation, rotation_ijkw, capacity, kinds, slots, indices);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 
 int64_t salva_hip_particles_intersecting_mesh(SalvaHipWorld* world, const float translation[3], const float rotation_ijkw[4],
                                               uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices) { WorldLock _lk(world);
-    int64_t total = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        total = (int64_t)world->w->particles_in_mesh(translation, rotation_ijkw, mesh, capacity, kinds, slots, indices);
-        return SALVA_HIP_OK;
+    return count_entry(world, {translation, rotation_ijkw}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.particles_in({SALVA_HIP_SHAPE_MESH, mesh}, translation, rotation_ijkw, capacity, kinds, slots, indices);
     });
-    return rc == SALVA_HIP_OK ? total : (int64_t)rc;
 }
 
 int64_t salva_hip_sample_compound(SalvaHipWorld* world, uint32_t compound, float particle_rad, int32_t mode, uint64_t capacity,
                                   float* out_xyz) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        r = world->w->sample_compound(compound, particle_rad, mode, capacity, out_xyz);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.sample({SALVA_HIP_SHAPE_COMPOUND, compound}, particle_rad, mode, capacity, out_xyz);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_add_particles_sampled_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, const float translation[3],
                                                  const float rotation_ijkw[4], int32_t mode, const float velocity[3]) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        r = world->w->add_particles_sampled_compound(slot, compound, translation, rotation_ijkw, mode, velocity);
-        return SALVA_HIP_OK;
+    return count_entry(world, {translation, rotation_ijkw}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.add_particles_sampled(slot, {SALVA_HIP_SHAPE_COMPOUND, compound}, translation, rotation_ijkw, mode, velocity);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int64_t salva_hip_set_boundary_sampling_from_compound(SalvaHipWorld* world, uint32_t slot, uint32_t compound, uint32_t memberships,
                                                       uint32_t filter) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        r = world->w->set_boundary_sampling_from_compound(slot, compound, memberships, filter);
-        return SALVA_HIP_OK;
+    return count_entry(world, {}, NOT_IN_FORCE_CB, [&](World& w) {
+        return w.set_boundary_sampling_from(slot, {SALVA_HIP_SHAPE_COMPOUND, compound}, memberships, filter);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 static_assert(sizeof(SalvaHipRegion) == SALVA_HIP_REGION_BYTES, "SalvaHipRegion: the header's size constant is what the mirrors check");
 int64_t salva_hip_delete_particles_in_region(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot,
                                              uint8_t* deleted_mask_or_null) { WorldLock _lk(world);
-    int64_t r = 0;
-    const int rc = guarded([&]() -> int {
-        if (!world || !region) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        not_in_coupling_callback(world);
-        r = world->w->delete_particles_in_region(*region, fluid_slot, deleted_mask_or_null);
-        return SALVA_HIP_OK;
+    return count_entry(world, {region}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        return w.delete_particles_in_region(*region, fluid_slot, deleted_mask_or_null);
     });
-    return rc == SALVA_HIP_OK ? r : (int64_t)rc;
 }
 
 int salva_hip_add_sink(SalvaHipWorld* world, const SalvaHipRegion* region, uint32_t fluid_slot, uint32_t* sink_out) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !region || !sink_out) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        not_in_coupling_callback(world);
-        *sink_out = world->w->add_sink(*region, fluid_slot);
-        return SALVA_HIP_OK;
+    return status_entry(world, {region, sink_out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        *sink_out = w.add_sink(*region, fluid_slot);
     });
 }
 
 int salva_hip_remove_sink(SalvaHipWorld* world, uint32_t sink) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world) throw salva::HipError(SALVA_HIP_E_INVALID, "null world");
-        not_in_force_callback(world);
-        not_in_coupling_callback(world);
-        world->w->remove_sink(sink);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.remove_sink(sink); });
 }
 
 int salva_hip_set_sink_pose(SalvaHipWorld* world, uint32_t sink, const float translation[3], const float rotation_ijkw[4]) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !translation || !rotation_ijkw) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        not_in_force_callback(world);
-        not_in_coupling_callback(world);
-        world->w->set_sink_pose(sink, translation, rotation_ijkw);
-        return SALVA_HIP_OK;
+    return status_entry(world, {translation, rotation_ijkw}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.set_sink_pose(sink, translation, rotation_ijkw);
     });
 }
 
 int salva_hip_get_sink_stats(const SalvaHipWorld* world, uint32_t sink, uint64_t out2[2]) { WorldLock _lk(world);
-    return guarded([&]() -> int {
-        if (!world || !out2) throw salva::HipError(SALVA_HIP_E_INVALID, "null argument");
-        world->w->get_sink_stats(sink, out2);
-        return SALVA_HIP_OK;
-    });
+    return status_entry(world, {out2}, ANYWHERE, [&](World& w) { w.get_sink_stats(sink, out2); });
 }
 
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }

@@ -333,16 +333,36 @@ void World::sample_lattice(const float mins[3], const float maxs[3], float parti
     g.cx = smp_coords.p; g.cy = g.cx + g.nx; g.cz = g.cy + g.ny;
 }
 
-void World::sample_mark(const SalvaHipShape& shape, float particle_rad, int mode, SampleLattice& L) {
+// The bit lattice of a geometry: one lattice, three mark kernels.  A built-in shape is marked in closed form over its
+// own half extents.  A mesh or a compound (§17) is cast at hit by hit over the lattice of its local box — a
+// compound's is the unloosened merge of the parts' boxes, parry's local AABB of a compound — and its error word is a ray with more
+// than 64 accepted hits.
+void World::sample_mark(const Geom& geom, float particle_rad, int mode, SampleLattice& L) {
     check_sample_args(particle_rad, mode);
-    float ext[3], mins[3];
-    shape_half_extents(shape, ext);
-    for (int a = 0; a < 3; ++a) mins[a] = -ext[a];
-    sample_lattice(mins, ext, particle_rad, L);
+    const int volume = mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0;
     const SampleGrid& g = L.g;
-    const uint64_t rays = (uint64_t)g.ny * g.nz + (uint64_t)g.nz * g.nx + (uint64_t)g.nx * g.ny;
-    k_sample_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, shape, mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0, smp_bits.p);
+    auto rays = [&] { return (uint64_t)g.ny * g.nz + (uint64_t)g.nz * g.nx + (uint64_t)g.nx * g.ny; };
+    if (geom.kind != SALVA_HIP_SHAPE_MESH && geom.kind != SALVA_HIP_SHAPE_COMPOUND) {
+        float ext[3], mins[3];
+        shape_half_extents(geom.shape, ext);
+        for (int a = 0; a < 3; ++a) mins[a] = -ext[a];
+        sample_lattice(mins, ext, particle_rad, L);
+        k_sample_mark<<<div_up(rays(), BLOCK), BLOCK, 0, stream>>>(g, geom.shape, volume, smp_bits.p);
+        SALVA_HIP_CHECK(hipGetLastError());
+        return;
+    }
+    sample_lattice(geom.mins(), geom.maxs(), particle_rad, L);
+    smp_err.ensure(1);
+    SALVA_HIP_CHECK(hipMemsetAsync(smp_err.p, 0, sizeof(uint32_t), stream));
+    if (geom.mesh) k_sample_mesh_mark<<<div_up(rays(), BLOCK), BLOCK, 0, stream>>>(g, geom.mesh->dev(), volume, smp_bits.p, smp_err.p);
+    else k_compound_mark<<<div_up(rays(), BLOCK), BLOCK, 0, stream>>>(g, geom.parts(), geom.nparts(), volume, smp_bits.p, smp_err.p);
     SALVA_HIP_CHECK(hipGetLastError());
+    uint32_t err = 0;
+    SALVA_HIP_CHECK(hipMemcpyAsync(&err, smp_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+    if (err)
+        throw HipError(SALVA_HIP_E_CAPACITY, geom.mesh ? "mesh sampling: a ray crosses the mesh more than 64 times"
+                                                       : "compound sampling: a ray crosses the parts' boundaries more than 64 times");
 }
 
 // count + scan; returns the number of samples (smp_off then holds every word's first output index)
@@ -373,10 +393,10 @@ int64_t World::sample_download(const SampleLattice& L, uint64_t capacity, float*
     return total;
 }
 
-int64_t World::sample_shape(const SalvaHipShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
+int64_t World::sample(const GeomArg& geom, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
     use_device();
     SampleLattice L;
-    sample_mark(shape, particle_rad, mode, L);
+    sample_mark(geom_of(geom), particle_rad, mode, L);
     return sample_download(L, capacity, out_xyz);
 }
 
@@ -458,13 +478,6 @@ static const char* const kDecomposedSampling =
 
 // Fluid::add_particles of the posed samples, one velocity for all: the positions go from the bit lattice straight into the staging
 // array.
-void World::check_add_sampled(uint32_t slot, const float t[3], const float q[4]) const {
-    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
-    for (int a = 0; a < 4; ++a)
-        if (!std::isfinite(q[a]) || (a < 3 && !std::isfinite(t[a]))) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
-}
-
 int64_t World::append_sampled(uint32_t slot, const SampleLattice& L, const float t[3], const float q[4], const float* vel_h) {
     const uint32_t total = sample_count(L);
     if (!total) return 0;
@@ -483,11 +496,14 @@ int64_t World::append_sampled(uint32_t slot, const SampleLattice& L, const float
     return total;
 }
 
-int64_t World::add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel_h) {
+int64_t World::add_particles_sampled(uint32_t slot, const GeomArg& geom, const float t[3], const float q[4], int mode, const float* vel_h) {
     use_device();
-    check_add_sampled(slot, t, q);
+    if (slot >= fluids.size()) throw HipError(SALVA_HIP_E_INVALID, "fluid slot out of range");
+    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
+    for (int a = 0; a < 4; ++a)
+        if (!std::isfinite(q[a]) || (a < 3 && !std::isfinite(t[a]))) throw HipError(SALVA_HIP_E_INVALID, "non-finite pose");
     SampleLattice L;
-    sample_mark(shape, prm.particle_radius, mode, L);
+    sample_mark(geom_of(geom), prm.particle_radius, mode, L);
     return append_sampled(slot, L, t, q, vel_h);
 }
 
@@ -504,93 +520,13 @@ int64_t World::boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint
     return total;
 }
 
-int64_t World::set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter) {
+int64_t World::set_boundary_sampling_from(uint32_t slot, const GeomArg& geom, uint32_t memberships, uint32_t filter) {
     use_device();
     if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
     if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
     SampleLattice L;
-    sample_mark(shape, prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
-    return boundary_from_sampled(slot, L, memberships, filter);
-}
-
-// ---- the same three for a triangle mesh (mesh.h): a second mark kernel, everything behind it shared.  `launch` starts
-// the mark kernel of a shape that is cast at hit by hit (a mesh, a compound) over the lattice of [mins, maxs]; its error word is a
-// ray with more than 64 accepted hits.
-void World::sample_mark_cast(const float mins[3], const float maxs[3], float particle_rad, int mode, SampleLattice& L,
-                             const std::function<void(const SampleGrid&, uint64_t, int)>& launch, const char* too_many_hits) {
-    check_sample_args(particle_rad, mode);
-    sample_lattice(mins, maxs, particle_rad, L);
-    const SampleGrid& g = L.g;
-    const uint64_t rays = (uint64_t)g.ny * g.nz + (uint64_t)g.nz * g.nx + (uint64_t)g.nx * g.ny;
-    smp_err.ensure(1);
-    SALVA_HIP_CHECK(hipMemsetAsync(smp_err.p, 0, sizeof(uint32_t), stream));
-    launch(g, rays, mode == SALVA_HIP_SAMPLE_VOLUME ? 1 : 0);
-    SALVA_HIP_CHECK(hipGetLastError());
-    uint32_t err = 0;
-    SALVA_HIP_CHECK(hipMemcpyAsync(&err, smp_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-    if (err) throw HipError(SALVA_HIP_E_CAPACITY, too_many_hits);
-}
-
-void World::sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L) {
-    sample_mark_cast(mesh.mins, mesh.maxs, particle_rad, mode, L, [&](const SampleGrid& g, uint64_t rays, int volume) {
-        k_sample_mesh_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, mesh.dev(), volume, smp_bits.p, smp_err.p);
-    }, "mesh sampling: a ray crosses the mesh more than 64 times");
-}
-
-int64_t World::sample_mesh(uint32_t mesh, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
-    use_device();
-    SampleLattice L;
-    sample_mark_mesh(*mesh_at(mesh), particle_rad, mode, L);
-    return sample_download(L, capacity, out_xyz);
-}
-
-int64_t World::add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel_h) {
-    use_device();
-    check_add_sampled(slot, t, q);
-    SampleLattice L;
-    sample_mark_mesh(*mesh_at(mesh), prm.particle_radius, mode, L);
-    return append_sampled(slot, L, t, q, vel_h);
-}
-
-int64_t World::set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter) {
-    use_device();
-    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
-    SampleLattice L;
-    sample_mark_mesh(*mesh_at(mesh), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
-    return boundary_from_sampled(slot, L, memberships, filter);
-}
-
-// ---- and for a compound (raycast.h): a third mark kernel.  The lattice is that of the unloosened merge of the parts'
-// boxes, parry's local AABB of a compound.  Nothing keeps the compound: a boundary sampled from it holds its points only.
-void World::sample_mark_compound(const CompoundRes& c, float particle_rad, int mode, SampleLattice& L) {
-    sample_mark_cast(c.mins, c.maxs, particle_rad, mode, L, [&](const SampleGrid& g, uint64_t rays, int volume) {
-        k_compound_mark<<<div_up(rays, BLOCK), BLOCK, 0, stream>>>(g, c.parts.p, c.nparts, volume, smp_bits.p, smp_err.p);
-    }, "compound sampling: a ray crosses the parts' boundaries more than 64 times");
-}
-
-int64_t World::sample_compound(uint32_t compound, float particle_rad, int mode, uint64_t capacity, float* out_xyz) {
-    use_device();
-    SampleLattice L;
-    sample_mark_compound(*compound_at(compound), particle_rad, mode, L);
-    return sample_download(L, capacity, out_xyz);
-}
-
-int64_t World::add_particles_sampled_compound(uint32_t slot, uint32_t compound, const float t[3], const float q[4], int mode, const float* vel_h) {
-    use_device();
-    check_add_sampled(slot, t, q);
-    SampleLattice L;
-    sample_mark_compound(*compound_at(compound), prm.particle_radius, mode, L);
-    return append_sampled(slot, L, t, q, vel_h);
-}
-
-int64_t World::set_boundary_sampling_from_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter) {
-    use_device();
-    if (slot > bounds.size()) throw HipError(SALVA_HIP_E_INVALID, "boundary slot out of range (slots are dense)");
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, kDecomposedSampling);
-    SampleLattice L;
-    sample_mark_compound(*compound_at(compound), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
+    // (nothing keeps a mesh or a compound: a boundary sampled from it holds its points only)
+    sample_mark(geom_of(geom), prm.particle_radius, SALVA_HIP_SAMPLE_SURFACE, L);
     return boundary_from_sampled(slot, L, memberships, filter);
 }
 

@@ -23,24 +23,48 @@ namespace salva {
 
 struct DcsParams;  // dcs.h
 struct DcsbEntry;
-struct SampleGrid;  // sample.hip
+
+// A geometry as it reaches the library — a built-in SalvaHipShape, or the handle of a mesh or compound of this world
+// — and the same resolved (World::geom_of): what it is and what keeps it alive.  An operation resolves its argument once, where it
+// used to look the handle up, and hands the Geom on by const reference.  Only a DynSampling and a sink store one:
+// salva_hip_destroy_mesh / _compound refuse while a handle's resource is held.
+struct GeomArg {
+    int kind;                    // SALVA_HIP_SHAPE_MESH / _COMPOUND for a handle
+    const SalvaHipShape* shape;  // non-null: a built-in shape, whatever `kind` says
+    uint32_t handle;
+    GeomArg(const SalvaHipShape& s) : kind(s.kind), shape(&s), handle(0) {}
+    GeomArg(int kind_, uint32_t handle_) : kind(kind_), shape(nullptr), handle(handle_) {}
+};
+struct Geom {
+    int kind = 0;                           // SALVA_HIP_SHAPE_BALL .. _COMPOUND; 0: a SalvaHipShape of no built-in kind (check_shape_params refuses it)
+    SalvaHipShape shape{};                  // a built-in shape (ball, cuboid, capsule, cylinder)
+    std::shared_ptr<MeshRes> mesh;          // SALVA_HIP_SHAPE_MESH
+    std::shared_ptr<CompoundRes> compound;  // SALVA_HIP_SHAPE_COMPOUND
+    bool built_in() const { return kind >= SALVA_HIP_SHAPE_BALL && kind <= SALVA_HIP_SHAPE_CYLINDER; }
+    // of a mesh or compound: the local box, whether a solid distance exists, and the device arguments the kernels take
+    const float* mins() const { return mesh ? mesh->mins : compound->mins; }
+    const float* maxs() const { return mesh ? mesh->maxs : compound->maxs; }
+    bool solid() const { return mesh ? (mesh->flags & SALVA_HIP_MESH_ORIENTED) != 0 : !compound || compound->solid; }
+    const CompoundPartDev* parts() const { return compound ? compound->parts.p : nullptr; }
+    uint32_t nparts() const { return compound ? compound->nparts : 0u; }
+};
+// the two checks every posed operation shares; `what` opens the message ("shape query", "region"), `hint` closes it
+void check_pose(const float t[3], const float q[4], const char* what);
+void check_solid(const Geom& g, const char* what, const char* hint = "");
 
 // ColliderSampling::DynamicContactSampling (integrations/rapier/fluids_pipeline.rs:42-43): the one description of a dynamically
 // sampled collider.  The boundary's particles are re-emitted by every step (World::run_dynamic_sampling, world_coupling.hip); a
 // BoundarySlot that drops the description drops everything of the sampling method with it — the mesh or compound it kept alive
 // (salva_hip_destroy_mesh / _compound refuse while one is held), the host's callbacks and user pointer, the source arrays.
 struct DynSampling {
-    int kind = 0;                           // SALVA_HIP_SHAPE_*
-    SalvaHipShape shape{};                  // a built-in shape (ball, cuboid, capsule, cylinder)
-    SalvaHipHostShape host{};               // SALVA_HIP_SHAPE_HOST: the host's compute_aabb / project_point callbacks
-    std::shared_ptr<MeshRes> mesh;          // SALVA_HIP_SHAPE_MESH
-    std::shared_ptr<CompoundRes> compound;  // SALVA_HIP_SHAPE_COMPOUND
+    Geom geom;                              // resolved at registration; geom.kind == SALVA_HIP_SHAPE_HOST: none, the shape is `host`
+    SalvaHipHostShape host{};               // the host's compute_aabb / project_point callbacks
     SalvaHipRigidPose pose{};               // the collider's last pose (identity until salva_hip_update_boundary_pose)
     // host index of the fluid particle behind each emitted row (decomposed run: its global id, and `src_model` its fluid — the
     // particle may live on another rank)
     DevBuf<uint32_t> src, src_model;
     DynSampling() { pose.rotation[3] = 1.0f; }
-    bool built_in() const { return kind >= SALVA_HIP_SHAPE_BALL && kind <= SALVA_HIP_SHAPE_CYLINDER; }  // projects inside the pass over the fluid
+    bool built_in() const { return geom.built_in(); }  // projects inside the pass over the fluid
     // the only two places that know what each kind needs: the pass's parameters for (h, particle radius, dt) — a host shape's box
     // comes from its aabb callback — and the collider's half of a batched run's table entry
     DcsParams params(float h, float particle_radius, float dt) const;
@@ -112,8 +136,8 @@ class World {
     void get_sink_stats(uint32_t sink, uint64_t out[2]) const;
     uint64_t particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                uint32_t* indices);
-    uint64_t particles_in_shape(const float t[3], const float q[4], const SalvaHipShape& shape, uint64_t capacity, uint32_t* kinds,
-                                uint32_t* slots, uint32_t* indices);
+    uint64_t particles_in(const GeomArg& geom, const float t[3], const float q[4], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                          uint32_t* indices);
     uint64_t particles_in_host_shape(const SalvaHipHostQueryShape& shape, uint64_t capacity, uint32_t* kinds, uint32_t* slots, uint32_t* indices);
     void map_query_hits(std::vector<uint64_t>& keys, uint32_t* kinds, uint32_t* slots, uint32_t* indices);
     void get_fluid(uint32_t slot, float* pos, float* vel);
@@ -129,34 +153,20 @@ class World {
     void get_boundary(uint32_t slot, float* volumes, float* forces);
     void set_boundary_sampling(uint32_t slot, uint64_t n, const float* local_points, uint32_t memberships, uint32_t filter,
                                const std::function<void(float4*)>* fill_dev = nullptr);
-    // ---- sampling/ray_sampling.rs on the device (sample.hip)
-    int64_t sample_shape(const SalvaHipShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
+    // ---- sampling/ray_sampling.rs on the device (sample.hip), of any geometry
+    int64_t sample(const GeomArg& geom, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
     int64_t sample_host_shape(const SalvaHipHostRayShape& shape, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
-    int64_t add_particles_sampled(uint32_t slot, const SalvaHipShape& shape, const float t[3], const float q[4], int mode, const float* vel);
-    int64_t set_boundary_sampling_from_shape(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
-    // ---- triangle meshes and height fields (mesh.hip): the world's table, the sampler and DynamicContactSampling on one
+    int64_t add_particles_sampled(uint32_t slot, const GeomArg& geom, const float t[3], const float q[4], int mode, const float* vel);
+    int64_t set_boundary_sampling_from(uint32_t slot, const GeomArg& geom, uint32_t memberships, uint32_t filter);
+    // ---- the world's tables of triangle meshes and height fields (mesh.hip) and of compounds (compound.hip; §17)
     uint32_t create_mesh(const float* vertices_xyz, uint32_t nv, const uint32_t* indices, uint32_t nt, uint32_t flags);
     uint32_t create_heightfield(const float* heights, uint32_t nrows, uint32_t ncols, const float scale[3]);
     void destroy_mesh(uint32_t mesh);
-    int64_t sample_mesh(uint32_t mesh, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
-    int64_t add_particles_sampled_mesh(uint32_t slot, uint32_t mesh, const float t[3], const float q[4], int mode, const float* vel);
-    int64_t set_boundary_sampling_from_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
-    void set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter);
-    // ---- compound colliders (compound.hip): the world's table; DynamicContactSampling on one (world_coupling.hip) and
-    // the shape query (world_query.hip)
     uint32_t create_compound(const SalvaHipCompoundPart* parts, uint32_t nparts);
     void destroy_compound(uint32_t compound);
-    void set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
-    int64_t sample_compound(uint32_t compound, float particle_rad, int mode, uint64_t capacity, float* out_xyz);
-    int64_t add_particles_sampled_compound(uint32_t slot, uint32_t compound, const float t[3], const float q[4], int mode, const float* vel);
-    int64_t set_boundary_sampling_from_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter);
-    uint64_t particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                   uint32_t* indices);
-    uint64_t particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                               uint32_t* indices);
     void update_boundary_pose(uint32_t slot, const SalvaHipRigidPose& pose);
     void update_boundary_poses(uint32_t count, const uint32_t* slots, const SalvaHipRigidPose* poses);
-    void set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter);
+    void set_boundary_dynamic_sampling(uint32_t slot, const GeomArg& geom, uint32_t memberships, uint32_t filter);
     void set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter);
     void clear_boundary_sampling(uint32_t slot);
     uint64_t local_len() const { return n; }
@@ -255,7 +265,7 @@ class World {
     // fluid they drop (world_objects.hip)
     void apply_keep_flags(const uint8_t* d_keep, const uint32_t* deleted_per_slot);
     // a region with what it keeps alive, validated; a registered one, and the scratch of both
-    struct RegionRes { SinkRegionDev dev{}; std::shared_ptr<MeshRes> mesh; std::shared_ptr<CompoundRes> compound; };
+    struct RegionRes { SinkRegionDev dev{}; Geom geom; };
     RegionRes resolve_region(const SalvaHipRegion& region) const;
     uint64_t delete_in_regions(uint32_t count, const RegionRes* const* rs, const uint32_t* slots, uint64_t* deleted, uint8_t* deleted_mask,
                                SlotSpan sp);
@@ -278,19 +288,18 @@ class World {
     void sample_lattice(const float mins[3], const float maxs[3], float particle_rad, SampleLattice& L);
     uint32_t sample_count(const SampleLattice& L);
     int64_t sample_download(const SampleLattice& L, uint64_t capacity, float* out_xyz);
-    void sample_mark(const SalvaHipShape& shape, float particle_rad, int mode, SampleLattice& L);
-    void sample_mark_mesh(const MeshRes& mesh, float particle_rad, int mode, SampleLattice& L);
-    void sample_mark_compound(const CompoundRes& c, float particle_rad, int mode, SampleLattice& L);
-    void sample_mark_cast(const float mins[3], const float maxs[3], float particle_rad, int mode, SampleLattice& L,
-                          const std::function<void(const SampleGrid&, uint64_t, int)>& launch, const char* too_many_hits);
+    void sample_mark(const Geom& g, float particle_rad, int mode, SampleLattice& L);
     DevBuf<uint32_t> smp_err;  // k_sample_mesh_mark, k_compound_mark: a ray with more than 64 accepted hits
-    void check_add_sampled(uint32_t slot, const float t[3], const float q[4]) const;
     int64_t append_sampled(uint32_t slot, const SampleLattice& L, const float t[3], const float q[4], const float* vel);
     int64_t boundary_from_sampled(uint32_t slot, const SampleLattice& L, uint32_t memberships, uint32_t filter);
     std::vector<std::shared_ptr<MeshRes>> meshes;  // by handle; a destroyed mesh leaves a free entry
     const std::shared_ptr<MeshRes>& mesh_at(uint32_t mesh) const;
     std::vector<std::shared_ptr<CompoundRes>> compounds;  // by handle, like `meshes`
     const std::shared_ptr<CompoundRes>& compound_at(uint32_t compound) const;
+    Geom geom_of(const SalvaHipShape& shape) const;      // (validates nothing: each operation checks the shape where it always has)
+    Geom geom_of(int kind, uint32_t handle) const;       // "no such mesh" / "no such compound"
+    Geom geom_of(const GeomArg& a) const { return a.shape ? geom_of(*a.shape) : geom_of(a.kind, a.handle); }
+    void refuse_handle_when_decomposed(const GeomArg& a) const;  // a mesh or a compound in a running decomposed world
     void stamp_fluid_models();
     void stamp_boundary_models();
     // ---- rigid-body coupling (world_coupling.hip)

@@ -169,7 +169,7 @@ void World::update_boundary_poses(uint32_t count, const uint32_t* slots, const S
 // ------------------------------------------------------------------------------------------------ DynamicContactSampling
 // ColliderCouplingSet::register_coupling(boundary, collider, ColliderSampling::DynamicContactSampling) (fluids_pipeline.rs:42-43,
 // 96-114): the boundary starts empty; every step re-emits its particles from the fluid near the collider.  The one registration
-// behind the four setters below: the slot keeps whether it wants forces and carries the description from now on (identity pose, no
+// behind the two setters below: the slot keeps whether it wants forces and carries the description from now on (identity pose, no
 // rows emitted yet).
 void World::register_dynamic_sampling(uint32_t slot, std::shared_ptr<DynSampling> d, uint32_t memberships, uint32_t filter) {
     const bool keep_forces = slot < bounds.size() ? bounds[slot].wants_forces : false;
@@ -178,36 +178,21 @@ void World::register_dynamic_sampling(uint32_t slot, std::shared_ptr<DynSampling
     bounds[slot].dyn = std::move(d);
 }
 
-void World::set_boundary_dynamic_sampling(uint32_t slot, const SalvaHipShape& shape, uint32_t memberships, uint32_t filter) {
-    check_shape_params(shape, "shape parameters must be positive");
+// A collider that is a built-in shape, or a triangle mesh or a height field of this world (mesh.hip) or a compound (compound.hip):
+// gather, projection and apply all stay on the device, and the pose handed to salva_hip_update_boundary_pose places the collider.
+void World::set_boundary_dynamic_sampling(uint32_t slot, const GeomArg& geom, uint32_t memberships, uint32_t filter) {
+    if (geom.shape) check_shape_params(*geom.shape, "shape parameters must be positive");
+    refuse_handle_when_decomposed(geom);
     auto d = std::make_shared<DynSampling>();
-    d->kind = shape.kind;
-    d->shape = shape;
+    d->geom = geom_of(geom);
     register_dynamic_sampling(slot, std::move(d), memberships, filter);
 }
 
 void World::set_boundary_dynamic_sampling_host(uint32_t slot, const SalvaHipHostShape& shape, uint32_t memberships, uint32_t filter) {
     if (!shape.aabb || !shape.project) throw HipError(SALVA_HIP_E_INVALID, "a host shape needs both callbacks");
     auto d = std::make_shared<DynSampling>();
-    d->kind = SALVA_HIP_SHAPE_HOST;
+    d->geom.kind = SALVA_HIP_SHAPE_HOST;
     d->host = shape;
-    register_dynamic_sampling(slot, std::move(d), memberships, filter);
-}
-
-// The same arm for a collider that is a triangle mesh or a height field of this world (mesh.hip), or a compound (compound.hip): gather,
-// projection and apply all stay on the device, and the pose handed to salva_hip_update_boundary_pose places the collider.
-void World::set_boundary_dynamic_sampling_mesh(uint32_t slot, uint32_t mesh, uint32_t memberships, uint32_t filter) {
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
-    auto d = std::make_shared<DynSampling>();
-    d->kind = SALVA_HIP_SHAPE_MESH;
-    d->mesh = mesh_at(mesh);
-    register_dynamic_sampling(slot, std::move(d), memberships, filter);
-}
-void World::set_boundary_dynamic_sampling_compound(uint32_t slot, uint32_t compound, uint32_t memberships, uint32_t filter) {
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "compound colliders are not available in a running decomposed world");
-    auto d = std::make_shared<DynSampling>();
-    d->kind = SALVA_HIP_SHAPE_COMPOUND;
-    d->compound = compound_at(compound);
     register_dynamic_sampling(slot, std::move(d), memberships, filter);
 }
 
@@ -225,23 +210,23 @@ void World::clear_boundary_sampling(uint32_t slot) {
 
 // The two places that know what each kind of collider needs (world.h DynSampling).
 DcsParams DynSampling::params(float h, float particle_radius, float dt) const {
-    if (kind == SALVA_HIP_SHAPE_HOST) {
+    if (geom.kind == SALVA_HIP_SHAPE_HOST) {
         float mins[3], maxs[3];
         host.aabb(host.user, mins, maxs);
         for (int a = 0; a < 3; ++a)
             if (!(mins[a] <= maxs[a])) throw HipError(SALVA_HIP_E_INVALID, "host shape: the aabb callback returned an empty or NaN box");
         return dcs_params_host(mins, maxs, h, particle_radius, dt);
     }
-    if (kind == SALVA_HIP_SHAPE_COMPOUND) return dcs_params_compound(*compound, pose, h, particle_radius, dt);
-    if (kind == SALVA_HIP_SHAPE_MESH) return dcs_params_mesh(mesh->mins, mesh->maxs, pose, h, particle_radius, dt);
-    return dcs_params(shape, pose, h, particle_radius, dt);
+    if (geom.compound) return dcs_params_compound(*geom.compound, pose, h, particle_radius, dt);
+    if (geom.mesh) return dcs_params_mesh(geom.mins(), geom.maxs(), pose, h, particle_radius, dt);
+    return dcs_params(geom.shape, pose, h, particle_radius, dt);
 }
 void DynSampling::fill_entry(DcsbEntry& e) const {
-    if (kind == SALVA_HIP_SHAPE_MESH) {
-        e.mesh = mesh->dev();
-    } else if (kind == SALVA_HIP_SHAPE_COMPOUND) {
-        e.parts = compound->parts.p;
-        e.nparts = compound->nparts;
+    if (geom.mesh) {
+        e.mesh = geom.mesh->dev();
+    } else if (geom.compound) {
+        e.parts = geom.parts();
+        e.nparts = geom.nparts();
     }
     e.pose = pose;
 }
@@ -287,7 +272,7 @@ void World::run_dynamic_sampling() {
         if (!bounds[slot].dyn) { ++slot; continue; }
         run.clear();
         if (!comm && !sw.dcs_batch_off && n)
-            for (uint32_t s = slot; s < bounds.size() && !(bounds[s].dyn && bounds[s].dyn->kind == SALVA_HIP_SHAPE_HOST); ++s)
+            for (uint32_t s = slot; s < bounds.size() && !(bounds[s].dyn && bounds[s].dyn->geom.kind == SALVA_HIP_SHAPE_HOST); ++s)
                 if (bounds[s].dyn) run.push_back(s);
         if (run.size() >= DCS_BATCH_MIN_RUN) {
             run_dynamic_sampling_batch(run, gv);
@@ -338,7 +323,7 @@ void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
                 emit_src = cpl.dcs_out.p;
             } else if (ng) {
                 cpl.dcs_proj.ensure(ng, stream, false, 1.5f); cpl.dcs_cand2.ensure(ng, stream, false, 1.5f);
-                if (d.kind == SALVA_HIP_SHAPE_HOST) {
+                if (d.geom.kind == SALVA_HIP_SHAPE_HOST) {
                     std::vector<float4>& f4 = cpl.dcs_h_f4;
                     std::vector<float>& pts = cpl.dcs_h_pts;
                     std::vector<float>& proj = cpl.dcs_h_proj;
@@ -350,10 +335,10 @@ void World::run_dynamic_sampling_slot(uint32_t slot, const TileGrid& gv) {
                     for (uint32_t k = 0; k < ng; ++k)
                         f4[k] = make_float4(proj[3 * k], proj[3 * k + 1], proj[3 * k + 2], cpl.dcs_h_inside[k] ? 1.0f : 0.0f);
                     SALVA_HIP_CHECK(hipMemcpyAsync(cpl.dcs_proj.p, f4.data(), (size_t)ng * sizeof(float4), hipMemcpyHostToDevice, stream));
-                } else if (d.kind == SALVA_HIP_SHAPE_COMPOUND) {
-                    launch_dcs_compound_project(ng, cpl.dcs_out.p, d.compound->parts.p, d.compound->nparts, prm_d, cpl.dcs_proj.p, stream);
+                } else if (d.geom.compound) {
+                    launch_dcs_compound_project(ng, cpl.dcs_out.p, d.geom.parts(), d.geom.nparts(), prm_d, cpl.dcs_proj.p, stream);
                 } else {
-                    launch_dcs_project_mesh(ng, cpl.dcs_out.p, d.mesh->dev(), prm_d, cpl.dcs_proj.p, stream);
+                    launch_dcs_project_mesh(ng, cpl.dcs_out.p, d.geom.mesh->dev(), prm_d, cpl.dcs_proj.p, stream);
                 }
                 // (dcs_out holds the gathered candidates; its compaction goes back into dcs_cand, which is free again)
                 launch_dcs_apply(ng, cpl.dcs_out.p, cpl.dcs_proj.p, posm[cur].p, vel[cur].p, perm[cur].p, comm ? gtag[cur].p : nullptr, prm_d,
@@ -412,7 +397,7 @@ void World::run_dynamic_sampling_batch(const std::vector<uint32_t>& run, const T
         d.fill_entry(e);
         e.slot = run[c];
         tab_h[c] = e;
-        if (d.kind == SALVA_HIP_SHAPE_COMPOUND) has_compound = true;
+        if (d.geom.compound) has_compound = true;
     }
     cpl.dcsb_tab.ensure(ncol, stream, false, 1.5f);
     cpl.dcsb_counts.ensure((size_t)ncol + 2, stream, false, 1.5f);

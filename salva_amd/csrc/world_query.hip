@@ -138,37 +138,6 @@ __global__ __launch_bounds__(BLOCK) void k_shape_query(QuerySrc q, ShapeQuery s,
     if (!(d <= s.r)) return;
     query_emit(q, i, kind, counter, cap, out_kind, out_index);
 }
-// The pose of a shape query must be a rigid motion (the reference takes an Isometry, which cannot be anything else): NaN / huge
-// values would otherwise reach the cell range's float -> int conversion
-static void check_query_pose(const float t[3], const float q[4]) {
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite translation");
-    float qn = 0.0f;
-    for (int a = 0; a < 4; ++a) {
-        if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, "shape query: non-finite rotation");
-        qn += q[a] * q[a];
-    }
-    if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, "shape query: the rotation must be a unit quaternion (x, y, z, w)");
-}
-uint64_t World::particles_in_shape(const float t[3], const float q[4], const SalvaHipShape& shape, uint64_t capacity, uint32_t* kinds,
-                                   uint32_t* slots, uint32_t* indices) {
-    use_device();
-    shape_param_count(shape.kind);  // (an unknown kind is reported before a bad pose)
-    check_query_pose(t, q);
-    check_shape_params(shape, "shape query: radius / half extents must be positive and finite");  // (the shape non-degenerate, likewise)
-    ShapeQuery s{};
-    for (int a = 0; a < 3; ++a) { s.t[a] = t[a]; s.p[a] = shape.params[a]; }
-    for (int a = 0; a < 4; ++a) s.q[a] = q[a];
-    s.kind = shape.kind; s.h = sc.h; s.r = prm.particle_radius;
-    // world AABB (parry compute_aabb; dcs.hip)
-    float ext[3], lo[3], hi[3];
-    shape_world_extent(shape, q, ext);
-    for (int a = 0; a < 3; ++a) { lo[a] = t[a] - ext[a]; hi[a] = t[a] + ext[a]; }
-    cell_range(lo, hi, sc.h, s.clo, s.chi);
-    return run_query(capacity, kinds, slots, indices, [&](const QuerySrc& src, uint32_t kind, unsigned int* cnt, uint32_t cap, uint32_t* dk, uint32_t* di) {
-        k_shape_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, kind, cnt, cap, dk, di);
-    });
-}
 
 // The same query for a posed compound and for a posed oriented mesh (the distances: solid_distance.h).  The cell range comes from the posed local box (parry's Aabb::transform_by, dcs.hip).
 struct PosedQuery {
@@ -203,40 +172,83 @@ __global__ __launch_bounds__(BLOCK) void k_mesh_query(QuerySrc q, PosedQuery s, 
     if (!(mesh_solid_distance(mesh, lx, ly, lz) <= s.r)) return;
     query_emit(q, i, kind, counter, cap, out_kind, out_index);
 }
-// the pose of particles_in_shape's checks, and the cell range of the posed box
-static PosedQuery posed_query(const float t[3], const float q[4], const float mins[3], const float maxs[3], float h, float r) {
-    check_query_pose(t, q);
-    PosedQuery s{};
-    for (int a = 0; a < 3; ++a) s.t[a] = t[a];
+
+// ---- a geometry, resolved (world.h Geom)
+Geom World::geom_of(const SalvaHipShape& shape) const {
+    Geom g;
+    g.shape = shape;
+    g.kind = shape.kind;
+    if (!g.built_in()) g.kind = 0;  // (a handle's kind in a SalvaHipShape is an unknown shape kind like any other)
+    return g;
+}
+Geom World::geom_of(int kind, uint32_t handle) const {
+    Geom g;
+    g.kind = kind;
+    if (kind == SALVA_HIP_SHAPE_MESH) g.mesh = mesh_at(handle);
+    else g.compound = compound_at(handle);
+    return g;
+}
+void World::refuse_handle_when_decomposed(const GeomArg& a) const {
+    if (a.shape || !(comm && dist_started)) return;
+    throw HipError(SALVA_HIP_E_INVALID, a.kind == SALVA_HIP_SHAPE_MESH ? "mesh colliders are not available in a running decomposed world"
+                                                                      : "compound colliders are not available in a running decomposed world");
+}
+// A pose must be a rigid motion (the reference takes an Isometry, which cannot be anything else): NaN / huge values would otherwise
+// reach the cell range's float -> int conversion
+void check_pose(const float t[3], const float q[4], const char* what) {
+    const std::string w(what);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, w + ": non-finite translation");
+    float qn = 0.0f;
+    for (int a = 0; a < 4; ++a) {
+        if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, w + ": non-finite rotation");
+        qn += q[a] * q[a];
+    }
+    if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, w + ": the rotation must be a unit quaternion (x, y, z, w)");
+}
+void check_solid(const Geom& g, const char* what, const char* hint) {
+    if (g.solid()) return;
+    throw HipError(SALVA_HIP_E_INVALID, std::string(what) + (g.mesh ? ": a mesh without SALVA_HIP_MESH_ORIENTED has no solid distance"
+                                                                     : ": a mesh part of the compound lacks SALVA_HIP_MESH_ORIENTED and has no solid distance") + hint);
+}
+
+// LiquidWorld::particles_intersecting_shape for any geometry.  What the forms do differently, kept as it was and not yet decided
+// (DESIGN.md §19), stands in the lines marked `form:`.
+uint64_t World::particles_in(const GeomArg& geom, const float t[3], const float q[4], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
+                             uint32_t* indices) {
+    use_device();
+    if (geom.shape) shape_param_count(geom.shape->kind);  // form: a shape's unknown kind is reported before a bad pose, its parameters after
+    refuse_handle_when_decomposed(geom);                   // form: a shape is queried in a running decomposed world, a handle is not
+    const Geom g = geom_of(geom);                          // form: an unknown handle and a handle without a solid distance, before a bad pose
+    check_solid(g, "shape query", " (use salva_hip_particles_intersecting_host_shape)");
+    check_pose(t, q, "shape query");
+    if (g.mesh || g.compound) {
+        PosedQuery s{};
+        for (int a = 0; a < 3; ++a) s.t[a] = t[a];
+        for (int a = 0; a < 4; ++a) s.q[a] = q[a];
+        s.h = sc.h; s.r = prm.particle_radius;
+        float lo[3], hi[3];
+        aabb_transform_by(g.mins(), g.maxs(), t, q, lo, hi);  // form: the cell range of the posed local box
+        cell_range(lo, hi, sc.h, s.clo, s.chi);
+        return run_query(capacity, kinds, slots, indices, [&](const QuerySrc& src, uint32_t kind, unsigned int* cnt, uint32_t cap, uint32_t* dk, uint32_t* di) {
+            if (g.mesh) k_mesh_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, g.mesh->dev(), kind, cnt, cap, dk, di);
+            else k_compound_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, g.parts(), g.nparts(), kind, cnt, cap, dk, di);
+        });
+    }
+    const SalvaHipShape& shape = g.shape;
+    check_shape_params(shape, "shape query: radius / half extents must be positive and finite");  // (the shape non-degenerate, likewise)
+    ShapeQuery s{};
+    for (int a = 0; a < 3; ++a) { s.t[a] = t[a]; s.p[a] = shape.params[a]; }
     for (int a = 0; a < 4; ++a) s.q[a] = q[a];
-    s.h = h; s.r = r;
-    float lo[3], hi[3];
-    aabb_transform_by(mins, maxs, t, q, lo, hi);
-    cell_range(lo, hi, h, s.clo, s.chi);
-    return s;
-}
-uint64_t World::particles_in_compound(const float t[3], const float q[4], uint32_t compound, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                      uint32_t* indices) {
-    use_device();
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "compound colliders are not available in a running decomposed world");
-    const std::shared_ptr<CompoundRes> c = compound_at(compound);
-    if (!c->solid)
-        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh part of the compound lacks SALVA_HIP_MESH_ORIENTED and has no solid distance (use salva_hip_particles_intersecting_host_shape)");
-    const PosedQuery s = posed_query(t, q, c->mins, c->maxs, sc.h, prm.particle_radius);
+    s.kind = shape.kind; s.h = sc.h; s.r = prm.particle_radius;
+    // form: the cell range of the world AABB about the centre (parry compute_aabb; dcs.hip), and a kernel of its own — it rotates into
+    // the local frame in another order of operations than quat_rot, and a hit is decided by d <= r
+    float ext[3], lo[3], hi[3];
+    shape_world_extent(shape, q, ext);
+    for (int a = 0; a < 3; ++a) { lo[a] = t[a] - ext[a]; hi[a] = t[a] + ext[a]; }
+    cell_range(lo, hi, sc.h, s.clo, s.chi);
     return run_query(capacity, kinds, slots, indices, [&](const QuerySrc& src, uint32_t kind, unsigned int* cnt, uint32_t cap, uint32_t* dk, uint32_t* di) {
-        k_compound_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, c->parts.p, c->nparts, kind, cnt, cap, dk, di);
-    });
-}
-uint64_t World::particles_in_mesh(const float t[3], const float q[4], uint32_t mesh, uint64_t capacity, uint32_t* kinds, uint32_t* slots,
-                                  uint32_t* indices) {
-    use_device();
-    if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "mesh colliders are not available in a running decomposed world");
-    const std::shared_ptr<MeshRes> m = mesh_at(mesh);
-    if (!(m->flags & SALVA_HIP_MESH_ORIENTED))
-        throw HipError(SALVA_HIP_E_INVALID, "shape query: a mesh without SALVA_HIP_MESH_ORIENTED has no solid distance (use salva_hip_particles_intersecting_host_shape)");
-    const PosedQuery s = posed_query(t, q, m->mins, m->maxs, sc.h, prm.particle_radius);
-    return run_query(capacity, kinds, slots, indices, [&](const QuerySrc& src, uint32_t kind, unsigned int* cnt, uint32_t cap, uint32_t* dk, uint32_t* di) {
-        k_mesh_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, m->dev(), kind, cnt, cap, dk, di);
+        k_shape_query<<<nblk(src.n), BLOCK, 0, stream>>>(src, s, kind, cnt, cap, dk, di);
     });
 }
 

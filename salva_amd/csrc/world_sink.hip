@@ -9,17 +9,6 @@
 
 namespace salva {
 
-static void check_region_pose(const float t[3], const float q[4]) {  // (the rule of the shape queries, world_query.hip)
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(t[a])) throw HipError(SALVA_HIP_E_INVALID, "region: non-finite translation");
-    float qn = 0.0f;
-    for (int a = 0; a < 4; ++a) {
-        if (!std::isfinite(q[a])) throw HipError(SALVA_HIP_E_INVALID, "region: non-finite rotation");
-        qn += q[a] * q[a];
-    }
-    if (fabsf(qn - 1.0f) > 1.0e-3f) throw HipError(SALVA_HIP_E_INVALID, "region: the rotation must be a unit quaternion (x, y, z, w)");
-}
-
 World::RegionRes World::resolve_region(const SalvaHipRegion& g) const {
     if (g.struct_size != SALVA_HIP_REGION_BYTES || g.version != SALVA_HIP_REGION_VERSION)
         throw HipError(SALVA_HIP_E_INVALID, "region: struct_size / version are not this library's SalvaHipRegion (SALVA_HIP_REGION_BYTES, SALVA_HIP_REGION_VERSION)");
@@ -48,22 +37,16 @@ World::RegionRes World::resolve_region(const SalvaHipRegion& g) const {
         }
         return r;
     }
+    // a posed geometry, checked in the order of the shape query (World::particles_in, world_query.hip)
+    if (g.kind == SALVA_HIP_REGION_SHAPE) shape_param_count(g.shape.kind);
+    r.geom = g.kind == SALVA_HIP_REGION_SHAPE ? geom_of(g.shape)
+                                              : geom_of(g.kind == SALVA_HIP_REGION_MESH ? SALVA_HIP_SHAPE_MESH : SALVA_HIP_SHAPE_COMPOUND, g.handle);
+    check_solid(r.geom, "region");
+    check_pose(g.translation, g.rotation_ijkw, "region");
     if (g.kind == SALVA_HIP_REGION_SHAPE) {
-        shape_param_count(g.shape.kind);  // (an unknown kind is reported before a bad pose, as by the shape query)
-        check_region_pose(g.translation, g.rotation_ijkw);
         check_shape_params(g.shape, "region: radius / half extents must be positive and finite");
         d.shape_kind = g.shape.kind;
         for (int a = 0; a < 3; ++a) d.p[a] = g.shape.params[a];
-    } else if (g.kind == SALVA_HIP_REGION_MESH) {
-        r.mesh = mesh_at(g.handle);
-        if (!(r.mesh->flags & SALVA_HIP_MESH_ORIENTED))
-            throw HipError(SALVA_HIP_E_INVALID, "region: a mesh without SALVA_HIP_MESH_ORIENTED has no solid distance");
-        check_region_pose(g.translation, g.rotation_ijkw);
-    } else {
-        r.compound = compound_at(g.handle);
-        if (!r.compound->solid)
-            throw HipError(SALVA_HIP_E_INVALID, "region: a mesh part of the compound lacks SALVA_HIP_MESH_ORIENTED and has no solid distance");
-        check_region_pose(g.translation, g.rotation_ijkw);
     }
     for (int a = 0; a < 3; ++a) d.t[a] = g.translation[a];
     for (int a = 0; a < 4; ++a) d.q[a] = g.rotation_ijkw[a];
@@ -86,9 +69,9 @@ uint64_t World::delete_in_regions(uint32_t count, const RegionRes* const* rs, co
     auto enqueue = [&](const float4* pos, const uint32_t* mdl, bool tally) {
         for (uint32_t k = 0; k < count; ++k) {
             const RegionRes& r = *rs[k];
-            const MeshDev mesh = r.mesh ? r.mesh->dev() : MeshDev{};
-            launch_sink_predicate(SinkSrc{pos, mdl, n, slots[k], k ? 1u : 0u}, r.dev, r.mesh ? &mesh : nullptr,
-                                  r.compound ? r.compound->parts.p : nullptr, r.compound ? r.compound->nparts : 0u, sink_keep.p,
+            const Geom& g = r.geom;
+            const MeshDev mesh = g.mesh ? g.mesh->dev() : MeshDev{};
+            launch_sink_predicate(SinkSrc{pos, mdl, n, slots[k], k ? 1u : 0u}, r.dev, g.mesh ? &mesh : nullptr, g.parts(), g.nparts(), sink_keep.p,
                                   tally ? sink_deleted.p + (size_t)k * SINK_MAX_SLOTS : nullptr, stream);
         }
     };
@@ -160,7 +143,7 @@ void World::remove_sink(uint32_t sink) {
 void World::set_sink_pose(uint32_t sink, const float t[3], const float q[4]) {
     Sink& s = sink_at(sink);
     if (s.res.dev.kind < SALVA_HIP_REGION_SHAPE) throw HipError(SALVA_HIP_E_INVALID, "a half-space or box sink has no pose");
-    check_region_pose(t, q);
+    check_pose(t, q, "region");
     for (int a = 0; a < 3; ++a) s.res.dev.t[a] = t[a];
     for (int a = 0; a < 4; ++a) s.res.dev.q[a] = q[a];
 }

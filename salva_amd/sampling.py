@@ -145,30 +145,41 @@ class Compound:
             del table[id(self)]
 
 
-def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
+# the entry that takes a built-in SalvaHipShape, where its name is not `salva_hip_<family>_shape`
+_SHAPE_ENTRY = {"add_particles_sampled": "salva_hip_add_particles_sampled",
+                "set_boundary_dynamic_sampling": "salva_hip_set_boundary_dynamic_sampling"}
+
+
+def geometry_entry(world, family: str, shape):
+    """The one place that knows the forms a geometry takes: -> (entry point of `family` for `shape`, its geometry
+    argument).  `family` is "sample", "add_particles_sampled", "set_boundary_sampling_from", "set_boundary_dynamic_sampling" or
+    "particles_intersecting"; `shape` is a Mesh or a Compound (the argument is its handle in `world`, created on first use), a
+    HostRayShape where the family has a host entry (sampling only), or what coupling.make_shape takes."""
     from .coupling import make_shape
+
+    for cls, form in ((Mesh, "mesh"), (Compound, "compound")):
+        if isinstance(shape, cls):
+            return getattr(world._L, f"salva_hip_{family}_{form}"), shape.handle(world)
+    if isinstance(shape, HostRayShape) and family == "sample":
+        return world._L.salva_hip_sample_host_shape, C.byref(shape.shape)
+    s = shape if isinstance(shape, L.Shape) else make_shape(shape)
+    return getattr(world._L, _SHAPE_ENTRY.get(family, f"salva_hip_{family}_shape")), C.byref(s)
+
+
+def _sample(shape, particle_rad: float, mode: int, world=None) -> np.ndarray:
     from .world import DFSPHSolver, LiquidWorld
 
     w = world if world is not None else LiquidWorld(DFSPHSolver(), float(particle_rad), 2.0)  # (supplies the device and the stream)
     fp = C.POINTER(C.c_float)
-    if isinstance(shape, HostRayShape):
-        def call(cap, out):
-            n = w._L.salva_hip_sample_host_shape(w._h, C.byref(shape.shape), float(particle_rad), mode, cap, out)
-            err, shape._error = shape._error, None
-            if err is not None:
-                raise err
-            return n
-    elif isinstance(shape, Mesh):
-        def call(cap, out):
-            return w._L.salva_hip_sample_mesh(w._h, shape.handle(w), float(particle_rad), mode, cap, out)
-    elif isinstance(shape, Compound):
-        def call(cap, out):
-            return w._L.salva_hip_sample_compound(w._h, shape.handle(w), float(particle_rad), mode, cap, out)
-    else:
-        s = shape if isinstance(shape, L.Shape) else make_shape(shape)
+    entry, geom = geometry_entry(w, "sample", shape)
 
-        def call(cap, out):
-            return w._L.salva_hip_sample_shape(w._h, C.byref(s), float(particle_rad), mode, cap, out)
+    def call(cap, out):
+        n = entry(w._h, geom, float(particle_rad), mode, cap, out)
+        err = getattr(shape, "_error", None)  # (a HostRayShape's callbacks park their exceptions)
+        if err is not None:
+            shape._error = None
+            raise err
+        return n
     # (a host shape's casts run again with every call: a first buffer that usually suffices spares them the second pass)
     cap = 65536 if isinstance(shape, HostRayShape) else 0
     pts = np.zeros((cap, 3), F32)

@@ -503,26 +503,19 @@ class Fluid:
         (salva_hip_add_particles_sampled): the shape — what coupling.make_shape takes, a sampling.Mesh or a sampling.Compound — is sampled at the world's particle radius
         (mode 1 = volume, 0 = surface), posed by `translation` and the unit quaternion `rotation` (i, j, k, w) and appended; the
         points never visit the host.  The fluid must live in a world.  Returns the number of particles added."""
-        from .coupling import make_shape
-
         w = self._world
         if w is None:
             raise ValueError("add_particles_from_shape needs a fluid that was added to a LiquidWorld")
         w._upload_new_objects()
         if self._resized or self._dirty:
             w._sync_fluid(self, apply_removal=False)
-        from .sampling import Compound, Mesh
+        from .sampling import geometry_entry
 
         t, q = np.ascontiguousarray(translation, F32).reshape(3), np.ascontiguousarray(rotation, F32).reshape(4)
         v = np.ascontiguousarray(velocity, F32).reshape(3) if velocity is not None else None
         self._pull()  # (the host copies must be current BEFORE the fluid grows: a read-back fills as many rows as the device holds)
-        if isinstance(shape, Mesh):  # (salva_hip_add_particles_sampled_mesh)
-            k = int(w._L.salva_hip_add_particles_sampled_mesh(w._h, self._slot, shape.handle(w), _fp(t), _fp(q), int(mode), _fp(v)))
-        elif isinstance(shape, Compound):  # (salva_hip_add_particles_sampled_compound)
-            k = int(w._L.salva_hip_add_particles_sampled_compound(w._h, self._slot, shape.handle(w), _fp(t), _fp(q), int(mode), _fp(v)))
-        else:
-            s = shape if isinstance(shape, L.Shape) else make_shape(shape)
-            k = int(w._L.salva_hip_add_particles_sampled(w._h, self._slot, C.byref(s), _fp(t), _fp(q), int(mode), _fp(v)))
+        entry, geom = geometry_entry(w, "add_particles_sampled", shape)  # (salva_hip_add_particles_sampled / _mesh / _compound)
+        k = int(entry(w._h, self._slot, geom, _fp(t), _fp(q), int(mode), _fp(v)))
         if k < 0:
             L.check(k)
         if k:  # (the new rows are read back on the next access)
@@ -1518,25 +1511,16 @@ class LiquidWorld:
         (translation, unit quaternion (i, j, k, w)): particles within the particle radius of the solid shape.  `shape` may also be
         a sampling.Compound or an oriented sampling.Mesh (salva_hip_particles_intersecting_compound / _mesh)."""
         self.sync_to_device(apply_removal=False)
-        from .coupling import make_shape
-        from .sampling import Compound, Mesh
+        from .sampling import geometry_entry
 
-        if isinstance(shape, Compound):
-            handle = shape.handle(self)
-            call = lambda *a: self._L.salva_hip_particles_intersecting_compound(self._h, t, q, handle, *a)  # noqa: E731
-        elif isinstance(shape, Mesh):
-            handle = shape.handle(self)
-            call = lambda *a: self._L.salva_hip_particles_intersecting_mesh(self._h, t, q, handle, *a)  # noqa: E731
-        else:
-            sh = make_shape(shape)
-            call = lambda *a: self._L.salva_hip_particles_intersecting_shape(self._h, t, q, C.byref(sh), *a)  # noqa: E731
+        entry, geom = geometry_entry(self, "particles_intersecting", shape)
         t = (C.c_float * 3)(*[float(x) for x in translation])
         q = (C.c_float * 4)(*[float(x) for x in rotation])
         u32p = C.POINTER(C.c_uint32)
         cap = 1024
         while True:
             k, s, i = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
-            total = int(call(cap, k.ctypes.data_as(u32p), s.ctypes.data_as(u32p), i.ctypes.data_as(u32p)))
+            total = int(entry(self._h, t, q, geom, cap, k.ctypes.data_as(u32p), s.ctypes.data_as(u32p), i.ctypes.data_as(u32p)))
             if total < 0:
                 L.check(total)
             if total <= cap:
