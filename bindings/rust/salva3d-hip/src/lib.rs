@@ -8,6 +8,7 @@ pub mod ffi;
 pub mod dist;
 mod liquid_world;
 pub mod region;
+pub mod field;
 #[cfg(feature = "rapier")]
 pub mod coupling;
 #[cfg(feature = "parry")]
@@ -16,3 +17,4 @@ pub mod sampling;
 pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};
 pub use region::Region;
+pub use field::{FieldSet, Fields};

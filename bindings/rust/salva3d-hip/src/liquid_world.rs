@@ -528,6 +528,19 @@ impl LiquidWorld {
         }
         Ok(k as usize)
     }
+    /// The SPH fields of the fluids selected by `fluid_mask` (bit s: slot s) at `points`, summed on the device over the particles as
+    /// they are now (`salva_hip_evaluate_fields`; field.rs).
+    pub fn evaluate_fields(&mut self, points: &[nalgebra::Point3<Real>], fluid_mask: u32, want: crate::FieldSet) -> Result<crate::Fields, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::field::evaluate_points(self.raw, fluid_mask, points, want)
+    }
+    /// The same at the nodes `origin + i * spacing` of a lattice of `dims` nodes (`salva_hip_evaluate_fields_lattice`).
+    pub fn evaluate_lattice(&mut self, origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], fluid_mask: u32, want: crate::FieldSet) -> Result<crate::Fields, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::field::evaluate_lattice(self.raw, fluid_mask, origin, spacing, dims, want)
+    }
     /// Registers `region` as a sink of `fluid` (None: of every fluid): every step starts by deleting what it selects, on the device,
     /// at the cost of one small host wait (`salva_hip_add_sink`).  Returns the sink's handle.
     pub fn add_sink(&mut self, region: &crate::Region, fluid: Option<FluidHandle>) -> Result<u32, Error> {

@@ -910,6 +910,47 @@ int salva_hip_remove_sink(SalvaHipWorld* world, uint32_t sink);
 int salva_hip_set_sink_pose(SalvaHipWorld* world, uint32_t sink, const float translation[3], const float rotation_ijkw[4]);
 int salva_hip_get_sink_stats(const SalvaHipWorld* world, uint32_t sink, uint64_t out2[2]);
 
+/* ---- SPH fields at points and on a lattice: the fluid as a continuum, summed on the device at places that are not
+ * particles — a voxel grid for an iso-surface or a volume render, a flow probe, a fill level.
+ *
+ * Particles.  Bit s of `fluid_mask` selects fluid s; a mask that selects no existing fluid is SALVA_HIP_E_INVALID.  Boundaries
+ * contribute nothing.  The particles are those of the selected fluids as salva_hip_get_fluid would return them now: current positions,
+ * velocities (the reference's fluid.velocities, without the pending velocity_changes) and volumes; m_j = volumes[j] * density0 of the
+ * particle's fluid.  The calls work before the first step and between any two steps and change nothing a step reads.
+ * Kernels.  W is the world's KernelDensity and grad W its KernelGradient (all four kinds); with d = x - x_j a particle is in
+ * support iff |d|^2 <= h^2, the contact search's test with its rounding (f32, no FMA).
+ * Order.  Every sum runs over the cells of the call's own grid in ascending order (x slowest, z fastest) and over ascending host
+ * index within a cell, for both entry points: a second call gives the same bits.
+ * Lattice.  Node (ix, iy, iz) sits at origin + (float)i * spacing per axis, product and sum each rounded in f32 (no FMA), and its
+ * results are at index (ix * ny + iy) * nz + iz.
+ * Own grid.  Each call builds a plain table of cells of width h over the box of the query (the finite points, or the lattice) grown by
+ * h, and drops the particles outside it first: a stray particle far away costs nothing, the step's grid is not used.  A query whose own
+ * box exceeds 2^27 cells is SALVA_HIP_E_CAPACITY: split the query.
+ * Edge cases.  A point with a non-finite coordinate gets zeros and count 0; it is never an error.  npoints == 0 is SALVA_HIP_OK and
+ * does nothing.  SALVA_HIP_E_INVALID: out == NULL; an unknown flag; spacing non-finite or <= 0; a dims[k] == 0; a decomposed world
+ * (salva_hip_set_domain: host-order arrays are not maintained there); a call from inside a force, device force or coupling callback.
+ * SALVA_HIP_E_CAPACITY: more than 2^32 points or nodes.
+ * Buffers.  `points_xyz` and the non-null pointers of `out` are host memory unless the flags say otherwise; device pointers must be
+ * on the world's device.  With SALVA_HIP_FIELD_OUT_ON_DEVICE the results are complete when the call returns. */
+enum {
+    SALVA_HIP_FIELD_POINTS_ON_DEVICE = 1, /* `points_xyz` is a device pointer */
+    SALVA_HIP_FIELD_OUT_ON_DEVICE = 2     /* every non-null pointer of `out` is a device pointer */
+};
+typedef struct SalvaHipFieldOut { /* any pointer may be NULL: that field is not computed and nothing is written */
+    float* density;               /* M   sum_j m_j W(x - x_j) */
+    float* fraction;              /* M   sum_j V_j W(x - x_j)   (V_j = volumes[j]) */
+    float* velocity;              /* 3M  sum_j m_j v_j W / sum_j m_j W; 0 where the denominator is 0 */
+    float* gradient;              /* 3M  sum_j m_j grad W(x - x_j) */
+    uint32_t* count;              /* M   particles with |d|^2 <= h^2 */
+} SalvaHipFieldOut;
+int salva_hip_evaluate_fields(SalvaHipWorld* world, uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags,
+                              const SalvaHipFieldOut* out);
+/* The same at the nodes of a lattice.  Two kernels compute the same bits: one lane per node, and one workgroup per brick of
+ * 8 x 8 x 8 nodes that shares the brick's candidates through LDS.  The first was measured faster at every spacing and
+ * is what a call takes; SALVA_HIP_FIELD_ARM=points|lattice in the environment of salva_hip_create forces one. */
+int salva_hip_evaluate_fields_lattice(SalvaHipWorld* world, uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3],
+                                      uint32_t flags, const SalvaHipFieldOut* out);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

@@ -943,6 +943,32 @@ class LiquidWorld {  // liquid_world.rs
         check(salva_hip_get_sink_stats(w_, sink, out.data()));
         return out;
     }
+    // SPH fields at points and on a lattice, summed on the device over the particles as they are now (salva_hip_evaluate_fields /
+    // _lattice).  `what`: the fields wanted (FieldSet::DENSITY | ...); `fluid_mask`: bit s selects fluid s.  The vectors
+    // of the fields not asked for stay empty; `velocity` / `gradient` hold three floats per place; a lattice's node (ix, iy, iz) is at
+    // index (ix * ny + iy) * nz + iz.
+    struct FieldSet { enum : uint32_t { DENSITY = 1, FRACTION = 2, VELOCITY = 4, GRADIENT = 8, COUNT = 16, ALL = 31 }; };
+    struct Fields {
+        std::vector<Real> density, fraction, velocity, gradient;
+        std::vector<uint32_t> count;
+    };
+    Fields evaluate_fields(const std::vector<Vec3>& points, uint32_t what = FieldSet::DENSITY, uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        Fields f;
+        SalvaHipFieldOut out = field_out(f, points.size(), what);
+        check(salva_hip_evaluate_fields(w_, fluid_mask, points.size(), points.empty() ? nullptr : points[0].data(), 0, &out));
+        return f;
+    }
+    Fields evaluate_lattice(const Vec3& origin, Real spacing, const std::array<uint32_t, 3>& dims, uint32_t what = FieldSet::DENSITY,
+                            uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        Fields f;
+        const uint64_t xy = (uint64_t)dims[0] * dims[1];
+        const bool fits = xy <= (1ull << 32) && xy * dims[2] <= (1ull << 32);  // (beyond: the library's refusal, nothing to allocate)
+        SalvaHipFieldOut out = field_out(f, fits ? (size_t)(xy * dims[2]) : 1, what);
+        check(salva_hip_evaluate_fields_lattice(w_, fluid_mask, origin.data(), spacing, dims.data(), 0, &out));
+        return f;
+    }
     // The reference's host arrays are current after every step, which costs a read-back per step.  A loop that does not look at
     // them (an emitter and sinks that stay on the device) switches it off; refresh() then reads one fluid, or all, back on demand.
     // While it is off `positions` / `velocities` have the right length and stale content: the rows add_particles_from_shape appends
@@ -994,6 +1020,21 @@ class LiquidWorld {  // liquid_world.rs
             f.volumes.resize(n);
             if (n && !uniform) check(salva_hip_get_fluid_field(w_, (uint32_t)s, SALVA_HIP_FIELD_VOLUME, f.volumes.data()));
         }
+    }
+    // what an evaluation starts with, as delete_particles_in(region) does: the device sees what the host arrays hold
+    void upload_all() {
+        upload_new_objects();
+        for (size_t s = 0; s < fluids_.size(); ++s) upload(fluids_[s], (uint32_t)s);
+    }
+    static SalvaHipFieldOut field_out(Fields& f, size_t m, uint32_t what) {
+        SalvaHipFieldOut out{nullptr, nullptr, nullptr, nullptr, nullptr};
+        const size_t room = m ? m : 1;
+        if (what & FieldSet::DENSITY) { f.density.assign(room, 0); out.density = f.density.data(); f.density.resize(m); }
+        if (what & FieldSet::FRACTION) { f.fraction.assign(room, 0); out.fraction = f.fraction.data(); f.fraction.resize(m); }
+        if (what & FieldSet::VELOCITY) { f.velocity.assign(3 * room, 0); out.velocity = f.velocity.data(); f.velocity.resize(3 * m); }
+        if (what & FieldSet::GRADIENT) { f.gradient.assign(3 * room, 0); out.gradient = f.gradient.data(); f.gradient.resize(3 * m); }
+        if (what & FieldSet::COUNT) { f.count.assign(room, 0); out.count = f.count.data(); f.count.resize(m); }
+        return out;
     }
     uint32_t nsinks_ = 0;
     bool readback_ = true;

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_particles_intersecting_compound", "salva_hip_particles_intersecting_mesh",
     "salva_hip_sample_compound", "salva_hip_add_particles_sampled_compound", "salva_hip_set_boundary_sampling_from_compound",
     "salva_hip_delete_particles_in_region", "salva_hip_add_sink", "salva_hip_remove_sink", "salva_hip_set_sink_pose", "salva_hip_get_sink_stats",
+    "salva_hip_evaluate_fields", "salva_hip_evaluate_fields_lattice",
 ]
 
 
@@ -166,6 +167,14 @@ class Region(C.Structure):
                 ("handle", C.c_uint32), ("shape", Shape), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("mins", C.c_float * 3),
                 ("maxs", C.c_float * 3), ("translation", C.c_float * 3), ("rotation_ijkw", C.c_float * 4), ("reserved", C.c_uint32 * 3)]
 
+
+class FieldOut(C.Structure):
+    """SalvaHipFieldOut (include/salva_hip.h): where salva_hip_evaluate_fields / _lattice write; a null pointer is not computed."""
+    _fields_ = [("density", C.POINTER(C.c_float)), ("fraction", C.POINTER(C.c_float)), ("velocity", C.POINTER(C.c_float)),
+                ("gradient", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_uint32))]
+
+
+FIELD_POINTS_ON_DEVICE, FIELD_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_FIELD_POINTS_ON_DEVICE / _OUT_ON_DEVICE
 
 REGION_HALFSPACE, REGION_AABB, REGION_SHAPE, REGION_MESH, REGION_COMPOUND = 1, 2, 3, 4, 5
 REGION_INVERT = 1
@@ -390,6 +399,9 @@ def lib():
         L.salva_hip_remove_sink.argtypes = [vp, u32]
         L.salva_hip_set_sink_pose.argtypes = [vp, u32, fp, fp]
         L.salva_hip_get_sink_stats.argtypes = [vp, u32, C.POINTER(u64)]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_evaluate_fields"):
+        L.salva_hip_evaluate_fields.argtypes = [vp, u32, u64, fp, u32, C.POINTER(FieldOut)]
+        L.salva_hip_evaluate_fields_lattice.argtypes = [vp, u32, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(FieldOut)]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

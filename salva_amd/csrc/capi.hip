@@ -778,6 +778,20 @@ int salva_hip_get_sink_stats(const SalvaHipWorld* world, uint32_t sink, uint64_t
     return status_entry(world, {out2}, ANYWHERE, [&](World& w) { w.get_sink_stats(sink, out2); });
 }
 
+int salva_hip_evaluate_fields(SalvaHipWorld* world, uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags,
+                              const SalvaHipFieldOut* out) { WorldLock _lk(world);
+    return status_entry(world, {out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.evaluate_fields(fluid_mask, npoints, points_xyz, flags, *out);
+    });
+}
+
+int salva_hip_evaluate_fields_lattice(SalvaHipWorld* world, uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3],
+                                      uint32_t flags, const SalvaHipFieldOut* out) { WorldLock _lk(world);
+    return status_entry(world, {origin, dims, out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.evaluate_fields_lattice(fluid_mask, origin, spacing, dims, flags, *out);
+    });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -45,6 +45,7 @@ struct Switches {
     uint32_t list_cap0 = 0;
     bool dcs_batch_off = false;    // SALVA_HIP_NO_DCS_BATCH=1 (A/B, tests): every DynamicContactSampling collider takes the per-collider path
     uint32_t dcsb_cap0 = 0;        // SALVA_HIP_DCSB_CAP0=k (tests: force a repeat): the first capacity of the batched pass's record buffer
+    int field_arm = 0;             // SALVA_HIP_FIELD_ARM=points|lattice (tests, measurements): the arm every lattice evaluation takes
     bool tile_trace = false;       // SALVA_HIP_TILE_TRACE=1: one line of tile statistics per step on stderr
     bool dist_trace = false;       // SALVA_HIP_DIST_TRACE: one line per decomposed divergence solve whose applies ran beside the all-reduce
 #ifdef SALVA_HIP_DIAG

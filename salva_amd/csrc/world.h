@@ -18,6 +18,7 @@
 #include "mesh.h"
 #include "compound.h"
 #include "sink.h"
+#include "field.h"
 
 namespace salva {
 
@@ -134,6 +135,10 @@ class World {
     void remove_sink(uint32_t sink);
     void set_sink_pose(uint32_t sink, const float t[3], const float q[4]);
     void get_sink_stats(uint32_t sink, uint64_t out[2]) const;
+    // ---- SPH fields at points and on a lattice (world_field.hip, field.hip)
+    void evaluate_fields(uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags, const SalvaHipFieldOut& out);
+    void evaluate_fields_lattice(uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                 const SalvaHipFieldOut& out);
     uint64_t particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                uint32_t* indices);
     uint64_t particles_in(const GeomArg& geom, const float t[3], const float q[4], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
@@ -278,6 +283,18 @@ class World {
     DevBuf<float4> st_spare[4];  // where apply_keep_flags compacts to; the arrays it replaces become the next call's room
     DevBuf<uint32_t> sink_deleted, sink_scan;
     PinnedStage sink_stage;
+    // the field evaluator: its grid's tables, the sorted records and the staged results of host buffers, grown on demand and kept
+    struct FieldScratch {
+        DevBuf<uint32_t> keys, rank, cells, keys_sorted, idx_tmp;
+        DevBuf<float4> rec0, rec1;
+        DevBuf<float> out;
+        DevBuf<int32_t> box;
+        DevBuf<char> temp;
+    } fld;
+    FieldFluids field_begin(uint32_t fluid_mask, uint32_t flags, const char* what);
+    FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g);
+    void field_run(const FieldFluids& f, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m, uint32_t flags,
+                   const SalvaHipFieldOut& out, bool brick_arm);
     void set_boundary_from(uint32_t slot, uint64_t n, const float* pos, const float* vel, uint32_t memberships, uint32_t filter,
                            bool wants_forces, const std::function<void(float4*)>* fill_dev);
     // the shape sampler's lattice (sample.hip): bit lattice, per-word counts and offsets, the three coordinate arrays, packed output;

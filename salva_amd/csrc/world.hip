@@ -70,6 +70,7 @@ Switches Switches::from_env() {
     s.dist_trace = on("SALVA_HIP_DIST_TRACE");
     s.no_fused_div = on("SALVA_HIP_NO_FUSED_DIV");
     s.dcs_batch_off = on("SALVA_HIP_NO_DCS_BATCH");
+    if (const char* e = getenv("SALVA_HIP_FIELD_ARM")) s.field_arm = !strcmp(e, "points") ? 1 : !strcmp(e, "lattice") ? 2 : 0;
     if (const char* e = getenv("SALVA_HIP_DCSB_CAP0")) s.dcsb_cap0 = (uint32_t)std::max(atoi(e), 1);
     if (const char* e = getenv("SALVA_HIP_RADIX_SORT")) s.sort_mode = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("SALVA_HIP_DS_LEVEL")) s.ds_level = (uint32_t)std::max(0, atoi(e));

@@ -1634,6 +1634,86 @@ class LiquidWorld:
         L.check(self._L.salva_hip_get_sink_stats(self._h, int(sink), out))
         return int(out[0]), int(out[1])
 
+    # ---- SPH fields at points and on a lattice (include/salva_hip.h salva_hip_evaluate_fields)
+    _FIELD_WIDTHS = (("density", 1), ("fraction", 1), ("velocity", 3), ("gradient", 3), ("count", 1))
+
+    def _field_mask(self, fluids) -> int:
+        if fluids is None:
+            fluids = self._fluids
+        elif isinstance(fluids, Fluid):
+            fluids = [fluids]
+        mask = 0
+        for f in fluids:
+            mask |= 1 << (f._slot if isinstance(f, Fluid) else int(f))
+        return mask & 0xFFFFFFFF
+
+    def _field_host_out(self, m, want):
+        arrays, out = {}, L.FieldOut()
+        for name, width in self._FIELD_WIDTHS:
+            if not want[name]:
+                continue
+            a = np.zeros(m * width, np.uint32 if name == "count" else F32)
+            arrays[name] = a
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
+        return arrays, out
+
+    @staticmethod
+    def _field_device_out(addresses):
+        out = L.FieldOut()
+        for name, _ in LiquidWorld._FIELD_WIDTHS:
+            if addresses.get(name):
+                setattr(out, name, C.cast(C.c_void_p(int(addresses[name])), C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
+        return out
+
+    def evaluate_fields(self, points, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False):
+        """The SPH fields of `fluids` (None: all; Fluid objects or slot numbers) at `points` (m x 3), summed on the device over the
+        particles as they are now: a dict of numpy arrays, `density` / `fraction` / `count` of length m, `velocity` / `gradient` m x 3,
+        for the fields asked for.  A point with a non-finite coordinate gets zeros."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        pts = np.ascontiguousarray(points, F32).reshape(-1, 3)
+        m = len(pts)
+        arrays, out = self._field_host_out(m, dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count))
+        L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), m, _fp(pts), 0, C.byref(out)))
+        return {k: (a.reshape(m, 3) if k in ("velocity", "gradient") else a) for k, a in arrays.items()}
+
+    def evaluate_lattice(self, origin, spacing, dims, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False):
+        """The same at the nodes origin + i * spacing of a lattice of dims = (nx, ny, nz) nodes: arrays shaped (nx, ny, nz) and
+        (nx, ny, nz, 3)."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        o = np.ascontiguousarray(origin, F32).reshape(3)
+        d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+        nx, ny, nz = (int(v) for v in d)
+        m = nx * ny * nz
+        if m > 1 << 32:  # (the library's refusal, before numpy tries to allocate the arrays)
+            raise L.SalvaHipError(L.E_CAPACITY, "salva_hip_evaluate_fields_lattice: more than 2^32 nodes: split the query")
+        arrays, out = self._field_host_out(m, dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count))
+        L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), d.ctypes.data_as(C.POINTER(C.c_uint32)), 0,
+                                                          C.byref(out)))
+        return {k: (a.reshape(nx, ny, nz, 3) if k in ("velocity", "gradient") else a.reshape(nx, ny, nz)) for k, a in arrays.items()}
+
+    def evaluate_fields_device(self, points_address: int, npoints: int, fluids=None, **addresses):
+        """evaluate_fields with everything in device memory: `points_address` and the keyword arguments density= / fraction= /
+        velocity= / gradient= / count= are integer device addresses (e.g. torch's data_ptr()) of buffers of the sizes above on the
+        world's device; an address left out or 0 is not computed.  The results are complete when the call returns."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        out = self._field_device_out(addresses)
+        pts = C.cast(C.c_void_p(int(points_address)), C.POINTER(C.c_float))
+        L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), int(npoints), pts,
+                                                  L.FIELD_POINTS_ON_DEVICE | L.FIELD_OUT_ON_DEVICE, C.byref(out)))
+
+    def evaluate_lattice_device(self, origin, spacing, dims, fluids=None, **addresses):
+        """evaluate_lattice into device memory: the keyword arguments are integer device addresses, as in evaluate_fields_device."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        o = np.ascontiguousarray(origin, F32).reshape(3)
+        d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+        out = self._field_device_out(addresses)
+        L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), d.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                          L.FIELD_OUT_ON_DEVICE, C.byref(out)))
+
     def _resize_after_sinks(self):
         """A step in which a sink fired shortened fluids on the device: the host copies follow (positions and velocities are read
         back on the next access, accelerations are zero after a step, the volumes come from the device unless they are uniform)."""
