@@ -9,6 +9,7 @@ pub mod dist;
 mod liquid_world;
 pub mod region;
 pub mod field;
+pub mod surface;
 #[cfg(feature = "rapier")]
 pub mod coupling;
 #[cfg(feature = "parry")]
@@ -18,3 +19,4 @@ pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};
 pub use region::Region;
 pub use field::{FieldSet, Fields};
+pub use surface::{SurfaceField, SurfaceMesh};

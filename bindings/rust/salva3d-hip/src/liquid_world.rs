@@ -541,6 +541,25 @@ impl LiquidWorld {
         self.upload()?;
         crate::field::evaluate_lattice(self.raw, fluid_mask, origin, spacing, dims, want)
     }
+    /// The iso-surface `field` = `iso` of the fluids selected by `fluid_mask` on the lattice `origin + i * spacing` of `dims` nodes,
+    /// extracted on the device as an indexed triangle mesh (`salva_hip_extract_surface`; surface.rs).
+    #[allow(clippy::too_many_arguments)]
+    pub fn extract_surface(&mut self, origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], iso: Real, field: crate::SurfaceField,
+                           fluid_mask: u32, normals: bool, velocities: bool) -> Result<crate::SurfaceMesh, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::surface::extract(self.raw, fluid_mask, field, iso, origin, spacing, dims, normals, velocities)
+    }
+    /// The same for a lattice of values of the caller's (`salva_hip_extract_surface_from_values`).
+    pub fn extract_surface_from_values(&mut self, values: &[Real], origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], iso: Real) -> Result<crate::SurfaceMesh, Error> {
+        crate::surface::extract_from_values(self.raw, values, iso, origin, spacing, dims)
+    }
+    /// The box of the finite positions of the selected fluids and their number, reduced on the device (`salva_hip_get_fluid_bounds`).
+    pub fn fluid_bounds(&mut self, fluid_mask: u32) -> Result<(nalgebra::Point3<Real>, nalgebra::Point3<Real>, u64), Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::surface::fluid_bounds(self.raw, fluid_mask)
+    }
     /// Registers `region` as a sink of `fluid` (None: of every fluid): every step starts by deleting what it selects, on the device,
     /// at the cost of one small host wait (`salva_hip_add_sink`).  Returns the sink's handle.
     pub fn add_sink(&mut self, region: &crate::Region, fluid: Option<FluidHandle>) -> Result<u32, Error> {

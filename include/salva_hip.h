@@ -951,6 +951,68 @@ int salva_hip_evaluate_fields(SalvaHipWorld* world, uint32_t fluid_mask, uint64_
 int salva_hip_evaluate_fields_lattice(SalvaHipWorld* world, uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3],
                                       uint32_t flags, const SalvaHipFieldOut* out);
 
+/* ---- The iso-surface of a field as an indexed triangle mesh, extracted on the device: the surface of the fluid for a
+ * renderer, a wetted area, an enclosed volume, a mesh export.  The method is marching tetrahedra on the Freudenthal (Kuhn) split of
+ * every lattice cell, and everything below is a pure function of the node values: a second call gives the same mesh, bit for bit.
+ *
+ * Lattice and values.  Nodes, their order and their coordinates are those of salva_hip_evaluate_fields_lattice: node (ix, iy, iz) at
+ * origin + (float)i * spacing per axis (product and sum each rounded in f32) and at index (ix * ny + iy) * nz + iz.  A node with value
+ * f is inside iff f >= iso.
+ * Edges and vertices.  Node p owns the edges to p + o for the seven offsets o in {0,1}^3 other than 0, wherever p + o is a node; the
+ * edge's bit is b = 4 ox + 2 oy + oz - 1.  An edge carries a vertex iff exactly one of its ends is inside.  With a = p (value fa,
+ * position Pa) and b = p + o (fb, Pb): t = (iso - fa) / (fb - fa) and x = Pa + t * (Pb - Pa) per axis, every operation rounded once in
+ * f32 (no FMA; the division correctly rounded).  Vertices are numbered by owner node index ascending, then by edge bit ascending.
+ * Tetrahedra and triangles.  Every dims[k] >= 2; a cell is named by its min corner c.  Its six tetrahedra follow the permutations
+ * (a, b, c) of the axes in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx, with corners v0 = c, v1 = v0 + e_a, v2 = v1 + e_b,
+ * v3 = v2 + e_c; the tetrahedron edge (v_i, v_j), i < j, is the lattice edge owned by v_i, and "ij" below is the vertex on it.
+ *   one corner a inside, b < c < d outside, or one corner a outside, b < c < d inside:  the triangle (ab, ac, ad);
+ *   a < b inside, c < d outside:  the quad (ac, ad, bd, bc), as the triangles (q0, q1, q2) and (q0, q2, q3).
+ * Orientation is combinatorial: on the unit tetrahedron, with the edge midpoints standing in for the vertices, the right-hand normal of
+ * a triangle must point from the centroid of the inside corners to the centroid of the outside corners; where it does not, the
+ * triangle's last two indices are swapped.  Normals so point towards lower values.  Triangles are ordered by cell (the min corner's
+ * node index ascending), then tetrahedron, then as listed above.
+ * Degenerate and open cases.  A node value equal to iso gives t = 0 and coincident vertices, hence triangles of zero area: they are
+ * kept.  The mesh is open where the surface leaves the lattice; a lattice that encloses the selected fluids by h gives a closed mesh,
+ * the fields being exactly 0 there.
+ *
+ * salva_hip_extract_surface evaluates `field` (density or fraction) of the fluids in `fluid_mask` at the nodes into scratch of its own
+ * - bit for bit the values salva_hip_evaluate_fields_lattice returns for the same arguments - and contours them.  normals[v] is
+ * -g / |g| with g the evaluator's `gradient` at vertex v (the zero vector where g is zero) and velocities[v] its `velocity` there:
+ * both are salva_hip_evaluate_fields run on the vertex array in device memory.
+ * salva_hip_extract_surface_from_values contours a lattice of `values` the caller supplies (nx * ny * nz floats, host memory, or device
+ * memory with SALVA_HIP_SURFACE_VALUES_ON_DEVICE): a filtered field, a combination of the evaluator's outputs.  Its `normals` and
+ * `velocities` must be NULL.
+ * Counts and capacity.  counts[0] = vertices, counts[1] = triangles; written on SALVA_HIP_OK and on SALVA_HIP_E_CAPACITY for want of
+ * room.  out == NULL: count only.  Otherwise, if vertex_capacity < counts[0] or triangle_capacity < counts[1], nothing is written
+ * through `out` and the call returns SALVA_HIP_E_CAPACITY with the need in `counts`.  With SALVA_HIP_SURFACE_OUT_ON_DEVICE every
+ * non-null pointer of `out` is device memory and the mesh is complete when the call returns.
+ * SALVA_HIP_E_INVALID: iso not finite; a dims[k] < 2; spacing not finite or <= 0; an unknown flag (SALVA_HIP_SURFACE_VALUES_ON_DEVICE
+ * where there are no values included) or field; null `counts`, `origin`, `dims`, `values`, or an `out` without `vertices` or
+ * `triangles`; a node value of a supplied lattice that is not finite (nothing is written); and what the evaluator refuses: a
+ * decomposed world, a call from inside a force, device force or coupling callback, a mask that selects no existing fluid.
+ * SALVA_HIP_E_CAPACITY: 2^31 - 1 nodes or more; 2^32 vertices or more, or 2^32 triangle indices (3 per triangle) or more.
+ * The calls change nothing a step reads. */
+enum { SALVA_HIP_SURFACE_DENSITY = 0, SALVA_HIP_SURFACE_FRACTION = 1 }; /* the evaluator's `density` / `fraction` */
+enum {
+    SALVA_HIP_SURFACE_VALUES_ON_DEVICE = 1, /* `values` is a device pointer */
+    SALVA_HIP_SURFACE_OUT_ON_DEVICE = 2     /* every non-null pointer of `out` is a device pointer */
+};
+typedef struct SalvaHipSurfaceOut {
+    float* vertices;     /* 3 nv */
+    float* normals;      /* 3 nv, or NULL: not computed */
+    float* velocities;   /* 3 nv, or NULL: not computed */
+    uint32_t* triangles; /* 3 nt */
+    uint64_t vertex_capacity, triangle_capacity; /* in vertices and triangles */
+} SalvaHipSurfaceOut;
+int salva_hip_extract_surface(SalvaHipWorld* world, uint32_t fluid_mask, uint32_t field, float iso, const float origin[3], float spacing,
+                              const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+int salva_hip_extract_surface_from_values(SalvaHipWorld* world, const float* values, float iso, const float origin[3], float spacing,
+                                          const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+/* The box of the finite positions of the fluids in `fluid_mask`, reduced on the device (ordered-integer min / max; 32 bytes come back:
+ * the box and the count): where to put the lattice, without downloading a position.  *nfinite = how many positions are finite; with
+ * none, lo = +inf and hi = -inf.  Refusals as salva_hip_evaluate_fields. */
+int salva_hip_get_fluid_bounds(SalvaHipWorld* world, uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

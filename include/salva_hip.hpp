@@ -16,6 +16,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <exception>
@@ -518,6 +519,15 @@ static_assert(sizeof(Comm::PeerHandle) == SALVA_HIP_PEER_HANDLE_BYTES, "handles 
 using FluidHandle = size_t;     // dense index; remove_fluid is a swap-remove like ContiguousArena (contiguous_arena.rs)
 using BoundaryHandle = size_t;
 
+// An indexed triangle mesh as salva_hip_extract_surface writes it: three floats per vertex, three vertex indices per triangle;
+// `normals` / `velocities` are empty unless asked for.  The order of both arrays is fixed by the header's contract.
+struct SurfaceMesh {
+    std::vector<Real> vertices, normals, velocities;
+    std::vector<uint32_t> triangles;
+    size_t num_vertices() const { return vertices.size() / 3; }
+    size_t num_triangles() const { return triangles.size() / 3; }
+};
+
 class LiquidWorld {  // liquid_world.rs
   public:
     LiquidWorld(const PressureSolver& solver, Real particle_radius, Real smoothing_factor, int device = 0)
@@ -969,6 +979,52 @@ class LiquidWorld {  // liquid_world.rs
         check(salva_hip_evaluate_fields_lattice(w_, fluid_mask, origin.data(), spacing, dims.data(), 0, &out));
         return f;
     }
+    // The iso-surface `field` = iso (SALVA_HIP_SURFACE_FRACTION or _DENSITY) of the fluids in `fluid_mask` on a lattice, extracted on the
+    // device as an indexed triangle mesh (salva_hip_extract_surface): the count call, then the fill call.  `normals`
+    // (unit, towards lower values) and `velocities` are filled where asked for, three floats per vertex.
+    SurfaceMesh extract_surface(const Vec3& origin, Real spacing, const std::array<uint32_t, 3>& dims, Real iso = 0.5f,
+                                uint32_t field = SALVA_HIP_SURFACE_FRACTION, bool normals = false, bool velocities = false,
+                                uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        return surface_fill(normals, velocities, [&](const SalvaHipSurfaceOut* out, uint64_t* counts) {
+            return salva_hip_extract_surface(w_, fluid_mask, field, iso, origin.data(), spacing, dims.data(), 0, out, counts);
+        });
+    }
+    // ... of a lattice of values of the caller's, nx * ny * nz floats with z fastest
+    SurfaceMesh extract_surface_from_values(const std::vector<Real>& values, const Vec3& origin, Real spacing, const std::array<uint32_t, 3>& dims,
+                                            Real iso) {
+        if (values.size() != (size_t)dims[0] * dims[1] * dims[2]) throw Error(SALVA_HIP_E_INVALID, "extract_surface_from_values: values.size() != nx * ny * nz");
+        return surface_fill(false, false, [&](const SalvaHipSurfaceOut* out, uint64_t* counts) {
+            return salva_hip_extract_surface_from_values(w_, values.data(), iso, origin.data(), spacing, dims.data(), 0, out, counts);
+        });
+    }
+    // The box of the finite positions of the fluids in `fluid_mask`, reduced on the device (salva_hip_get_fluid_bounds).
+    struct Bounds { Vec3 lo, hi; uint64_t nfinite; };
+    Bounds fluid_bounds(uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        Bounds b{};
+        check(salva_hip_get_fluid_bounds(w_, fluid_mask, b.lo.data(), b.hi.data(), &b.nfinite));
+        return b;
+    }
+    // A lattice at `spacing` that encloses fluid_bounds grown by `margin` (negative: h, which closes the surface); its origin is snapped
+    // down to a multiple of the spacing - the f32 product of an integer and the spacing - so that it does not swim from frame to frame.
+    struct Lattice { Vec3 origin; std::array<uint32_t, 3> dims; };
+    Lattice surface_lattice(Real spacing, Real margin = -1.0f, uint32_t fluid_mask = 0xffffffffu) {
+        const Bounds b = fluid_bounds(fluid_mask);
+        if (!b.nfinite) throw Error(SALVA_HIP_E_INVALID, "surface_lattice: the selected fluids have no finite position");
+        const double m = margin < 0.0f ? (double)h() : (double)margin, s = (double)spacing;
+        Lattice l{};
+        for (int a = 0; a < 3; ++a) {
+            const double want_lo = (double)b.lo[a] - m, want_hi = (double)b.hi[a] + m;
+            long long k = (long long)std::floor(want_lo / s);
+            while ((double)((Real)k * spacing) > want_lo) --k;
+            l.origin[a] = (Real)k * spacing;
+            long long d = std::max<long long>((long long)std::ceil((want_hi - (double)l.origin[a]) / s) + 1, 2);
+            while ((double)(l.origin[a] + (Real)(d - 1) * spacing) < want_hi) ++d;  // (the last node as the library computes it)
+            l.dims[a] = (uint32_t)d;
+        }
+        return l;
+    }
     // The reference's host arrays are current after every step, which costs a read-back per step.  A loop that does not look at
     // them (an emitter and sinks that stay on the device) switches it off; refresh() then reads one fluid, or all, back on demand.
     // While it is off `positions` / `velocities` have the right length and stale content: the rows add_particles_from_shape appends
@@ -1025,6 +1081,26 @@ class LiquidWorld {  // liquid_world.rs
     void upload_all() {
         upload_new_objects();
         for (size_t s = 0; s < fluids_.size(); ++s) upload(fluids_[s], (uint32_t)s);
+    }
+    template <typename Call>
+    SurfaceMesh surface_fill(bool normals, bool velocities, Call&& call) {
+        uint64_t counts[2] = {0, 0};
+        check(call(nullptr, counts));
+        SurfaceMesh mesh;
+        const size_t nv = (size_t)counts[0], nt = (size_t)counts[1];
+        // (room the library can name even for an empty mesh)
+        mesh.vertices.assign(3 * nv + 3, 0);
+        mesh.triangles.assign(3 * nt + 3, 0);
+        if (normals) mesh.normals.assign(3 * nv + 3, 0);
+        if (velocities) mesh.velocities.assign(3 * nv + 3, 0);
+        const SalvaHipSurfaceOut out{mesh.vertices.data(), normals ? mesh.normals.data() : nullptr, velocities ? mesh.velocities.data() : nullptr,
+                                     mesh.triangles.data(), nv, nt};
+        check(call(&out, counts));
+        mesh.vertices.resize(3 * nv);
+        mesh.triangles.resize(3 * nt);
+        if (normals) mesh.normals.resize(3 * nv);
+        if (velocities) mesh.velocities.resize(3 * nv);
+        return mesh;
     }
     static SalvaHipFieldOut field_out(Fields& f, size_t m, uint32_t what) {
         SalvaHipFieldOut out{nullptr, nullptr, nullptr, nullptr, nullptr};

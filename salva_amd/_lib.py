@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_sample_compound", "salva_hip_add_particles_sampled_compound", "salva_hip_set_boundary_sampling_from_compound",
     "salva_hip_delete_particles_in_region", "salva_hip_add_sink", "salva_hip_remove_sink", "salva_hip_set_sink_pose", "salva_hip_get_sink_stats",
     "salva_hip_evaluate_fields", "salva_hip_evaluate_fields_lattice",
+    "salva_hip_extract_surface", "salva_hip_extract_surface_from_values", "salva_hip_get_fluid_bounds",
 ]
 
 
@@ -175,6 +176,17 @@ class FieldOut(C.Structure):
 
 
 FIELD_POINTS_ON_DEVICE, FIELD_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_FIELD_POINTS_ON_DEVICE / _OUT_ON_DEVICE
+
+
+class SurfaceOut(C.Structure):
+    """SalvaHipSurfaceOut (include/salva_hip.h): where salva_hip_extract_surface / _from_values write the mesh, and how much room
+    there is; null normals / velocities are not computed."""
+    _fields_ = [("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("velocities", C.POINTER(C.c_float)),
+                ("triangles", C.POINTER(C.c_uint32)), ("vertex_capacity", C.c_uint64), ("triangle_capacity", C.c_uint64)]
+
+
+SURFACE_DENSITY, SURFACE_FRACTION = 0, 1  # SALVA_HIP_SURFACE_DENSITY / _FRACTION
+SURFACE_VALUES_ON_DEVICE, SURFACE_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_SURFACE_VALUES_ON_DEVICE / _OUT_ON_DEVICE
 
 REGION_HALFSPACE, REGION_AABB, REGION_SHAPE, REGION_MESH, REGION_COMPOUND = 1, 2, 3, 4, 5
 REGION_INVERT = 1
@@ -402,6 +414,10 @@ def lib():
     if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_evaluate_fields"):
         L.salva_hip_evaluate_fields.argtypes = [vp, u32, u64, fp, u32, C.POINTER(FieldOut)]
         L.salva_hip_evaluate_fields_lattice.argtypes = [vp, u32, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(FieldOut)]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_extract_surface"):
+        L.salva_hip_extract_surface.argtypes = [vp, u32, u32, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut), C.POINTER(u64)]
+        L.salva_hip_extract_surface_from_values.argtypes = [vp, fp, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut), C.POINTER(u64)]
+        L.salva_hip_get_fluid_bounds.argtypes = [vp, u32, fp, fp, C.POINTER(u64)]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

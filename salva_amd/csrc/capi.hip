@@ -792,6 +792,26 @@ int salva_hip_evaluate_fields_lattice(SalvaHipWorld* world, uint32_t fluid_mask,
     });
 }
 
+int salva_hip_extract_surface(SalvaHipWorld* world, uint32_t fluid_mask, uint32_t field, float iso, const float origin[3], float spacing,
+                              const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]) { WorldLock _lk(world);
+    return status_entry(world, {origin, dims, counts}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.extract_surface(fluid_mask, field, iso, origin, spacing, dims, flags, out, counts);
+    });
+}
+
+int salva_hip_extract_surface_from_values(SalvaHipWorld* world, const float* values, float iso, const float origin[3], float spacing,
+                                          const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]) { WorldLock _lk(world);
+    return status_entry(world, {values, origin, dims, counts}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.extract_surface_from_values(values, iso, origin, spacing, dims, flags, out, counts);
+    });
+}
+
+int salva_hip_get_fluid_bounds(SalvaHipWorld* world, uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite) { WorldLock _lk(world);
+    return status_entry(world, {lo, hi, nfinite}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.get_fluid_bounds(fluid_mask, lo, hi, nfinite);
+    });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -19,6 +19,7 @@
 #include "compound.h"
 #include "sink.h"
 #include "field.h"
+#include "surface.h"
 
 namespace salva {
 
@@ -139,6 +140,13 @@ class World {
     void evaluate_fields(uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags, const SalvaHipFieldOut& out);
     void evaluate_fields_lattice(uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                  const SalvaHipFieldOut& out);
+    // ---- the iso-surface of a field as a triangle mesh (world_surface.hip, surface.hip).  counts = (vertices, triangles)
+    // is written before SALVA_HIP_E_CAPACITY is thrown for want of room.
+    void extract_surface(uint32_t fluid_mask, uint32_t field, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                         const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+    void extract_surface_from_values(const float* values, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                     const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+    void get_fluid_bounds(uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite);
     uint64_t particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                uint32_t* indices);
     uint64_t particles_in(const GeomArg& geom, const float t[3], const float q[4], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
@@ -291,6 +299,18 @@ class World {
         DevBuf<int32_t> box;
         DevBuf<char> temp;
     } fld;
+    // the surface extractor: the node values (an evaluated field, or a host lattice staged), one word and two offsets per node, the
+    // totals, and the staged mesh of host buffers, grown on demand and kept
+    struct SurfaceScratch {
+        DevBuf<float> values, vertices, normals, velocities;
+        DevBuf<uint32_t> word, voff, toff, triangles;
+        DevBuf<SurfaceTotals> totals;
+        DevBuf<int32_t> box;
+        DevBuf<char> temp;
+    } srf;
+    SurfaceLattice surface_lattice(float iso, const float origin[3], float spacing, const uint32_t dims[3], const char* what) const;
+    void surface_run(const float* d_values, float iso, const SurfaceLattice& g, uint32_t fluid_mask, bool on_device, const SalvaHipSurfaceOut* out,
+                     uint64_t counts[2], const char* what);
     FieldFluids field_begin(uint32_t fluid_mask, uint32_t flags, const char* what);
     FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g);
     void field_run(const FieldFluids& f, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m, uint32_t flags,

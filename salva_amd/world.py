@@ -1714,6 +1714,118 @@ class LiquidWorld:
         L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), d.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                           L.FIELD_OUT_ON_DEVICE, C.byref(out)))
 
+    # ---- the iso-surface of a field as a triangle mesh (include/salva_hip.h salva_hip_extract_surface)
+    _SURFACE_FIELDS = {"density": L.SURFACE_DENSITY, "fraction": L.SURFACE_FRACTION}
+
+    @staticmethod
+    def _surface_lattice_args(origin, spacing, dims):
+        o = np.ascontiguousarray(origin, F32).reshape(3)
+        d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+        return o, float(spacing), d, d.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def _surface_fill(self, call, normals, velocities):
+        """the count call, then the fill call: `call(out_or_None, counts)` returns the status"""
+        counts = (C.c_uint64 * 2)()
+        L.check(call(None, counts))
+        nv, nt = int(counts[0]), int(counts[1])
+        mesh = {"vertices": np.zeros((nv, 3), F32), "triangles": np.zeros((nt, 3), np.uint32)}
+        out = L.SurfaceOut()
+        out.vertex_capacity, out.triangle_capacity = nv, nt
+        if normals:
+            mesh["normals"] = np.zeros((nv, 3), F32)
+        if velocities:
+            mesh["velocities"] = np.zeros((nv, 3), F32)
+        # (an empty numpy array may have a null data pointer: the library wants room it can name)
+        room = {k: (a if a.size else np.zeros(3, a.dtype)) for k, a in mesh.items()}
+        for k, a in room.items():
+            setattr(out, k, a.ctypes.data_as(C.POINTER(C.c_uint32 if k == "triangles" else C.c_float)))
+        L.check(call(C.byref(out), counts))
+        assert (int(counts[0]), int(counts[1])) == (nv, nt)
+        return mesh
+
+    def extract_surface(self, origin, spacing, dims, iso=0.5, field="fraction", fluids=None, normals=False, velocities=False):
+        """The surface `field` = iso ("fraction" or "density") of `fluids` (None: all) on the lattice of dims = (nx, ny, nz) nodes at
+        origin + i * spacing, extracted on the device as an indexed triangle mesh: a dict of numpy arrays, `vertices` (nv, 3) float32
+        and `triangles` (nt, 3) uint32, with `normals` (unit, towards lower values) and `velocities` (nv, 3) where asked for."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        o, s, _, dp = self._surface_lattice_args(origin, spacing, dims)
+        mask, fld = self._field_mask(fluids), self._SURFACE_FIELDS[field]
+        return self._surface_fill(lambda out, counts: self._L.salva_hip_extract_surface(self._h, mask, fld, float(iso), _fp(o), s, dp, 0, out, counts),
+                                  normals, velocities)
+
+    def extract_surface_from_values(self, values, origin, spacing, iso):
+        """The same for a lattice of values of the caller's, shaped (nx, ny, nz): `vertices` and `triangles`."""
+        v = np.ascontiguousarray(values, F32)
+        if v.ndim != 3:
+            raise ValueError("values must be shaped (nx, ny, nz)")
+        o, s, _, dp = self._surface_lattice_args(origin, spacing, v.shape)
+        return self._surface_fill(lambda out, counts: self._L.salva_hip_extract_surface_from_values(self._h, _fp(v), float(iso), _fp(o), s, dp, 0, out, counts),
+                                  False, False)
+
+    def extract_surface_device(self, origin, spacing, dims, iso=0.5, field="fraction", fluids=None, values=0, vertices=0, triangles=0, normals=0,
+                               velocities=0, vertex_capacity=0, triangle_capacity=0):
+        """extract_surface into device memory: `vertices`, `triangles`, `normals`, `velocities` are integer device addresses (e.g.
+        torch's data_ptr()) of buffers with room for `vertex_capacity` vertices and `triangle_capacity` triangles on the world's device;
+        normals / velocities left out or 0 are not computed.  With `values` (the device address of nx * ny * nz floats) that lattice is
+        contoured instead of a field.  Without `vertices` the call only counts.  Returns (nv, nt); raises SalvaHipError with code
+        E_CAPACITY where the room does not suffice (the counts are then in the error's `counts`)."""
+        o, s, _, dp = self._surface_lattice_args(origin, spacing, dims)
+        counts = (C.c_uint64 * 2)()
+        out = None
+        if vertices:
+            out = L.SurfaceOut()
+            for name, address in (("vertices", vertices), ("normals", normals), ("velocities", velocities), ("triangles", triangles)):
+                if address:
+                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if name == "triangles" else C.c_float)))
+            out.vertex_capacity, out.triangle_capacity = int(vertex_capacity), int(triangle_capacity)
+        ref = C.byref(out) if out is not None else None
+        if values:
+            rc = self._L.salva_hip_extract_surface_from_values(self._h, C.cast(C.c_void_p(int(values)), C.POINTER(C.c_float)), float(iso), _fp(o), s, dp,
+                                                               L.SURFACE_VALUES_ON_DEVICE | L.SURFACE_OUT_ON_DEVICE, ref, counts)
+        else:
+            self.wait_download()
+            self.sync_to_device(apply_removal=False)
+            rc = self._L.salva_hip_extract_surface(self._h, self._field_mask(fluids), self._SURFACE_FIELDS[field], float(iso), _fp(o), s, dp,
+                                                   L.SURFACE_OUT_ON_DEVICE, ref, counts)
+        try:
+            L.check(rc)
+        except L.SalvaHipError as e:
+            e.counts = (int(counts[0]), int(counts[1]))
+            raise
+        return int(counts[0]), int(counts[1])
+
+    def fluid_bounds(self, fluids=None):
+        """(lo, hi, nfinite): the box of the finite positions of `fluids` (None: all), reduced on the device; with no finite
+        position lo = +inf and hi = -inf."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        lo, hi, n = np.zeros(3, F32), np.zeros(3, F32), C.c_uint64(0)
+        L.check(self._L.salva_hip_get_fluid_bounds(self._h, self._field_mask(fluids), _fp(lo), _fp(hi), C.byref(n)))
+        return lo, hi, int(n.value)
+
+    def surface_lattice(self, spacing, margin=None, fluids=None):
+        """(origin, dims) of a lattice at `spacing` that encloses the box of `fluids` (fluid_bounds) grown by `margin` (default h: the
+        fields are zero on its faces, the surface closed).  The origin is snapped down to a multiple of the spacing - the f32 product
+        of an integer and the spacing - so that the lattice does not swim from frame to frame."""
+        lo, hi, n = self.fluid_bounds(fluids)
+        if not n:
+            raise ValueError("surface_lattice: the selected fluids have no finite position")
+        s = F32(spacing)
+        m = float(self.h() if margin is None else margin)
+        origin, dims = np.zeros(3, F32), [0, 0, 0]
+        for a in range(3):
+            want_lo, want_hi = float(lo[a]) - m, float(hi[a]) + m
+            k = int(np.floor(want_lo / float(s)))
+            while float(F32(k) * s) > want_lo:
+                k -= 1
+            origin[a] = F32(k) * s
+            d = max(int(np.ceil((want_hi - float(origin[a])) / float(s))) + 1, 2)
+            while float(origin[a] + F32(d - 1) * s) < want_hi:  # (the last node as the library computes it)
+                d += 1
+            dims[a] = d
+        return origin, tuple(dims)
+
     def _resize_after_sinks(self):
         """A step in which a sink fired shortened fluids on the device: the host copies follow (positions and velocities are read
         back on the next access, accelerations are zero after a step, the volumes come from the device unless they are uniform)."""
