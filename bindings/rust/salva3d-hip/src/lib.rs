@@ -10,6 +10,7 @@ mod liquid_world;
 pub mod region;
 pub mod field;
 pub mod surface;
+pub mod ray;
 #[cfg(feature = "rapier")]
 pub mod coupling;
 #[cfg(feature = "parry")]
@@ -20,3 +21,4 @@ pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWor
 pub use region::Region;
 pub use field::{FieldSet, Fields};
 pub use surface::{SurfaceField, SurfaceMesh};
+pub use ray::{RayCamera, RayHits, RayOptions, RaySet};

@@ -541,6 +541,20 @@ impl LiquidWorld {
         self.upload()?;
         crate::field::evaluate_lattice(self.raw, fluid_mask, origin, spacing, dims, want)
     }
+    /// Casts the rays `origins[i] + t directions[i]` at the particles, each a sphere of `opt.radius`, on the device: the first hit of
+    /// every ray, its normal, the thickness of fluid along it (`salva_hip_cast_rays`; ray.rs).
+    pub fn cast_rays(&mut self, origins: &[nalgebra::Point3<Real>], directions: &[Vector3<Real>], want: crate::RaySet, opt: &crate::RayOptions)
+                     -> Result<crate::RayHits, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::ray::cast_rays(self.raw, self.particle_radius, origins, directions, want, opt)
+    }
+    /// The same for the pixels of a camera: a depth image and a thickness image (`salva_hip_cast_rays_camera`).
+    pub fn cast_camera(&mut self, camera: &crate::RayCamera, want: crate::RaySet, opt: &crate::RayOptions) -> Result<crate::RayHits, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::ray::cast_camera(self.raw, self.particle_radius, camera, want, opt)
+    }
     /// The iso-surface `field` = `iso` of the fluids selected by `fluid_mask` on the lattice `origin + i * spacing` of `dims` nodes,
     /// extracted on the device as an indexed triangle mesh (`salva_hip_extract_surface`; surface.rs).
     #[allow(clippy::too_many_arguments)]

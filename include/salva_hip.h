@@ -1013,6 +1013,88 @@ int salva_hip_extract_surface_from_values(SalvaHipWorld* world, const float* val
  * none, lo = +inf and hi = -inf.  Refusals as salva_hip_evaluate_fields. */
 int salva_hip_get_fluid_bounds(SalvaHipWorld* world, uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite);
 
+/* ---- Rays cast at the fluid: every particle of the selected fluids is a sphere of radius R, and a ray o + t d is asked
+ * for its first hit (t, the particle, the sphere's normal there) and for the thickness of fluid along it - picking, a depth or lidar
+ * sensor, splash detection along a line, the depth and thickness images of screen-space fluid rendering - without downloading a
+ * particle.  The rays are a list, or the pixels of a camera.  Every operation below is f32, rounded once, never contracted into an FMA;
+ * `/` and sqrt are correctly rounded.  dot(a, b) = ((ax bx) + (ay by)) + (az bz).
+ *
+ * 1. Particles.  The rows of the fluids in `fluid_mask` as salva_hip_get_fluid would return them now (as for the fields above).  A row
+ *    counts when its position is finite and lies in the box B, faces included.  B is [clip_lo, clip_hi] when has_clip is 1; otherwise
+ *    it is exactly what salva_hip_get_fluid_bounds returns for the mask.  When no row is finite (no clip box), or no row lies in the
+ *    cells of the clip box grown by one cell, every ray misses and no ray is walked.  Each call builds a table of cells of width h over B grown by one cell: more than 2^27 cells, or more than 2^16 on an
+ *    axis, is SALVA_HIP_E_CAPACITY - give a clip box (one stray particle far away is enough to get there).
+ * 2. Advance.  G = B grown by R: glo = blo - R, ghi = bhi + R per axis.  The ray's interval [e0, e1] in G starts as [-inf, +inf]; an
+ *    axis with d = 0 leaves it alone and needs glo <= o <= ghi; any other axis has u = (glo - o) / d, v = (ghi - o) / d and
+ *    e0 = max(e0, min(u, v)), e1 = min(e1, max(u, v)) (ray_slab's rule, x, y, z in turn).  The ray is a miss when an axis with d = 0
+ *    lies outside, when e0 > e1, when e1 < 0 or when e0 > tmax.  Otherwise ta = max(e0, 0) and o' = o + (ta * d) per component.
+ *    This is part of the contract, not an optimisation: everything in 3. to 5. is computed from o', so its magnitudes - and its
+ *    rounding errors - are bounded by the size of the box and not by how far away the camera stands.
+ * 3. Cast.  Per counting particle j at x_j: q = o' - x_j; a = dot(d, d), b = dot(q, d), tm = (-b) / a, p = q + (tm * d),
+ *    disc = (R * R) - dot(p, p); without disc > 0 the sphere is not met; half = sqrt(disc / a), t0 = tm - half, t1 = tm + half.  The
+ *    candidate exists when t1 >= 0; its value is t_j = ta + max(t0, 0) - the solid rule: a ray that starts inside a sphere hits it at
+ *    once - and it is a hit when t_j <= tmax.  The result is the smallest t_j; ties go to the lower fluid slot, then to the lower
+ *    index.  d is not normalised: t is in units of |d|.  A ray with a non-finite component, or whose dot(d, d) is not a finite
+ *    positive f32, is a miss.  A miss has t = +inf, fluid = index = 0xffffffff, normal = 0 and thickness 0.
+ * 4. Normal.  n = q + ((t_j - ta) * d) per component; with m = max |n_k| > 0: s = n / m, len = sqrt(((sx sx) + (sy sy)) + (sz sz)),
+ *    normal = s / len.  The zero vector where n is zero.
+ * 5. Thickness.  The sum over the counting particles of max(0, min(ta + t1, tmax) - (ta + max(t0, 0))), an f32 sum whose order is
+ *    not pinned; a particle the ray does not meet adds 0, and each particle counts once.
+ * 6. Camera.  Pixel (ix, iy), 0 <= ix < width, 0 <= iy < height, has su = (((float)ix + 0.5f) * (2.0f / (float)width)) - 1.0f, sv
+ *    likewise from iy and height, the ray o = origin, d = (forward + (su * right)) + (sv * up) per component, and the output index
+ *    iy * width + ix.  With a unit `forward` orthogonal to `right` and `up`, t is the depth along `forward`.
+ * `index` is the particle's index within its fluid as salva_hip_get_fluid returns it.  Any pointer of `out` may be NULL: that output
+ * is neither computed nor written; a call that asks for thickness alone does not track the first hit.  A second call gives the same
+ * bits for everything but thickness.
+ * Buffers: SALVA_HIP_RAY_RAYS_ON_DEVICE / _OUT_ON_DEVICE as for the fields; with _OUT_ON_DEVICE the results are complete when the call
+ * returns.  The calls work before the first step and change nothing a step reads.  nrays == 0 is SALVA_HIP_OK and does nothing.
+ * SALVA_HIP_E_INVALID: a decomposed world; a call from inside a force, device force or coupling callback; a mask that selects no
+ * existing fluid; out, params, camera NULL, or origins / directions NULL with nrays > 0; an unknown flag (for a camera:
+ * SALVA_HIP_RAY_RAYS_ON_DEVICE too); a struct_size / version other than this header's; a radius that is not finite, not > 0 or above
+ * h / 2; a tmax that is NaN or < 0; has_clip other than 0 or 1; clip_lo > clip_hi or a non-finite clip box; a zero camera dimension.
+ * SALVA_HIP_E_CAPACITY: more than 2^32 rays; the table, as above. */
+enum {
+    SALVA_HIP_RAY_RAYS_ON_DEVICE = 1, /* `origins_xyz` and `directions_xyz` are device pointers */
+    SALVA_HIP_RAY_OUT_ON_DEVICE = 2   /* every non-null pointer of `out` is a device pointer */
+};
+#define SALVA_HIP_RAY_VERSION 1
+#define SALVA_HIP_RAY_PARAMS_BYTES 64
+#define SALVA_HIP_RAY_CAMERA_BYTES 64
+typedef struct SalvaHipRayParams {
+    uint32_t struct_size;   /* SALVA_HIP_RAY_PARAMS_BYTES */
+    uint32_t version;       /* SALVA_HIP_RAY_VERSION */
+    float radius;           /* R: finite, 0 < R <= h / 2 */
+    float tmax;             /* >= 0, +inf allowed */
+    uint32_t has_clip;      /* 1: B = [clip_lo, clip_hi]; 0: B = the fluids' own box */
+    float clip_lo[3], clip_hi[3];
+    uint32_t reserved[5];
+} SalvaHipRayParams;
+typedef struct SalvaHipRayCamera {
+    uint32_t struct_size;   /* SALVA_HIP_RAY_CAMERA_BYTES */
+    uint32_t version;       /* SALVA_HIP_RAY_VERSION */
+    float origin[3], forward[3], right[3], up[3];
+    uint32_t width, height;
+} SalvaHipRayCamera;
+typedef struct SalvaHipRayOut { /* M rays; any pointer may be NULL */
+    float* t;               /* M */
+    uint32_t* fluid;        /* M   the fluid's slot */
+    uint32_t* index;        /* M   the particle's index within its fluid */
+    float* normal;          /* 3M */
+    float* thickness;       /* M */
+} SalvaHipRayOut;
+int salva_hip_cast_rays(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, uint64_t nrays, const float* origins_xyz,
+                        const float* directions_xyz, uint32_t flags, const SalvaHipRayOut* out);
+int salva_hip_cast_rays_camera(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera,
+                               uint32_t flags, const SalvaHipRayOut* out);
+/* What a cast costs: tested[i] = the number of particles the walk of ray i put to the exact cast of 3. (the candidates of the cells it
+ * visited), for the walk of a first-hit call (thickness_walk 0: it stops early) or of a call that sums the thickness (1: it does
+ * not).  The rays are the camera's when `camera_or_null` is given (nrays, origins and directions are then ignored), else the list's;
+ * flags, refusals and the order of `tested` as for the casts, SALVA_HIP_RAY_OUT_ON_DEVICE naming `tested`.  A measuring aid
+ * (tools/raycast_bench.py): the figures depend on the walk, which the contract above does not pin. */
+int salva_hip_count_ray_candidates(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera_or_null,
+                                   uint64_t nrays, const float* origins_xyz, const float* directions_xyz, uint32_t flags, uint32_t thickness_walk,
+                                   uint32_t* tested);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

@@ -23,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <functional>
+#include <limits>
 #include <utility>
 #include <vector>
 
@@ -528,6 +529,22 @@ struct SurfaceMesh {
     size_t num_triangles() const { return triangles.size() / 3; }
 };
 
+// What LiquidWorld::cast_rays / cast_camera return, one entry per ray (three floats per ray in `normal`); a miss has t = +inf and
+// fluid = index = 0xffffffff.  The vectors not asked for stay empty.
+struct RayHits {
+    std::vector<Real> t, normal, thickness;
+    std::vector<uint32_t> fluid, index;
+    bool hit(size_t i) const { return fluid[i] != 0xffffffffu; }
+};
+struct RaySet { enum : uint32_t { HIT = 1, NORMAL = 2, THICKNESS = 4, ALL = 7 }; };
+struct RayOptions {
+    Real radius = 0.0f, tmax = std::numeric_limits<Real>::infinity();  // radius <= 0: the particle radius
+    uint32_t fluid_mask = 0xffffffffu;
+    bool has_clip = false;
+    Vec3 clip_lo{}, clip_hi{};
+};
+struct RayCamera { Vec3 origin, forward, right, up; uint32_t width, height; };
+
 class LiquidWorld {  // liquid_world.rs
   public:
     LiquidWorld(const PressureSolver& solver, Real particle_radius, Real smoothing_factor, int device = 0)
@@ -998,6 +1015,35 @@ class LiquidWorld {  // liquid_world.rs
             return salva_hip_extract_surface_from_values(w_, values.data(), iso, origin.data(), spacing, dims.data(), 0, out, counts);
         });
     }
+    // Rays cast at the fluid's particles, each a sphere of `radius` (<= 0: the particle radius; at most h / 2), on the device
+    // (salva_hip_cast_rays / _cast_rays_camera): the first hit of every ray - t in units of |d| (+inf: a miss), the
+    // particle (fluid, index; 0xffffffff: a miss), with RaySet::NORMAL the sphere's unit normal there - and with RaySet::THICKNESS the
+    // length of the ray inside spheres up to tmax.  The vectors not asked for stay empty.  `clip`: only the particles in that box are
+    // seen.  A camera's pixel (ix, iy) casts forward + su right + sv up, su = (ix + 0.5) 2 / width - 1, and lands at iy * width + ix.
+    RayHits cast_rays(const std::vector<Vec3>& origins, const std::vector<Vec3>& directions, uint32_t what = RaySet::HIT,
+                      const RayOptions& opt = RayOptions()) {
+        if (origins.size() != directions.size()) throw Error(SALVA_HIP_E_INVALID, "cast_rays: origins.size() != directions.size()");
+        upload_all();
+        RayHits hits;
+        const SalvaHipRayParams p = ray_params(opt);
+        const SalvaHipRayOut out = ray_out(hits, origins.size(), what);
+        check(salva_hip_cast_rays(w_, opt.fluid_mask, &p, origins.size(), origins.empty() ? nullptr : origins[0].data(),
+                                  directions.empty() ? nullptr : directions[0].data(), 0, &out));
+        return hits;
+    }
+    RayHits cast_camera(const RayCamera& camera, uint32_t what = RaySet::HIT, const RayOptions& opt = RayOptions()) {
+        upload_all();
+        RayHits hits;
+        const SalvaHipRayParams p = ray_params(opt);
+        SalvaHipRayCamera c{};
+        c.struct_size = SALVA_HIP_RAY_CAMERA_BYTES; c.version = SALVA_HIP_RAY_VERSION;
+        for (int a = 0; a < 3; ++a) { c.origin[a] = camera.origin[a]; c.forward[a] = camera.forward[a]; c.right[a] = camera.right[a]; c.up[a] = camera.up[a]; }
+        c.width = camera.width; c.height = camera.height;
+        const uint64_t m = (uint64_t)camera.width * camera.height;
+        const SalvaHipRayOut out = ray_out(hits, m <= (1ull << 32) ? (size_t)m : 1, what);  // (beyond: the library's refusal)
+        check(salva_hip_cast_rays_camera(w_, opt.fluid_mask, &p, &c, 0, &out));
+        return hits;
+    }
     // The box of the finite positions of the fluids in `fluid_mask`, reduced on the device (salva_hip_get_fluid_bounds).
     struct Bounds { Vec3 lo, hi; uint64_t nfinite; };
     Bounds fluid_bounds(uint32_t fluid_mask = 0xffffffffu) {
@@ -1101,6 +1147,27 @@ class LiquidWorld {  // liquid_world.rs
         if (normals) mesh.normals.resize(3 * nv);
         if (velocities) mesh.velocities.resize(3 * nv);
         return mesh;
+    }
+    SalvaHipRayParams ray_params(const RayOptions& opt) const {
+        SalvaHipRayParams p{};
+        p.struct_size = SALVA_HIP_RAY_PARAMS_BYTES; p.version = SALVA_HIP_RAY_VERSION;
+        p.radius = opt.radius > 0.0f ? opt.radius : particle_radius_;
+        p.tmax = opt.tmax;
+        p.has_clip = opt.has_clip ? 1u : 0u;
+        for (int a = 0; a < 3; ++a) { p.clip_lo[a] = opt.clip_lo[a]; p.clip_hi[a] = opt.clip_hi[a]; }
+        return p;
+    }
+    static SalvaHipRayOut ray_out(RayHits& h, size_t m, uint32_t what) {
+        SalvaHipRayOut out{nullptr, nullptr, nullptr, nullptr, nullptr};
+        const size_t room = m ? m : 1;
+        if (what & RaySet::HIT) {
+            h.t.assign(room, 0); out.t = h.t.data(); h.t.resize(m);
+            h.fluid.assign(room, 0); out.fluid = h.fluid.data(); h.fluid.resize(m);
+            h.index.assign(room, 0); out.index = h.index.data(); h.index.resize(m);
+        }
+        if (what & RaySet::NORMAL) { h.normal.assign(3 * room, 0); out.normal = h.normal.data(); h.normal.resize(3 * m); }
+        if (what & RaySet::THICKNESS) { h.thickness.assign(room, 0); out.thickness = h.thickness.data(); h.thickness.resize(m); }
+        return out;
     }
     static SalvaHipFieldOut field_out(Fields& f, size_t m, uint32_t what) {
         SalvaHipFieldOut out{nullptr, nullptr, nullptr, nullptr, nullptr};

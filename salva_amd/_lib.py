@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "salva_hip_delete_particles_in_region", "salva_hip_add_sink", "salva_hip_remove_sink", "salva_hip_set_sink_pose", "salva_hip_get_sink_stats",
     "salva_hip_evaluate_fields", "salva_hip_evaluate_fields_lattice",
     "salva_hip_extract_surface", "salva_hip_extract_surface_from_values", "salva_hip_get_fluid_bounds",
+    "salva_hip_cast_rays", "salva_hip_cast_rays_camera", "salva_hip_count_ray_candidates",
 ]
 
 
@@ -169,6 +170,24 @@ class Region(C.Structure):
                 ("maxs", C.c_float * 3), ("translation", C.c_float * 3), ("rotation_ijkw", C.c_float * 4), ("reserved", C.c_uint32 * 3)]
 
 
+class RayParams(C.Structure):
+    """SalvaHipRayParams (include/salva_hip.h): the sphere radius, tmax and the optional clip box of a ray cast."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("radius", C.c_float), ("tmax", C.c_float), ("has_clip", C.c_uint32),
+                ("clip_lo", C.c_float * 3), ("clip_hi", C.c_float * 3), ("reserved", C.c_uint32 * 5)]
+
+
+class RayCamera(C.Structure):
+    """SalvaHipRayCamera: pixel (ix, iy) casts origin, forward + su right + sv up."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("origin", C.c_float * 3), ("forward", C.c_float * 3),
+                ("right", C.c_float * 3), ("up", C.c_float * 3), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class RayOut(C.Structure):
+    """SalvaHipRayOut: where salva_hip_cast_rays / _camera write; a null pointer is not computed."""
+    _fields_ = [("t", C.POINTER(C.c_float)), ("fluid", C.POINTER(C.c_uint32)), ("index", C.POINTER(C.c_uint32)),
+                ("normal", C.POINTER(C.c_float)), ("thickness", C.POINTER(C.c_float))]
+
+
 class FieldOut(C.Structure):
     """SalvaHipFieldOut (include/salva_hip.h): where salva_hip_evaluate_fields / _lattice write; a null pointer is not computed."""
     _fields_ = [("density", C.POINTER(C.c_float)), ("fraction", C.POINTER(C.c_float)), ("velocity", C.POINTER(C.c_float)),
@@ -184,6 +203,10 @@ class SurfaceOut(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("velocities", C.POINTER(C.c_float)),
                 ("triangles", C.POINTER(C.c_uint32)), ("vertex_capacity", C.c_uint64), ("triangle_capacity", C.c_uint64)]
 
+
+RAY_RAYS_ON_DEVICE, RAY_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_RAY_RAYS_ON_DEVICE / _OUT_ON_DEVICE
+RAY_VERSION, RAY_PARAMS_BYTES, RAY_CAMERA_BYTES = 1, 64, 64  # SALVA_HIP_RAY_VERSION / _PARAMS_BYTES / _CAMERA_BYTES
+RAY_NONE = 0xFFFFFFFF  # fluid and index of a miss
 
 SURFACE_DENSITY, SURFACE_FRACTION = 0, 1  # SALVA_HIP_SURFACE_DENSITY / _FRACTION
 SURFACE_VALUES_ON_DEVICE, SURFACE_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_SURFACE_VALUES_ON_DEVICE / _OUT_ON_DEVICE
@@ -418,6 +441,10 @@ def lib():
         L.salva_hip_extract_surface.argtypes = [vp, u32, u32, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut), C.POINTER(u64)]
         L.salva_hip_extract_surface_from_values.argtypes = [vp, fp, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut), C.POINTER(u64)]
         L.salva_hip_get_fluid_bounds.argtypes = [vp, u32, fp, fp, C.POINTER(u64)]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_cast_rays"):
+        L.salva_hip_cast_rays.argtypes = [vp, u32, C.POINTER(RayParams), u64, fp, fp, u32, C.POINTER(RayOut)]
+        L.salva_hip_cast_rays_camera.argtypes = [vp, u32, C.POINTER(RayParams), C.POINTER(RayCamera), u32, C.POINTER(RayOut)]
+        L.salva_hip_count_ray_candidates.argtypes = [vp, u32, C.POINTER(RayParams), C.POINTER(RayCamera), u64, fp, fp, u32, u32, C.POINTER(u32)]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

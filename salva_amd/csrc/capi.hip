@@ -812,6 +812,28 @@ int salva_hip_get_fluid_bounds(SalvaHipWorld* world, uint32_t fluid_mask, float 
     });
 }
 
+int salva_hip_cast_rays(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, uint64_t nrays, const float* origins_xyz,
+                        const float* directions_xyz, uint32_t flags, const SalvaHipRayOut* out) { WorldLock _lk(world);
+    return status_entry(world, {params, out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.cast_rays(fluid_mask, params, nrays, origins_xyz, directions_xyz, flags, *out);
+    });
+}
+
+int salva_hip_cast_rays_camera(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera,
+                               uint32_t flags, const SalvaHipRayOut* out) { WorldLock _lk(world);
+    return status_entry(world, {params, camera, out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.cast_rays_camera(fluid_mask, params, camera, flags, *out);
+    });
+}
+
+int salva_hip_count_ray_candidates(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera_or_null,
+                                   uint64_t nrays, const float* origins_xyz, const float* directions_xyz, uint32_t flags, uint32_t thickness_walk,
+                                   uint32_t* tested) { WorldLock _lk(world);
+    return status_entry(world, {params, tested}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.count_ray_candidates(fluid_mask, params, camera_or_null, nrays, origins_xyz, directions_xyz, flags, thickness_walk, tested);
+    });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -59,10 +59,11 @@ inline float field_unordered(int32_t i) { i ^= (i >> 31) & 0x7fffffff; float f; 
 // served; cells[c] = rows of cell c (zeroed by the caller, g.ncells + 1 words)
 void launch_field_keys(const float4* st_pos, const uint32_t* st_model, uint32_t n, const FieldFluids& f, const FieldGrid& g, uint32_t* keys,
                        uint32_t* rank, uint32_t* cells, hipStream_t st);
-// after the exclusive scan of `cells` in place: the kept rows by cell, then by host index, gathered into rec0 / rec1 (rec1 may be null)
+// after the exclusive scan of `cells` in place: the kept rows by cell, then by host index, gathered into rec0 / rec1 (rec1 may be null);
+// rows (may be null): the host-order row behind each sorted row
 void launch_field_sort(const float4* st_pos, const float4* st_vel, const uint32_t* st_model, uint32_t n, const FieldFluids& f, const FieldGrid& g,
                        const uint32_t* keys, const uint32_t* rank, const uint32_t* cells, uint32_t* keys_sorted, uint32_t* idx_tmp, float4* rec0,
-                       float4* rec1, hipStream_t st);
+                       float4* rec1, uint32_t* rows, hipStream_t st);
 void launch_field_points(const FieldQuery& q, const FieldGrid& g, const FieldCandidates& cand, const SphConsts& c, const FieldOutDev& out,
                          hipStream_t st);
 void launch_field_lattice(const FieldQuery& q, const FieldGrid& g, const FieldCandidates& cand, const SphConsts& c, const FieldOutDev& out,

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(BLOCK) void k_field_scatter(uint32_t n, const uint3
 __global__ __launch_bounds__(BLOCK) void k_field_order(uint32_t n, const uint32_t* __restrict__ keys_sorted, const uint32_t* __restrict__ cells,
                                                        uint32_t ncells, const uint32_t* __restrict__ idx_tmp, const float4* __restrict__ st_pos,
                                                        const float4* __restrict__ st_vel, const uint32_t* __restrict__ st_model, FieldFluids f,
-                                                       float4* __restrict__ rec0, float4* __restrict__ rec1) {
+                                                       float4* __restrict__ rec0, float4* __restrict__ rec1, uint32_t* __restrict__ rows) {
     const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n || p >= cells[ncells]) return;  // (cells[ncells]: the kept rows)
     const uint32_t k = keys_sorted[p];
@@ -106,13 +106,14 @@ __global__ __launch_bounds__(BLOCK) void k_field_order(uint32_t n, const uint32_
         const float4 u = st_vel[v];
         rec1[at] = make_float4(u.x, u.y, u.z, x.w);
     }
+    if (rows) rows[at] = v;  // (fluidcast.h: who the sorted row is)
 }
 void launch_field_sort(const float4* st_pos, const float4* st_vel, const uint32_t* st_model, uint32_t n, const FieldFluids& f, const FieldGrid& g,
                        const uint32_t* keys, const uint32_t* rank, const uint32_t* cells, uint32_t* keys_sorted, uint32_t* idx_tmp, float4* rec0,
-                       float4* rec1, hipStream_t st) {
+                       float4* rec1, uint32_t* rows, hipStream_t st) {
     if (!n) return;
     k_field_scatter<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, keys, rank, cells, g.ncells, keys_sorted, idx_tmp);
-    k_field_order<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, keys_sorted, cells, g.ncells, idx_tmp, st_pos, st_vel, st_model, f, rec0, rec1);
+    k_field_order<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, keys_sorted, cells, g.ncells, idx_tmp, st_pos, st_vel, st_model, f, rec0, rec1, rows);
     SALVA_HIP_CHECK(hipGetLastError());
 }
 

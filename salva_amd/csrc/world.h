@@ -20,6 +20,7 @@
 #include "sink.h"
 #include "field.h"
 #include "surface.h"
+#include "fluidcast.h"
 
 namespace salva {
 
@@ -147,6 +148,13 @@ class World {
     void extract_surface_from_values(const float* values, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                      const SalvaHipSurfaceOut* out, uint64_t counts[2]);
     void get_fluid_bounds(uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite);
+    // ---- rays cast at the fluid's particles (world_cast.hip, fluidcast.hip)
+    void cast_rays(uint32_t fluid_mask, const SalvaHipRayParams* params, uint64_t nrays, const float* origins_xyz, const float* directions_xyz,
+                   uint32_t flags, const SalvaHipRayOut& out);
+    void cast_rays_camera(uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera, uint32_t flags,
+                          const SalvaHipRayOut& out);
+    void count_ray_candidates(uint32_t fluid_mask, const SalvaHipRayParams* params, const SalvaHipRayCamera* camera, uint64_t nrays,
+                              const float* origins_xyz, const float* directions_xyz, uint32_t flags, uint32_t thickness_walk, uint32_t* tested);
     uint64_t particles_in_aabb(const float mins[3], const float maxs[3], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
                                uint32_t* indices);
     uint64_t particles_in(const GeomArg& geom, const float t[3], const float q[4], uint64_t capacity, uint32_t* kinds, uint32_t* slots,
@@ -312,7 +320,15 @@ class World {
     void surface_run(const float* d_values, float iso, const SurfaceLattice& g, uint32_t fluid_mask, bool on_device, const SalvaHipSurfaceOut* out,
                      uint64_t counts[2], const char* what);
     FieldFluids field_begin(uint32_t fluid_mask, uint32_t flags, const char* what);
-    FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g);
+    FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g,
+                                     DevBuf<uint32_t>* rows_out = nullptr);
+    // the ray casts: the host-order row of every sorted row of the table, staged rays and staged results, grown on demand and kept
+    struct CastScratch {
+        DevBuf<uint32_t> rows;
+        DevBuf<float> rays, out;
+    } cst;
+    void cast_run(uint32_t fluid_mask, const SalvaHipRayParams* params, CastRays rays, uint32_t flags, const SalvaHipRayOut& out, const char* what,
+                  int count_walk = 0, uint32_t* tested = nullptr);
     void field_run(const FieldFluids& f, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m, uint32_t flags,
                    const SalvaHipFieldOut& out, bool brick_arm);
     void set_boundary_from(uint32_t slot, uint64_t n, const float* pos, const float* vel, uint32_t memberships, uint32_t filter,

@@ -34,8 +34,8 @@ FieldFluids World::field_begin(uint32_t fluid_mask, uint32_t flags, const char* 
 }
 
 // The evaluator's grid over [lo, hi] grown by h — one cell more on every side of the cells the box touches — and the selected
-// particles inside it, sorted by cell, then by host index
-FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g) {
+// particles inside it, sorted by cell, then by host index (rows, when given: the host-order row of each, for the ray casts)
+FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g, DevBuf<uint32_t>* rows_out) {
     int clo[3], chi[3];
     cell_range(lo, hi, sc.h, clo, chi);
     uint64_t ncells = 1;
@@ -54,6 +54,7 @@ FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3],
     fld.keys_sorted.ensure(rows, stream, false, 1.1f); fld.idx_tmp.ensure(rows, stream, false, 1.1f);
     fld.rec0.ensure(rows, stream, false, 1.1f);
     if (second) fld.rec1.ensure(rows, stream, false, 1.1f);
+    if (rows_out) rows_out->ensure(rows, stream, false, 1.1f);
     fld.cells.ensure((size_t)g.ncells + 1, stream, false, 1.1f);
     const size_t tb = scan_temp_bytes(g.ncells + 1u);
     fld.temp.ensure(tb ? tb : 1);
@@ -61,7 +62,7 @@ FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3],
     launch_field_keys(st_pos.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, stream);
     scan_u32(fld.temp.p, tb, fld.cells.p, fld.cells.p, g.ncells + 1u, stream);
     launch_field_sort(st_pos.p, st_vel.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, fld.keys_sorted.p, fld.idx_tmp.p, fld.rec0.p,
-                      second ? fld.rec1.p : nullptr, stream);
+                      second ? fld.rec1.p : nullptr, rows_out ? rows_out->p : nullptr, stream);
     return FieldCandidates{fld.cells.p, fld.rec0.p, second ? fld.rec1.p : nullptr};
 }
 

@@ -1804,6 +1804,141 @@ class LiquidWorld:
         L.check(self._L.salva_hip_get_fluid_bounds(self._h, self._field_mask(fluids), _fp(lo), _fp(hi), C.byref(n)))
         return lo, hi, int(n.value)
 
+    # ---- rays cast at the fluid's particles (include/salva_hip.h salva_hip_cast_rays)
+    _RAY_WIDTHS = (("t", 1), ("fluid", 1), ("index", 1), ("normal", 3), ("thickness", 1))
+
+    def _ray_params(self, radius, tmax, clip):
+        p = L.RayParams()
+        p.struct_size, p.version = L.RAY_PARAMS_BYTES, L.RAY_VERSION
+        p.radius = float(self.particle_radius() if radius is None else radius)
+        p.tmax = float(tmax)
+        if clip is not None:
+            lo, hi = (np.ascontiguousarray(v, F32).reshape(3) for v in clip)
+            p.has_clip = 1
+            p.clip_lo[:], p.clip_hi[:] = [float(v) for v in lo], [float(v) for v in hi]
+        return p
+
+    @staticmethod
+    def _ray_camera(camera):
+        """camera: a dict with origin, forward, right, up (3 floats each), width and height"""
+        c = L.RayCamera()
+        c.struct_size, c.version = L.RAY_CAMERA_BYTES, L.RAY_VERSION
+        for k in ("origin", "forward", "right", "up"):
+            getattr(c, k)[:] = [float(v) for v in np.ascontiguousarray(camera[k], F32).reshape(3)]
+        c.width, c.height = int(camera["width"]), int(camera["height"])
+        return c
+
+    def _ray_host_out(self, m, normals, thickness, hits):
+        arrays, out = {}, L.RayOut()
+        want = dict(t=hits, fluid=hits, index=hits, normal=normals, thickness=thickness)
+        for name, width in self._RAY_WIDTHS:
+            if not want[name]:
+                continue
+            integer = name in ("fluid", "index")
+            a = np.zeros(m * width, np.uint32 if integer else F32)
+            arrays[name] = a
+            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_uint32 if integer else C.c_float)))
+        return arrays, out
+
+    @staticmethod
+    def _ray_device_out(addresses):
+        out = L.RayOut()
+        for name, _ in LiquidWorld._RAY_WIDTHS:
+            if addresses.get(name):
+                setattr(out, name, C.cast(C.c_void_p(int(addresses[name])), C.POINTER(C.c_uint32 if name in ("fluid", "index") else C.c_float)))
+        return out
+
+    def cast_rays(self, origins, directions, radius=None, tmax=np.inf, fluids=None, clip=None, normals=False, thickness=False, hits=True):
+        """Casts the rays origins[i] + t directions[i] (m x 3 each) at the particles of `fluids` (None: all), each a sphere of
+        `radius` (None: the particle radius; at most h / 2), on the device: a dict of numpy arrays `t` (+inf: a miss), `fluid` and
+        `index` (0xffffffff: a miss), with normals=True `normal` (m x 3) and with thickness=True `thickness`, the length of the ray
+        inside spheres up to `tmax`.  `clip` = (lo, hi): only the particles in that box are seen.  hits=False with thickness=True
+        sums the thickness alone."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        o = np.ascontiguousarray(origins, F32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, F32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("cast_rays: as many directions as origins")
+        m = len(o)
+        p = self._ray_params(radius, tmax, clip)
+        arrays, out = self._ray_host_out(m, normals, thickness, hits)
+        L.check(self._L.salva_hip_cast_rays(self._h, self._field_mask(fluids), C.byref(p), m, _fp(o), _fp(d), 0, C.byref(out)))
+        return {k: (a.reshape(m, 3) if k == "normal" else a) for k, a in arrays.items()}
+
+    def cast_camera(self, camera, radius=None, tmax=np.inf, fluids=None, clip=None, normals=False, thickness=False, hits=True):
+        """cast_rays for the pixels of `camera` (a dict: origin, forward, right, up, width, height): pixel (ix, iy) casts
+        forward + su right + sv up with su = (ix + 0.5) 2 / width - 1, sv likewise; arrays shaped (height, width) and
+        (height, width, 3).  With a unit forward orthogonal to right and up, `t` is a depth image."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        c = self._ray_camera(camera)
+        m = int(c.width) * int(c.height)
+        p = self._ray_params(radius, tmax, clip)
+        arrays, out = self._ray_host_out(m if m <= 1 << 32 else 1, normals, thickness, hits)  # (beyond: the library refuses before it writes)
+        L.check(self._L.salva_hip_cast_rays_camera(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), 0, C.byref(out)))
+        hh, ww = int(c.height), int(c.width)
+        return {k: (a.reshape(hh, ww, 3) if k == "normal" else a.reshape(hh, ww)) for k, a in arrays.items()}
+
+    def cast_rays_device(self, origins_address: int, directions_address: int, nrays: int, radius=None, tmax=np.inf, fluids=None, clip=None,
+                         **addresses):
+        """cast_rays with everything in device memory: the two ray arrays and the keyword arguments t= / fluid= / index= / normal= /
+        thickness= are integer device addresses (e.g. torch's data_ptr()) on the world's device; an address left out or 0 is not
+        computed.  The results are complete when the call returns."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        p = self._ray_params(radius, tmax, clip)
+        out = self._ray_device_out(addresses)
+        o = C.cast(C.c_void_p(int(origins_address)), C.POINTER(C.c_float))
+        d = C.cast(C.c_void_p(int(directions_address)), C.POINTER(C.c_float))
+        L.check(self._L.salva_hip_cast_rays(self._h, self._field_mask(fluids), C.byref(p), int(nrays), o, d,
+                                            L.RAY_RAYS_ON_DEVICE | L.RAY_OUT_ON_DEVICE, C.byref(out)))
+
+    def cast_camera_device(self, camera, radius=None, tmax=np.inf, fluids=None, clip=None, **addresses):
+        """cast_camera into device memory: the keyword arguments are integer device addresses, as in cast_rays_device."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        c = self._ray_camera(camera)
+        p = self._ray_params(radius, tmax, clip)
+        out = self._ray_device_out(addresses)
+        L.check(self._L.salva_hip_cast_rays_camera(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), L.RAY_OUT_ON_DEVICE, C.byref(out)))
+
+    def count_ray_candidates(self, origins=None, directions=None, camera=None, radius=None, tmax=np.inf, fluids=None, clip=None, thickness_walk=False):
+        """How many particles the walk of each ray put to the exact cast (salva_hip_count_ray_candidates): of the first-hit walk, or with
+        thickness_walk=True of the walk that sums the thickness.  The rays are `camera`'s pixels, or the list's.  A measuring aid."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        p = self._ray_params(radius, tmax, clip)
+        if camera is not None:
+            c = self._ray_camera(camera)
+            tested = np.zeros(int(c.width) * int(c.height), np.uint32)
+            L.check(self._L.salva_hip_count_ray_candidates(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), 0, None, None, 0,
+                                                           int(bool(thickness_walk)), tested.ctypes.data_as(C.POINTER(C.c_uint32))))
+            return tested.reshape(int(c.height), int(c.width))
+        o = np.ascontiguousarray(origins, F32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, F32).reshape(-1, 3)
+        tested = np.zeros(max(len(o), 1), np.uint32)
+        L.check(self._L.salva_hip_count_ray_candidates(self._h, self._field_mask(fluids), C.byref(p), None, len(o), _fp(o), _fp(d), 0,
+                                                       int(bool(thickness_walk)), tested.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return tested[:len(o)]
+
+    def count_ray_candidates_device(self, tested_address: int, origins_address: int = 0, directions_address: int = 0, nrays: int = 0, camera=None,
+                                    radius=None, tmax=np.inf, fluids=None, clip=None, thickness_walk=False):
+        """count_ray_candidates with the rays (unless a camera makes them) and `tested` in device memory, as integer addresses."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        p = self._ray_params(radius, tmax, clip)
+        t = C.cast(C.c_void_p(int(tested_address)), C.POINTER(C.c_uint32))
+        if camera is not None:
+            c = self._ray_camera(camera)
+            L.check(self._L.salva_hip_count_ray_candidates(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), 0, None, None,
+                                                           L.RAY_OUT_ON_DEVICE, int(bool(thickness_walk)), t))
+            return
+        o = C.cast(C.c_void_p(int(origins_address)), C.POINTER(C.c_float))
+        d = C.cast(C.c_void_p(int(directions_address)), C.POINTER(C.c_float))
+        L.check(self._L.salva_hip_count_ray_candidates(self._h, self._field_mask(fluids), C.byref(p), None, int(nrays), o, d,
+                                                       L.RAY_RAYS_ON_DEVICE | L.RAY_OUT_ON_DEVICE, int(bool(thickness_walk)), t))
+
     def surface_lattice(self, spacing, margin=None, fluids=None):
         """(origin, dims) of a lattice at `spacing` that encloses the box of `fluids` (fluid_bounds) grown by `margin` (default h: the
         fields are zero on its faces, the surface closed).  The origin is snapped down to a multiple of the spacing - the f32 product
