@@ -80,6 +80,97 @@ impl Buffers {
     }
 }
 
+/// The parameters of the anisotropic kernels (`SalvaHipAnisotropy`, include/salva_hip.h "Anisotropic kernels"),
+/// lengths in units of h.  `Default` is `salva_hip_default_anisotropy`.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct Anisotropy {
+    /// how far a centre moves towards the weighted mean of its neighbourhood: [0, 1]
+    pub lambda: Real,
+    /// the largest ratio of two eigenvalues: >= 1
+    pub k_r: Real,
+    pub k_s: Real,
+    /// the stretch of an isolated particle
+    pub k_n: Real,
+    /// a particle with at most this many neighbours is isolated
+    pub n_eps: u32,
+}
+
+impl Default for Anisotropy {
+    fn default() -> Self {
+        Self { lambda: 0.9, k_r: 4.0, k_s: 5.0 / 3.0, k_n: 0.5, n_eps: 25 }
+    }
+}
+
+impl Anisotropy {
+    pub(crate) fn raw(&self) -> ffi::SalvaHipAnisotropy {
+        let mut p: ffi::SalvaHipAnisotropy = unsafe { std::mem::zeroed() };
+        p.struct_size = ffi::SALVA_HIP_ANISOTROPY_BYTES as u32;
+        p.version = ffi::SALVA_HIP_ANISOTROPY_VERSION as u32;
+        p.lambda = self.lambda;
+        p.k_r = self.k_r;
+        p.k_s = self.k_s;
+        p.k_n = self.k_n;
+        p.n_eps = self.n_eps;
+        p
+    }
+}
+
+/// Per particle of the selected fluids, by slot and then by index: the smoothed centre, the metric G as (xx, xy, xz, yy, yz, zz) and
+/// the number of neighbours within 2h.
+#[derive(Clone, Debug, Default)]
+pub struct AnisotropyRows {
+    pub centres: Vec<Point3<Real>>,
+    pub metric: Vec<[Real; 6]>,
+    pub count: Vec<u32>,
+}
+
+pub(crate) fn compute_anisotropy(world: *mut ffi::SalvaHipWorld, fluid_mask: u32, params: &Anisotropy) -> Result<AnisotropyRows, Error> {
+    let p = params.raw();
+    let mut n = 0u64;
+    check(unsafe { ffi::salva_hip_compute_anisotropy(world, fluid_mask, &p, 0, std::ptr::null(), &mut n) })?;
+    let rows = n as usize;
+    let (mut centres, mut metric, mut count) = (vec![0.0 as Real; 3 * rows.max(1)], vec![0.0 as Real; 6 * rows.max(1)], vec![0u32; rows.max(1)]);
+    let out = ffi::SalvaHipAnisotropyOut { centres: centres.as_mut_ptr(), metric: metric.as_mut_ptr(), count: count.as_mut_ptr(), row_capacity: n };
+    check(unsafe { ffi::salva_hip_compute_anisotropy(world, fluid_mask, &p, 0, &out, &mut n) })?;
+    count.truncate(rows);
+    Ok(AnisotropyRows {
+        centres: centres.chunks_exact(3).take(rows).map(|c| Point3::new(c[0], c[1], c[2])).collect(),
+        metric: metric.chunks_exact(6).take(rows).map(|c| [c[0], c[1], c[2], c[3], c[4], c[5]]).collect(),
+        count,
+    })
+}
+
+/// The anisotropic fields are density, fraction and gradient: `want.velocity` and `want.count` must be false.
+fn anisotropic_out(bufs: &mut Buffers, want: FieldSet) -> ffi::SalvaHipAnisoFieldOut {
+    assert!(!want.velocity && !want.count, "the anisotropic fields are density, fraction and gradient");
+    let raw = bufs.raw();
+    ffi::SalvaHipAnisoFieldOut { density: raw.density, fraction: raw.fraction, gradient: raw.gradient }
+}
+
+pub(crate) fn evaluate_points_anisotropic(
+    world: *mut ffi::SalvaHipWorld, fluid_mask: u32, params: &Anisotropy, points: &[Point3<Real>], want: FieldSet,
+) -> Result<Fields, Error> {
+    let xyz: Vec<Real> = points.iter().flat_map(|p| [p.x, p.y, p.z]).collect();
+    let mut bufs = Buffers::new(points.len(), want);
+    let out = anisotropic_out(&mut bufs, want);
+    let p = params.raw();
+    check(unsafe { ffi::salva_hip_evaluate_fields_anisotropic(world, fluid_mask, &p, points.len() as u64, xyz.as_ptr(), 0, &out) })?;
+    Ok(bufs.finish(points.len()))
+}
+
+pub(crate) fn evaluate_lattice_anisotropic(
+    world: *mut ffi::SalvaHipWorld, fluid_mask: u32, params: &Anisotropy, origin: &Point3<Real>, spacing: Real, dims: [u32; 3], want: FieldSet,
+) -> Result<Fields, Error> {
+    let nodes = dims.iter().try_fold(1u64, |a, &d| a.checked_mul(d as u64)).filter(|&m| m <= 1u64 << 32);
+    let m = nodes.unwrap_or(0) as usize;
+    let mut bufs = Buffers::new(m, want);
+    let out = anisotropic_out(&mut bufs, want);
+    let o = [origin.x, origin.y, origin.z];
+    let p = params.raw();
+    check(unsafe { ffi::salva_hip_evaluate_fields_anisotropic_lattice(world, fluid_mask, &p, o.as_ptr(), spacing, dims.as_ptr(), 0, &out) })?;
+    Ok(bufs.finish(m))
+}
+
 /// `fluid_mask`: bit s selects the fluid in slot s.
 pub(crate) fn evaluate_points(world: *mut ffi::SalvaHipWorld, fluid_mask: u32, points: &[Point3<Real>], want: FieldSet) -> Result<Fields, Error> {
     let xyz: Vec<Real> = points.iter().flat_map(|p| [p.x, p.y, p.z]).collect();

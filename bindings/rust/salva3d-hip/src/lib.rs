@@ -19,6 +19,6 @@ pub mod sampling;
 pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};
 pub use region::Region;
-pub use field::{FieldSet, Fields};
+pub use field::{Anisotropy, AnisotropyRows, FieldSet, Fields};
 pub use surface::{SurfaceField, SurfaceMesh};
 pub use ray::{RayCamera, RayHits, RayOptions, RaySet};

@@ -564,6 +564,37 @@ impl LiquidWorld {
         self.upload()?;
         crate::surface::extract(self.raw, fluid_mask, field, iso, origin, spacing, dims, normals, velocities)
     }
+    /// The smoothed centres, metrics and neighbour counts of the anisotropic kernels for the particles of the selected fluids
+    /// (`salva_hip_compute_anisotropy`; field.rs).
+    pub fn anisotropy(&mut self, params: &crate::Anisotropy, fluid_mask: u32) -> Result<crate::AnisotropyRows, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::field::compute_anisotropy(self.raw, fluid_mask, params)
+    }
+    /// `evaluate_fields` with the anisotropic kernels: density, fraction and gradient (`salva_hip_evaluate_fields_anisotropic`).
+    pub fn evaluate_fields_anisotropic(&mut self, points: &[nalgebra::Point3<Real>], params: &crate::Anisotropy, fluid_mask: u32,
+                                       want: crate::FieldSet) -> Result<crate::Fields, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::field::evaluate_points_anisotropic(self.raw, fluid_mask, params, points, want)
+    }
+    /// `evaluate_lattice` with the anisotropic kernels (`salva_hip_evaluate_fields_anisotropic_lattice`).
+    pub fn evaluate_lattice_anisotropic(&mut self, origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], params: &crate::Anisotropy,
+                                        fluid_mask: u32, want: crate::FieldSet) -> Result<crate::Fields, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::field::evaluate_lattice_anisotropic(self.raw, fluid_mask, params, origin, spacing, dims, want)
+    }
+    /// `extract_surface` with the anisotropic kernels behind the node values and the normals
+    /// (`salva_hip_extract_surface_anisotropic`; surface.rs).
+    #[allow(clippy::too_many_arguments)]
+    pub fn extract_surface_anisotropic(&mut self, origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], params: &crate::Anisotropy,
+                                       iso: Real, field: crate::SurfaceField, fluid_mask: u32, normals: bool, velocities: bool)
+                                       -> Result<crate::SurfaceMesh, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::surface::extract_anisotropic(self.raw, fluid_mask, params, field, iso, origin, spacing, dims, normals, velocities)
+    }
     /// The same for a lattice of values of the caller's (`salva_hip_extract_surface_from_values`).
     pub fn extract_surface_from_values(&mut self, values: &[Real], origin: &nalgebra::Point3<Real>, spacing: Real, dims: [u32; 3], iso: Real) -> Result<crate::SurfaceMesh, Error> {
         crate::surface::extract_from_values(self.raw, values, iso, origin, spacing, dims)

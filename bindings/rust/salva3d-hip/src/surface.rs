@@ -69,6 +69,23 @@ pub(crate) fn extract(
     })
 }
 
+/// The same with the anisotropic kernels behind the node values and the normals (`salva_hip_extract_surface_anisotropic`).
+#[allow(clippy::too_many_arguments)]
+pub(crate) fn extract_anisotropic(
+    world: *mut ffi::SalvaHipWorld, fluid_mask: u32, params: &crate::field::Anisotropy, field: SurfaceField, iso: Real, origin: &Point3<Real>,
+    spacing: Real, dims: [u32; 3], normals: bool, velocities: bool,
+) -> Result<SurfaceMesh, Error> {
+    let o = [origin.x, origin.y, origin.z];
+    let f = match field {
+        SurfaceField::Density => ffi::SALVA_HIP_SURFACE_DENSITY,
+        SurfaceField::Fraction => ffi::SALVA_HIP_SURFACE_FRACTION,
+    } as u32;
+    let p = params.raw();
+    fill(normals, velocities, |out, counts| unsafe {
+        ffi::salva_hip_extract_surface_anisotropic(world, fluid_mask, &p, f, iso, o.as_ptr(), spacing, dims.as_ptr(), 0, out, counts)
+    })
+}
+
 /// `values`: nx * ny * nz node values, z fastest.
 pub(crate) fn extract_from_values(
     world: *mut ffi::SalvaHipWorld, values: &[Real], iso: Real, origin: &Point3<Real>, spacing: Real, dims: [u32; 3],

@@ -1095,6 +1095,93 @@ int salva_hip_count_ray_candidates(SalvaHipWorld* world, uint32_t fluid_mask, co
                                    uint64_t nrays, const float* origins_xyz, const float* directions_xyz, uint32_t flags, uint32_t thickness_walk,
                                    uint32_t* tested);
 
+/* ---- Anisotropic kernels: the fields above sum spheres of radius h around the raw positions, and their iso-surface
+ * shows it - bumps where the particles sit, sheets that break into beads.  After Yu & Turk, "Reconstructing surfaces of particle-based
+ * fluids using anisotropic kernels" (ACM TOG 2013), every particle gets a smoothed centre and an ellipsoidal kernel, both from the
+ * weighted covariance of its neighbourhood of radius 2h.  All arithmetic is f32; the membership tests (|d|^2 <= (2h)^2 in 2., q <= 1
+ * in 4.) are evaluated as dist2_exact-style sums ((a a) + (b b)) + (c c) without FMA, and nothing else of their rounding is pinned.
+ * Lengths are in units of h, so the defaults do not depend on the scale of the scene.
+ *
+ * 1. Particles.  The rows of the fluids in `fluid_mask` as salva_hip_get_fluid would return them now (as for the fields above:
+ *    positions, volumes, m_j = volumes[j] * density0).  A particle with a non-finite position takes no part anywhere: it is nobody's
+ *    neighbour and contributes to no field.  Rows are ordered by ascending fluid slot, then by index within the fluid.
+ * 2. Moments, per finite particle i.  N_i = the finite selected particles j, i included, with |d_j|^2 <= (2h)^2, d_j = x_j - x_i.
+ *    w_j = 1 - (|d_j| / 2h)^3.  S0 = sum w_j, S1 = sum w_j d_j, S2 = sum w_j d_j d_j^T (six entries), m = S1 / S0,
+ *    C = S2 / S0 - m m^T, count n_i = |N_i| - 1, centre c_i = x_i + lambda m.  The sums run over the cells of the call's own table
+ *    (width 2h, cell = floor(x / 2h) per axis) in ascending order, x slowest and z fastest, and over ascending host index within a
+ *    cell: a second call gives the same bits, and so does any other entry point of this section.
+ * 3. Metric.  C = R diag(sigma) R^T with sigma_1 >= sigma_2 >= sigma_3.  If n_i > n_eps:
+ *      s_k = min(max(k_s * max(sigma_k, sigma_1 / k_r) / h^2, S_LO), S_HI),    otherwise s_k = k_n  (an isolated particle).
+ *    G_i = (1/h) R diag(1 / s_k) R^T, a symmetric matrix stored as its six entries xx, xy, xz, yy, yz, zz, and
+ *    det G_i = 1 / (h^3 s_1 s_2 s_3).  G is one scalar function applied to every eigenvalue of C: it is continuous where eigenvalues
+ *    coincide, and the contract pins G, never R.  S_HI = 2 bounds the reach of every kernel by 2h.
+ * 4. Fields at a place x, summed over the finite selected particles with q_j = |G_j (x - c_j)| <= 1.  P is the world's KernelDensity
+ *    and P' its KernelGradient's dW/dr, both evaluated with h = 1, with the reference's zero rules at small q (P' = 0 where
+ *    q^2 <= eps^2, and for the cubic spline where q <= 1e-5):
+ *      density  = sum m_j det G_j P(q_j)
+ *      fraction = sum V_j det G_j P(q_j)
+ *      gradient = sum m_j det G_j P'(q_j) G_j (G_j (x - c_j)) / q_j
+ *    in the order of 2. over the table built on the centres.  With G = I / h and lambda = 0 (n_eps = 2^32 - 1, k_n = 1) this is
+ *    salva_hip_evaluate_fields.  Every kernel and derivative vanishes at q = 1: the rounding of the membership test costs nothing.
+ * 5. Tables.  Cells are 2h wide.  The evaluating calls build theirs over the box of the query (the finite points, or the lattice) grown
+ *    by what can matter - a centre lies within 2h of its particle, reaches 2h, and is made from neighbours within 2h - so a stray
+ *    particle far away costs nothing and changes nothing; more than 2^27 cells is SALVA_HIP_E_CAPACITY: split the query.
+ *    salva_hip_compute_anisotropy builds its table over the box salva_hip_get_fluid_bounds returns, with the same limit.
+ * Parameters.  struct_size / version as for SalvaHipRegion; salva_hip_default_anisotropy fills lambda = 0.9, k_r = 4, k_s = 5/3,
+ * k_n = 0.5, n_eps = 25.  SALVA_HIP_E_INVALID: lambda outside [0, 1]; k_r < 1 or not finite; k_s not finite or <= 0; k_n outside
+ * [S_LO, S_HI]; a NaN anywhere; another struct_size / version; params == NULL.
+ *
+ * salva_hip_compute_anisotropy writes, per row of 1., centres (3 floats), metric (6 floats) and count; any of the three pointers may
+ * be NULL.  *nrows = the number of rows, written on SALVA_HIP_OK and on SALVA_HIP_E_CAPACITY for want of room.  out == NULL only
+ * counts; with out->row_capacity < *nrows nothing is written and the call returns SALVA_HIP_E_CAPACITY.  The row of a particle with a
+ * non-finite position is its position as it is, a zero metric and count 0.  Buffers are host memory, or device memory with
+ * SALVA_HIP_ANISOTROPY_OUT_ON_DEVICE (complete when the call returns).
+ * salva_hip_evaluate_fields_anisotropic / _lattice take the arguments of salva_hip_evaluate_fields / _lattice and `params`; points,
+ * node coordinates, output order, flags (SALVA_HIP_FIELD_*), edge cases (a non-finite point gets zeros, npoints == 0 does nothing)
+ * and refusals are theirs.  Every pointer of `out` is optional.
+ * salva_hip_extract_surface_anisotropic takes the arguments of salva_hip_extract_surface and `params`: the node values are the
+ * anisotropic lattice call's, bit for bit, into scratch; the contouring is the same code; normals[v] = -g / |g| with g the anisotropic
+ * `gradient` at vertex v; velocities[v] is salva_hip_evaluate_fields' `velocity` there (isotropic, as for salva_hip_extract_surface).
+ * Refusals of all five: those of the fields above (a decomposed world, a callback of a step, a mask that selects no existing
+ * fluid, an unknown flag) and of the surface.  The calls change nothing a step reads. */
+#define SALVA_HIP_ANISOTROPY_VERSION 1
+#define SALVA_HIP_ANISOTROPY_BYTES 64
+#define SALVA_HIP_ANISOTROPY_S_LO 0.25f
+#define SALVA_HIP_ANISOTROPY_S_HI 2.0f
+enum { SALVA_HIP_ANISOTROPY_OUT_ON_DEVICE = 1 }; /* every non-null pointer of SalvaHipAnisotropyOut is a device pointer */
+typedef struct SalvaHipAnisotropy {
+    uint32_t struct_size;   /* SALVA_HIP_ANISOTROPY_BYTES */
+    uint32_t version;       /* SALVA_HIP_ANISOTROPY_VERSION */
+    float lambda;           /* how far a centre moves towards the weighted mean of its neighbourhood: [0, 1] */
+    float k_r;              /* the largest ratio of two eigenvalues: >= 1 */
+    float k_s;              /* eigenvalues of C / h^2 to stretches: finite, > 0 */
+    float k_n;              /* the stretch of an isolated particle: [S_LO, S_HI] */
+    uint32_t n_eps;         /* a particle with at most this many neighbours is isolated */
+    uint32_t reserved[9];
+} SalvaHipAnisotropy;
+typedef struct SalvaHipAnisotropyOut { /* N rows; any pointer may be NULL */
+    float* centres;         /* 3N */
+    float* metric;          /* 6N  xx, xy, xz, yy, yz, zz of G */
+    uint32_t* count;        /* N   neighbours within 2h, the particle itself not counted */
+    uint64_t row_capacity;  /* in rows */
+} SalvaHipAnisotropyOut;
+typedef struct SalvaHipAnisoFieldOut { /* M places; any pointer may be NULL: that field is not computed and nothing is written */
+    float* density;         /* M */
+    float* fraction;        /* M */
+    float* gradient;        /* 3M */
+} SalvaHipAnisoFieldOut;
+void salva_hip_default_anisotropy(SalvaHipAnisotropy* params);
+int salva_hip_compute_anisotropy(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t flags,
+                                 const SalvaHipAnisotropyOut* out, uint64_t* nrows);
+int salva_hip_evaluate_fields_anisotropic(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint64_t npoints,
+                                          const float* points_xyz, uint32_t flags, const SalvaHipAnisoFieldOut* out);
+int salva_hip_evaluate_fields_anisotropic_lattice(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params,
+                                                  const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                                  const SalvaHipAnisoFieldOut* out);
+int salva_hip_extract_surface_anisotropic(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t field, float iso,
+                                          const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                          const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

@@ -529,6 +529,25 @@ struct SurfaceMesh {
     size_t num_triangles() const { return triangles.size() / 3; }
 };
 
+// The parameters of the anisotropic kernels (SalvaHipAnisotropy; salva_hip.h "Anisotropic kernels"), lengths in units of
+// h; the defaults are salva_hip_default_anisotropy's.  What LiquidWorld::anisotropy returns: per particle of the selected fluids (by
+// slot, then by index) the smoothed centre (3 floats), the metric G (6 floats: xx, xy, xz, yy, yz, zz) and the neighbours within 2h.
+struct Anisotropy {
+    Real lambda = 0.9f, k_r = 4.0f, k_s = 5.0f / 3.0f, k_n = 0.5f;
+    uint32_t n_eps = 25;
+    SalvaHipAnisotropy c_struct() const {
+        SalvaHipAnisotropy p{};
+        p.struct_size = SALVA_HIP_ANISOTROPY_BYTES; p.version = SALVA_HIP_ANISOTROPY_VERSION;
+        p.lambda = lambda; p.k_r = k_r; p.k_s = k_s; p.k_n = k_n; p.n_eps = n_eps;
+        return p;
+    }
+};
+struct AnisotropyRows {
+    std::vector<Real> centres, metric;
+    std::vector<uint32_t> count;
+    size_t num_rows() const { return count.size(); }
+};
+
 // What LiquidWorld::cast_rays / cast_camera return, one entry per ray (three floats per ray in `normal`); a miss has t = +inf and
 // fluid = index = 0xffffffff.  The vectors not asked for stay empty.
 struct RayHits {
@@ -1015,6 +1034,50 @@ class LiquidWorld {  // liquid_world.rs
             return salva_hip_extract_surface_from_values(w_, values.data(), iso, origin.data(), spacing, dims.data(), 0, out, counts);
         });
     }
+    // The same three with the anisotropic kernels (salva_hip_compute_anisotropy, salva_hip_evaluate_fields_anisotropic / _lattice,
+    // salva_hip_extract_surface_anisotropic).  The anisotropic fields are DENSITY, FRACTION and GRADIENT; the surface's
+    // normals follow the anisotropic gradient, its velocities are the isotropic evaluator's.
+    AnisotropyRows anisotropy(const Anisotropy& a = Anisotropy(), uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        const SalvaHipAnisotropy p = a.c_struct();
+        uint64_t n = 0;
+        check(salva_hip_compute_anisotropy(w_, fluid_mask, &p, 0, nullptr, &n));
+        AnisotropyRows rows;
+        const size_t room = n ? (size_t)n : 1;
+        rows.centres.assign(3 * room, 0); rows.metric.assign(6 * room, 0); rows.count.assign(room, 0);
+        const SalvaHipAnisotropyOut out{rows.centres.data(), rows.metric.data(), rows.count.data(), n};
+        check(salva_hip_compute_anisotropy(w_, fluid_mask, &p, 0, &out, &n));
+        rows.centres.resize(3 * (size_t)n); rows.metric.resize(6 * (size_t)n); rows.count.resize((size_t)n);
+        return rows;
+    }
+    Fields evaluate_fields(const std::vector<Vec3>& points, const Anisotropy& a, uint32_t what = FieldSet::DENSITY, uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        Fields f;
+        const SalvaHipAnisotropy p = a.c_struct();
+        const SalvaHipAnisoFieldOut out = aniso_field_out(f, points.size(), what);
+        check(salva_hip_evaluate_fields_anisotropic(w_, fluid_mask, &p, points.size(), points.empty() ? nullptr : points[0].data(), 0, &out));
+        return f;
+    }
+    Fields evaluate_lattice(const Vec3& origin, Real spacing, const std::array<uint32_t, 3>& dims, const Anisotropy& a,
+                            uint32_t what = FieldSet::DENSITY, uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        Fields f;
+        const uint64_t xy = (uint64_t)dims[0] * dims[1];
+        const bool fits = xy <= (1ull << 32) && xy * dims[2] <= (1ull << 32);  // (beyond: the library's refusal, nothing to allocate)
+        const SalvaHipAnisotropy p = a.c_struct();
+        const SalvaHipAnisoFieldOut out = aniso_field_out(f, fits ? (size_t)(xy * dims[2]) : 1, what);
+        check(salva_hip_evaluate_fields_anisotropic_lattice(w_, fluid_mask, &p, origin.data(), spacing, dims.data(), 0, &out));
+        return f;
+    }
+    SurfaceMesh extract_surface(const Vec3& origin, Real spacing, const std::array<uint32_t, 3>& dims, const Anisotropy& a, Real iso = 0.5f,
+                                uint32_t field = SALVA_HIP_SURFACE_FRACTION, bool normals = false, bool velocities = false,
+                                uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        const SalvaHipAnisotropy p = a.c_struct();
+        return surface_fill(normals, velocities, [&](const SalvaHipSurfaceOut* out, uint64_t* counts) {
+            return salva_hip_extract_surface_anisotropic(w_, fluid_mask, &p, field, iso, origin.data(), spacing, dims.data(), 0, out, counts);
+        });
+    }
     // Rays cast at the fluid's particles, each a sphere of `radius` (<= 0: the particle radius; at most h / 2), on the device
     // (salva_hip_cast_rays / _cast_rays_camera): the first hit of every ray - t in units of |d| (+inf: a miss), the
     // particle (fluid, index; 0xffffffff: a miss), with RaySet::NORMAL the sphere's unit normal there - and with RaySet::THICKNESS the
@@ -1178,6 +1241,12 @@ class LiquidWorld {  // liquid_world.rs
         if (what & FieldSet::GRADIENT) { f.gradient.assign(3 * room, 0); out.gradient = f.gradient.data(); f.gradient.resize(3 * m); }
         if (what & FieldSet::COUNT) { f.count.assign(room, 0); out.count = f.count.data(); f.count.resize(m); }
         return out;
+    }
+    static SalvaHipAnisoFieldOut aniso_field_out(Fields& f, size_t m, uint32_t what) {
+        if (what & ~(uint32_t)(FieldSet::DENSITY | FieldSet::FRACTION | FieldSet::GRADIENT))
+            throw Error(SALVA_HIP_E_INVALID, "the anisotropic fields are DENSITY, FRACTION and GRADIENT");
+        const SalvaHipFieldOut o = field_out(f, m, what);
+        return SalvaHipAnisoFieldOut{o.density, o.fraction, o.gradient};
     }
     uint32_t nsinks_ = 0;
     bool readback_ = true;

@@ -8,6 +8,7 @@ from . import coupling, dist, regions, sampling, scenes  # noqa: F401
 from .sampling import HostRayShape, shape_surface_ray_sample, shape_volume_ray_sample  # noqa: F401
 from .world import (  # noqa: F401
     Akinci2013SurfaceTension,
+    Anisotropy,
     ArtificialViscosity,
     Becker2009Elasticity,
     Boundary,
@@ -31,7 +32,7 @@ from .world import (  # noqa: F401
 )
 
 __all__ = [
-    "Akinci2013SurfaceTension", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "DeviceForce", "Fluid", "He2014SurfaceTension", "IISPHSolver",
+    "Akinci2013SurfaceTension", "Anisotropy", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "DeviceForce", "Fluid", "He2014SurfaceTension", "IISPHSolver",
     "InteractionGroups", "LiquidWorld", "NonPressureForce", "PluginForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "dist", "regions", "sampling", "scenes", "HostRayShape", "shape_surface_ray_sample", "shape_volume_ray_sample",
 ]
 

@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "salva_hip_evaluate_fields", "salva_hip_evaluate_fields_lattice",
     "salva_hip_extract_surface", "salva_hip_extract_surface_from_values", "salva_hip_get_fluid_bounds",
     "salva_hip_cast_rays", "salva_hip_cast_rays_camera", "salva_hip_count_ray_candidates",
+    "salva_hip_default_anisotropy", "salva_hip_compute_anisotropy", "salva_hip_evaluate_fields_anisotropic",
+    "salva_hip_evaluate_fields_anisotropic_lattice", "salva_hip_extract_surface_anisotropic",
 ]
 
 
@@ -203,6 +205,27 @@ class SurfaceOut(C.Structure):
     _fields_ = [("vertices", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("velocities", C.POINTER(C.c_float)),
                 ("triangles", C.POINTER(C.c_uint32)), ("vertex_capacity", C.c_uint64), ("triangle_capacity", C.c_uint64)]
 
+
+class AnisotropyParams(C.Structure):
+    """SalvaHipAnisotropy (include/salva_hip.h): the parameters of the anisotropic kernels."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("lam", C.c_float), ("k_r", C.c_float), ("k_s", C.c_float),
+                ("k_n", C.c_float), ("n_eps", C.c_uint32), ("reserved", C.c_uint32 * 9)]
+
+
+class AnisotropyOut(C.Structure):
+    """SalvaHipAnisotropyOut: where salva_hip_compute_anisotropy writes, and how many rows there is room for."""
+    _fields_ = [("centres", C.POINTER(C.c_float)), ("metric", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_uint32)),
+                ("row_capacity", C.c_uint64)]
+
+
+class AnisoFieldOut(C.Structure):
+    """SalvaHipAnisoFieldOut: where salva_hip_evaluate_fields_anisotropic / _lattice write; a null pointer is not computed."""
+    _fields_ = [("density", C.POINTER(C.c_float)), ("fraction", C.POINTER(C.c_float)), ("gradient", C.POINTER(C.c_float))]
+
+
+ANISOTROPY_BYTES, ANISOTROPY_VERSION = 64, 1  # SALVA_HIP_ANISOTROPY_BYTES / _VERSION
+ANISOTROPY_S_LO, ANISOTROPY_S_HI = 0.25, 2.0  # SALVA_HIP_ANISOTROPY_S_LO / _S_HI
+ANISOTROPY_OUT_ON_DEVICE = 1
 
 RAY_RAYS_ON_DEVICE, RAY_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_RAY_RAYS_ON_DEVICE / _OUT_ON_DEVICE
 RAY_VERSION, RAY_PARAMS_BYTES, RAY_CAMERA_BYTES = 1, 64, 64  # SALVA_HIP_RAY_VERSION / _PARAMS_BYTES / _CAMERA_BYTES
@@ -445,6 +468,15 @@ def lib():
         L.salva_hip_cast_rays.argtypes = [vp, u32, C.POINTER(RayParams), u64, fp, fp, u32, C.POINTER(RayOut)]
         L.salva_hip_cast_rays_camera.argtypes = [vp, u32, C.POINTER(RayParams), C.POINTER(RayCamera), u32, C.POINTER(RayOut)]
         L.salva_hip_count_ray_candidates.argtypes = [vp, u32, C.POINTER(RayParams), C.POINTER(RayCamera), u64, fp, fp, u32, u32, C.POINTER(u32)]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_compute_anisotropy"):
+        ap = C.POINTER(AnisotropyParams)
+        L.salva_hip_default_anisotropy.argtypes = [ap]
+        L.salva_hip_default_anisotropy.restype = None
+        L.salva_hip_compute_anisotropy.argtypes = [vp, u32, ap, u32, C.POINTER(AnisotropyOut), C.POINTER(u64)]
+        L.salva_hip_evaluate_fields_anisotropic.argtypes = [vp, u32, ap, u64, fp, u32, C.POINTER(AnisoFieldOut)]
+        L.salva_hip_evaluate_fields_anisotropic_lattice.argtypes = [vp, u32, ap, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(AnisoFieldOut)]
+        L.salva_hip_extract_surface_anisotropic.argtypes = [vp, u32, ap, u32, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut),
+                                                            C.POINTER(u64)]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

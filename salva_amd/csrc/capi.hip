@@ -834,6 +834,48 @@ int salva_hip_count_ray_candidates(SalvaHipWorld* world, uint32_t fluid_mask, co
     });
 }
 
+void salva_hip_default_anisotropy(SalvaHipAnisotropy* params) {
+    if (!params) return;
+    *params = SalvaHipAnisotropy{};
+    params->struct_size = SALVA_HIP_ANISOTROPY_BYTES;
+    params->version = SALVA_HIP_ANISOTROPY_VERSION;
+    params->lambda = 0.9f;
+    params->k_r = 4.0f;
+    params->k_s = 5.0f / 3.0f;
+    params->k_n = 0.5f;
+    params->n_eps = 25;
+}
+
+int salva_hip_compute_anisotropy(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t flags,
+                                 const SalvaHipAnisotropyOut* out, uint64_t* nrows) { WorldLock _lk(world);
+    return status_entry(world, {params, nrows}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.compute_anisotropy(fluid_mask, params, flags, out, nrows);
+    });
+}
+
+int salva_hip_evaluate_fields_anisotropic(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint64_t npoints,
+                                          const float* points_xyz, uint32_t flags, const SalvaHipAnisoFieldOut* out) { WorldLock _lk(world);
+    return status_entry(world, {params, out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.evaluate_fields_anisotropic(fluid_mask, params, npoints, points_xyz, flags, *out);
+    });
+}
+
+int salva_hip_evaluate_fields_anisotropic_lattice(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params,
+                                                  const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                                  const SalvaHipAnisoFieldOut* out) { WorldLock _lk(world);
+    return status_entry(world, {params, origin, dims, out}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.evaluate_fields_anisotropic_lattice(fluid_mask, params, origin, spacing, dims, flags, *out);
+    });
+}
+
+int salva_hip_extract_surface_anisotropic(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t field, float iso,
+                                          const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                          const SalvaHipSurfaceOut* out, uint64_t counts[2]) { WorldLock _lk(world);
+    return status_entry(world, {params, origin, dims, counts}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.extract_surface_anisotropic(fluid_mask, params, field, iso, origin, spacing, dims, flags, out, counts);
+    });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

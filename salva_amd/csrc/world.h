@@ -19,6 +19,7 @@
 #include "compound.h"
 #include "sink.h"
 #include "field.h"
+#include "anisotropy.h"
 #include "surface.h"
 #include "fluidcast.h"
 
@@ -148,6 +149,15 @@ class World {
     void extract_surface_from_values(const float* values, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                      const SalvaHipSurfaceOut* out, uint64_t counts[2]);
     void get_fluid_bounds(uint32_t fluid_mask, float lo[3], float hi[3], uint64_t* nfinite);
+    // ---- anisotropic kernels for the surface (world_anisotropy.hip, anisotropy.hip).  *nrows is written before
+    // SALVA_HIP_E_CAPACITY is thrown for want of room.
+    void compute_anisotropy(uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t flags, const SalvaHipAnisotropyOut* out, uint64_t* nrows);
+    void evaluate_fields_anisotropic(uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint64_t npoints, const float* points_xyz, uint32_t flags,
+                                     const SalvaHipAnisoFieldOut& out);
+    void evaluate_fields_anisotropic_lattice(uint32_t fluid_mask, const SalvaHipAnisotropy* params, const float origin[3], float spacing,
+                                             const uint32_t dims[3], uint32_t flags, const SalvaHipAnisoFieldOut& out);
+    void extract_surface_anisotropic(uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t field, float iso, const float origin[3], float spacing,
+                                     const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]);
     // ---- rays cast at the fluid's particles (world_cast.hip, fluidcast.hip)
     void cast_rays(uint32_t fluid_mask, const SalvaHipRayParams* params, uint64_t nrays, const float* origins_xyz, const float* directions_xyz,
                    uint32_t flags, const SalvaHipRayOut& out);
@@ -318,10 +328,30 @@ class World {
     } srf;
     SurfaceLattice surface_lattice(float iso, const float origin[3], float spacing, const uint32_t dims[3], const char* what) const;
     void surface_run(const float* d_values, float iso, const SurfaceLattice& g, uint32_t fluid_mask, bool on_device, const SalvaHipSurfaceOut* out,
-                     uint64_t counts[2], const char* what);
+                     uint64_t counts[2], const char* what, const AnisoParams* aniso = nullptr);
     FieldFluids field_begin(uint32_t fluid_mask, uint32_t flags, const char* what);
     FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g,
                                      DevBuf<uint32_t>* rows_out = nullptr);
+    FieldCandidates field_table(const FieldFluids& f, const float4* pos, float width, int grow, const float lo[3], const float hi[3], bool second,
+                                FieldGrid& g, DevBuf<uint32_t>* rows_out, const char* too_large);
+    FieldQuery field_points_query(uint64_t npoints, const float* points_xyz, uint32_t flags, float lo[3], float hi[3], const char* what);
+    FieldQuery field_lattice_query(const float origin[3], float spacing, const uint32_t dims[3], float lo[3], float hi[3], bool& box_empty,
+                                   const char* what);
+    // the anisotropic kernels: per host-order row the centre and the metric records of the last moments pass, the metric records of the
+    // sorted rows of the table on the centres, who each sorted row is, and the staged results of host buffers, grown on demand and kept
+    struct AnisoScratch {
+        DevBuf<float4> centre, m0, m1, g0, g1;
+        DevBuf<uint32_t> count, rows;
+        DevBuf<float> out;
+    } ani;
+    AnisoParams aniso_params(const SalvaHipAnisotropy* params, const char* what) const;
+    AnisoRows aniso_moments(const FieldFluids& f, const AnisoParams& prm, const float lo[3], const float hi[3], int grow, uint32_t ring);
+    void aniso_run(const FieldFluids& f, const AnisoParams& prm, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m,
+                   uint32_t flags, const SalvaHipAnisoFieldOut& out);
+    void evaluate_aniso_points(const FieldFluids& f, const AnisoParams& prm, uint64_t npoints, const float* points_xyz, uint32_t flags,
+                               const SalvaHipAnisoFieldOut& out, const char* what);
+    void evaluate_aniso_lattice(const FieldFluids& f, const AnisoParams& prm, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                const SalvaHipAnisoFieldOut& out, const char* what);
     // the ray casts: the host-order row of every sorted row of the table, staged rays and staged results, grown on demand and kept
     struct CastScratch {
         DevBuf<uint32_t> rows;

@@ -36,19 +36,25 @@ FieldFluids World::field_begin(uint32_t fluid_mask, uint32_t flags, const char* 
 // The evaluator's grid over [lo, hi] grown by h — one cell more on every side of the cells the box touches — and the selected
 // particles inside it, sorted by cell, then by host index (rows, when given: the host-order row of each, for the ray casts)
 FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g, DevBuf<uint32_t>* rows_out) {
+    return field_table(f, st_pos.p, sc.h, 1, lo, hi, second, g, rows_out, "field evaluation: the box of the query exceeds 2^27 cells of width h: split the query");
+}
+
+// The same table with its knobs out in the open: the rows of `pos` ((x, y, z, V) in host order: the staging positions, or the centres
+// of world_anisotropy.hip) in cells of `width`, over the cells [lo, hi] touches and `grow` more on every side
+FieldCandidates World::field_table(const FieldFluids& f, const float4* pos, float width, int grow, const float lo[3], const float hi[3], bool second,
+                                   FieldGrid& g, DevBuf<uint32_t>* rows_out, const char* too_large) {
     int clo[3], chi[3];
-    cell_range(lo, hi, sc.h, clo, chi);
+    cell_range(lo, hi, width, clo, chi);
     uint64_t ncells = 1;
     for (int a = 0; a < 3; ++a) {
-        const uint64_t d = (uint64_t)((int64_t)chi[a] - (int64_t)clo[a] + 3);
-        g.o[a] = clo[a] - 1;
+        const uint64_t d = (uint64_t)((int64_t)chi[a] - (int64_t)clo[a] + 1 + 2 * grow);
+        g.o[a] = clo[a] - grow;
         g.d[a] = (uint32_t)std::min<uint64_t>(d, 0xffffffffull);
         ncells = d > FIELD_MAX_CELLS || ncells * d > FIELD_MAX_CELLS ? FIELD_MAX_CELLS + 1 : ncells * d;
     }
-    if (ncells > FIELD_MAX_CELLS)
-        throw HipError(SALVA_HIP_E_CAPACITY, "field evaluation: the box of the query exceeds 2^27 cells of width h: split the query");
+    if (ncells > FIELD_MAX_CELLS) throw HipError(SALVA_HIP_E_CAPACITY, too_large);
     g.ncells = (uint32_t)ncells;
-    g.h = sc.h;
+    g.h = width;
     const size_t rows = n ? n : 1;
     fld.keys.ensure(rows, stream, false, 1.1f); fld.rank.ensure(rows, stream, false, 1.1f);
     fld.keys_sorted.ensure(rows, stream, false, 1.1f); fld.idx_tmp.ensure(rows, stream, false, 1.1f);
@@ -59,9 +65,9 @@ FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3],
     const size_t tb = scan_temp_bytes(g.ncells + 1u);
     fld.temp.ensure(tb ? tb : 1);
     SALVA_HIP_CHECK(hipMemsetAsync(fld.cells.p, 0, ((size_t)g.ncells + 1) * sizeof(uint32_t), stream));
-    launch_field_keys(st_pos.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, stream);
+    launch_field_keys(pos, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, stream);
     scan_u32(fld.temp.p, tb, fld.cells.p, fld.cells.p, g.ncells + 1u, stream);
-    launch_field_sort(st_pos.p, st_vel.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, fld.keys_sorted.p, fld.idx_tmp.p, fld.rec0.p,
+    launch_field_sort(pos, st_vel.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, fld.keys_sorted.p, fld.idx_tmp.p, fld.rec0.p,
                       second ? fld.rec1.p : nullptr, rows_out ? rows_out->p : nullptr, stream);
     return FieldCandidates{fld.cells.p, fld.rec0.p, second ? fld.rec1.p : nullptr};
 }
@@ -104,12 +110,12 @@ void World::field_run(const FieldFluids& f, const FieldQuery& q, const float lo[
         if (host[k]) download_f32(dev[k], width[k] * m, host[k]);
 }
 
-void World::evaluate_fields(uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags, const SalvaHipFieldOut& out) {
-    const FieldFluids f = field_begin(fluid_mask, flags, "salva_hip_evaluate_fields");
-    if (npoints == 0) return;
-    if (!points_xyz) throw HipError(SALVA_HIP_E_INVALID, "salva_hip_evaluate_fields: null points");
-    if (npoints > (1ull << 32)) throw HipError(SALVA_HIP_E_CAPACITY, "salva_hip_evaluate_fields: more than 2^32 points: split the query");
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+// npoints > 0 places of the caller's: where the kernels read them, and the box of the finite ones (lo > hi: none is finite)
+FieldQuery World::field_points_query(uint64_t npoints, const float* points_xyz, uint32_t flags, float lo[3], float hi[3], const char* what) {
+    const std::string w(what);
+    if (!points_xyz) throw HipError(SALVA_HIP_E_INVALID, w + ": null points");
+    if (npoints > (1ull << 32)) throw HipError(SALVA_HIP_E_CAPACITY, w + ": more than 2^32 points: split the query");
+    for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
     FieldQuery q{};
     q.npoints = npoints;
     if (flags & SALVA_HIP_FIELD_POINTS_ON_DEVICE) {
@@ -131,27 +137,34 @@ void World::evaluate_fields(uint32_t fluid_mask, uint64_t npoints, const float* 
             if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
             for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); }
         }
-        q.pts = stage_floats(points_xyz, 3 * npoints);  // (scratch_f: free again once the kernels below have run — every path waits)
+        q.pts = stage_floats(points_xyz, 3 * npoints);  // (scratch_f: free again once the kernels of the call have run — every path waits)
     }
+    return q;
+}
+
+void World::evaluate_fields(uint32_t fluid_mask, uint64_t npoints, const float* points_xyz, uint32_t flags, const SalvaHipFieldOut& out) {
+    const FieldFluids f = field_begin(fluid_mask, flags, "salva_hip_evaluate_fields");
+    if (npoints == 0) return;
+    float lo[3], hi[3];
+    const FieldQuery q = field_points_query(npoints, points_xyz, flags, lo, hi, "salva_hip_evaluate_fields");
     const bool box_empty = !(lo[0] <= hi[0]);
     field_run(f, q, lo, hi, box_empty, npoints, flags, out, false);
     if (!(flags & SALVA_HIP_FIELD_POINTS_ON_DEVICE)) SALVA_HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-void World::evaluate_fields_lattice(uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
-                                    const SalvaHipFieldOut& out) {
-    const FieldFluids f = field_begin(fluid_mask, flags, "salva_hip_evaluate_fields_lattice");
-    if (!(std::isfinite(spacing) && spacing > 0.0f)) throw HipError(SALVA_HIP_E_INVALID, "salva_hip_evaluate_fields_lattice: spacing must be finite and > 0");
-    if (!dims[0] || !dims[1] || !dims[2]) throw HipError(SALVA_HIP_E_INVALID, "salva_hip_evaluate_fields_lattice: every dimension must be at least 1");
+// the nodes of a lattice, their box, and whether no node is finite
+FieldQuery World::field_lattice_query(const float origin[3], float spacing, const uint32_t dims[3], float lo[3], float hi[3], bool& box_empty,
+                                      const char* what) {
+    const std::string w(what);
+    if (!(std::isfinite(spacing) && spacing > 0.0f)) throw HipError(SALVA_HIP_E_INVALID, w + ": spacing must be finite and > 0");
+    if (!dims[0] || !dims[1] || !dims[2]) throw HipError(SALVA_HIP_E_INVALID, w + ": every dimension must be at least 1");
     const uint64_t xy = (uint64_t)dims[0] * dims[1];
-    if (xy > (1ull << 32) || xy * dims[2] > (1ull << 32))
-        throw HipError(SALVA_HIP_E_CAPACITY, "salva_hip_evaluate_fields_lattice: more than 2^32 nodes: split the query");
+    if (xy > (1ull << 32) || xy * dims[2] > (1ull << 32)) throw HipError(SALVA_HIP_E_CAPACITY, w + ": more than 2^32 nodes: split the query");
     const uint64_t m = xy * dims[2];
     FieldQuery q{};
     q.npoints = m;
     q.spacing = spacing;
-    float lo[3], hi[3];
-    bool box_empty = false;
+    box_empty = false;
     for (int a = 0; a < 3; ++a) {
         q.origin[a] = origin[a]; q.dims[a] = dims[a];
         // the first and the last node of the axis, as the kernels compute them
@@ -161,7 +174,17 @@ void World::evaluate_fields_lattice(uint32_t fluid_mask, const float origin[3], 
     }
     if (!box_empty)
         for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(hi[a])) throw HipError(SALVA_HIP_E_CAPACITY, "salva_hip_evaluate_fields_lattice: the lattice leaves the range of f32: split the query");
+            if (!std::isfinite(hi[a])) throw HipError(SALVA_HIP_E_CAPACITY, w + ": the lattice leaves the range of f32: split the query");
+    return q;
+}
+
+void World::evaluate_fields_lattice(uint32_t fluid_mask, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
+                                    const SalvaHipFieldOut& out) {
+    const FieldFluids f = field_begin(fluid_mask, flags, "salva_hip_evaluate_fields_lattice");
+    float lo[3], hi[3];
+    bool box_empty = false;
+    const FieldQuery q = field_lattice_query(origin, spacing, dims, lo, hi, box_empty, "salva_hip_evaluate_fields_lattice");
+    const uint64_t m = q.npoints;
     const bool brick_arm = sw.field_arm == 2 || (sw.field_arm == 0 && FIELD_CROSSOVER > 0.0f && spacing <= FIELD_CROSSOVER * sc.h);
     field_run(f, q, lo, hi, box_empty, m, flags, out, brick_arm);
 }

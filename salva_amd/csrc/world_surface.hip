@@ -33,7 +33,7 @@ SurfaceLattice World::surface_lattice(float iso, const float origin[3], float sp
 
 // d_values: the n node values in device memory.  fluid_mask: whose gradient and velocity the vertices get (where `out` asks).
 void World::surface_run(const float* d_values, float iso, const SurfaceLattice& g, uint32_t fluid_mask, bool on_device, const SalvaHipSurfaceOut* out,
-                        uint64_t counts[2], const char* what) {
+                        uint64_t counts[2], const char* what, const AnisoParams* aniso) {
     const std::string w(what);
     const size_t tb = surface_temp_bytes(g.n);
     srf.word.ensure((size_t)g.n + 1, stream, false, 1.1f);
@@ -71,9 +71,15 @@ void World::surface_run(const float* d_values, float iso, const SurfaceLattice& 
     if ((d_normals || d_velocities) && nv) {
         // the evaluator's own sums at the vertices, through its points path: the gradient lands where the normals go
         SalvaHipFieldOut fo{};
-        fo.gradient = d_normals;
+        fo.gradient = aniso ? nullptr : d_normals;
         fo.velocity = d_velocities;
-        evaluate_fields(fluid_mask, nv, d_vertices, SALVA_HIP_FIELD_POINTS_ON_DEVICE | SALVA_HIP_FIELD_OUT_ON_DEVICE, fo);
+        const uint32_t there = SALVA_HIP_FIELD_POINTS_ON_DEVICE | SALVA_HIP_FIELD_OUT_ON_DEVICE;
+        if (fo.gradient || fo.velocity) evaluate_fields(fluid_mask, nv, d_vertices, there, fo);
+        if (aniso && d_normals) {  // (the surface of the anisotropic fields: their gradient)
+            SalvaHipAnisoFieldOut ao{};
+            ao.gradient = d_normals;
+            evaluate_aniso_points(field_begin(fluid_mask, there, what), *aniso, nv, d_vertices, there, ao, what);
+        }
         if (d_normals) launch_surface_normals(d_normals, nv, stream);
     }
     if (on_device) {
@@ -103,6 +109,24 @@ void World::extract_surface(uint32_t fluid_mask, uint32_t field, float iso, cons
     (field == SALVA_HIP_SURFACE_DENSITY ? fo.density : fo.fraction) = srf.values.p;
     evaluate_fields_lattice(f.mask, origin, spacing, dims, SALVA_HIP_FIELD_OUT_ON_DEVICE, fo);
     surface_run(srf.values.p, iso, g, f.mask, (flags & SALVA_HIP_SURFACE_OUT_ON_DEVICE) != 0u, out, counts, what);
+}
+
+// the same with the anisotropic kernels of world_anisotropy.hip behind the node values and the normals
+void World::extract_surface_anisotropic(uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t field, float iso, const float origin[3],
+                                        float spacing, const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]) {
+    const char* what = "salva_hip_extract_surface_anisotropic";
+    counts[0] = counts[1] = 0;
+    if (flags & ~(uint32_t)SALVA_HIP_SURFACE_OUT_ON_DEVICE) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": unknown flag");
+    if (field != SALVA_HIP_SURFACE_DENSITY && field != SALVA_HIP_SURFACE_FRACTION) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": unknown field");
+    const FieldFluids f = field_begin(fluid_mask, 0, what);
+    const AnisoParams prm = aniso_params(params, what);
+    const SurfaceLattice g = surface_lattice(iso, origin, spacing, dims, what);
+    surface_check_out(out, true, what);
+    srf.values.ensure(g.n, stream, false, 1.1f);
+    SalvaHipAnisoFieldOut fo{};
+    (field == SALVA_HIP_SURFACE_DENSITY ? fo.density : fo.fraction) = srf.values.p;
+    evaluate_aniso_lattice(f, prm, origin, spacing, dims, SALVA_HIP_FIELD_OUT_ON_DEVICE, fo, what);
+    surface_run(srf.values.p, iso, g, f.mask, (flags & SALVA_HIP_SURFACE_OUT_ON_DEVICE) != 0u, out, counts, what, &prm);
 }
 
 void World::extract_surface_from_values(const float* values, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,

@@ -685,6 +685,23 @@ class Counters:
             L.check(self._world._L.salva_hip_enable_counters(self._world._h, 0))
 
 
+@dataclass
+class Anisotropy:
+    """SalvaHipAnisotropy (include/salva_hip.h "Anisotropic kernels"): the parameters of Yu & Turk's anisotropic kernels,
+    lengths in units of h.  The defaults are salva_hip_default_anisotropy's."""
+    lam: float = 0.9      # lambda: how far a centre moves towards the weighted mean of its neighbourhood, [0, 1]
+    k_r: float = 4.0      # the largest ratio of two eigenvalues
+    k_s: float = 5.0 / 3.0
+    k_n: float = 0.5      # the stretch of an isolated particle
+    n_eps: int = 25       # a particle with at most this many neighbours is isolated
+
+    def _struct(self):
+        p = L.AnisotropyParams()
+        p.struct_size, p.version = L.ANISOTROPY_BYTES, L.ANISOTROPY_VERSION
+        p.lam, p.k_r, p.k_s, p.k_n, p.n_eps = float(self.lam), float(self.k_r), float(self.k_s), float(self.k_n), int(self.n_eps)
+        return p
+
+
 class _ObjectSet:
     """FluidSet / BoundarySet: dense slots with swap-remove (object/contiguous_arena.rs:12-135)."""
 
@@ -1665,19 +1682,39 @@ class LiquidWorld:
                 setattr(out, name, C.cast(C.c_void_p(int(addresses[name])), C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
         return out
 
-    def evaluate_fields(self, points, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False):
+    @staticmethod
+    def _aniso_host_out(m, want):
+        """the three outputs of the anisotropic evaluator; velocity and count belong to the isotropic one"""
+        if want["velocity"] or want["count"]:
+            raise ValueError("with anisotropy= the fields are density, fraction and gradient")
+        arrays, out = {}, L.AnisoFieldOut()
+        for name, width in (("density", 1), ("fraction", 1), ("gradient", 3)):
+            if want[name]:
+                arrays[name] = np.zeros(m * width, F32)
+                setattr(out, name, _fp(arrays[name]))
+        return arrays, out
+
+    def evaluate_fields(self, points, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False, anisotropy=None):
         """The SPH fields of `fluids` (None: all; Fluid objects or slot numbers) at `points` (m x 3), summed on the device over the
         particles as they are now: a dict of numpy arrays, `density` / `fraction` / `count` of length m, `velocity` / `gradient` m x 3,
-        for the fields asked for.  A point with a non-finite coordinate gets zeros."""
+        for the fields asked for.  A point with a non-finite coordinate gets zeros.  With `anisotropy` (an Anisotropy) the sums use
+        the anisotropic kernels: density, fraction and gradient only."""
         self.wait_download()
         self.sync_to_device(apply_removal=False)
         pts = np.ascontiguousarray(points, F32).reshape(-1, 3)
         m = len(pts)
-        arrays, out = self._field_host_out(m, dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count))
-        L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), m, _fp(pts), 0, C.byref(out)))
+        want = dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count)
+        if anisotropy is not None:
+            arrays, out = self._aniso_host_out(m, want)
+            p = anisotropy._struct()
+            L.check(self._L.salva_hip_evaluate_fields_anisotropic(self._h, self._field_mask(fluids), C.byref(p), m, _fp(pts), 0, C.byref(out)))
+        else:
+            arrays, out = self._field_host_out(m, want)
+            L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), m, _fp(pts), 0, C.byref(out)))
         return {k: (a.reshape(m, 3) if k in ("velocity", "gradient") else a) for k, a in arrays.items()}
 
-    def evaluate_lattice(self, origin, spacing, dims, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False):
+    def evaluate_lattice(self, origin, spacing, dims, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False,
+                         anisotropy=None):
         """The same at the nodes origin + i * spacing of a lattice of dims = (nx, ny, nz) nodes: arrays shaped (nx, ny, nz) and
         (nx, ny, nz, 3)."""
         self.wait_download()
@@ -1688,10 +1725,36 @@ class LiquidWorld:
         m = nx * ny * nz
         if m > 1 << 32:  # (the library's refusal, before numpy tries to allocate the arrays)
             raise L.SalvaHipError(L.E_CAPACITY, "salva_hip_evaluate_fields_lattice: more than 2^32 nodes: split the query")
-        arrays, out = self._field_host_out(m, dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count))
-        L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), d.ctypes.data_as(C.POINTER(C.c_uint32)), 0,
-                                                          C.byref(out)))
+        want = dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count)
+        dp = d.ctypes.data_as(C.POINTER(C.c_uint32))
+        if anisotropy is not None:
+            arrays, out = self._aniso_host_out(m, want)
+            p = anisotropy._struct()
+            L.check(self._L.salva_hip_evaluate_fields_anisotropic_lattice(self._h, self._field_mask(fluids), C.byref(p), _fp(o), float(spacing), dp, 0,
+                                                                          C.byref(out)))
+        else:
+            arrays, out = self._field_host_out(m, want)
+            L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), dp, 0, C.byref(out)))
         return {k: (a.reshape(nx, ny, nz, 3) if k in ("velocity", "gradient") else a.reshape(nx, ny, nz)) for k, a in arrays.items()}
+
+    def anisotropy(self, params=None, fluids=None):
+        """The smoothed centres (N x 3), metrics (N x 6: xx, xy, xz, yy, yz, zz of G) and neighbour counts (N) of the anisotropic
+        kernels (include/salva_hip.h "Anisotropic kernels") for the particles of `fluids` (None: all) as they are now, rows by fluid
+        slot, then by index: a dict of numpy arrays `centres`, `metric`, `count`."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        p = (params or Anisotropy())._struct()
+        mask, nrows = self._field_mask(fluids), C.c_uint64(0)
+        L.check(self._L.salva_hip_compute_anisotropy(self._h, mask, C.byref(p), 0, None, C.byref(nrows)))
+        n = int(nrows.value)
+        got = {"centres": np.zeros((n, 3), F32), "metric": np.zeros((n, 6), F32), "count": np.zeros(n, np.uint32)}
+        room = {k: (a if a.size else np.zeros(6, a.dtype)) for k, a in got.items()}
+        out = L.AnisotropyOut()
+        out.centres, out.metric = _fp(room["centres"]), _fp(room["metric"])
+        out.count = room["count"].ctypes.data_as(C.POINTER(C.c_uint32))
+        out.row_capacity = n
+        L.check(self._L.salva_hip_compute_anisotropy(self._h, mask, C.byref(p), 0, C.byref(out), C.byref(nrows)))
+        return got
 
     def evaluate_fields_device(self, points_address: int, npoints: int, fluids=None, **addresses):
         """evaluate_fields with everything in device memory: `points_address` and the keyword arguments density= / fraction= /
@@ -1704,15 +1767,44 @@ class LiquidWorld:
         L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), int(npoints), pts,
                                                   L.FIELD_POINTS_ON_DEVICE | L.FIELD_OUT_ON_DEVICE, C.byref(out)))
 
-    def evaluate_lattice_device(self, origin, spacing, dims, fluids=None, **addresses):
-        """evaluate_lattice into device memory: the keyword arguments are integer device addresses, as in evaluate_fields_device."""
+    def evaluate_lattice_device(self, origin, spacing, dims, fluids=None, anisotropy=None, **addresses):
+        """evaluate_lattice into device memory: the keyword arguments are integer device addresses, as in evaluate_fields_device.
+        With `anisotropy`: density=, fraction= and gradient= only."""
         self.wait_download()
         self.sync_to_device(apply_removal=False)
         o = np.ascontiguousarray(origin, F32).reshape(3)
         d = np.ascontiguousarray(dims, np.uint32).reshape(3)
+        dp = d.ctypes.data_as(C.POINTER(C.c_uint32))
+        if anisotropy is not None:
+            if set(addresses) - {"density", "fraction", "gradient"}:
+                raise ValueError("with anisotropy= the fields are density, fraction and gradient")
+            out, p = L.AnisoFieldOut(), anisotropy._struct()
+            for name, address in addresses.items():
+                if address:
+                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_float)))
+            L.check(self._L.salva_hip_evaluate_fields_anisotropic_lattice(self._h, self._field_mask(fluids), C.byref(p), _fp(o), float(spacing), dp,
+                                                                          L.FIELD_OUT_ON_DEVICE, C.byref(out)))
+            return
         out = self._field_device_out(addresses)
-        L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), d.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                          L.FIELD_OUT_ON_DEVICE, C.byref(out)))
+        L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), dp, L.FIELD_OUT_ON_DEVICE, C.byref(out)))
+
+    def anisotropy_device(self, params=None, fluids=None, centres=0, metric=0, count=0, row_capacity=0):
+        """anisotropy() into device memory: `centres`, `metric`, `count` are integer device addresses of buffers with room for
+        `row_capacity` rows (3, 6 and 1 words per row); one left out or 0 is not written.  Without any the call only counts.  Returns
+        the number of rows."""
+        self.wait_download()
+        self.sync_to_device(apply_removal=False)
+        p = (params or Anisotropy())._struct()
+        nrows, out = C.c_uint64(0), None
+        if centres or metric or count:
+            out = L.AnisotropyOut()
+            for name, address in (("centres", centres), ("metric", metric), ("count", count)):
+                if address:
+                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
+            out.row_capacity = int(row_capacity)
+        L.check(self._L.salva_hip_compute_anisotropy(self._h, self._field_mask(fluids), C.byref(p), L.ANISOTROPY_OUT_ON_DEVICE,
+                                                     C.byref(out) if out is not None else None, C.byref(nrows)))
+        return int(nrows.value)
 
     # ---- the iso-surface of a field as a triangle mesh (include/salva_hip.h salva_hip_extract_surface; DESIGN.md §21)
     _SURFACE_FIELDS = {"density": L.SURFACE_DENSITY, "fraction": L.SURFACE_FRACTION}
@@ -1743,14 +1835,19 @@ class LiquidWorld:
         assert (int(counts[0]), int(counts[1])) == (nv, nt)
         return mesh
 
-    def extract_surface(self, origin, spacing, dims, iso=0.5, field="fraction", fluids=None, normals=False, velocities=False):
+    def extract_surface(self, origin, spacing, dims, iso=0.5, field="fraction", fluids=None, normals=False, velocities=False, anisotropy=None):
         """The surface `field` = iso ("fraction" or "density") of `fluids` (None: all) on the lattice of dims = (nx, ny, nz) nodes at
         origin + i * spacing, extracted on the device as an indexed triangle mesh: a dict of numpy arrays, `vertices` (nv, 3) float32
-        and `triangles` (nt, 3) uint32, with `normals` (unit, towards lower values) and `velocities` (nv, 3) where asked for."""
+        and `triangles` (nt, 3) uint32, with `normals` (unit, towards lower values) and `velocities` (nv, 3) where asked for.  With
+        `anisotropy` (an Anisotropy) the field and the normals are those of the anisotropic kernels."""
         self.wait_download()
         self.sync_to_device(apply_removal=False)
         o, s, _, dp = self._surface_lattice_args(origin, spacing, dims)
         mask, fld = self._field_mask(fluids), self._SURFACE_FIELDS[field]
+        if anisotropy is not None:
+            p = anisotropy._struct()
+            return self._surface_fill(lambda out, counts: self._L.salva_hip_extract_surface_anisotropic(self._h, mask, C.byref(p), fld, float(iso), _fp(o),
+                                                                                                        s, dp, 0, out, counts), normals, velocities)
         return self._surface_fill(lambda out, counts: self._L.salva_hip_extract_surface(self._h, mask, fld, float(iso), _fp(o), s, dp, 0, out, counts),
                                   normals, velocities)
 
@@ -1764,7 +1861,7 @@ class LiquidWorld:
                                   False, False)
 
     def extract_surface_device(self, origin, spacing, dims, iso=0.5, field="fraction", fluids=None, values=0, vertices=0, triangles=0, normals=0,
-                               velocities=0, vertex_capacity=0, triangle_capacity=0):
+                               velocities=0, vertex_capacity=0, triangle_capacity=0, anisotropy=None):
         """extract_surface into device memory: `vertices`, `triangles`, `normals`, `velocities` are integer device addresses (e.g.
         torch's data_ptr()) of buffers with room for `vertex_capacity` vertices and `triangle_capacity` triangles on the world's device;
         normals / velocities left out or 0 are not computed.  With `values` (the device address of nx * ny * nz floats) that lattice is
@@ -1786,8 +1883,13 @@ class LiquidWorld:
         else:
             self.wait_download()
             self.sync_to_device(apply_removal=False)
-            rc = self._L.salva_hip_extract_surface(self._h, self._field_mask(fluids), self._SURFACE_FIELDS[field], float(iso), _fp(o), s, dp,
-                                                   L.SURFACE_OUT_ON_DEVICE, ref, counts)
+            if anisotropy is not None:
+                p = anisotropy._struct()
+                rc = self._L.salva_hip_extract_surface_anisotropic(self._h, self._field_mask(fluids), C.byref(p), self._SURFACE_FIELDS[field], float(iso),
+                                                                   _fp(o), s, dp, L.SURFACE_OUT_ON_DEVICE, ref, counts)
+            else:
+                rc = self._L.salva_hip_extract_surface(self._h, self._field_mask(fluids), self._SURFACE_FIELDS[field], float(iso), _fp(o), s, dp,
+                                                       L.SURFACE_OUT_ON_DEVICE, ref, counts)
         try:
             L.check(rc)
         except L.SalvaHipError as e:
