@@ -1,6 +1,11 @@
 """A numpy reading of Becker2009Elasticity (solver/elasticity/becker2009_elasticity.rs), written from the reference's semantics:
 float64 inside, f32 epsilon and 20 iterations in the rotation extraction, vectorised over particles (CSR + einsum / bincount).
 
+`rotation_from_matrix_eps`, `rotations_and_stresses` and `accelerations` take a `dtype`.  With np.float32 every array they touch is
+f32, so every sum, product, division, square root, sine and cosine rounds to f32 (numpy never widens an f32 ufunc; Python scalars
+are weak under NEP 50, which numpy >= 2 implements); the neighbour sums add contact by contact in row order.  The distance between
+that replay and the float64 reading is the noise floor the device is held to (tests/test_elasticity_reading_cpu.py).
+
 `ElasticityReading(E, nu, nonlinear)` keeps the force's state (positions0, contacts0, volumes0, rotations, ...) like the reference
 and has the `solve(...)` of a NonPressureForce, so it runs as a host force of a LiquidWorld (SALVA_HIP_FORCE_CUSTOM) or of the CPU
 checker.  Test infrastructure only."""
@@ -10,9 +15,9 @@ EPS32 = float(np.finfo(np.float32).eps)
 CUBIC, POLY6, SPIKY, VISCOSITY = 0, 1, 2, 3
 
 
-def kernel_w(r, h, kind=CUBIC):
+def kernel_w(r, h, kind=CUBIC, dtype=np.float64):
     """KernelDensity::scalar_apply (kernel/*_kernel.rs, dim3)."""
-    r = np.asarray(r, np.float64)
+    r, h = np.asarray(r, dtype), float(h)
     if kind == CUBIC:
         q = r / h
         inner = 1.0 + (q * q * q - q * q) * 6.0
@@ -27,9 +32,9 @@ def kernel_w(r, h, kind=CUBIC):
     return np.where((r <= h) & (r > 0.0), v, 0.0)
 
 
-def kernel_dw(r, h, kind=CUBIC):
+def kernel_dw(r, h, kind=CUBIC, dtype=np.float64):
     """KernelGradient::scalar_apply_diff."""
-    r = np.asarray(r, np.float64)
+    r, h = np.asarray(r, dtype), float(h)
     if kind == CUBIC:
         q = r / h
         inner = (q * 3.0 - 2.0) * q * 6.0
@@ -45,11 +50,18 @@ def kernel_dw(r, h, kind=CUBIC):
     return np.where((r <= h) & (r > 0.0), v, 0.0)
 
 
-def gradient(d, h, kind=CUBIC):
+def norm(v, dtype=np.float64):
+    """|v| along the last axis as sqrt((x x + y y) + z z), every step in `dtype`."""
+    v = np.asarray(v, dtype)
+    return np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+
+
+def gradient(d, h, kind=CUBIC, dtype=np.float64):
     """Kernel::apply_diff1(v) (kernel.rs:18-24): (v / |v|) dW/dr, zero when |v| <= eps."""
-    r = np.linalg.norm(d, axis=-1)
+    d = np.asarray(d, dtype)
+    r = norm(d, dtype)
     with np.errstate(divide="ignore", invalid="ignore"):
-        f = np.where(r > EPS32, kernel_dw(r, h, kind) / r, 0.0)
+        f = np.where(r > EPS32, kernel_dw(r, h, kind, dtype) / r, dtype(0.0))
     return d * f[..., None]
 
 
@@ -94,10 +106,11 @@ def coefficients(E, nu):
     return d0, d1, d2
 
 
-def rotation_from_matrix_eps(A, R, eps=EPS32, max_iter=20):
+def rotation_from_matrix_eps(A, R, eps=EPS32, max_iter=20, dtype=np.float64):
     """Rotation3::from_matrix_eps (nalgebra; Mueller et al. 2016) for a stack of matrices, warm-started from R."""
-    A = np.asarray(A, np.float64)
-    R = np.array(R, np.float64)
+    A = np.asarray(A, dtype)
+    R = np.array(R, dtype)
+    eps = float(eps)
     active = np.ones(len(A), bool)
     for _ in range(max_iter):
         if not active.any():
@@ -105,17 +118,17 @@ def rotation_from_matrix_eps(A, R, eps=EPS32, max_iter=20):
         w = np.cross(R[:, :, 0], A[:, :, 0]) + np.cross(R[:, :, 1], A[:, :, 1]) + np.cross(R[:, :, 2], A[:, :, 2])
         den = np.einsum("nrc,nrc->n", R, A)
         w = w / (np.abs(den) + eps)[:, None]
-        ang = np.linalg.norm(w, axis=1)
+        ang = norm(w, dtype)
         active &= ang > eps
         if not active.any():
             break
         u = w[active] / ang[active, None]
         a = ang[active]
         s, c = np.sin(a), np.cos(a)
-        K = np.zeros((len(a), 3, 3))
+        K = np.zeros((len(a), 3, 3), dtype)
         K[:, 0, 1], K[:, 0, 2], K[:, 1, 2] = -u[:, 2], u[:, 1], -u[:, 0]
         K[:, 1, 0], K[:, 2, 0], K[:, 2, 1] = u[:, 2], -u[:, 1], u[:, 0]
-        Q = np.eye(3) * c[:, None, None] + s[:, None, None] * K + (1.0 - c)[:, None, None] * np.einsum("ni,nj->nij", u, u)
+        Q = np.eye(3, dtype=dtype) * c[:, None, None] + s[:, None, None] * K + (1.0 - c)[:, None, None] * np.einsum("ni,nj->nij", u, u)
         R[active] = np.einsum("nij,njk->nik", Q, R[active])
     return R
 
@@ -128,8 +141,12 @@ def sym_mul(s, v):
 
 
 def segsum(ci, vals, n):
-    """sum of per-contact rows into their particles."""
+    """sum of per-contact rows into their particles (f32 rows: added one contact after the other, in f32)."""
     flat = vals.reshape(len(vals), -1)
+    if vals.dtype == np.float32:
+        out = np.zeros((n, flat.shape[1]), np.float32)
+        np.add.at(out, ci, flat)
+        return out.reshape((n,) + vals.shape[1:])
     out = np.stack([np.bincount(ci, weights=flat[:, k], minlength=n) for k in range(flat.shape[1])], axis=1)
     return out.reshape((n,) + vals.shape[1:])
 
@@ -170,26 +187,28 @@ class ElasticityReading:
         self.off, self.j = rest_contacts(np.asarray(self.positions0, np.float32), h)
 
     # compute_rotations + compute_stresses (:115-262)
-    def rotations_and_stresses(self, h, positions, masses):
+    def rotations_and_stresses(self, h, positions, masses, dtype=np.float64):
         n = len(positions)
-        p = np.asarray(positions, np.float64)
-        m = np.asarray(masses, np.float64)
+        p = np.asarray(positions, dtype)
+        m = np.asarray(masses, dtype)
         ci, cj = rows(self.off), self.j
-        p0 = self.positions0
+        p0 = np.asarray(self.positions0, dtype)
+        v0 = np.asarray(self.volumes0, dtype)
         pji = p[cj] - p[ci]
         p0ji = p0[cj] - p0[ci]
         d0 = p0[ci] - p0[cj]
-        w = kernel_w(np.linalg.norm(d0, axis=1), h, self.kd) * m[cj]
+        w = kernel_w(norm(d0, dtype), h, self.kd, dtype) * m[cj]
         A = segsum(ci, np.einsum("ni,nj->nij", pji, p0ji * w[:, None]), n)
-        self.rotations = rotation_from_matrix_eps(A, self.rotations)
-        g = gradient(d0, h, self.kg)
+        self.A_pq = A
+        self.rotations = rotation_from_matrix_eps(A, self.rotations, dtype=dtype)
+        g = gradient(d0, h, self.kg, dtype)
         self._g = g
         u = np.einsum("nji,nj->ni", self.rotations[ci], pji) - p0ji
-        F = segsum(ci, np.einsum("ni,nj->nij", g * self.volumes0[cj][:, None], u), n)
+        F = segsum(ci, np.einsum("ni,nj->nij", g * v0[cj][:, None], u), n)
         k = 0.564  # quirk 3
-        C = np.array([[self.d0, self.d1, self.d1], [self.d1, self.d0, self.d1], [self.d1, self.d1, self.d0]])
+        C = np.array([[self.d0, self.d1, self.d1], [self.d1, self.d0, self.d1], [self.d1, self.d1, self.d0]], dtype)
         if self.nonlinear:
-            J = F + np.eye(3)
+            J = F + np.eye(3, dtype=dtype)
             S = np.einsum("nij,nkj->nik", J, J)
             diag = np.einsum("ij,nj->ni", C, np.stack([S[:, 0, 0] - 1, S[:, 1, 1] - 1, S[:, 2, 2] - 1], axis=1)) * k
             off = np.stack([S[:, 1, 0], S[:, 2, 0], S[:, 2, 1]], axis=1) * k * self.d2
@@ -199,11 +218,11 @@ class ElasticityReading:
         self.grad_tr = F
         self.stress = np.concatenate([diag, off], axis=1)
 
-    # the force loop of solve (:268-334)
-    def accelerations(self, volumes, density0):
+    # the force loop of solve (:268-334), on the rotations, stresses and gradients the object holds
+    def accelerations(self, volumes, density0, dtype=np.float64):
         n = len(self.volumes0)
         ci, cj = rows(self.off), self.j
-        g, v0, s, F, R = self._g, self.volumes0, self.stress, self.grad_tr, self.rotations
+        g, v0, s, F, R = (np.asarray(x, dtype) for x in (self._g, self.volumes0, self.stress, self.grad_tr, self.rotations))
         sd = sym_mul(s[ci], g * v0[cj][:, None])
         if self.nonlinear:
             sd = sd + np.einsum("nij,nj->ni", F[ci], sd)
@@ -213,7 +232,7 @@ class ElasticityReading:
             sd = sd + np.einsum("nij,nj->ni", F[cj], sd)
         f_ij = sd * -v0[cj][:, None]
         force = (np.einsum("nij,nj->ni", R[cj], f_ij) - np.einsum("nij,nj->ni", R[ci], f_ji)) * 0.5
-        return segsum(ci, force, n) / (np.asarray(volumes, np.float64) * density0)[:, None]
+        return segsum(ci, force, n) / (np.asarray(volumes, dtype) * float(density0))[:, None]
 
     def step(self, h, positions, volumes, density0):
         """One `solve`: returns the accelerations it adds."""
