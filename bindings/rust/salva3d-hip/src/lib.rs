@@ -9,6 +9,7 @@ pub mod dist;
 mod liquid_world;
 pub mod region;
 pub mod field;
+pub mod diffuse;
 pub mod surface;
 pub mod ray;
 #[cfg(feature = "rapier")]
@@ -20,5 +21,6 @@ pub use dist::{Comm, OwnedParticles};
 pub use liquid_world::{Becker2009Elasticity, Error, GpuPressureSolver, LiquidWorld};
 pub use region::Region;
 pub use field::{Anisotropy, AnisotropyRows, FieldSet, Fields};
+pub use diffuse::{Diffuse, DiffuseHandle, DiffuseParticles, DiffusePotentials};
 pub use surface::{SurfaceField, SurfaceMesh};
 pub use ray::{RayCamera, RayHits, RayOptions, RaySet};

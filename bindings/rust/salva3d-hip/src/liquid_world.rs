@@ -571,6 +571,41 @@ impl LiquidWorld {
         self.upload()?;
         crate::field::compute_anisotropy(self.raw, fluid_mask, params)
     }
+    /// What spray, foam and bubbles are made from, per particle of the selected fluids (`salva_hip_diffuse_potentials`; diffuse.rs,
+    /// DESIGN.md §24).
+    pub fn diffuse_potentials(&mut self, params: &crate::Diffuse, fluid_mask: u32) -> Result<crate::DiffusePotentials, Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::diffuse::potentials(self.raw, fluid_mask, params)
+    }
+    /// A set of diffuse particles in device memory with room for `capacity` of them (`salva_hip_create_diffuse`; diffuse.rs).
+    pub fn create_diffuse(&mut self, capacity: u64) -> Result<crate::DiffuseHandle, Error> {
+        crate::diffuse::create(self.raw, capacity)
+    }
+    /// Appends particles to a set (kind "new"): this is how a user seeds.
+    pub fn add_diffuse(&mut self, set: crate::DiffuseHandle, positions: &[nalgebra::Point3<Real>], velocities: &[nalgebra::Vector3<Real>],
+                       lifetimes: Option<&[Real]>) -> Result<(), Error> {
+        crate::diffuse::add(self.raw, set, positions, velocities, lifetimes)
+    }
+    /// Advect and age, remove, emit (`salva_hip_update_diffuse`): after a step of the world, with the same dt.
+    pub fn update_diffuse(&mut self, set: crate::DiffuseHandle, params: &crate::Diffuse, dt: Real, fluid_mask: u32) -> Result<(), Error> {
+        self.sync()?;
+        self.upload()?;
+        crate::diffuse::update(self.raw, set, fluid_mask, params, dt)
+    }
+    pub fn get_diffuse(&mut self, set: crate::DiffuseHandle) -> Result<crate::DiffuseParticles, Error> {
+        crate::diffuse::get(self.raw, set)
+    }
+    /// The particles of each kind, and emitted / dissolved / killed / dropped by the last update and in total.
+    pub fn diffuse_stats(&mut self, set: crate::DiffuseHandle) -> Result<crate::ffi::SalvaHipDiffuseStats, Error> {
+        crate::diffuse::stats(self.raw, set)
+    }
+    pub fn clear_diffuse(&mut self, set: crate::DiffuseHandle) -> Result<(), Error> {
+        crate::diffuse::clear(self.raw, set)
+    }
+    pub fn destroy_diffuse(&mut self, set: crate::DiffuseHandle) -> Result<(), Error> {
+        crate::diffuse::destroy(self.raw, set)
+    }
     /// `evaluate_fields` with the anisotropic kernels: density, fraction and gradient (`salva_hip_evaluate_fields_anisotropic`).
     pub fn evaluate_fields_anisotropic(&mut self, points: &[nalgebra::Point3<Real>], params: &crate::Anisotropy, fluid_mask: u32,
                                        want: crate::FieldSet) -> Result<crate::Fields, Error> {

@@ -1182,6 +1182,156 @@ int salva_hip_extract_surface_anisotropic(SalvaHipWorld* world, uint32_t fluid_m
                                           const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                           const SalvaHipSurfaceOut* out, uint64_t counts[2]);
 
+/* ---- Diffuse particles: spray, foam and bubbles after Ihmsen, Akinci, Akinci, Teschner, "Unified spray, foam and
+ * bubbles for particle-based fluids" (The Visual Computer 2012).  Whitewater is made where the fluid traps air, where wave crests break
+ * and where it moves fast; salva_hip_diffuse_potentials reads those three potentials out per particle, with the neighbour count and the
+ * surface normal they are made from, without downloading a particle.  Every operation below is f32, rounded once, never contracted into
+ * an FMA; `/` and sqrt are correctly rounded; dot(a, b) = ((ax bx) + (ay by)) + (az bz) and |a|^2 = dot(a, a).  The one exception is
+ * grad W, which is the field evaluator's (the world's KernelGradient, as salva_hip_evaluate_fields' `gradient` evaluates it).
+ *
+ * 1. Particles.  The rows of the fluids in `fluid_mask` as salva_hip_get_fluid would return them now: positions, velocities (without
+ *    the pending velocity changes), volumes V_j, m_j = V_j * density0 as one f32 product.  Rows are ordered by ascending fluid slot,
+ *    then by index within the fluid.  A particle with a non-finite position is nobody's neighbour; its row is all zeros.
+ * 2. Neighbours of i: the other finite selected particles j (another row: a particle at the same place is a neighbour) with
+ *    |x_ij|^2 <= h * h, x_ij = x_i - x_j per component.  The sums below run over the cells of the call's own table (width h,
+ *    cell = floor(x / h) per axis, over the box salva_hip_get_fluid_bounds returns; more than 2^27 cells is SALVA_HIP_E_CAPACITY) in
+ *    ascending order, x slowest and z fastest, and over ascending host index within a cell: a second call gives the same bits.
+ *    With r = sqrt(|x_ij|^2): W_d = 1 - r / h.
+ * 3. count = the number of neighbours.
+ * 4. trapped_air = sum_j t_j.  v_ij = v_i - v_j per component, s = sqrt(|v_ij|^2).  t_j = 0 when |v_ij|^2 = 0 or |x_ij|^2 = 0;
+ *    otherwise c = min(max((dot(v_ij, x_ij) / s) / r, -1), 1) and t_j = (s * (1 - c)) * W_d.
+ * 5. normal.  g_i = sum_j (V_j * G_j) * x_ij per component, G_j = (dW/dr) / r of the world's KernelGradient at r (0 where the
+ *    reference's gradient is 0: r <= eps, and r <= 1e-5 h for the cubic spline).  With |g| = sqrt(|g|^2):
+ *    normal = (-g_x / |g|, -g_y / |g|, -g_z / |g|) when |g| > 0 and h * |g| >= surface_min, otherwise the zero vector.  An interior
+ *    particle's g is the rounding noise of a sum that cancels, and its direction means nothing: that is what surface_min is for.
+ * 6. wave_crest.  kappa_i = sum_j (1 - min(dot(n_i, n_j), 1)) * W_d over the neighbours j with n_j != 0 and dot(x_ij, n_i) > 0 (the
+ *    neighbours behind the surface: x_ji . n_i < 0 - normalising x_ji would change no sign).  wave_crest = kappa_i when n_i != 0,
+ *    |v_i|^2 > 0 and dot(v_i, n_i) / sqrt(|v_i|^2) >= crest_cos; otherwise 0.
+ * 7. energy = (0.5 * m_i) * |v_i|^2.
+ * A velocity that is not finite is not caught, and what it does to the sums it enters is not pinned.
+ *
+ * salva_hip_diffuse_potentials writes, per row of 1., trapped_air, wave_crest, energy (1 float each), normal (3 floats) and count; any
+ * of the five pointers may be NULL: that output is not written, and the sums only it needs are not made.  *nrows = the number of rows,
+ * written on SALVA_HIP_OK and on SALVA_HIP_E_CAPACITY for want of room.  out == NULL only counts; with out->row_capacity < *nrows
+ * nothing is written and the call returns SALVA_HIP_E_CAPACITY.  Buffers are host memory, or device memory with
+ * SALVA_HIP_DIFFUSE_OUT_ON_DEVICE (complete when the call returns).  The call works before the first step and changes nothing a step
+ * reads.
+ *
+ * The diffuse set: diffuse particles that live on the device, made from the potentials, carried by the fluid and
+ * removed again.  A set is (x, v, lifetime, kind, id) per particle in a fixed order - the order of creation; removal is stable -
+ * with room for `capacity` particles; ids are a running u32 counter of the set.  kind: 0 spray, 1 foam, 2 bubble, 3 new (added or
+ * emitted, not yet advected).
+ *   salva_hip_create_diffuse / _destroy_diffuse: a set of the world (destroyed with it).  capacity 0 or above 2^31 - 1 is E_INVALID.
+ *   salva_hip_add_diffuse appends n particles (kind 3, the next ids) - this is how a user seeds.  lifetimes == NULL: life_hi of the
+ *     defaults.  More than the room left: SALVA_HIP_E_CAPACITY, nothing added.  Pointers are host memory, or device memory with
+ *     SALVA_HIP_DIFFUSE_IN_ON_DEVICE.
+ *   salva_hip_clear_diffuse empties the set; ids and totals run on.
+ *   salva_hip_get_diffuse: positions, velocities (3 floats), lifetime, kind, id per particle, any pointer NULL; *n and row_capacity as
+ *     for the potentials; SALVA_HIP_DIFFUSE_OUT_ON_DEVICE.
+ *   salva_hip_get_diffuse_stats: the particles of each kind now, and emitted / dissolved / killed / dropped by the last update and in total.
+ * salva_hip_update_diffuse(world, set, fluid_mask, params, dt) does three things in this order; it waits on the host for the fluids'
+ * box and for the counts it returns through the stats.
+ * a. Advect and age every particle.  N and v_f are, bit for bit, what salva_hip_evaluate_fields returns as `count` and `velocity` at
+ *    its position for the same mask.  With g = params->gravity, per component k:
+ *      N < n_spray (spray, kind 0):               v_k = v_k + (dt * g_k)
+ *      n_spray <= N <= n_bubble (foam, kind 1):   v_k = vf_k;  life = life - dt
+ *      N > n_bubble (bubble, kind 2):             v_k = (v_k - ((dt * k_b) * g_k)) + (k_d * (vf_k - v_k))
+ *    and then x_k = x_k + (dt * v_k) with the new v.
+ * b. Remove, stably.  A particle whose position is not finite, or that lies outside [kill_lo, kill_hi] on an axis when has_kill_box is
+ *    1, is killed; otherwise one with life <= 0 is dissolved.
+ * c. Emit.  The potentials of the fluid as they are now (the call above, same mask and params).  Per row i, in row order:
+ *      Phi(I, lo, hi) = (min(I, hi) - min(I, lo)) / (hi - lo)
+ *      rate = (Phi(energy) * ((k_ta * Phi(trapped_air)) + (k_wc * Phi(wave_crest)))) * dt
+ *      c_i = min(floor(rate + u(0)), max_per_particle) when rate + u(0) >= 1, |v_i|^2 > 0 and x_i is finite; otherwise 0.
+ *    An exclusive scan of c in row order places the new particles behind the old ones; what does not fit `capacity` is dropped from
+ *    the end and counted, and takes no id.  Random numbers are counter-based, integer-only and independent of launch geometry:
+ *      fmix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16        (u32, wrapping)
+ *      bits(d) = fmix(fmix(fmix(fmix(fmix(seed) + updates) + slot) + index) + d),   u(d) = (float)(bits(d) >> 8) * 2^-24
+ *    with `updates` the number of updates the set has had before this one, slot the fluid's slot, index the particle's index within
+ *    its fluid and d the draw.  fmix(0) = 0, fmix(1) = 0x688990c0 and bits(0) for seed = updates = slot = index = 0 is 0;
+ *    for seed 1, updates 2, slot 3, index 4: bits(5) = 0x509ba2de.
+ *    New particle k (0 <= k < c_i) of row i uses the draws D = 1 + 20 k ...: attempt t = 0..7 takes a = (2 * u(D + 2t)) - 1 and
+ *    b = (2 * u(D + 2t + 1)) - 1 and is accepted when (a * a) + (b * b) <= 1; after eight refusals a = b = 0.  cc = u(D + 16),
+ *    life = life_lo + (u(D + 17) * (life_hi - life_lo)).  With s = sqrt(|v_i|^2) and w = v_i / s per component, let m be the axis on which
+ *    |w_m| is smallest (the lowest such axis on a tie) and t the unit vector of that axis; cross(p, q) = ((py qz) - (pz qy),
+ *    (pz qx) - (px qz), (px qy) - (py qx)); c = cross(w, t), e1 = c / sqrt(|c|^2) per component, e2 = cross(w, e1).  Then
+ *      x_k = (x_ik + (R * ((a * e1_k) + (b * e2_k)))) + ((cc * dt) * v_ik),   v = v_i,   kind 3,   the next id
+ *    with R the particle radius of the world.  No trigonometry anywhere.
+ * The calls write nothing a step reads.
+ *
+ * Parameters.  struct_size / version as for SalvaHipAnisotropy.  The potentials read surface_min and crest_cos; every call validates
+ * the whole struct.  salva_hip_default_diffuse fills surface_min = 0.25, crest_cos = 0.6, trapped air in (5, 20), wave crest in (2, 8),
+ * energy in (5, 50) - Ihmsen's ranges -, k_ta = 4000, k_wc = 50000 - rates are per scene; these are of the order his scenes use -,
+ * max_per_particle = 16, n_spray = 6, n_bubble = 20 - his class limits -, k_b = 2, k_d = 0.8, lifetimes in [2, 5], seed = 0, no kill
+ * box and gravity = (0, -9.81, 0): give the gravity the world is stepped with.
+ * SALVA_HIP_E_INVALID: params, nrows, set, stats NULL; another struct_size / version; a NaN anywhere; surface_min < 0 or infinite;
+ * crest_cos outside [-1, 1]; a clamp range with lo < 0, an infinite end or without lo < hi; a rate that is negative or infinite;
+ * max_per_particle above 64; n_spray > n_bubble; k_b infinite; k_d outside [0, 1]; life_lo < 0, life_hi infinite or life_lo > life_hi;
+ * has_kill_box other than 0 or 1; with a kill box, kill_lo > kill_hi on an axis; an infinite gravity; an unknown flag; dt not finite
+ * or < 0; a set that does not exist or was destroyed; NULL positions or velocities with n > 0; and what the fields refuse: a
+ * decomposed world, a call from inside a force, device force or coupling callback, a mask that selects no existing fluid. */
+#define SALVA_HIP_DIFFUSE_VERSION 1
+#define SALVA_HIP_DIFFUSE_BYTES 128
+#define SALVA_HIP_DIFFUSE_STATS_BYTES 104
+#define SALVA_HIP_DIFFUSE_MAX_PER_PARTICLE 64
+enum {
+    SALVA_HIP_DIFFUSE_OUT_ON_DEVICE = 1, /* every non-null pointer of SalvaHipDiffusePotentialsOut / SalvaHipDiffuseOut is a device pointer */
+    SALVA_HIP_DIFFUSE_IN_ON_DEVICE = 2   /* positions, velocities and lifetimes of salva_hip_add_diffuse are device pointers */
+};
+enum { SALVA_HIP_DIFFUSE_SPRAY = 0, SALVA_HIP_DIFFUSE_FOAM = 1, SALVA_HIP_DIFFUSE_BUBBLE = 2, SALVA_HIP_DIFFUSE_NEW = 3 };
+typedef struct SalvaHipDiffuse {
+    uint32_t struct_size;   /* SALVA_HIP_DIFFUSE_BYTES */
+    uint32_t version;       /* SALVA_HIP_DIFFUSE_VERSION */
+    float surface_min;      /* a particle has a normal when h |g| reaches this: finite, >= 0 */
+    float crest_cos;        /* a crest moves along its normal at least this much: [-1, 1] */
+    float ta_lo, ta_hi;     /* the clamp range of trapped_air: 0 <= lo < hi, finite */
+    float wc_lo, wc_hi;     /* of wave_crest */
+    float en_lo, en_hi;     /* of energy */
+    float k_ta, k_wc;       /* particles per unit of time at full potential: finite, >= 0 */
+    uint32_t max_per_particle; /* <= SALVA_HIP_DIFFUSE_MAX_PER_PARTICLE */
+    uint32_t n_spray, n_bubble; /* spray below n_spray fluid neighbours, bubble above n_bubble: n_spray <= n_bubble */
+    float k_b, k_d;         /* buoyancy: finite; drag: [0, 1] */
+    float life_lo, life_hi; /* 0 <= lo <= hi, finite */
+    uint32_t seed;
+    uint32_t has_kill_box;  /* 1: a diffuse particle outside [kill_lo, kill_hi] is removed */
+    float kill_lo[3], kill_hi[3];
+    float gravity[3];       /* what spray falls by and bubbles rise against: finite */
+    uint32_t reserved[2];
+} SalvaHipDiffuse;
+typedef struct SalvaHipDiffusePotentialsOut { /* N rows; any pointer may be NULL */
+    float* trapped_air;     /* N */
+    float* wave_crest;      /* N */
+    float* energy;          /* N */
+    float* normal;          /* 3N */
+    uint32_t* count;        /* N   neighbours within h, the particle itself not counted */
+    uint64_t row_capacity;  /* in rows */
+} SalvaHipDiffusePotentialsOut;
+typedef struct SalvaHipDiffuseOut { /* N particles; any pointer may be NULL */
+    float* positions;       /* 3N */
+    float* velocities;      /* 3N */
+    float* lifetime;        /* N */
+    uint32_t* kind;         /* N   SALVA_HIP_DIFFUSE_SPRAY ... _NEW */
+    uint32_t* id;           /* N */
+    uint64_t row_capacity;  /* in particles */
+} SalvaHipDiffuseOut;
+typedef struct SalvaHipDiffuseStats {
+    uint64_t count;         /* particles in the set */
+    uint64_t kinds[4];      /* of each kind */
+    uint64_t emitted, dissolved, killed, dropped;                         /* by the last update */
+    uint64_t total_emitted, total_dissolved, total_killed, total_dropped; /* since the set was created */
+} SalvaHipDiffuseStats;
+void salva_hip_default_diffuse(SalvaHipDiffuse* params);
+int salva_hip_diffuse_potentials(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipDiffuse* params, uint32_t flags,
+                                 const SalvaHipDiffusePotentialsOut* out, uint64_t* nrows);
+int salva_hip_create_diffuse(SalvaHipWorld* world, uint64_t capacity, uint32_t* set);
+int salva_hip_destroy_diffuse(SalvaHipWorld* world, uint32_t set);
+int salva_hip_add_diffuse(SalvaHipWorld* world, uint32_t set, uint64_t n, const float* positions, const float* velocities, const float* lifetimes,
+                          uint32_t flags);
+int salva_hip_clear_diffuse(SalvaHipWorld* world, uint32_t set);
+int salva_hip_get_diffuse(SalvaHipWorld* world, uint32_t set, uint32_t flags, const SalvaHipDiffuseOut* out, uint64_t* n);
+int salva_hip_get_diffuse_stats(SalvaHipWorld* world, uint32_t set, SalvaHipDiffuseStats* stats);
+int salva_hip_update_diffuse(SalvaHipWorld* world, uint32_t set, uint32_t fluid_mask, const SalvaHipDiffuse* params, float dt);
+
 const char* salva_hip_last_error(void);
 const char* salva_hip_version(void);
 

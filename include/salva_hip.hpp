@@ -542,6 +542,42 @@ struct Anisotropy {
         return p;
     }
 };
+// The parameters of diffuse particles (SalvaHipDiffuse; salva_hip.h "Diffuse particles"); the defaults are
+// salva_hip_default_diffuse's.  What LiquidWorld::diffuse_potentials returns: per particle of the selected fluids (by slot, then by
+// index) trapped air, wave crest, kinetic energy, the surface normal (3 floats) and the neighbours within h.
+struct Diffuse {
+    Real surface_min = 0.25f, crest_cos = 0.6f;
+    Real ta_lo = 5.0f, ta_hi = 20.0f, wc_lo = 2.0f, wc_hi = 8.0f, en_lo = 5.0f, en_hi = 50.0f;
+    Real k_ta = 4000.0f, k_wc = 50000.0f;
+    uint32_t max_per_particle = 16, n_spray = 6, n_bubble = 20;
+    Real k_b = 2.0f, k_d = 0.8f, life_lo = 2.0f, life_hi = 5.0f;
+    uint32_t seed = 0;
+    bool has_kill_box = false;
+    Vec3 kill_lo{{0, 0, 0}}, kill_hi{{0, 0, 0}};
+    Vec3 gravity{{0.0f, -9.81f, 0.0f}};  // what the world is stepped with
+    SalvaHipDiffuse c_struct() const {
+        SalvaHipDiffuse p{};
+        p.struct_size = SALVA_HIP_DIFFUSE_BYTES; p.version = SALVA_HIP_DIFFUSE_VERSION;
+        p.surface_min = surface_min; p.crest_cos = crest_cos;
+        p.ta_lo = ta_lo; p.ta_hi = ta_hi; p.wc_lo = wc_lo; p.wc_hi = wc_hi; p.en_lo = en_lo; p.en_hi = en_hi;
+        p.k_ta = k_ta; p.k_wc = k_wc; p.max_per_particle = max_per_particle; p.n_spray = n_spray; p.n_bubble = n_bubble;
+        p.k_b = k_b; p.k_d = k_d; p.life_lo = life_lo; p.life_hi = life_hi; p.seed = seed;
+        p.has_kill_box = has_kill_box ? 1u : 0u;
+        for (int a = 0; a < 3; ++a) { p.kill_lo[a] = kill_lo[a]; p.kill_hi[a] = kill_hi[a]; p.gravity[a] = gravity[a]; }
+        return p;
+    }
+};
+struct DiffusePotentials {
+    std::vector<Real> trapped_air, wave_crest, energy, normal;
+    std::vector<uint32_t> count;
+};
+// A diffuse set of a LiquidWorld (salva_hip_create_diffuse), and what LiquidWorld::get_diffuse returns: the particles in the order of
+// creation, three floats per particle in positions and velocities.
+using DiffuseHandle = uint32_t;
+struct DiffuseParticles {
+    std::vector<Real> positions, velocities, lifetime;
+    std::vector<uint32_t> kind, id;
+};
 struct AnisotropyRows {
     std::vector<Real> centres, metric;
     std::vector<uint32_t> count;
@@ -1049,6 +1085,55 @@ class LiquidWorld {  // liquid_world.rs
         check(salva_hip_compute_anisotropy(w_, fluid_mask, &p, 0, &out, &n));
         rows.centres.resize(3 * (size_t)n); rows.metric.resize(6 * (size_t)n); rows.count.resize((size_t)n);
         return rows;
+    }
+    // The potentials of diffuse particles (salva_hip_diffuse_potentials)
+    DiffusePotentials diffuse_potentials(const Diffuse& d = Diffuse(), uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        const SalvaHipDiffuse p = d.c_struct();
+        uint64_t n = 0;
+        check(salva_hip_diffuse_potentials(w_, fluid_mask, &p, 0, nullptr, &n));
+        DiffusePotentials r;
+        const size_t room = n ? (size_t)n : 1;
+        r.trapped_air.assign(room, 0); r.wave_crest.assign(room, 0); r.energy.assign(room, 0); r.normal.assign(3 * room, 0); r.count.assign(room, 0);
+        const SalvaHipDiffusePotentialsOut out{r.trapped_air.data(), r.wave_crest.data(), r.energy.data(), r.normal.data(), r.count.data(), n};
+        check(salva_hip_diffuse_potentials(w_, fluid_mask, &p, 0, &out, &n));
+        r.trapped_air.resize((size_t)n); r.wave_crest.resize((size_t)n); r.energy.resize((size_t)n); r.normal.resize(3 * (size_t)n); r.count.resize((size_t)n);
+        return r;
+    }
+    // The diffuse sets (salva_hip_create_diffuse ... salva_hip_update_diffuse): update after a step of the world, with the same dt.
+    DiffuseHandle create_diffuse(uint64_t capacity) {
+        DiffuseHandle h = 0;
+        check(salva_hip_create_diffuse(w_, capacity, &h));
+        return h;
+    }
+    void destroy_diffuse(DiffuseHandle set) { check(salva_hip_destroy_diffuse(w_, set)); }
+    void clear_diffuse(DiffuseHandle set) { check(salva_hip_clear_diffuse(w_, set)); }
+    void add_diffuse(DiffuseHandle set, const std::vector<Vec3>& positions, const std::vector<Vec3>& velocities, const std::vector<Real>* lifetimes = nullptr) {
+        if (velocities.size() != positions.size() || (lifetimes && lifetimes->size() != positions.size()))
+            throw Error(SALVA_HIP_E_INVALID, "add_diffuse: one velocity (and lifetime) per position");
+        check(salva_hip_add_diffuse(w_, set, positions.size(), positions.empty() ? nullptr : positions[0].data(),
+                                    velocities.empty() ? nullptr : velocities[0].data(), lifetimes ? lifetimes->data() : nullptr, 0));
+    }
+    void update_diffuse(DiffuseHandle set, const Diffuse& d, Real dt, uint32_t fluid_mask = 0xffffffffu) {
+        upload_all();
+        const SalvaHipDiffuse p = d.c_struct();
+        check(salva_hip_update_diffuse(w_, set, fluid_mask, &p, dt));
+    }
+    DiffuseParticles get_diffuse(DiffuseHandle set) {
+        uint64_t n = 0;
+        check(salva_hip_get_diffuse(w_, set, 0, nullptr, &n));
+        DiffuseParticles r;
+        const size_t room = n ? (size_t)n : 1;
+        r.positions.assign(3 * room, 0); r.velocities.assign(3 * room, 0); r.lifetime.assign(room, 0); r.kind.assign(room, 0); r.id.assign(room, 0);
+        const SalvaHipDiffuseOut out{r.positions.data(), r.velocities.data(), r.lifetime.data(), r.kind.data(), r.id.data(), n};
+        check(salva_hip_get_diffuse(w_, set, 0, &out, &n));
+        r.positions.resize(3 * (size_t)n); r.velocities.resize(3 * (size_t)n); r.lifetime.resize((size_t)n); r.kind.resize((size_t)n); r.id.resize((size_t)n);
+        return r;
+    }
+    SalvaHipDiffuseStats diffuse_stats(DiffuseHandle set) {
+        SalvaHipDiffuseStats st{};
+        check(salva_hip_get_diffuse_stats(w_, set, &st));
+        return st;
     }
     Fields evaluate_fields(const std::vector<Vec3>& points, const Anisotropy& a, uint32_t what = FieldSet::DENSITY, uint32_t fluid_mask = 0xffffffffu) {
         upload_all();

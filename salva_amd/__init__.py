@@ -4,7 +4,8 @@ The product is `salva_amd/csrc/libsalva_hip.so` (C ABI in include/salva_hip.h); 
 the reference's host API used by the tests and the benchmark.  Importing the API objects does not load the
 library; creating a `LiquidWorld` does, and fails loudly when it is missing or no HIP device is usable.
 """
-from . import coupling, dist, regions, sampling, scenes  # noqa: F401
+from . import coupling, diffuse, dist, regions, sampling, scenes  # noqa: F401
+from .diffuse import Diffuse, DiffuseSet  # noqa: F401
 from .sampling import HostRayShape, shape_surface_ray_sample, shape_volume_ray_sample  # noqa: F401
 from .world import (  # noqa: F401
     Akinci2013SurfaceTension,
@@ -32,8 +33,8 @@ from .world import (  # noqa: F401
 )
 
 __all__ = [
-    "Akinci2013SurfaceTension", "Anisotropy", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "DeviceForce", "Fluid", "He2014SurfaceTension", "IISPHSolver",
-    "InteractionGroups", "LiquidWorld", "NonPressureForce", "PluginForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "dist", "regions", "sampling", "scenes", "HostRayShape", "shape_surface_ray_sample", "shape_volume_ray_sample",
+    "Akinci2013SurfaceTension", "Anisotropy", "ArtificialViscosity", "Becker2009Elasticity", "Boundary", "Counters", "CubicSplineKernel", "DFSPHSolver", "DFSPHViscosity", "DeviceForce", "Diffuse", "DiffuseSet", "Fluid", "He2014SurfaceTension", "IISPHSolver",
+    "InteractionGroups", "LiquidWorld", "NonPressureForce", "PluginForce", "Poly6Kernel", "SpikyKernel", "ViscosityKernel", "WCSPHSurfaceTension", "XSPHViscosity", "coupling", "diffuse", "dist", "regions", "sampling", "scenes", "HostRayShape", "shape_surface_ray_sample", "shape_volume_ray_sample",
 ]
 
 

@@ -60,6 +60,9 @@ EXPORTED_SYMBOLS = [
     "salva_hip_cast_rays", "salva_hip_cast_rays_camera", "salva_hip_count_ray_candidates",
     "salva_hip_default_anisotropy", "salva_hip_compute_anisotropy", "salva_hip_evaluate_fields_anisotropic",
     "salva_hip_evaluate_fields_anisotropic_lattice", "salva_hip_extract_surface_anisotropic",
+    "salva_hip_default_diffuse", "salva_hip_diffuse_potentials",
+    "salva_hip_create_diffuse", "salva_hip_destroy_diffuse", "salva_hip_add_diffuse", "salva_hip_clear_diffuse", "salva_hip_get_diffuse",
+    "salva_hip_get_diffuse_stats", "salva_hip_update_diffuse",
 ]
 
 
@@ -226,6 +229,41 @@ class AnisoFieldOut(C.Structure):
 ANISOTROPY_BYTES, ANISOTROPY_VERSION = 64, 1  # SALVA_HIP_ANISOTROPY_BYTES / _VERSION
 ANISOTROPY_S_LO, ANISOTROPY_S_HI = 0.25, 2.0  # SALVA_HIP_ANISOTROPY_S_LO / _S_HI
 ANISOTROPY_OUT_ON_DEVICE = 1
+
+
+class DiffuseParams(C.Structure):
+    """SalvaHipDiffuse (include/salva_hip.h "Diffuse particles"): the parameters of spray, foam and bubbles."""
+    _fields_ = [("struct_size", C.c_uint32), ("version", C.c_uint32), ("surface_min", C.c_float), ("crest_cos", C.c_float),
+                ("ta_lo", C.c_float), ("ta_hi", C.c_float), ("wc_lo", C.c_float), ("wc_hi", C.c_float), ("en_lo", C.c_float), ("en_hi", C.c_float),
+                ("k_ta", C.c_float), ("k_wc", C.c_float), ("max_per_particle", C.c_uint32), ("n_spray", C.c_uint32), ("n_bubble", C.c_uint32),
+                ("k_b", C.c_float), ("k_d", C.c_float), ("life_lo", C.c_float), ("life_hi", C.c_float), ("seed", C.c_uint32),
+                ("has_kill_box", C.c_uint32), ("kill_lo", C.c_float * 3), ("kill_hi", C.c_float * 3), ("gravity", C.c_float * 3),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class DiffusePotentialsOut(C.Structure):
+    """SalvaHipDiffusePotentialsOut: where salva_hip_diffuse_potentials writes, and how many rows there is room for."""
+    _fields_ = [("trapped_air", C.POINTER(C.c_float)), ("wave_crest", C.POINTER(C.c_float)), ("energy", C.POINTER(C.c_float)),
+                ("normal", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_uint32)), ("row_capacity", C.c_uint64)]
+
+
+class DiffuseOut(C.Structure):
+    """SalvaHipDiffuseOut: where salva_hip_get_diffuse writes, and how many particles there is room for."""
+    _fields_ = [("positions", C.POINTER(C.c_float)), ("velocities", C.POINTER(C.c_float)), ("lifetime", C.POINTER(C.c_float)),
+                ("kind", C.POINTER(C.c_uint32)), ("id", C.POINTER(C.c_uint32)), ("row_capacity", C.c_uint64)]
+
+
+class DiffuseStats(C.Structure):
+    """SalvaHipDiffuseStats: what is in a diffuse set, and what the last update and all updates did."""
+    _fields_ = [("count", C.c_uint64), ("kinds", C.c_uint64 * 4), ("emitted", C.c_uint64), ("dissolved", C.c_uint64), ("killed", C.c_uint64),
+                ("dropped", C.c_uint64), ("total_emitted", C.c_uint64), ("total_dissolved", C.c_uint64), ("total_killed", C.c_uint64),
+                ("total_dropped", C.c_uint64)]
+
+
+DIFFUSE_BYTES, DIFFUSE_VERSION, DIFFUSE_STATS_BYTES = 128, 1, 104  # SALVA_HIP_DIFFUSE_BYTES / _VERSION / _STATS_BYTES
+DIFFUSE_MAX_PER_PARTICLE = 64
+DIFFUSE_OUT_ON_DEVICE, DIFFUSE_IN_ON_DEVICE = 1, 2
+DIFFUSE_SPRAY, DIFFUSE_FOAM, DIFFUSE_BUBBLE, DIFFUSE_NEW = 0, 1, 2, 3
 
 RAY_RAYS_ON_DEVICE, RAY_OUT_ON_DEVICE = 1, 2  # SALVA_HIP_RAY_RAYS_ON_DEVICE / _OUT_ON_DEVICE
 RAY_VERSION, RAY_PARAMS_BYTES, RAY_CAMERA_BYTES = 1, 64, 64  # SALVA_HIP_RAY_VERSION / _PARAMS_BYTES / _CAMERA_BYTES
@@ -477,6 +515,17 @@ def lib():
         L.salva_hip_evaluate_fields_anisotropic_lattice.argtypes = [vp, u32, ap, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(AnisoFieldOut)]
         L.salva_hip_extract_surface_anisotropic.argtypes = [vp, u32, ap, u32, C.c_float, fp, C.c_float, C.POINTER(u32), u32, C.POINTER(SurfaceOut),
                                                             C.POINTER(u64)]
+    if not os.environ.get("SALVA_HIP_LIB_VARIANT") or hasattr(L, "salva_hip_diffuse_potentials"):
+        L.salva_hip_default_diffuse.argtypes = [C.POINTER(DiffuseParams)]
+        L.salva_hip_default_diffuse.restype = None
+        L.salva_hip_diffuse_potentials.argtypes = [vp, u32, C.POINTER(DiffuseParams), u32, C.POINTER(DiffusePotentialsOut), C.POINTER(u64)]
+        L.salva_hip_create_diffuse.argtypes = [vp, u64, C.POINTER(u32)]
+        L.salva_hip_destroy_diffuse.argtypes = [vp, u32]
+        L.salva_hip_add_diffuse.argtypes = [vp, u32, u64, fp, fp, fp, u32]
+        L.salva_hip_clear_diffuse.argtypes = [vp, u32]
+        L.salva_hip_get_diffuse.argtypes = [vp, u32, u32, C.POINTER(DiffuseOut), C.POINTER(u64)]
+        L.salva_hip_get_diffuse_stats.argtypes = [vp, u32, C.POINTER(DiffuseStats)]
+        L.salva_hip_update_diffuse.argtypes = [vp, u32, u32, C.POINTER(DiffuseParams), C.c_float]
     L.salva_hip_last_error.restype = C.c_char_p
     L.salva_hip_version.restype = C.c_char_p
     _lib = L

@@ -876,6 +876,62 @@ int salva_hip_extract_surface_anisotropic(SalvaHipWorld* world, uint32_t fluid_m
     });
 }
 
+void salva_hip_default_diffuse(SalvaHipDiffuse* params) {
+    if (!params) return;
+    *params = SalvaHipDiffuse{};
+    params->struct_size = SALVA_HIP_DIFFUSE_BYTES;
+    params->version = SALVA_HIP_DIFFUSE_VERSION;
+    params->surface_min = 0.25f;
+    params->crest_cos = 0.6f;
+    params->ta_lo = 5.0f; params->ta_hi = 20.0f;
+    params->wc_lo = 2.0f; params->wc_hi = 8.0f;
+    params->en_lo = 5.0f; params->en_hi = 50.0f;
+    params->k_ta = 4000.0f; params->k_wc = 50000.0f;
+    params->max_per_particle = 16;
+    params->n_spray = 6; params->n_bubble = 20;
+    params->k_b = 2.0f; params->k_d = 0.8f;
+    params->life_lo = 2.0f; params->life_hi = 5.0f;
+    params->gravity[1] = -9.81f;
+}
+
+int salva_hip_diffuse_potentials(SalvaHipWorld* world, uint32_t fluid_mask, const SalvaHipDiffuse* params, uint32_t flags,
+                                 const SalvaHipDiffusePotentialsOut* out, uint64_t* nrows) { WorldLock _lk(world);
+    return status_entry(world, {params, nrows}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.diffuse_potentials(fluid_mask, params, flags, out, nrows);
+    });
+}
+
+int salva_hip_create_diffuse(SalvaHipWorld* world, uint64_t capacity, uint32_t* set) { WorldLock _lk(world);
+    return status_entry(world, {set}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { *set = w.create_diffuse(capacity); });
+}
+
+int salva_hip_destroy_diffuse(SalvaHipWorld* world, uint32_t set) { WorldLock _lk(world);
+    return status_entry(world, {}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.destroy_diffuse(set); });
+}
+
+int salva_hip_add_diffuse(SalvaHipWorld* world, uint32_t set, uint64_t n, const float* positions, const float* velocities, const float* lifetimes,
+                          uint32_t flags) { WorldLock _lk(world);
+    return status_entry(world, {}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) {
+        w.add_diffuse(set, n, positions, velocities, lifetimes, flags);
+    });
+}
+
+int salva_hip_clear_diffuse(SalvaHipWorld* world, uint32_t set) { WorldLock _lk(world);
+    return status_entry(world, {}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.clear_diffuse(set); });
+}
+
+int salva_hip_get_diffuse(SalvaHipWorld* world, uint32_t set, uint32_t flags, const SalvaHipDiffuseOut* out, uint64_t* n) { WorldLock _lk(world);
+    return status_entry(world, {n}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.get_diffuse(set, flags, out, n); });
+}
+
+int salva_hip_get_diffuse_stats(SalvaHipWorld* world, uint32_t set, SalvaHipDiffuseStats* stats) { WorldLock _lk(world);
+    return status_entry(world, {stats}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.get_diffuse_stats(set, stats); });
+}
+
+int salva_hip_update_diffuse(SalvaHipWorld* world, uint32_t set, uint32_t fluid_mask, const SalvaHipDiffuse* params, float dt) { WorldLock _lk(world);
+    return status_entry(world, {params}, NOT_IN_FORCE_CB | NOT_IN_COUPLING_CB, [&](World& w) { w.update_diffuse(set, fluid_mask, params, dt); });
+}
+
 const char* salva_hip_last_error(void) { return g_last_error.c_str(); }
 const char* salva_hip_version(void) { return "salva_hip 0.1 (gfx950)"; }
 

@@ -20,6 +20,7 @@
 #include "sink.h"
 #include "field.h"
 #include "anisotropy.h"
+#include "diffuse.h"
 #include "surface.h"
 #include "fluidcast.h"
 
@@ -158,6 +159,16 @@ class World {
                                              const uint32_t dims[3], uint32_t flags, const SalvaHipAnisoFieldOut& out);
     void extract_surface_anisotropic(uint32_t fluid_mask, const SalvaHipAnisotropy* params, uint32_t field, float iso, const float origin[3], float spacing,
                                      const uint32_t dims[3], uint32_t flags, const SalvaHipSurfaceOut* out, uint64_t counts[2]);
+    // ---- the potentials of diffuse particles (world_diffuse.hip, diffuse.hip).  *nrows is written before
+    // SALVA_HIP_E_CAPACITY is thrown for want of room.
+    void diffuse_potentials(uint32_t fluid_mask, const SalvaHipDiffuse* params, uint32_t flags, const SalvaHipDiffusePotentialsOut* out, uint64_t* nrows);
+    uint32_t create_diffuse(uint64_t capacity);
+    void destroy_diffuse(uint32_t set);
+    void add_diffuse(uint32_t set, uint64_t count, const float* positions, const float* velocities, const float* lifetimes, uint32_t flags);
+    void clear_diffuse(uint32_t set);
+    void get_diffuse(uint32_t set, uint32_t flags, const SalvaHipDiffuseOut* out, uint64_t* count);
+    void get_diffuse_stats(uint32_t set, SalvaHipDiffuseStats* stats);
+    void update_diffuse(uint32_t set, uint32_t fluid_mask, const SalvaHipDiffuse* params, float dt);
     // ---- rays cast at the fluid's particles (world_cast.hip, fluidcast.hip)
     void cast_rays(uint32_t fluid_mask, const SalvaHipRayParams* params, uint64_t nrays, const float* origins_xyz, const float* directions_xyz,
                    uint32_t flags, const SalvaHipRayOut& out);
@@ -352,6 +363,32 @@ class World {
                                const SalvaHipAnisoFieldOut& out, const char* what);
     void evaluate_aniso_lattice(const FieldFluids& f, const AnisoParams& prm, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                 const SalvaHipAnisoFieldOut& out, const char* what);
+    // the diffuse potentials: per host-order row the sums and the normal of the last call, the normals in the table's order, who each
+    // sorted row is, and the staged results of host buffers, grown on demand and kept
+    // ... and for the sets: staged input, the evaluator's velocity and count at the diffuse particles, flags, counts and their scans
+    struct DiffuseScratch {
+        DevBuf<float4> a, normal, normal_sorted;
+        DevBuf<uint32_t> rows, fc, keep, keep_off, cnt, cnt_off;
+        DevBuf<float> out, in, pts, fv;
+        DevBuf<DiffuseCounters> counters;
+        DevBuf<char> temp;
+    } dif;
+    // a diffuse set: two copies of the arrays (removal compacts from one into the other), what is in it and what has happened to it
+    struct DiffuseSet {
+        bool live = false;
+        uint32_t capacity = 0, count = 0, next_id = 0, updates = 0, cur = 0;
+        DevBuf<float4> pos[2], vel[2];
+        DevBuf<uint32_t> id[2];
+        SalvaHipDiffuseStats stats{};
+        DiffuseSetDev dev(uint32_t which) { return DiffuseSetDev{pos[which].p, vel[which].p, id[which].p}; }
+    };
+    std::vector<std::unique_ptr<DiffuseSet>> diffuse_sets;  // by handle; a destroyed set leaves a dead entry
+    DiffuseSet& diffuse_set(uint32_t set, const char* what);
+    DiffuseParams diffuse_params(const SalvaHipDiffuse* params, const char* what) const;
+    AnisoPack diffuse_pack(const FieldFluids& f, uint64_t& total) const;
+    DiffuseRows diffuse_rows();
+    bool diffuse_table(const FieldFluids& f, FieldGrid& g, FieldCandidates& cand, bool second);
+    DiffuseRows diffuse_sums(const FieldFluids& f, const DiffuseParams& prm, uint32_t want);
     // the ray casts: the host-order row of every sorted row of the table, staged rays and staged results, grown on demand and kept
     struct CastScratch {
         DevBuf<uint32_t> rows;

@@ -1806,6 +1806,28 @@ class LiquidWorld:
                                                      C.byref(out) if out is not None else None, C.byref(nrows)))
         return int(nrows.value)
 
+    # ---- diffuse particles (include/salva_hip.h "Diffuse particles"; salva_amd/diffuse.py)
+    def diffuse_potentials(self, params=None, fluids=None, **which):
+        """Per particle of `fluids` (None: all) as it is now, what spray, foam and bubbles are made from: `trapped_air`, `wave_crest`,
+        `energy` (N each), `normal` (N x 3) and the neighbour `count` (N), rows by fluid slot, then by index.  `params`: a Diffuse."""
+        from . import diffuse
+
+        return diffuse.potentials(self, params, fluids, **which)
+
+    def create_diffuse(self, capacity, params=None):
+        """A set of diffuse particles in device memory with room for `capacity` of them: an object with add / update / get / stats /
+        clear (salva_amd.diffuse.DiffuseSet).  `params`: the Diffuse its updates use."""
+        from . import diffuse
+
+        return diffuse.DiffuseSet(self, capacity, params)
+
+    def diffuse_potentials_device(self, params=None, fluids=None, row_capacity=0, **addresses):
+        """diffuse_potentials() into device memory: trapped_air= / wave_crest= / energy= / normal= / count= are integer device
+        addresses of buffers with room for `row_capacity` rows.  Returns the number of rows."""
+        from . import diffuse
+
+        return diffuse.potentials_device(self, params, fluids, row_capacity, **addresses)
+
     # ---- the iso-surface of a field as a triangle mesh (include/salva_hip.h salva_hip_extract_surface; DESIGN.md §21)
     _SURFACE_FIELDS = {"density": L.SURFACE_DENSITY, "fraction": L.SURFACE_FRACTION}
 
