@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libsalva_hip.so")
@@ -258,6 +260,38 @@ class DiffuseStats(C.Structure):
     _fields_ = [("count", C.c_uint64), ("kinds", C.c_uint64 * 4), ("emitted", C.c_uint64), ("dissolved", C.c_uint64), ("killed", C.c_uint64),
                 ("dropped", C.c_uint64), ("total_emitted", C.c_uint64), ("total_dissolved", C.c_uint64), ("total_killed", C.c_uint64),
                 ("total_dropped", C.c_uint64)]
+
+
+def _pointer_fields(cls):
+    """the pointer fields of an ...Out struct: name -> ctypes pointer type (its _type_ is the element: c_float or c_uint32)"""
+    return {name: t for name, t in cls._fields_ if isinstance(t, type) and issubclass(t, C._Pointer)}
+
+
+def host_out(cls, shapes):
+    """An ...Out struct over fresh host arrays: `shapes` maps the pointer fields asked for to the shape of each; a field left out
+    stays null.  The numpy dtype and the pointer type are the struct's own.  Returns (arrays, out, room).  An empty numpy array may
+    have a null data pointer and the library wants room it can name: the field of an empty array points at a substitute in `room`,
+    which the caller keeps until the call has returned."""
+    types = _pointer_fields(cls)
+    arrays, out, room = {}, cls(), []
+    for name, shape in shapes.items():
+        a = arrays[name] = np.zeros(shape, np.dtype(types[name]._type_))
+        if not a.size:
+            a = np.zeros(6, a.dtype)
+            room.append(a)
+        setattr(out, name, a.ctypes.data_as(types[name]))
+    return arrays, out, room
+
+
+def device_out(cls, addresses):
+    """An ...Out struct over device memory: `addresses` maps pointer fields to integer device addresses; 0 or None is not asked
+    for, and a name the struct does not have is ignored."""
+    types = _pointer_fields(cls)
+    out = cls()
+    for name, address in addresses.items():
+        if address and name in types:
+            setattr(out, name, C.cast(C.c_void_p(int(address)), types[name]))
+    return out
 
 
 DIFFUSE_BYTES, DIFFUSE_VERSION, DIFFUSE_STATS_BYTES = 128, 1, 104  # SALVA_HIP_DIFFUSE_BYTES / _VERSION / _STATS_BYTES

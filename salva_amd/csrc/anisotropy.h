@@ -17,11 +17,6 @@ struct AnisoRows {
     float4 *centre, *m0, *m1;
     uint32_t* count;
 };
-// where compute_anisotropy's rows go: fluid s has its len[s] host rows at first[s] and its output rows at base[s] (selected fluids only)
-struct AnisoPack {
-    uint32_t mask;
-    uint32_t first[FIELD_MAX_SLOTS], len[FIELD_MAX_SLOTS], base[FIELD_MAX_SLOTS];
-};
 struct AnisoOutDev {  // a null pointer: not written
     float *density, *fraction, *gradient;
 };
@@ -39,7 +34,7 @@ void launch_aniso_gather(uint32_t n, const uint32_t* cells, uint32_t ncells, con
 void launch_aniso_points(const FieldQuery& q, const FieldGrid& g, const FieldCandidates& cand, const float4* g0, const float4* g1, const SphConsts& c,
                          const AnisoOutDev& out, hipStream_t st);
 // host-order rows -> the packed rows of salva_hip_compute_anisotropy (any output may be null)
-void launch_aniso_pack(uint32_t n, const float4* st_pos, const uint32_t* st_model, const AnisoPack& pk, const AnisoRows& in, float* centres,
+void launch_aniso_pack(uint32_t n, const float4* st_pos, const uint32_t* st_model, const RowPack& pk, const AnisoRows& in, float* centres,
                        float* metric, uint32_t* count, hipStream_t st);
 
 }  // namespace salva

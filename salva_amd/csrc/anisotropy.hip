@@ -194,7 +194,7 @@ void launch_aniso_points(const FieldQuery& q, const FieldGrid& g, const FieldCan
     SALVA_HIP_CHECK(hipGetLastError());
 }
 
-__global__ __launch_bounds__(BLOCK) void k_aniso_pack(uint32_t n, const float4* __restrict__ st_pos, const uint32_t* __restrict__ st_model, AnisoPack pk,
+__global__ __launch_bounds__(BLOCK) void k_aniso_pack(uint32_t n, const float4* __restrict__ st_pos, const uint32_t* __restrict__ st_model, RowPack pk,
                                                       AnisoRows in, float* __restrict__ centres, float* __restrict__ metric,
                                                       uint32_t* __restrict__ count) {
     const uint32_t v = blockIdx.x * BLOCK + threadIdx.x;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void k_aniso_pack(uint32_t n, const float4* 
     }
     if (count) count[r] = finite ? in.count[v] : 0u;
 }
-void launch_aniso_pack(uint32_t n, const float4* st_pos, const uint32_t* st_model, const AnisoPack& pk, const AnisoRows& in, float* centres,
+void launch_aniso_pack(uint32_t n, const float4* st_pos, const uint32_t* st_model, const RowPack& pk, const AnisoRows& in, float* centres,
                        float* metric, uint32_t* count, hipStream_t st) {
     if (!n) return;
     k_aniso_pack<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, st_pos, st_model, pk, in, centres, metric, count);

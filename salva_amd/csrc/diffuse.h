@@ -4,7 +4,7 @@
 // table of cells of width h built by the field evaluator's own keys, scan and order kernels (field.h): the second needs the normals
 // the first leaves.
 #pragma once
-#include "anisotropy.h"
+#include "field.h"
 
 namespace salva {
 
@@ -33,7 +33,7 @@ void launch_diffuse_sums(uint32_t n, const FieldGrid& g, const FieldCandidates& 
 void launch_diffuse_crest(uint32_t n, const FieldGrid& g, const FieldCandidates& cand, const uint32_t* rows, const SphConsts& c, const DiffuseParams& prm,
                           const DiffuseRows& out, hipStream_t st);
 // host-order rows -> the packed rows of salva_hip_diffuse_potentials (any output may be null)
-void launch_diffuse_pack(uint32_t n, const uint32_t* st_model, const AnisoPack& pk, const DiffuseRows& in, float* trapped_air, float* wave_crest,
+void launch_diffuse_pack(uint32_t n, const uint32_t* st_model, const RowPack& pk, const DiffuseRows& in, float* trapped_air, float* wave_crest,
                          float* energy, float* normal, uint32_t* count, hipStream_t st);
 
 // ---- the diffuse set: pos[i] = (x, lifetime), vel[i] = (v, the kind's bits), id[i]; in the order of creation
@@ -47,7 +47,7 @@ struct DiffuseCounters {
 };
 // who emits: the fluid's slot, the index within it and the draws are the random numbers' counters
 struct DiffuseEmit {
-    AnisoPack pk;
+    RowPack pk;
     uint32_t total;     // rows of the selected fluids
     uint32_t seed, updates, first_id, capacity;
     float radius, dt;

@@ -131,7 +131,7 @@ void launch_diffuse_crest(uint32_t n, const FieldGrid& g, const FieldCandidates&
     SALVA_HIP_CHECK(hipGetLastError());
 }
 
-__global__ __launch_bounds__(BLOCK) void k_diffuse_pack(uint32_t n, const uint32_t* __restrict__ st_model, AnisoPack pk, DiffuseRows in,
+__global__ __launch_bounds__(BLOCK) void k_diffuse_pack(uint32_t n, const uint32_t* __restrict__ st_model, RowPack pk, DiffuseRows in,
                                                         float* __restrict__ trapped_air, float* __restrict__ wave_crest, float* __restrict__ energy,
                                                         float* __restrict__ normal, uint32_t* __restrict__ count) {
     const uint32_t v = blockIdx.x * BLOCK + threadIdx.x;
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(BLOCK) void k_diffuse_pack(uint32_t n, const uint32
         normal[3 * r] = nv.x; normal[3 * r + 1] = nv.y; normal[3 * r + 2] = nv.z;
     }
 }
-void launch_diffuse_pack(uint32_t n, const uint32_t* st_model, const AnisoPack& pk, const DiffuseRows& in, float* trapped_air, float* wave_crest,
+void launch_diffuse_pack(uint32_t n, const uint32_t* st_model, const RowPack& pk, const DiffuseRows& in, float* trapped_air, float* wave_crest,
                          float* energy, float* normal, uint32_t* count, hipStream_t st) {
     if (!n) return;
     k_diffuse_pack<<<div_up(n, BLOCK), BLOCK, 0, st>>>(n, st_model, pk, in, trapped_air, wave_crest, energy, normal, count);
@@ -282,7 +282,7 @@ __device__ __forceinline__ uint32_t diffuse_key(const DiffuseEmit& em, uint32_t 
 }
 __device__ __forceinline__ float diffuse_phi(float value, float lo, float hi) { return (fminf(value, hi) - fminf(value, lo)) / (hi - lo); }
 // the packed row of host row v and its fluid, or false: the row is not of a selected fluid
-__device__ __forceinline__ bool diffuse_row(const AnisoPack& pk, uint32_t s, uint32_t v, uint32_t& r, uint32_t& index) {
+__device__ __forceinline__ bool diffuse_row(const RowPack& pk, uint32_t s, uint32_t v, uint32_t& r, uint32_t& index) {
     if (s >= FIELD_MAX_SLOTS || !((pk.mask >> s) & 1u) || v < pk.first[s] || v - pk.first[s] >= pk.len[s]) return false;
     index = v - pk.first[s];
     r = pk.base[s] + index;

@@ -49,6 +49,12 @@ struct FieldCandidates {
     const float4* rec0;
     const float4* rec1;
 };
+// where the rows of the selected fluids go in a packed output: fluid s has its len[s] host rows at first[s] and its output rows at
+// base[s] (selected fluids only)
+struct RowPack {
+    uint32_t mask;
+    uint32_t first[FIELD_MAX_SLOTS], len[FIELD_MAX_SLOTS], base[FIELD_MAX_SLOTS];
+};
 
 // box6 = {min x, y, z, max x, y, z} of the finite points among `pts`, as ordered integers (field_ordered / field_unordered);
 // the caller has set it to {INT32_MAX x 3, INT32_MIN x 3}

@@ -297,6 +297,32 @@ class World {
     void download_xyz(const float4* src, uint64_t count, float* out);
     void download_w(const float4* src, uint64_t count, float* out);
     void download_f32(const float* src, uint64_t count, float* out);
+    // ... and one description of the outputs of a device query (world_io.hip): up to six, in the order given; an entry left out is
+    // not asked for.  place: where the kernels write — the caller's own device memory, or consecutive slices of query_out;
+    // zero: what an empty box leaves; finish: one wait, or one download_f32 per output.
+    struct QueryOut {
+        struct One { void* host; uint64_t words; float* dev; } o[6];  // the caller's pointer (null: not asked for), its length, the kernels' pointer
+        bool on_device;
+        float* f32(int k) const { return o[k].dev; }
+        uint32_t* u32(int k) const { return reinterpret_cast<uint32_t*>(o[k].dev); }
+        bool any(int from = 0, int to = 6) const { for (int k = from; k < to; ++k) if (o[k].dev) return true; return false; }
+    };
+    void query_place(QueryOut& q, bool on_device);
+    void query_zero(const QueryOut& q);
+    void query_finish(const QueryOut& q);
+    // count, then fill: *count is written first; false: a count call, nothing to fill; a row_capacity below the total is refused
+    template <typename Out> static bool fill_wanted(uint64_t total, uint64_t* count, const Out* out, const char* what, const char* unit) {
+        *count = total;
+        if (out && out->row_capacity < total)
+            throw HipError(SALVA_HIP_E_CAPACITY, std::string(what) + ": " + std::to_string(total) + " " + unit + ": more than the row_capacity of out");
+        return out != nullptr;
+    }
+    // The staged outputs of whichever query runs with host buffers, grown on demand and kept.  One buffer serves all because a query that
+    // runs inside another always writes to device memory and so places nothing here: surface_run calls evaluate_fields and
+    // evaluate_aniso_points, extract_surface / _anisotropic call evaluate_fields_lattice / evaluate_aniso_lattice, each with
+    // SALVA_HIP_FIELD_OUT_ON_DEVICE, and update_diffuse calls launch_field_points on buffers of its own.  surface_run places all four of
+    // its outputs in one query_place before its first kernel: an ensure that grows frees the old block.
+    DevBuf<float> query_out;
     template <typename Launch>  // what salva_hip_get_fluid_contacts and _get_local_contacts share (world_io.hip)
     uint64_t export_contacts(uint64_t rows, const uint32_t* d_counts, bool with_moff, uint64_t* offsets, uint32_t* j_model, uint32_t* j,
                              uint64_t capacity, Launch&& launch);
@@ -320,19 +346,19 @@ class World {
     DevBuf<float4> st_spare[4];  // where apply_keep_flags compacts to; the arrays it replaces become the next call's room
     DevBuf<uint32_t> sink_deleted, sink_scan;
     PinnedStage sink_stage;
-    // the field evaluator: its grid's tables, the sorted records and the staged results of host buffers, grown on demand and kept
+    // the field evaluator: its grid's tables, the sorted records and (where a caller asks) the host-order row of every sorted row, grown
+    // on demand and kept; all of it is the last field_table's
     struct FieldScratch {
-        DevBuf<uint32_t> keys, rank, cells, keys_sorted, idx_tmp;
+        DevBuf<uint32_t> keys, rank, cells, keys_sorted, idx_tmp, rows;
         DevBuf<float4> rec0, rec1;
-        DevBuf<float> out;
         DevBuf<int32_t> box;
         DevBuf<char> temp;
     } fld;
-    // the surface extractor: the node values (an evaluated field, or a host lattice staged), one word and two offsets per node, the
-    // totals, and the staged mesh of host buffers, grown on demand and kept
+    // the surface extractor: the node values (an evaluated field, or a host lattice staged), one word and two offsets per node and the
+    // totals, grown on demand and kept
     struct SurfaceScratch {
-        DevBuf<float> values, vertices, normals, velocities;
-        DevBuf<uint32_t> word, voff, toff, triangles;
+        DevBuf<float> values;
+        DevBuf<uint32_t> word, voff, toff;
         DevBuf<SurfaceTotals> totals;
         DevBuf<int32_t> box;
         DevBuf<char> temp;
@@ -341,19 +367,18 @@ class World {
     void surface_run(const float* d_values, float iso, const SurfaceLattice& g, uint32_t fluid_mask, bool on_device, const SalvaHipSurfaceOut* out,
                      uint64_t counts[2], const char* what, const AnisoParams* aniso = nullptr);
     FieldFluids field_begin(uint32_t fluid_mask, uint32_t flags, const char* what);
-    FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g,
-                                     DevBuf<uint32_t>* rows_out = nullptr);
+    FieldCandidates field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g, bool rows = false);
     FieldCandidates field_table(const FieldFluids& f, const float4* pos, float width, int grow, const float lo[3], const float hi[3], bool second,
-                                FieldGrid& g, DevBuf<uint32_t>* rows_out, const char* too_large);
+                                FieldGrid& g, bool rows, const char* too_large);
+    RowPack rows_pack(const FieldFluids& f, uint64_t& total) const;  // where the rows of the selected fluids go: by slot, then by index
     FieldQuery field_points_query(uint64_t npoints, const float* points_xyz, uint32_t flags, float lo[3], float hi[3], const char* what);
     FieldQuery field_lattice_query(const float origin[3], float spacing, const uint32_t dims[3], float lo[3], float hi[3], bool& box_empty,
                                    const char* what);
     // the anisotropic kernels: per host-order row the centre and the metric records of the last moments pass, the metric records of the
-    // sorted rows of the table on the centres, who each sorted row is, and the staged results of host buffers, grown on demand and kept
+    // sorted rows of the table on the centres, grown on demand and kept
     struct AnisoScratch {
         DevBuf<float4> centre, m0, m1, g0, g1;
-        DevBuf<uint32_t> count, rows;
-        DevBuf<float> out;
+        DevBuf<uint32_t> count;
     } ani;
     AnisoParams aniso_params(const SalvaHipAnisotropy* params, const char* what) const;
     AnisoRows aniso_moments(const FieldFluids& f, const AnisoParams& prm, const float lo[3], const float hi[3], int grow, uint32_t ring);
@@ -363,13 +388,13 @@ class World {
                                const SalvaHipAnisoFieldOut& out, const char* what);
     void evaluate_aniso_lattice(const FieldFluids& f, const AnisoParams& prm, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,
                                 const SalvaHipAnisoFieldOut& out, const char* what);
-    // the diffuse potentials: per host-order row the sums and the normal of the last call, the normals in the table's order, who each
-    // sorted row is, and the staged results of host buffers, grown on demand and kept
+    // the diffuse potentials: per host-order row the sums and the normal of the last call and the normals in the table's order, grown on
+    // demand and kept
     // ... and for the sets: staged input, the evaluator's velocity and count at the diffuse particles, flags, counts and their scans
     struct DiffuseScratch {
         DevBuf<float4> a, normal, normal_sorted;
-        DevBuf<uint32_t> rows, fc, keep, keep_off, cnt, cnt_off;
-        DevBuf<float> out, in, pts, fv;
+        DevBuf<uint32_t> fc, keep, keep_off, cnt, cnt_off;
+        DevBuf<float> in, pts, fv;
         DevBuf<DiffuseCounters> counters;
         DevBuf<char> temp;
     } dif;
@@ -385,14 +410,12 @@ class World {
     std::vector<std::unique_ptr<DiffuseSet>> diffuse_sets;  // by handle; a destroyed set leaves a dead entry
     DiffuseSet& diffuse_set(uint32_t set, const char* what);
     DiffuseParams diffuse_params(const SalvaHipDiffuse* params, const char* what) const;
-    AnisoPack diffuse_pack(const FieldFluids& f, uint64_t& total) const;
     DiffuseRows diffuse_rows();
     bool diffuse_table(const FieldFluids& f, FieldGrid& g, FieldCandidates& cand, bool second);
     DiffuseRows diffuse_sums(const FieldFluids& f, const DiffuseParams& prm, uint32_t want);
-    // the ray casts: the host-order row of every sorted row of the table, staged rays and staged results, grown on demand and kept
+    // the ray casts: staged rays, grown on demand and kept
     struct CastScratch {
-        DevBuf<uint32_t> rows;
-        DevBuf<float> rays, out;
+        DevBuf<float> rays;
     } cst;
     void cast_run(uint32_t fluid_mask, const SalvaHipRayParams* params, CastRays rays, uint32_t flags, const SalvaHipRayOut& out, const char* what,
                   int count_walk = 0, uint32_t* tested = nullptr);

@@ -37,9 +37,9 @@ AnisoRows World::aniso_moments(const FieldFluids& f, const AnisoParams& prm, con
     SALVA_HIP_CHECK(hipMemsetAsync(r.count, 0, rows * sizeof(uint32_t), stream));
     if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return r;  // (no finite particle)
     FieldGrid g{};
-    const FieldCandidates cand = field_table(f, st_pos.p, sc.h + sc.h, grow, lo, hi, false, g, &ani.rows,
+    const FieldCandidates cand = field_table(f, st_pos.p, sc.h + sc.h, grow, lo, hi, false, g, true,
                                              "anisotropic kernels: the box exceeds 2^27 cells of width 2h: split the query");
-    launch_aniso_moments(n, g, cand, ani.rows.p, st_pos.p, ring, prm, sc.h, r, stream);
+    launch_aniso_moments(n, g, cand, fld.rows.p, st_pos.p, ring, prm, sc.h, r, stream);
     return r;
 }
 
@@ -50,86 +50,44 @@ void World::compute_anisotropy(uint32_t fluid_mask, const SalvaHipAnisotropy* pa
     const FieldFluids f = field_begin(fluid_mask, 0, what);
     if (flags & ~(uint32_t)SALVA_HIP_ANISOTROPY_OUT_ON_DEVICE) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": unknown flag");
     const AnisoParams prm = aniso_params(params, what);
-    AnisoPack pk{};
-    pk.mask = f.mask;
     uint64_t total = 0;
-    for (uint32_t s = 0; s < fluids.size() && s < FIELD_MAX_SLOTS; ++s) {
-        if (!((f.mask >> s) & 1u)) continue;
-        const SlotSpan sp = fluid_span(s);
-        pk.first[s] = (uint32_t)sp.off;
-        pk.len[s] = (uint32_t)sp.n;
-        pk.base[s] = (uint32_t)total;
-        total += sp.n;
-    }
-    *nrows = total;
-    if (!out) return;
-    if (out->row_capacity < total)
-        throw HipError(SALVA_HIP_E_CAPACITY, std::string(what) + ": " + std::to_string(total) + " rows: more than the row_capacity of out");
+    const RowPack pk = rows_pack(f, total);
+    if (!fill_wanted(total, nrows, out, what, "rows")) return;
     if (!total || !(out->centres || out->metric || out->count)) return;
     float lo[3], hi[3];
     uint64_t nfinite = 0;
     get_fluid_bounds(f.mask, lo, hi, &nfinite);
     const AnisoRows r = aniso_moments(f, prm, lo, hi, 1, 0);
-    const bool on_device = (flags & SALVA_HIP_ANISOTROPY_OUT_ON_DEVICE) != 0u;
-    float *d_centres = out->centres, *d_metric = out->metric;
-    uint32_t* d_count = out->count;
-    if (!on_device) {
-        ani.out.ensure(10 * total, stream, false, 1.1f);
-        d_centres = out->centres ? ani.out.p : nullptr;
-        d_metric = out->metric ? ani.out.p + 3 * total : nullptr;
-        d_count = out->count ? reinterpret_cast<uint32_t*>(ani.out.p + 9 * total) : nullptr;
-    }
-    launch_aniso_pack(n, st_pos.p, st_model.p, pk, r, d_centres, d_metric, d_count, stream);
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    if (out->centres) download_f32(d_centres, 3 * total, out->centres);
-    if (out->metric) download_f32(d_metric, 6 * total, out->metric);
-    if (out->count) download_f32(reinterpret_cast<const float*>(d_count), total, reinterpret_cast<float*>(out->count));
+    QueryOut o{{{out->centres, 3 * total}, {out->metric, 6 * total}, {out->count, total}}};
+    query_place(o, (flags & SALVA_HIP_ANISOTROPY_OUT_ON_DEVICE) != 0u);
+    launch_aniso_pack(n, st_pos.p, st_model.p, pk, r, o.f32(0), o.f32(1), o.u32(2), stream);
+    query_finish(o);
 }
 
 // m places, their box (box_empty: none of them is finite — everything is zero), the caller's buffers (world_field.hip field_run)
 void World::aniso_run(const FieldFluids& f, const AnisoParams& prm, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m,
                       uint32_t flags, const SalvaHipAnisoFieldOut& out) {
-    const bool on_device = (flags & SALVA_HIP_FIELD_OUT_ON_DEVICE) != 0u;
-    float* const host[3] = {out.density, out.fraction, out.gradient};
-    const uint64_t width[3] = {1, 1, 3};
-    float* dev[3] = {nullptr, nullptr, nullptr};
-    if (on_device) {
-        for (int k = 0; k < 3; ++k) dev[k] = host[k];
-    } else {
-        uint64_t words = 0;
-        for (int k = 0; k < 3; ++k) words += host[k] ? width[k] * m : 0;
-        ani.out.ensure(words ? words : 1, stream, false, 1.1f);
-        uint64_t at = 0;
-        for (int k = 0; k < 3; ++k)
-            if (host[k]) { dev[k] = ani.out.p + at; at += width[k] * m; }
-    }
-    if (!(dev[0] || dev[1] || dev[2])) return;
+    QueryOut o{{{out.density, m}, {out.fraction, m}, {out.gradient, 3 * m}}};
+    query_place(o, (flags & SALVA_HIP_FIELD_OUT_ON_DEVICE) != 0u);
+    if (!o.any()) return;
     if (box_empty) {
-        for (int k = 0; k < 3; ++k)
-            if (dev[k]) SALVA_HIP_CHECK(hipMemsetAsync(dev[k], 0, width[k] * m * sizeof(float), stream));
+        query_zero(o);
     } else {
         // What can matter to a place in [lo, hi]: a centre within 2h of it, whose particle lies within 2h of the centre and whose
         // neighbours lie within 2h of the particle — three cells of width 2h, of which the outermost layer holds neighbours only.
         const AnisoRows r = aniso_moments(f, prm, lo, hi, 3, 1);
         FieldGrid g{};
-        const FieldCandidates cand = field_table(f, r.centre, sc.h + sc.h, 1, lo, hi, false, g, &ani.rows,
+        // (this table's row map overwrites the first's, behind the moments pass on the stream)
+        const FieldCandidates cand = field_table(f, r.centre, sc.h + sc.h, 1, lo, hi, false, g, true,
                                                  "anisotropic kernels: the box exceeds 2^27 cells of width 2h: split the query");
         const size_t rows = n ? n : 1;
         ani.g0.ensure(rows, stream, false, 1.1f); ani.g1.ensure(rows, stream, false, 1.1f);
-        launch_aniso_gather(n, cand.cells, g.ncells, ani.rows.p, r, ani.g0.p, ani.g1.p, stream);
+        launch_aniso_gather(n, cand.cells, g.ncells, fld.rows.p, r, ani.g0.p, ani.g1.p, stream);
         SphConsts unit = make_sph_consts(1.0f);  // P and P' are the world's kernels at h = 1
         unit.kd = sc.kd; unit.kg = sc.kg;
-        launch_aniso_points(q, g, cand, ani.g0.p, ani.g1.p, unit, AnisoOutDev{dev[0], dev[1], dev[2]}, stream);
+        launch_aniso_points(q, g, cand, ani.g0.p, ani.g1.p, unit, AnisoOutDev{o.f32(0), o.f32(1), o.f32(2)}, stream);
     }
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    for (int k = 0; k < 3; ++k)
-        if (host[k]) download_f32(dev[k], width[k] * m, host[k]);
+    query_finish(o);
 }
 
 void World::evaluate_aniso_points(const FieldFluids& f, const AnisoParams& prm, uint64_t npoints, const float* points_xyz, uint32_t flags,

@@ -35,24 +35,11 @@ void World::cast_run(uint32_t fluid_mask, const SalvaHipRayParams* params, CastR
 
     // the caller's buffers
     const bool out_dev = (flags & SALVA_HIP_RAY_OUT_ON_DEVICE) != 0u, rays_dev = (flags & SALVA_HIP_RAY_RAYS_ON_DEVICE) != 0u;
-    constexpr int NOUT = 6;
-    float* const host[NOUT] = {out.t, reinterpret_cast<float*>(out.fluid), reinterpret_cast<float*>(out.index), out.normal, out.thickness,
-                               reinterpret_cast<float*>(tested)};
-    const uint64_t width[NOUT] = {1, 1, 1, 3, 1, 1};
-    float* dev[NOUT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (out_dev) {
-        for (int k = 0; k < NOUT; ++k) dev[k] = host[k];
-    } else {
-        uint64_t words = 0;
-        for (int k = 0; k < NOUT; ++k) words += host[k] ? width[k] * m : 0;
-        cst.out.ensure(words ? words : 1, stream, false, 1.1f);
-        uint64_t at = 0;
-        for (int k = 0; k < NOUT; ++k)
-            if (host[k]) { dev[k] = cst.out.p + at; at += width[k] * m; }
-    }
-    const bool hit = count_walk ? count_walk == 1 : (dev[0] || dev[1] || dev[2] || dev[3]), thick = count_walk ? count_walk == 2 : dev[4] != nullptr;
+    QueryOut o{{{out.t, m}, {out.fluid, m}, {out.index, m}, {out.normal, 3 * m}, {out.thickness, m}, {tested, m}}};
+    query_place(o, out_dev);
+    const bool hit = count_walk ? count_walk == 1 : o.any(0, 4), thick = count_walk ? count_walk == 2 : o.f32(4) != nullptr;
     if (!hit && !thick) return;
-    const CastOutDev od{dev[0], reinterpret_cast<uint32_t*>(dev[1]), reinterpret_cast<uint32_t*>(dev[2]), dev[3], dev[4], reinterpret_cast<uint32_t*>(dev[5])};
+    const CastOutDev od{o.f32(0), o.u32(1), o.u32(2), o.f32(3), o.f32(4), o.u32(5)};
 
     // the box B
     CastParams P{};
@@ -89,9 +76,9 @@ void World::cast_run(uint32_t fluid_mask, const SalvaHipRayParams* params, CastR
             rays.origins = cst.rays.p; rays.directions = cst.rays.p + 3 * m;
         }
         FieldGrid g{};
-        const FieldCandidates cand = field_candidates(f, P.blo, P.bhi, false, g, &cst.rows);
+        const FieldCandidates cand = field_candidates(f, P.blo, P.bhi, false, g, true);
         CastTable tab{};
-        tab.cells = cand.cells; tab.rec0 = cand.rec0; tab.rows = cst.rows.p; tab.st_model = st_model.p;
+        tab.cells = cand.cells; tab.rec0 = cand.rec0; tab.rows = fld.rows.p; tab.st_model = st_model.p;
         for (uint32_t s = 0; s < fluids.size() && s < FIELD_MAX_SLOTS; ++s) tab.first[s] = (uint32_t)fluid_offset(s);
         // a clip box may hold no particle at all: then every ray misses and the walk does not run
         uint32_t kept = 1u;
@@ -102,10 +89,7 @@ void World::cast_run(uint32_t fluid_mask, const SalvaHipRayParams* params, CastR
         if (kept) launch_fluid_cast(rays, P, g, tab, od, hit, thick, stream);
         else launch_fluid_cast_miss(m, od, stream);
     }
-    SALVA_HIP_CHECK(hipStreamSynchronize(stream));  // (the results are complete, and staged rays are free again)
-    if (out_dev) return;
-    for (int k = 0; k < NOUT; ++k)
-        if (host[k]) download_f32(dev[k], width[k] * m, host[k]);
+    query_finish(o);  // (it waits: the results are complete, and staged rays are free again)
 }
 
 static CastRays camera_rays(const SalvaHipRayCamera& camera, const std::string& w) {

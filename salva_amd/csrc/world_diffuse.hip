@@ -59,7 +59,7 @@ bool World::diffuse_table(const FieldFluids& f, FieldGrid& g, FieldCandidates& c
     uint64_t nfinite = 0;
     get_fluid_bounds(f.mask, lo, hi, &nfinite);
     if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return false;
-    cand = field_table(f, st_pos.p, sc.h, 1, lo, hi, second, g, &dif.rows, "diffuse particles: the fluids' box exceeds 2^27 cells of width h");
+    cand = field_table(f, st_pos.p, sc.h, 1, lo, hi, second, g, true, "diffuse particles: the fluids' box exceeds 2^27 cells of width h");
     return true;
 }
 // the two passes
@@ -68,25 +68,9 @@ DiffuseRows World::diffuse_sums(const FieldFluids& f, const DiffuseParams& prm, 
     FieldGrid g{};
     FieldCandidates cand{};
     if (!diffuse_table(f, g, cand, (want & ~(uint32_t)DIFFUSE_WANT_COUNT) != 0u)) return r;  // ((v, V): every output but the count reads it)
-    launch_diffuse_sums(n, g, cand, dif.rows.p, sc, prm, want, r, stream);
-    if (want & DIFFUSE_WANT_CREST) launch_diffuse_crest(n, g, cand, dif.rows.p, sc, prm, r, stream);
+    launch_diffuse_sums(n, g, cand, fld.rows.p, sc, prm, want, r, stream);
+    if (want & DIFFUSE_WANT_CREST) launch_diffuse_crest(n, g, cand, fld.rows.p, sc, prm, r, stream);
     return r;
-}
-
-// where the rows of the selected fluids go: by slot, then by index
-AnisoPack World::diffuse_pack(const FieldFluids& f, uint64_t& total) const {
-    AnisoPack pk{};
-    pk.mask = f.mask;
-    total = 0;
-    for (uint32_t s = 0; s < fluids.size() && s < FIELD_MAX_SLOTS; ++s) {
-        if (!((f.mask >> s) & 1u)) continue;
-        const SlotSpan sp = fluid_span(s);
-        pk.first[s] = (uint32_t)sp.off;
-        pk.len[s] = (uint32_t)sp.n;
-        pk.base[s] = (uint32_t)total;
-        total += sp.n;
-    }
-    return pk;
 }
 
 void World::diffuse_potentials(uint32_t fluid_mask, const SalvaHipDiffuse* params, uint32_t flags, const SalvaHipDiffusePotentialsOut* out,
@@ -97,38 +81,18 @@ void World::diffuse_potentials(uint32_t fluid_mask, const SalvaHipDiffuse* param
     if (flags & ~(uint32_t)SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": unknown flag");
     const DiffuseParams prm = diffuse_params(params, what);
     uint64_t total = 0;
-    const AnisoPack pk = diffuse_pack(f, total);
-    *nrows = total;
-    if (!out) return;
-    if (out->row_capacity < total)
-        throw HipError(SALVA_HIP_E_CAPACITY, std::string(what) + ": " + std::to_string(total) + " rows: more than the row_capacity of out");
+    const RowPack pk = rows_pack(f, total);
+    if (!fill_wanted(total, nrows, out, what, "rows")) return;
     const uint32_t want = (out->count ? DIFFUSE_WANT_COUNT : 0u) | (out->trapped_air ? DIFFUSE_WANT_TRAPPED : 0u) |
                           (out->normal ? DIFFUSE_WANT_NORMAL : 0u) | (out->wave_crest ? DIFFUSE_WANT_CREST : 0u) |
                           (out->energy ? DIFFUSE_WANT_ENERGY : 0u);
     if (!total || !want) return;
     const DiffuseRows r = diffuse_sums(f, prm, want);
-    const bool on_device = (flags & SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) != 0u;
-    // trapped_air, wave_crest, energy, normal, count: 1, 1, 1, 3 and 1 words per row
-    float* const host[5] = {out->trapped_air, out->wave_crest, out->energy, out->normal, reinterpret_cast<float*>(out->count)};
-    const uint64_t width[5] = {1, 1, 1, 3, 1};
-    float* dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (on_device) {
-        for (int k = 0; k < 5; ++k) dev[k] = host[k];
-    } else {
-        dif.out.ensure(7 * total, stream, false, 1.1f);
-        uint64_t at = 0;
-        for (int k = 0; k < 5; ++k)
-            if (host[k]) { dev[k] = dif.out.p + at; at += width[k] * total; }
-    }
-    launch_diffuse_pack(n, st_model.p, pk, r, dev[0], dev[1], dev[2], dev[3], reinterpret_cast<uint32_t*>(dev[4]), stream);
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    for (int k = 0; k < 5; ++k)
-        if (host[k]) download_f32(dev[k], width[k] * total, host[k]);
+    QueryOut o{{{out->trapped_air, total}, {out->wave_crest, total}, {out->energy, total}, {out->normal, 3 * total}, {out->count, total}}};
+    query_place(o, (flags & SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) != 0u);
+    launch_diffuse_pack(n, st_model.p, pk, r, o.f32(0), o.f32(1), o.f32(2), o.f32(3), o.u32(4), stream);
+    query_finish(o);
 }
-
 
 // ------------------------------------------------------------------------------------------------ the sets
 World::DiffuseSet& World::diffuse_set(uint32_t set, const char* what) {
@@ -197,31 +161,12 @@ void World::get_diffuse(uint32_t set, uint32_t flags, const SalvaHipDiffuseOut* 
     DiffuseSet& s = diffuse_set(set, what);
     if (flags & ~(uint32_t)SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": unknown flag");
     const uint64_t total = s.count;
-    *count = total;
-    if (!out) return;
-    if (out->row_capacity < total)
-        throw HipError(SALVA_HIP_E_CAPACITY, std::string(what) + ": " + std::to_string(total) + " particles: more than the row_capacity of out");
+    if (!fill_wanted(total, count, out, what, "particles")) return;
     if (!total || !(out->positions || out->velocities || out->lifetime || out->kind || out->id)) return;
-    // positions, velocities, lifetime, kind, id: 3, 3, 1, 1 and 1 words per particle
-    float* const host[5] = {out->positions, out->velocities, out->lifetime, reinterpret_cast<float*>(out->kind), reinterpret_cast<float*>(out->id)};
-    const uint64_t width[5] = {3, 3, 1, 1, 1};
-    float* dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const bool on_device = (flags & SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) != 0u;
-    if (on_device) {
-        for (int k = 0; k < 5; ++k) dev[k] = host[k];
-    } else {
-        dif.out.ensure(9 * total, stream, false, 1.1f);
-        uint64_t at = 0;
-        for (int k = 0; k < 5; ++k)
-            if (host[k]) { dev[k] = dif.out.p + at; at += width[k] * total; }
-    }
-    launch_diffuse_get((uint32_t)total, s.dev(s.cur), dev[0], dev[1], dev[2], reinterpret_cast<uint32_t*>(dev[3]), reinterpret_cast<uint32_t*>(dev[4]), stream);
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    for (int k = 0; k < 5; ++k)
-        if (host[k]) download_f32(dev[k], width[k] * total, host[k]);
+    QueryOut o{{{out->positions, 3 * total}, {out->velocities, 3 * total}, {out->lifetime, total}, {out->kind, total}, {out->id, total}}};
+    query_place(o, (flags & SALVA_HIP_DIFFUSE_OUT_ON_DEVICE) != 0u);
+    launch_diffuse_get((uint32_t)total, s.dev(s.cur), o.f32(0), o.f32(1), o.f32(2), o.u32(3), o.u32(4), stream);
+    query_finish(o);
 }
 
 void World::get_diffuse_stats(uint32_t set, SalvaHipDiffuseStats* stats) { *stats = diffuse_set(set, "salva_hip_get_diffuse_stats").stats; }
@@ -233,7 +178,7 @@ void World::update_diffuse(uint32_t set, uint32_t fluid_mask, const SalvaHipDiff
     const DiffuseParams prm = diffuse_params(params, what);
     if (!(std::isfinite(dt) && dt >= 0.0f)) throw HipError(SALVA_HIP_E_INVALID, std::string(what) + ": dt must be finite and >= 0");
     uint64_t total = 0;
-    const AnisoPack pk = diffuse_pack(f, total);
+    const RowPack pk = rows_pack(f, total);
     // one table serves the evaluator at the diffuse particles and both passes of the potentials: the fluid does not change in between
     const DiffuseRows rows = diffuse_rows();
     FieldGrid g{};
@@ -266,8 +211,8 @@ void World::update_diffuse(uint32_t set, uint32_t fluid_mask, const SalvaHipDiff
     }
     // c. emit
     if (table && total) {
-        launch_diffuse_sums(n, g, cand, dif.rows.p, sc, prm, DIFFUSE_WANT_TRAPPED | DIFFUSE_WANT_CREST | DIFFUSE_WANT_ENERGY, rows, stream);
-        launch_diffuse_crest(n, g, cand, dif.rows.p, sc, prm, rows, stream);
+        launch_diffuse_sums(n, g, cand, fld.rows.p, sc, prm, DIFFUSE_WANT_TRAPPED | DIFFUSE_WANT_CREST | DIFFUSE_WANT_ENERGY, rows, stream);
+        launch_diffuse_crest(n, g, cand, fld.rows.p, sc, prm, rows, stream);
         DiffuseEmit em{};
         em.pk = pk;
         em.total = (uint32_t)total;

@@ -34,15 +34,15 @@ FieldFluids World::field_begin(uint32_t fluid_mask, uint32_t flags, const char* 
 }
 
 // The evaluator's grid over [lo, hi] grown by h — one cell more on every side of the cells the box touches — and the selected
-// particles inside it, sorted by cell, then by host index (rows, when given: the host-order row of each, for the ray casts)
-FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g, DevBuf<uint32_t>* rows_out) {
-    return field_table(f, st_pos.p, sc.h, 1, lo, hi, second, g, rows_out, "field evaluation: the box of the query exceeds 2^27 cells of width h: split the query");
+// particles inside it, sorted by cell, then by host index (rows: fld.rows gets the host-order row of each, for the ray casts)
+FieldCandidates World::field_candidates(const FieldFluids& f, const float lo[3], const float hi[3], bool second, FieldGrid& g, bool rows) {
+    return field_table(f, st_pos.p, sc.h, 1, lo, hi, second, g, rows, "field evaluation: the box of the query exceeds 2^27 cells of width h: split the query");
 }
 
 // The same table with its knobs out in the open: the rows of `pos` ((x, y, z, V) in host order: the staging positions, or the centres
 // of world_anisotropy.hip) in cells of `width`, over the cells [lo, hi] touches and `grow` more on every side
 FieldCandidates World::field_table(const FieldFluids& f, const float4* pos, float width, int grow, const float lo[3], const float hi[3], bool second,
-                                   FieldGrid& g, DevBuf<uint32_t>* rows_out, const char* too_large) {
+                                   FieldGrid& g, bool rows_out, const char* too_large) {
     int clo[3], chi[3];
     cell_range(lo, hi, width, clo, chi);
     uint64_t ncells = 1;
@@ -60,7 +60,7 @@ FieldCandidates World::field_table(const FieldFluids& f, const float4* pos, floa
     fld.keys_sorted.ensure(rows, stream, false, 1.1f); fld.idx_tmp.ensure(rows, stream, false, 1.1f);
     fld.rec0.ensure(rows, stream, false, 1.1f);
     if (second) fld.rec1.ensure(rows, stream, false, 1.1f);
-    if (rows_out) rows_out->ensure(rows, stream, false, 1.1f);
+    if (rows_out) fld.rows.ensure(rows, stream, false, 1.1f);
     fld.cells.ensure((size_t)g.ncells + 1, stream, false, 1.1f);
     const size_t tb = scan_temp_bytes(g.ncells + 1u);
     fld.temp.ensure(tb ? tb : 1);
@@ -68,46 +68,43 @@ FieldCandidates World::field_table(const FieldFluids& f, const float4* pos, floa
     launch_field_keys(pos, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, stream);
     scan_u32(fld.temp.p, tb, fld.cells.p, fld.cells.p, g.ncells + 1u, stream);
     launch_field_sort(pos, st_vel.p, st_model.p, n, f, g, fld.keys.p, fld.rank.p, fld.cells.p, fld.keys_sorted.p, fld.idx_tmp.p, fld.rec0.p,
-                      second ? fld.rec1.p : nullptr, rows_out ? rows_out->p : nullptr, stream);
+                      second ? fld.rec1.p : nullptr, rows_out ? fld.rows.p : nullptr, stream);
     return FieldCandidates{fld.cells.p, fld.rec0.p, second ? fld.rec1.p : nullptr};
+}
+
+RowPack World::rows_pack(const FieldFluids& f, uint64_t& total) const {
+    RowPack pk{};
+    pk.mask = f.mask;
+    total = 0;
+    for (uint32_t s = 0; s < fluids.size() && s < FIELD_MAX_SLOTS; ++s) {
+        if (!((f.mask >> s) & 1u)) continue;
+        const SlotSpan sp = fluid_span(s);
+        pk.first[s] = (uint32_t)sp.off;
+        pk.len[s] = (uint32_t)sp.n;
+        pk.base[s] = (uint32_t)total;
+        total += sp.n;
+    }
+    return pk;
 }
 
 // m places, their box (box_empty: none of them is finite — everything is zero), the caller's buffers
 void World::field_run(const FieldFluids& f, const FieldQuery& q, const float lo[3], const float hi[3], bool box_empty, uint64_t m, uint32_t flags,
                       const SalvaHipFieldOut& out, bool brick_arm) {
-    const bool on_device = (flags & SALVA_HIP_FIELD_OUT_ON_DEVICE) != 0u;
-    float* const host[5] = {out.density, out.fraction, out.velocity, out.gradient, reinterpret_cast<float*>(out.count)};
-    const uint64_t width[5] = {1, 1, 3, 3, 1};
-    float* dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (on_device) {
-        for (int k = 0; k < 5; ++k) dev[k] = host[k];
-    } else {
-        uint64_t words = 0;
-        for (int k = 0; k < 5; ++k) words += host[k] ? width[k] * m : 0;
-        fld.out.ensure(words ? words : 1, stream, false, 1.1f);
-        uint64_t at = 0;
-        for (int k = 0; k < 5; ++k)
-            if (host[k]) { dev[k] = fld.out.p + at; at += width[k] * m; }
-    }
-    if (!(dev[0] || dev[1] || dev[2] || dev[3] || dev[4])) return;
+    QueryOut o{{{out.density, m}, {out.fraction, m}, {out.velocity, 3 * m}, {out.gradient, 3 * m}, {out.count, m}}};
+    query_place(o, (flags & SALVA_HIP_FIELD_OUT_ON_DEVICE) != 0u);
+    if (!o.any()) return;
     if (box_empty) {
-        for (int k = 0; k < 5; ++k)
-            if (dev[k]) SALVA_HIP_CHECK(hipMemsetAsync(dev[k], 0, width[k] * m * sizeof(float), stream));
+        query_zero(o);
     } else {
         const bool second = out.fraction || out.velocity;
         FieldGrid g{};
         const FieldCandidates cand = field_candidates(f, lo, hi, second, g);
-        const FieldOutDev od{dev[0], dev[1], dev[2], dev[3], reinterpret_cast<uint32_t*>(dev[4])};
+        const FieldOutDev od{o.f32(0), o.f32(1), o.f32(2), o.f32(3), o.u32(4)};
         SphConsts c = sc;
         if (brick_arm) launch_field_lattice(q, g, cand, c, od, stream);
         else launch_field_points(q, g, cand, c, od, stream);
     }
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    for (int k = 0; k < 5; ++k)
-        if (host[k]) download_f32(dev[k], width[k] * m, host[k]);
+    query_finish(o);
 }
 
 // npoints > 0 places of the caller's: where the kernels read them, and the box of the finite ones (lo > hi: none is finite)

@@ -26,6 +26,31 @@ void World::download_f32(const float* src, uint64_t count, float* out) {
     SALVA_HIP_CHECK(hipMemcpyAsync(out, src, count * sizeof(float), hipMemcpyDeviceToHost, stream));
     SALVA_HIP_CHECK(hipStreamSynchronize(stream));
 }
+// the outputs of a device query (world.h QueryOut)
+void World::query_place(QueryOut& q, bool on_device) {
+    q.on_device = on_device;
+    uint64_t total = 0;
+    for (const auto& e : q.o) total += e.host ? e.words : 0;
+    if (!on_device) query_out.ensure(total ? total : 1, stream, false, 1.1f);
+    uint64_t at = 0;
+    for (auto& e : q.o) {
+        if (!e.host) continue;
+        e.dev = on_device ? static_cast<float*>(e.host) : query_out.p + at;
+        at += e.words;
+    }
+}
+void World::query_zero(const QueryOut& q) {
+    for (const auto& e : q.o)
+        if (e.dev) SALVA_HIP_CHECK(hipMemsetAsync(e.dev, 0, e.words * sizeof(float), stream));
+}
+void World::query_finish(const QueryOut& q) {
+    if (q.on_device) {
+        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
+        return;
+    }
+    for (const auto& e : q.o)
+        if (e.dev && e.words) download_f32(e.dev, e.words, static_cast<float*>(e.host));
+}
 void World::download_xyz(const float4* src, uint64_t count, float* out) {
     scratch_f.ensure(3 * count, stream, false, 1.1f);
     k_unpack_xyz<<<nblk(count), BLOCK, 0, stream>>>((uint32_t)count, src, scratch_f.p);

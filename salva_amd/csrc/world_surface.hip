@@ -56,18 +56,14 @@ void World::surface_run(const float* d_values, float iso, const SurfaceLattice& 
         throw HipError(SALVA_HIP_E_CAPACITY, w + ": the mesh has " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
                                                  " triangles: more than the capacities of out");
     if (!nv && !nt) return;
-    float *d_vertices = out->vertices, *d_normals = out->normals, *d_velocities = out->velocities;
-    uint32_t* d_triangles = out->triangles;
-    if (!on_device) {
-        srf.vertices.ensure(3 * nv + 1, stream, false, 1.1f); d_vertices = srf.vertices.p;
-        srf.triangles.ensure(3 * nt + 1, stream, false, 1.1f); d_triangles = srf.triangles.p;
-        if (out->normals) { srf.normals.ensure(3 * nv + 1, stream, false, 1.1f); d_normals = srf.normals.p; }
-        if (out->velocities) { srf.velocities.ensure(3 * nv + 1, stream, false, 1.1f); d_velocities = srf.velocities.p; }
-    }
+    // all four at once, before the first kernel: the queries at the vertices below write to device memory and place nothing
+    QueryOut o{{{out->vertices, 3 * nv}, {out->normals, 3 * nv}, {out->velocities, 3 * nv}, {out->triangles, 3 * nt}}};
+    query_place(o, on_device);
+    float *const d_vertices = o.f32(0), *const d_normals = o.f32(1), *const d_velocities = o.f32(2);
     srf.voff.ensure((size_t)g.n + 1, stream, false, 1.1f);
     srf.toff.ensure((size_t)g.n + 1, stream, false, 1.1f);
     launch_surface_scans(srf.temp.p, tb, srf.word.p, g.n, srf.voff.p, srf.toff.p, stream);
-    launch_surface_emit(d_values, iso, g, srf.word.p, srf.voff.p, srf.toff.p, nv, nt, d_vertices, d_triangles, stream);
+    launch_surface_emit(d_values, iso, g, srf.word.p, srf.voff.p, srf.toff.p, nv, nt, d_vertices, o.u32(3), stream);
     if ((d_normals || d_velocities) && nv) {
         // the evaluator's own sums at the vertices, through its points path: the gradient lands where the normals go
         SalvaHipFieldOut fo{};
@@ -82,16 +78,7 @@ void World::surface_run(const float* d_values, float iso, const SurfaceLattice& 
         }
         if (d_normals) launch_surface_normals(d_normals, nv, stream);
     }
-    if (on_device) {
-        SALVA_HIP_CHECK(hipStreamSynchronize(stream));
-        return;
-    }
-    if (nv) {
-        download_f32(d_vertices, 3 * nv, out->vertices);
-        if (out->normals) download_f32(d_normals, 3 * nv, out->normals);
-        if (out->velocities) download_f32(d_velocities, 3 * nv, out->velocities);
-    }
-    if (nt) download_f32(reinterpret_cast<const float*>(d_triangles), 3 * nt, reinterpret_cast<float*>(out->triangles));
+    query_finish(o);  // (an output of no words is not copied)
 }
 
 void World::extract_surface(uint32_t fluid_mask, uint32_t field, float iso, const float origin[3], float spacing, const uint32_t dims[3], uint32_t flags,

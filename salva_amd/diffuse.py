@@ -66,11 +66,7 @@ def potentials(world, params=None, fluids=None, **which):
     mask, nrows = world._field_mask(fluids), C.c_uint64(0)
     L.check(world._L.salva_hip_diffuse_potentials(world._h, mask, C.byref(p), 0, None, C.byref(nrows)))
     n = int(nrows.value)
-    got = {k: np.zeros((n, 3) if w == 3 else n, np.uint32 if k == "count" else F32) for k, w in POTENTIALS.items() if which.get(k, True)}
-    out = L.DiffusePotentialsOut()
-    for k, a in got.items():
-        room = a if a.size else np.zeros(3, a.dtype)
-        setattr(out, k, room.ctypes.data_as(C.POINTER(C.c_uint32 if k == "count" else C.c_float)))
+    got, out, _room = L.host_out(L.DiffusePotentialsOut, {k: (n, 3) if w == 3 else (n,) for k, w in POTENTIALS.items() if which.get(k, True)})
     out.row_capacity = n
     L.check(world._L.salva_hip_diffuse_potentials(world._h, mask, C.byref(p), 0, C.byref(out), C.byref(nrows)))
     return got
@@ -87,10 +83,7 @@ def potentials_device(world, params=None, fluids=None, row_capacity=0, **address
     p = (params or Diffuse())._struct()
     nrows, out = C.c_uint64(0), None
     if any(addresses.values()):
-        out = L.DiffusePotentialsOut()
-        for k, address in addresses.items():
-            if address:
-                setattr(out, k, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if k == "count" else C.c_float)))
+        out = L.device_out(L.DiffusePotentialsOut, addresses)
         out.row_capacity = int(row_capacity)
     L.check(world._L.salva_hip_diffuse_potentials(world._h, world._field_mask(fluids), C.byref(p), L.DIFFUSE_OUT_ON_DEVICE,
                                                   C.byref(out) if out is not None else None, C.byref(nrows)))
@@ -144,12 +137,7 @@ class DiffuseSet:
     def get(self):
         """a dict of numpy arrays: positions, velocities (N x 3), lifetime, kind, id (N)"""
         n = len(self)
-        got = {"positions": np.zeros((n, 3), F32), "velocities": np.zeros((n, 3), F32), "lifetime": np.zeros(n, F32), "kind": np.zeros(n, np.uint32),
-               "id": np.zeros(n, np.uint32)}
-        out = L.DiffuseOut()
-        for k, a in got.items():
-            room = a if a.size else np.zeros(3, a.dtype)
-            setattr(out, k, room.ctypes.data_as(C.POINTER(C.c_uint32 if a.dtype == np.uint32 else C.c_float)))
+        got, out, _room = L.host_out(L.DiffuseOut, {"positions": (n, 3), "velocities": (n, 3), "lifetime": (n,), "kind": (n,), "id": (n,)})
         out.row_capacity = n
         m = C.c_uint64(0)
         L.check(self._world._L.salva_hip_get_diffuse(self._world._h, self._set, 0, C.byref(out), C.byref(m)))
@@ -157,10 +145,7 @@ class DiffuseSet:
 
     def get_device(self, row_capacity, **addresses):
         """get() into device memory: positions= / velocities= / lifetime= / kind= / id= are integer device addresses; returns N"""
-        out = L.DiffuseOut()
-        for k, address in addresses.items():
-            if address:
-                setattr(out, k, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if k in ("kind", "id") else C.c_float)))
+        out = L.device_out(L.DiffuseOut, addresses)
         out.row_capacity = int(row_capacity)
         m = C.c_uint64(0)
         L.check(self._world._L.salva_hip_get_diffuse(self._world._h, self._set, L.DIFFUSE_OUT_ON_DEVICE, C.byref(out), C.byref(m)))

@@ -1652,8 +1652,6 @@ class LiquidWorld:
         return int(out[0]), int(out[1])
 
     # ---- SPH fields at points and on a lattice (include/salva_hip.h salva_hip_evaluate_fields)
-    _FIELD_WIDTHS = (("density", 1), ("fraction", 1), ("velocity", 3), ("gradient", 3), ("count", 1))
-
     def _field_mask(self, fluids) -> int:
         if fluids is None:
             fluids = self._fluids
@@ -1664,35 +1662,14 @@ class LiquidWorld:
             mask |= 1 << (f._slot if isinstance(f, Fluid) else int(f))
         return mask & 0xFFFFFFFF
 
-    def _field_host_out(self, m, want):
-        arrays, out = {}, L.FieldOut()
-        for name, width in self._FIELD_WIDTHS:
-            if not want[name]:
-                continue
-            a = np.zeros(m * width, np.uint32 if name == "count" else F32)
-            arrays[name] = a
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
-        return arrays, out
-
     @staticmethod
-    def _field_device_out(addresses):
-        out = L.FieldOut()
-        for name, _ in LiquidWorld._FIELD_WIDTHS:
-            if addresses.get(name):
-                setattr(out, name, C.cast(C.c_void_p(int(addresses[name])), C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
-        return out
-
-    @staticmethod
-    def _aniso_host_out(m, want):
-        """the three outputs of the anisotropic evaluator; velocity and count belong to the isotropic one"""
-        if want["velocity"] or want["count"]:
+    def _field_shapes(shape, want, anisotropy):
+        """the struct and the array shapes of the fields asked for at places shaped `shape`; the anisotropic evaluator has three
+        outputs: velocity and count belong to the isotropic one"""
+        if anisotropy is not None and (want["velocity"] or want["count"]):
             raise ValueError("with anisotropy= the fields are density, fraction and gradient")
-        arrays, out = {}, L.AnisoFieldOut()
-        for name, width in (("density", 1), ("fraction", 1), ("gradient", 3)):
-            if want[name]:
-                arrays[name] = np.zeros(m * width, F32)
-                setattr(out, name, _fp(arrays[name]))
-        return arrays, out
+        return (L.FieldOut if anisotropy is None else L.AnisoFieldOut,
+                {k: shape + (3,) if k in ("velocity", "gradient") else shape for k, asked in want.items() if asked})
 
     def evaluate_fields(self, points, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False, anisotropy=None):
         """The SPH fields of `fluids` (None: all; Fluid objects or slot numbers) at `points` (m x 3), summed on the device over the
@@ -1704,14 +1681,13 @@ class LiquidWorld:
         pts = np.ascontiguousarray(points, F32).reshape(-1, 3)
         m = len(pts)
         want = dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count)
+        arrays, out, _room = L.host_out(*self._field_shapes((m,), want, anisotropy))
         if anisotropy is not None:
-            arrays, out = self._aniso_host_out(m, want)
             p = anisotropy._struct()
             L.check(self._L.salva_hip_evaluate_fields_anisotropic(self._h, self._field_mask(fluids), C.byref(p), m, _fp(pts), 0, C.byref(out)))
         else:
-            arrays, out = self._field_host_out(m, want)
             L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), m, _fp(pts), 0, C.byref(out)))
-        return {k: (a.reshape(m, 3) if k in ("velocity", "gradient") else a) for k, a in arrays.items()}
+        return arrays
 
     def evaluate_lattice(self, origin, spacing, dims, fluids=None, density=True, fraction=False, velocity=False, gradient=False, count=False,
                          anisotropy=None):
@@ -1727,15 +1703,14 @@ class LiquidWorld:
             raise L.SalvaHipError(L.E_CAPACITY, "salva_hip_evaluate_fields_lattice: more than 2^32 nodes: split the query")
         want = dict(density=density, fraction=fraction, velocity=velocity, gradient=gradient, count=count)
         dp = d.ctypes.data_as(C.POINTER(C.c_uint32))
+        arrays, out, _room = L.host_out(*self._field_shapes((nx, ny, nz), want, anisotropy))
         if anisotropy is not None:
-            arrays, out = self._aniso_host_out(m, want)
             p = anisotropy._struct()
             L.check(self._L.salva_hip_evaluate_fields_anisotropic_lattice(self._h, self._field_mask(fluids), C.byref(p), _fp(o), float(spacing), dp, 0,
                                                                           C.byref(out)))
         else:
-            arrays, out = self._field_host_out(m, want)
             L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), dp, 0, C.byref(out)))
-        return {k: (a.reshape(nx, ny, nz, 3) if k in ("velocity", "gradient") else a.reshape(nx, ny, nz)) for k, a in arrays.items()}
+        return arrays
 
     def anisotropy(self, params=None, fluids=None):
         """The smoothed centres (N x 3), metrics (N x 6: xx, xy, xz, yy, yz, zz of G) and neighbour counts (N) of the anisotropic
@@ -1747,11 +1722,7 @@ class LiquidWorld:
         mask, nrows = self._field_mask(fluids), C.c_uint64(0)
         L.check(self._L.salva_hip_compute_anisotropy(self._h, mask, C.byref(p), 0, None, C.byref(nrows)))
         n = int(nrows.value)
-        got = {"centres": np.zeros((n, 3), F32), "metric": np.zeros((n, 6), F32), "count": np.zeros(n, np.uint32)}
-        room = {k: (a if a.size else np.zeros(6, a.dtype)) for k, a in got.items()}
-        out = L.AnisotropyOut()
-        out.centres, out.metric = _fp(room["centres"]), _fp(room["metric"])
-        out.count = room["count"].ctypes.data_as(C.POINTER(C.c_uint32))
+        got, out, _room = L.host_out(L.AnisotropyOut, {"centres": (n, 3), "metric": (n, 6), "count": (n,)})
         out.row_capacity = n
         L.check(self._L.salva_hip_compute_anisotropy(self._h, mask, C.byref(p), 0, C.byref(out), C.byref(nrows)))
         return got
@@ -1762,7 +1733,7 @@ class LiquidWorld:
         world's device; an address left out or 0 is not computed.  The results are complete when the call returns."""
         self.wait_download()
         self.sync_to_device(apply_removal=False)
-        out = self._field_device_out(addresses)
+        out = L.device_out(L.FieldOut, addresses)
         pts = C.cast(C.c_void_p(int(points_address)), C.POINTER(C.c_float))
         L.check(self._L.salva_hip_evaluate_fields(self._h, self._field_mask(fluids), int(npoints), pts,
                                                   L.FIELD_POINTS_ON_DEVICE | L.FIELD_OUT_ON_DEVICE, C.byref(out)))
@@ -1778,14 +1749,11 @@ class LiquidWorld:
         if anisotropy is not None:
             if set(addresses) - {"density", "fraction", "gradient"}:
                 raise ValueError("with anisotropy= the fields are density, fraction and gradient")
-            out, p = L.AnisoFieldOut(), anisotropy._struct()
-            for name, address in addresses.items():
-                if address:
-                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_float)))
+            out, p = L.device_out(L.AnisoFieldOut, addresses), anisotropy._struct()
             L.check(self._L.salva_hip_evaluate_fields_anisotropic_lattice(self._h, self._field_mask(fluids), C.byref(p), _fp(o), float(spacing), dp,
                                                                           L.FIELD_OUT_ON_DEVICE, C.byref(out)))
             return
-        out = self._field_device_out(addresses)
+        out = L.device_out(L.FieldOut, addresses)
         L.check(self._L.salva_hip_evaluate_fields_lattice(self._h, self._field_mask(fluids), _fp(o), float(spacing), dp, L.FIELD_OUT_ON_DEVICE, C.byref(out)))
 
     def anisotropy_device(self, params=None, fluids=None, centres=0, metric=0, count=0, row_capacity=0):
@@ -1797,10 +1765,7 @@ class LiquidWorld:
         p = (params or Anisotropy())._struct()
         nrows, out = C.c_uint64(0), None
         if centres or metric or count:
-            out = L.AnisotropyOut()
-            for name, address in (("centres", centres), ("metric", metric), ("count", count)):
-                if address:
-                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if name == "count" else C.c_float)))
+            out = L.device_out(L.AnisotropyOut, dict(centres=centres, metric=metric, count=count))
             out.row_capacity = int(row_capacity)
         L.check(self._L.salva_hip_compute_anisotropy(self._h, self._field_mask(fluids), C.byref(p), L.ANISOTROPY_OUT_ON_DEVICE,
                                                      C.byref(out) if out is not None else None, C.byref(nrows)))
@@ -1842,17 +1807,13 @@ class LiquidWorld:
         counts = (C.c_uint64 * 2)()
         L.check(call(None, counts))
         nv, nt = int(counts[0]), int(counts[1])
-        mesh = {"vertices": np.zeros((nv, 3), F32), "triangles": np.zeros((nt, 3), np.uint32)}
-        out = L.SurfaceOut()
-        out.vertex_capacity, out.triangle_capacity = nv, nt
+        shapes = {"vertices": (nv, 3), "triangles": (nt, 3)}
         if normals:
-            mesh["normals"] = np.zeros((nv, 3), F32)
+            shapes["normals"] = (nv, 3)
         if velocities:
-            mesh["velocities"] = np.zeros((nv, 3), F32)
-        # (an empty numpy array may have a null data pointer: the library wants room it can name)
-        room = {k: (a if a.size else np.zeros(3, a.dtype)) for k, a in mesh.items()}
-        for k, a in room.items():
-            setattr(out, k, a.ctypes.data_as(C.POINTER(C.c_uint32 if k == "triangles" else C.c_float)))
+            shapes["velocities"] = (nv, 3)
+        mesh, out, _room = L.host_out(L.SurfaceOut, shapes)
+        out.vertex_capacity, out.triangle_capacity = nv, nt
         L.check(call(C.byref(out), counts))
         assert (int(counts[0]), int(counts[1])) == (nv, nt)
         return mesh
@@ -1893,10 +1854,7 @@ class LiquidWorld:
         counts = (C.c_uint64 * 2)()
         out = None
         if vertices:
-            out = L.SurfaceOut()
-            for name, address in (("vertices", vertices), ("normals", normals), ("velocities", velocities), ("triangles", triangles)):
-                if address:
-                    setattr(out, name, C.cast(C.c_void_p(int(address)), C.POINTER(C.c_uint32 if name == "triangles" else C.c_float)))
+            out = L.device_out(L.SurfaceOut, dict(vertices=vertices, normals=normals, velocities=velocities, triangles=triangles))
             out.vertex_capacity, out.triangle_capacity = int(vertex_capacity), int(triangle_capacity)
         ref = C.byref(out) if out is not None else None
         if values:
@@ -1929,8 +1887,6 @@ class LiquidWorld:
         return lo, hi, int(n.value)
 
     # ---- rays cast at the fluid's particles (include/salva_hip.h salva_hip_cast_rays)
-    _RAY_WIDTHS = (("t", 1), ("fluid", 1), ("index", 1), ("normal", 3), ("thickness", 1))
-
     def _ray_params(self, radius, tmax, clip):
         p = L.RayParams()
         p.struct_size, p.version = L.RAY_PARAMS_BYTES, L.RAY_VERSION
@@ -1952,25 +1908,11 @@ class LiquidWorld:
         c.width, c.height = int(camera["width"]), int(camera["height"])
         return c
 
-    def _ray_host_out(self, m, normals, thickness, hits):
-        arrays, out = {}, L.RayOut()
-        want = dict(t=hits, fluid=hits, index=hits, normal=normals, thickness=thickness)
-        for name, width in self._RAY_WIDTHS:
-            if not want[name]:
-                continue
-            integer = name in ("fluid", "index")
-            a = np.zeros(m * width, np.uint32 if integer else F32)
-            arrays[name] = a
-            setattr(out, name, a.ctypes.data_as(C.POINTER(C.c_uint32 if integer else C.c_float)))
-        return arrays, out
-
     @staticmethod
-    def _ray_device_out(addresses):
-        out = L.RayOut()
-        for name, _ in LiquidWorld._RAY_WIDTHS:
-            if addresses.get(name):
-                setattr(out, name, C.cast(C.c_void_p(int(addresses[name])), C.POINTER(C.c_uint32 if name in ("fluid", "index") else C.c_float)))
-        return out
+    def _ray_shapes(shape, normals, thickness, hits):
+        """the array shapes of the outputs asked for, for rays shaped `shape`"""
+        want = dict(t=hits, fluid=hits, index=hits, normal=normals, thickness=thickness)
+        return {k: shape + (3,) if k == "normal" else shape for k, asked in want.items() if asked}
 
     def cast_rays(self, origins, directions, radius=None, tmax=np.inf, fluids=None, clip=None, normals=False, thickness=False, hits=True):
         """Casts the rays origins[i] + t directions[i] (m x 3 each) at the particles of `fluids` (None: all), each a sphere of
@@ -1986,9 +1928,9 @@ class LiquidWorld:
             raise ValueError("cast_rays: as many directions as origins")
         m = len(o)
         p = self._ray_params(radius, tmax, clip)
-        arrays, out = self._ray_host_out(m, normals, thickness, hits)
+        arrays, out, _room = L.host_out(L.RayOut, self._ray_shapes((m,), normals, thickness, hits))
         L.check(self._L.salva_hip_cast_rays(self._h, self._field_mask(fluids), C.byref(p), m, _fp(o), _fp(d), 0, C.byref(out)))
-        return {k: (a.reshape(m, 3) if k == "normal" else a) for k, a in arrays.items()}
+        return arrays
 
     def cast_camera(self, camera, radius=None, tmax=np.inf, fluids=None, clip=None, normals=False, thickness=False, hits=True):
         """cast_rays for the pixels of `camera` (a dict: origin, forward, right, up, width, height): pixel (ix, iy) casts
@@ -1999,10 +1941,10 @@ class LiquidWorld:
         c = self._ray_camera(camera)
         m = int(c.width) * int(c.height)
         p = self._ray_params(radius, tmax, clip)
-        arrays, out = self._ray_host_out(m if m <= 1 << 32 else 1, normals, thickness, hits)  # (beyond: the library refuses before it writes)
+        shape = (int(c.height), int(c.width)) if m <= 1 << 32 else (1,)  # (beyond: the library refuses before it writes)
+        arrays, out, _room = L.host_out(L.RayOut, self._ray_shapes(shape, normals, thickness, hits))
         L.check(self._L.salva_hip_cast_rays_camera(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), 0, C.byref(out)))
-        hh, ww = int(c.height), int(c.width)
-        return {k: (a.reshape(hh, ww, 3) if k == "normal" else a.reshape(hh, ww)) for k, a in arrays.items()}
+        return arrays
 
     def cast_rays_device(self, origins_address: int, directions_address: int, nrays: int, radius=None, tmax=np.inf, fluids=None, clip=None,
                          **addresses):
@@ -2012,7 +1954,7 @@ class LiquidWorld:
         self.wait_download()
         self.sync_to_device(apply_removal=False)
         p = self._ray_params(radius, tmax, clip)
-        out = self._ray_device_out(addresses)
+        out = L.device_out(L.RayOut, addresses)
         o = C.cast(C.c_void_p(int(origins_address)), C.POINTER(C.c_float))
         d = C.cast(C.c_void_p(int(directions_address)), C.POINTER(C.c_float))
         L.check(self._L.salva_hip_cast_rays(self._h, self._field_mask(fluids), C.byref(p), int(nrays), o, d,
@@ -2024,7 +1966,7 @@ class LiquidWorld:
         self.sync_to_device(apply_removal=False)
         c = self._ray_camera(camera)
         p = self._ray_params(radius, tmax, clip)
-        out = self._ray_device_out(addresses)
+        out = L.device_out(L.RayOut, addresses)
         L.check(self._L.salva_hip_cast_rays_camera(self._h, self._field_mask(fluids), C.byref(p), C.byref(c), L.RAY_OUT_ON_DEVICE, C.byref(out)))
 
     def count_ray_candidates(self, origins=None, directions=None, camera=None, radius=None, tmax=np.inf, fluids=None, clip=None, thickness_walk=False):
