@@ -99,6 +99,40 @@ impl<KD: GpuKernel, KG: GpuKernel> salva3d::solver::NonPressureForce for Becker2
     }
 }
 
+/// Vorticity confinement (Fedkiw et al. 2001; Macklin & Müller 2013, section 5) for a device world; salva3d has none.  The
+/// contract is include/salva_hip.h, `SALVA_HIP_FORCE_VORTICITY_CONFINEMENT`: the force acts between particles of its fluid only,
+/// has no boundary arm, and a fluid takes one entry.  `strength` 0 computes the vorticity only (`LiquidWorld::vorticity`).  The
+/// default `kappa` is a choice, not a measurement.  Its host `solve` is never called.
+pub struct VorticityConfinement {
+    pub strength: Real,
+    pub kappa: Real,
+}
+
+impl VorticityConfinement {
+    pub fn new(strength: Real) -> Self {
+        Self { strength, kappa: 0.05 }
+    }
+}
+
+impl salva3d::solver::NonPressureForce for VorticityConfinement {
+    fn solve(
+        &mut self,
+        _timestep: &salva3d::TimestepManager,
+        _kernel_radius: Real,
+        _fluid_fluid_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid_boundaries_contacts: &salva3d::geometry::ParticlesContacts,
+        _fluid: &mut Fluid,
+        _boundaries: &[Boundary],
+        _densities: &[Real],
+    ) {
+        unreachable!("VorticityConfinement runs on the device (LiquidWorld::step)")
+    }
+
+    fn gpu_desc(&self) -> Option<(i32, [f32; 7])> {
+        Some((ffi::SALVA_HIP_FORCE_VORTICITY_CONFINEMENT, [self.strength, self.kappa, 0.0, 0.0, 0.0, 0.0, 0.0]))
+    }
+}
+
 /// Any other `impl NonPressureForce` written as a kernel (`SALVA_HIP_FORCE_DEVICE`, include/salva_hip.h): `entry` is an
 /// `extern "C"` function of a HIP object the crate links ("Linking a HIP object") that enqueues its kernel on
 /// `view.stream` and returns 0.  It is called in the middle of the substep, at the force's place in the list, without a wait; the
@@ -694,6 +728,19 @@ impl LiquidWorld {
             }
         }
         Ok(())
+    }
+
+    /// `SALVA_HIP_FIELD_VORTICITY`: the curl of the velocities the fluid's `VorticityConfinement` entry saw in the last substep of
+    /// the last step, in host order.  Only right after a step; an error when the fluid has no such entry.
+    pub fn vorticity(&mut self, handle: FluidHandle) -> Result<Vec<Vector3<Real>>, Error> {
+        let no_fluid = || Error { code: ffi::SALVA_HIP_E_INVALID, message: "no such fluid".into() };
+        let slot = self.fluids.iter().position(|(h, _)| h == handle).ok_or_else(no_fluid)?;
+        let n = self.fluids.as_slice()[slot].num_particles();
+        let mut out = vec![Vector3::<Real>::zeros(); n];
+        if n != 0 {
+            check(unsafe { ffi::salva_hip_get_fluid_field(self.raw, slot as u32, ffi::SALVA_HIP_FIELD_VORTICITY, out.as_mut_ptr() as *mut f32) })?;
+        }
+        Ok(out)
     }
 
     /// `LiquidWorld::step(dt, gravity)` (liquid_world.rs:62-158 with the `()` coupling manager).

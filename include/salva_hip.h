@@ -84,9 +84,11 @@ enum {
                                         kernel of their own takes SALVA_HIP_FORCE_DEVICE instead: nothing crosses PCIe */
     SALVA_HIP_FORCE_BECKER2009 = 8,  /* solver::Becker2009Elasticity::new(young_modulus, poisson_ratio, nonlinear_strain),
                                         becker2009_elasticity.rs:66-82: corotated SPH elasticity with a rest state of its own */
-    SALVA_HIP_FORCE_DEVICE = 9       /* any other `impl NonPressureForce` written as a kernel: the callback of
+    SALVA_HIP_FORCE_DEVICE = 9,      /* any other `impl NonPressureForce` written as a kernel: the callback of
                                         salva_hip_set_device_force_callback enqueues it on the world's stream, on the state where
                                         it lies in device memory (SalvaHipDeviceView below), at its place in the list */
+    SALVA_HIP_FORCE_VORTICITY_CONFINEMENT = 10 /* not in the reference: vorticity confinement (Fedkiw et al. 2001) in the particle
+                                        form of Macklin & Mueller 2013, section 5.  The contract is below, at SalvaHipForceDesc */
 };
 /* p[0] of a SALVA_HIP_FORCE_DEVICE entry: what the force needs besides the particles, as a sum of these (stored exactly in the float) */
 enum {
@@ -110,7 +112,24 @@ typedef struct SalvaHipForceDesc {
      *                  same kind and bit-identical p[]; any other entry k starts empty.  Not available in decomposed worlds
      *                  (salva_hip_set_domain): the rest lists cross slabs.
      * DEVICE:     p[0] SALVA_HIP_DEVICE_NEEDS_* bits (0 ... 7); p[1..6] are the user's and reach the kernel in SalvaHipDeviceView::params.
-     *                  Not available in decomposed worlds: ghost rows and ownership are not part of the view. */
+     *                  Not available in decomposed worlds: ghost rows and ownership are not part of the view.
+     * VORTICITY_CONFINEMENT: p[0] strength eps (m/s, finite, >= 0), p[1] kappa (dimensionless, finite, >= 0; the mirrors default
+     *                  it to 0.05, a choice and not a measurement); p[2..6] must be 0.  A fluid takes at most one such entry.
+     *                  The force belongs to one fluid and acts between particles of that fluid only.  It has NO boundary arm and
+     *                  applies no boundary reaction: a boundary's velocity is not a sample of the fluid's velocity field, and a
+     *                  curl across a wall would spin up every no-slip layer.  With v the velocities the other forces read at that
+     *                  point of the substep, grad W_ij the world's gradient kernel at x_i - x_j, h the kernel radius and the sums
+     *                  over the fluid-fluid contacts j of i that belong to the same fluid (all in f32):
+     *                    pass 1  omega_i = (sum_j m_j (v_i - v_j) x grad W_ij) / rho_i,  n_i = |omega_i|   (Monaghan 1992, 2.20;
+     *                            the self pair adds exactly nothing)
+     *                    pass 2  eta_i = sum_j (m_j / rho_j) (n_j - n_i) grad W_ij      (the difference form: exactly zero for
+     *                            uniform n everywhere, the free surface with its one-sided neighbourhood included)
+     *                    force   D_i = |eta_i| + kappa n_i / h;  D_i == 0: nothing is added;  otherwise
+     *                            a_i += eps (eta_i / D_i) x omega_i
+     *                  The regularised quotient makes the force a continuous function of the state: it fades where the relative
+     *                  change of |omega| over one h falls below kappa; kappa = 0 is the hard normalisation.  eps == 0 runs pass 1
+     *                  only and leaves the accelerations bit-identical: that entry exists to read the vorticity out
+     *                  (SALVA_HIP_FIELD_VORTICITY).  Stateless; available in decomposed worlds. */
     float p[7];
 } SalvaHipForceDesc;
 
@@ -192,7 +211,12 @@ enum {
     SALVA_HIP_FIELD_VELOCITY_CHANGE = 4,    /* velocity_changes     f32 x 3n */
     SALVA_HIP_FIELD_PRESSURE = 5,           /* pressures (IISPH)    f32 x n */
     SALVA_HIP_FIELD_VOLUME = 6,             /* volumes              f32 x n */
-    SALVA_HIP_FIELD_ACCELERATION = 7        /* accelerations        f32 x 3n */
+    SALVA_HIP_FIELD_ACCELERATION = 7,       /* accelerations        f32 x 3n */
+    SALVA_HIP_FIELD_VORTICITY = 8           /* f32 x 3n: the omega_i that the fluid's SALVA_HIP_FORCE_VORTICITY_CONFINEMENT entry computed in
+                                               the last substep of the last step: the curl of the velocities the force saw (before the
+                                               pressure solve), at the positions before the step's advection.  Only available right
+                                               after a step, like the other scratch fields; SALVA_HIP_E_INVALID when the fluid has no
+                                               such entry */
 };
 
 void salva_hip_default_params(SalvaHipParams* out);

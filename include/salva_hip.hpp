@@ -86,6 +86,17 @@ struct He2014SurfaceTension : NonPressureForce {  // surface_tension/he2014_surf
         return d;
     }
 };
+// Not in the reference: vorticity confinement (Fedkiw et al. 2001; Macklin & Mueller 2013, section 5).  The contract is
+// include/salva_hip.h, SALVA_HIP_FORCE_VORTICITY_CONFINEMENT: no boundary arm, one entry per fluid; strength 0 computes the vorticity
+// only (LiquidWorld::vorticity).  kappa = 0.05 is a choice, not a measurement.
+struct VorticityConfinement : NonPressureForce {
+    Real strength, kappa;
+    VorticityConfinement(Real strength_, Real kappa_ = (Real)0.05) : strength(strength_), kappa(kappa_) {}
+    SalvaHipForceDesc desc() const override {
+        SalvaHipForceDesc d{SALVA_HIP_FORCE_VORTICITY_CONFINEMENT, {strength, kappa}};
+        return d;
+    }
+};
 struct WCSPHSurfaceTension : NonPressureForce {  // surface_tension/wcsph_surface_tension.rs:15-28
     Real fluid_tension_coefficient, boundary_tension_coefficient;
     WCSPHSurfaceTension(Real t, Real b) : fluid_tension_coefficient(t), boundary_tension_coefficient(b) {}
@@ -1230,6 +1241,13 @@ class LiquidWorld {  // liquid_world.rs
     }
     void refresh() {
         for (size_t s = 0; s < fluids_.size(); ++s) refresh((FluidHandle)s);
+    }
+    // SALVA_HIP_FIELD_VORTICITY: the curl of the velocities the fluid's VorticityConfinement entry saw in the last substep of the last
+    // step, in host order.  Only right after a step; an error when the fluid has no such entry.
+    std::vector<Vec3> vorticity(FluidHandle h) {
+        std::vector<Vec3> out(fluids_[h].num_particles(), Vec3{0, 0, 0});
+        if (!out.empty()) check(salva_hip_get_fluid_field(w_, (uint32_t)h, SALVA_HIP_FIELD_VORTICITY, out[0].data()));
+        return out;
     }
     void boundary_wrench(BoundaryHandle h, const Vec3& point, Vec3& force, Vec3& torque) {
         check(salva_hip_get_boundary_wrench(w_, (uint32_t)h, point.data(), force.data(), torque.data()));

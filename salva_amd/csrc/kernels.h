@@ -145,6 +145,13 @@ void launch_he2014_forces(const StepCtx& c, const TileLds& L, uint32_t model, fl
 void launch_wcsph_tension(const StepCtx& c, const TileLds& L, uint32_t model, float tension, hipStream_t s);
 void launch_akinci_forces(const StepCtx& c, const TileLds& L, uint32_t model, float tension, float adhesion, hipStream_t s);
 
+// ---------------------------------------------------------------- vorticity.hip (SALVA_HIP_FORCE_VORTICITY_CONFINEMENT)
+// omega[i] = (curl of w at particle i, its norm) for the sorted rows of fluid `model`; other rows are not written
+void launch_vorticity_curl(const StepCtx& c, const TileLds& L, uint32_t model, float4* omega, hipStream_t s);
+// acc += eps (eta / (|eta| + kappa_over_h n)) x omega on the rows of fluid `model`
+void launch_vorticity_confine(const StepCtx& c, const TileLds& L, uint32_t model, float eps, float kappa_over_h, const float4* omega,
+                              hipStream_t s);
+
 // ---------------------------------------------------------------- iisph.hip
 void launch_iisph_begin(const StepCtx& c, float gx, float gy, float gz, bool acc_has_user, hipStream_t s);  // acc += g
 void launch_iisph_dii(const StepCtx& c, const TileLds& L, float dt, hipStream_t s);            // + p = 0.5 * dv.w
@@ -183,6 +190,9 @@ void launch_he2014_gradc(const StepCtx& c, const TileLds& L, uint32_t model, con
 void launch_he2014_forces(const StepCtx& c, const TileLds& L, uint32_t model, float tension, float boundary_tension,
                           const float* gradcs, hipStream_t s);
 void launch_wcsph_tension(const StepCtx& c, const TileLds& L, uint32_t model, float tension, hipStream_t s);
+void launch_vorticity_curl(const StepCtx& c, const TileLds& L, uint32_t model, float4* omega, hipStream_t s);
+void launch_vorticity_confine(const StepCtx& c, const TileLds& L, uint32_t model, float eps, float kappa_over_h, const float4* omega,
+                              hipStream_t s);
 void launch_visc_betas(const StepCtx& c, const TileLds& L, uint32_t model, float* beta, hipStream_t s);
 void launch_visc_strain(const StepCtx& c, const TileLds& L, uint32_t model, int mode, float coef, const float4* va,
                         const float* beta, float* target, float4* u0, float4* u1, hipStream_t s);

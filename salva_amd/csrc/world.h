@@ -89,6 +89,7 @@ struct FluidSlot {
     // SALVA_HIP_FORCE_BECKER2009 entries: their state, by force index (nullptr for the other kinds).  Shared pointers, so that the
     // state moves with the fluid in remove_fluid's swap-remove.
     std::vector<std::shared_ptr<ElasticState>> elastic;
+    bool vort_fresh = false;  // World::vort_omega holds this fluid's rows of the force list as it is now (SALVA_HIP_FIELD_VORTICITY)
 };
 struct BoundarySlot {
     uint64_t n = 0;
@@ -689,6 +690,9 @@ class World {
     DevBuf<float> visc_beta, visc_target;  // DFSPHViscosity scratch: betas [36][n], strain-rate targets [6][n]
     DevBuf<float4> visc_u0, visc_u1, visc_va;
     DevBuf<float> he_colors, he_gradcs;  // He2014SurfaceTension state (he2014_surface_tension.rs:15-16)
+    // vorticity confinement: (omega_i, |omega_i|) per sorted row; the fluids that carry the force write disjoint rows.  Stateless
+    // between substeps: what SALVA_HIP_FIELD_VORTICITY reads is the last substep's
+    DevBuf<float4> vort_omega;
     DevBuf<float> rho, alpha, kappa, kappa2, rho_star, aii;
     DevBuf<uint32_t> nff, nfb;
     // What the first part of a step builds from the positions alone — keys, the sort's permutation, the cell table, the non-empty

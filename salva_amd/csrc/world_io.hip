@@ -160,7 +160,7 @@ void World::get_fluid_field(uint32_t slot, int field, float* out) {
     if (comm && dist_started) throw HipError(SALVA_HIP_E_INVALID, "per-fluid host-order access is not available in a multi-GPU run: use salva_hip_get_owned");
     const uint64_t nn = sp.n, off = sp.off;
     if (nn == 0) return;
-    enum Part { XYZ, W, F32, U32_AS_F32 };
+    enum Part { XYZ, W, F32, U32_AS_F32, SORTED_XYZ };  // (SORTED_XYZ: the xyz of a float4 array in sorted order)
     struct Source { const void* array; Part part; bool staged; };
     Source src{nullptr, F32, false};
     switch (field) {
@@ -172,6 +172,13 @@ void World::get_fluid_field(uint32_t slot, int field, float* out) {
         case SALVA_HIP_FIELD_ALPHA: src = {alpha.p, F32, false}; break;
         case SALVA_HIP_FIELD_NUM_FLUID_CONTACTS: src = {nff.p, U32_AS_F32, false}; break;
         case SALVA_HIP_FIELD_NUM_BOUNDARY_CONTACTS: src = {nfb.p, U32_AS_F32, false}; break;
+        case SALVA_HIP_FIELD_VORTICITY: {
+            bool has = false;
+            for (const SalvaHipForceDesc& d : fluids[slot].forces) has |= d.kind == SALVA_HIP_FORCE_VORTICITY_CONFINEMENT;
+            if (!has) throw HipError(SALVA_HIP_E_INVALID, "SALVA_HIP_FIELD_VORTICITY: the fluid has no VorticityConfinement entry");
+            src = {vort_omega.p, SORTED_XYZ, false};
+            break;
+        }
         default: break;
     }
     scratch_f.ensure(std::max<size_t>(3 * nn, n), stream, false, 1.1f);  // (one size for every field)
@@ -190,7 +197,15 @@ void World::get_fluid_field(uint32_t slot, int field, float* out) {
     if (!sorted_valid || !have_last_ctx)
         throw HipError(SALVA_HIP_E_INVALID, "solver scratch fields are only available right after a step");
     if (field == SALVA_HIP_FIELD_NUM_BOUNDARY_CONTACTS && nb == 0) { memset(out, 0, nn * sizeof(float)); return; }
+    if (field == SALVA_HIP_FIELD_VORTICITY && (!fluids[slot].vort_fresh || vort_omega.cap < n))  // (the entry was set after the last step's forces ran)
+        throw HipError(SALVA_HIP_E_INVALID, "solver scratch fields are only available right after a step");
     if (!src.array) throw HipError(SALVA_HIP_E_INVALID, "unknown field");
+    if (src.part == SORTED_XYZ) {
+        scratch_f4.ensure(n);
+        launch_unsort_f4(n, perm[cur].p, static_cast<const float4*>(src.array), scratch_f4.p, stream);
+        download_xyz(scratch_f4.p + off, nn, out);
+        return;
+    }
     if (src.part == F32) launch_unsort_f32(n, perm[cur].p, static_cast<const float*>(src.array), scratch_f.p, stream);
     else launch_unsort_u32_as_f32(n, perm[cur].p, static_cast<const uint32_t*>(src.array), scratch_f.p, stream);
     download_f32(scratch_f.p + off, nn, out);

@@ -354,8 +354,19 @@ void World::apply_keep_flags(const uint8_t* d_keep, const uint32_t* deleted_per_
 void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t nf) {
     fluid_span(slot);
     for (uint32_t k = 0; k < nf; ++k)
-        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_DEVICE)
+        if (f[k].kind < SALVA_HIP_FORCE_XSPH || f[k].kind > SALVA_HIP_FORCE_VORTICITY_CONFINEMENT)
             throw HipError(SALVA_HIP_E_INVALID, "unknown non-pressure force kind (only built-ins run on the device)");
+    for (uint32_t k = 0, seen = 0; k < nf; ++k)
+        if (f[k].kind == SALVA_HIP_FORCE_VORTICITY_CONFINEMENT) {
+            if (!(std::isfinite(f[k].p[0]) && f[k].p[0] >= 0.0f))
+                throw HipError(SALVA_HIP_E_INVALID, "VorticityConfinement: p[0] (strength) must be finite and >= 0");
+            if (!(std::isfinite(f[k].p[1]) && f[k].p[1] >= 0.0f))
+                throw HipError(SALVA_HIP_E_INVALID, "VorticityConfinement: p[1] (kappa) must be finite and >= 0");
+            for (int q = 2; q < 7; ++q)
+                if (!(f[k].p[q] == 0.0f)) throw HipError(SALVA_HIP_E_INVALID, "VorticityConfinement: p[2..6] must be 0");
+            if (seen++)  // (SALVA_HIP_FIELD_VORTICITY would be ambiguous)
+                throw HipError(SALVA_HIP_E_INVALID, "VorticityConfinement: a fluid takes one entry of this kind");
+        }
     for (uint32_t k = 0; k < nf; ++k)
         if (f[k].kind == SALVA_HIP_FORCE_DEVICE) {
             if (comm)  // ghost rows and the local view's ownership rules are not part of SalvaHipDeviceView
@@ -388,6 +399,7 @@ void World::set_fluid_forces(uint32_t slot, const SalvaHipForceDesc* f, uint32_t
             el[k] = fs.elastic[k];
     fs.forces.assign(f, f + nf);
     fs.elastic = std::move(el);
+    fs.vort_fresh = false;
 }
 
 // ContiguousArena::remove is a swap-remove (contiguous_arena.rs): the last object takes the freed slot.

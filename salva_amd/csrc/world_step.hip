@@ -388,6 +388,15 @@ void World::run_forces(const StepCtx& c) {
                     launch_he2014_forces(c, lds, f, d.p[0], d.p[1], he_gradcs.p, stream);
                     break;
                 case SALVA_HIP_FORCE_WCSPH_TENSION: launch_wcsph_tension(c, lds, f, d.p[0], stream); break;
+                case SALVA_HIP_FORCE_VORTICITY_CONFINEMENT:
+                    // curl -> location vector and force (salva_hip.h); eps == 0 is the entry that only reads the vorticity out
+                    vort_omega.ensure(n, stream, false, 1.1f);
+                    fluids[f].vort_fresh = true;
+                    launch_vorticity_curl(c, lds, f, vort_omega.p, stream);
+                    // the outer ghost plane's omega is a sum over an incomplete neighbourhood, and the inner plane's eta reads it
+                    if (comm) refresh_f4(vort_omega.p);
+                    if (d.p[0] != 0.0f) launch_vorticity_confine(c, lds, f, d.p[0], d.p[1] / c.sc.h, vort_omega.p, stream);
+                    break;
                 case SALVA_HIP_FORCE_CUSTOM: {
                     // a host `NonPressureForce::solve` at its place in the list (nonpressure_force.rs:10-30)
                     if (!force_cb) throw HipError(SALVA_HIP_E_INVALID, "a SALVA_HIP_FORCE_CUSTOM entry needs salva_hip_set_force_callback");

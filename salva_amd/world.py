@@ -258,6 +258,23 @@ class WCSPHSurfaceTension(NonPressureForce):
         return d
 
 
+class VorticityConfinement(NonPressureForce):
+    """Vorticity confinement (Fedkiw et al. 2001) in the particle form of Macklin & Mueller 2013, section 5; not in the reference.
+    The contract is include/salva_hip.h, SALVA_HIP_FORCE_VORTICITY_CONFINEMENT: a_i += strength (eta_i / (|eta_i| + kappa n_i / h)) x
+    omega_i between particles of the same fluid, no boundary arm.  `kappa` = 0.05 is a choice, not a measurement.  `strength` = 0
+    computes the vorticity only (LiquidWorld.vorticity) and leaves the accelerations as they are.  One entry per fluid."""
+
+    def __init__(self, strength: float, kappa: float = 0.05):
+        self.strength = strength
+        self.kappa = kappa
+
+    def _desc(self):
+        d = L.ForceDesc()
+        d.kind = L.FORCE_VORTICITY_CONFINEMENT
+        d.p[0], d.p[1] = self.strength, self.kappa
+        return d
+
+
 # ------------------------------------------------------------------------------------------------ solvers
 class DFSPHViscosity(NonPressureForce):
     """solver::DFSPHViscosity (viscous DFSPH), dfsph_viscosity.rs:85-125: `new(viscosity_coefficient)` + pub tuning fields.
@@ -1460,7 +1477,7 @@ class LiquidWorld:
     # ---- solver scratch (private in the reference; exposed for the parity tests)
     def fluid_field(self, f: Fluid, field: int) -> np.ndarray:
         n = f.num_particles()
-        vec = field in (L.FIELD_VELOCITY_CHANGE, L.FIELD_ACCELERATION)
+        vec = field in (L.FIELD_VELOCITY_CHANGE, L.FIELD_ACCELERATION, L.FIELD_VORTICITY)
         out = np.zeros((n, 3) if vec else n, F32)
         if n:
             L.check(self._L.salva_hip_get_fluid_field(self._h, f._slot, field, _fp(out)))
@@ -1477,6 +1494,11 @@ class LiquidWorld:
 
     def pressures(self, f: Fluid) -> np.ndarray:
         return self.fluid_field(f, L.FIELD_PRESSURE)
+
+    def vorticity(self, f: Fluid) -> np.ndarray:
+        """(n, 3): the curl of the velocities the fluid's VorticityConfinement entry saw in the last substep of the last step, in
+        host order, at the positions before that step's advection.  Only right after a step; an error without such an entry."""
+        return self.fluid_field(f, L.FIELD_VORTICITY)
 
     def contact_counts(self, f: Fluid, boundary_contacts: bool = False) -> np.ndarray:
         fld = L.FIELD_NUM_BOUNDARY_CONTACTS if boundary_contacts else L.FIELD_NUM_FLUID_CONTACTS
